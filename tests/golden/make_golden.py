@@ -695,7 +695,74 @@ def gen_generate_streaming(custom=None):
     run("streaming_cap_on_text.npz", 23, 35, seed=191019, eos_bias=0.0)
 
 
+def _no_init_tables(build):
+    """{name: shape} of the model build() returns, instantiated in bf16 with every random initialisation skipped (only names and
+    shapes are read; at real widths the initialisers alone take minutes of CPU)"""
+    import torch.nn.init as init
+    old = torch.get_default_dtype()
+    torch.set_default_dtype(torch.bfloat16)
+    saved = {n: getattr(init, n) for n in ("normal_", "uniform_", "trunc_normal_", "kaiming_uniform_", "kaiming_normal_", "xavier_uniform_",
+                                           "xavier_normal_", "constant_", "zeros_", "ones_")}
+    tsaved = {n: getattr(torch.Tensor, n) for n in ("normal_", "uniform_", "fill_", "zero_")}
+    try:
+        for n in saved:
+            setattr(init, n, lambda t, *a, **k: t)
+        for n in tsaved:
+            setattr(torch.Tensor, n, lambda self, *a, **k: self)
+        model = build()
+        table = {k: list(v.shape) for k, v in model.state_dict().items()}
+        del model
+    finally:
+        for n, f in saved.items():
+            setattr(init, n, f)
+        for n, f in tsaved.items():
+            setattr(torch.Tensor, n, f)
+        torch.set_default_dtype(old)
+    return table
+
+
+def gen_reference_contract():
+    """reference_contract.json, what tests/test_reference_contract_cpu.py holds the loader to: the reference's shipped config files
+    (vibevoice/configs/qwen2.5_1.5b_64k.json, qwen2.5_7b_32k.json) as they are, and the parameter table (name -> shape) of the
+    reference's own model classes -- 1.5B / 7B from those files with the LM cut to two layers and a 1024-token vocabulary (per-layer
+    names and shapes repeat), Streaming-0.5B at full depth from vibevoice_amd.configs (no config file ships for it)."""
+    import copy
+    import json
+    from vibevoice_amd.configs import CONFIGS
+    files = {"1.5b": "qwen2.5_1.5b_64k.json", "7b": "qwen2.5_7b_32k.json"}
+    doc = {"config_files": {}, "param_tables": {}}
+    Ref = refshim.install_generate_shims()
+    from vibevoice.modular.configuration_vibevoice import VibeVoiceConfig
+    for tag, fn in files.items():
+        with open(os.path.join(refshim.REF_ROOT, "vibevoice", "configs", fn)) as f:
+            raw = json.load(f)
+        doc["config_files"][tag] = {"file": fn, "config": copy.deepcopy(raw)}
+        raw["decoder_config"]["num_hidden_layers"] = 2
+        raw["decoder_config"]["vocab_size"] = 1024
+
+        def build(raw=raw):
+            cfg = VibeVoiceConfig(**raw)
+            refshim.expose_text_config(cfg)
+            return Ref(cfg)
+        doc["param_tables"][tag] = _no_init_tables(build)
+    RefS = refshim.install_streaming_shims()
+    from vibevoice.modular.configuration_vibevoice_streaming import VibeVoiceStreamingConfig
+
+    def build_streaming():
+        cfg = VibeVoiceStreamingConfig(**copy.deepcopy(CONFIGS["0.5b-streaming"]))
+        refshim.expose_text_config(cfg)
+        return RefS(cfg)
+    doc["param_tables"]["0.5b-streaming"] = _no_init_tables(build_streaming)
+    with open(os.path.join(OUT_DIR, "reference_contract.json"), "w") as f:
+        json.dump(doc, f, sort_keys=True, separators=(",", ":"))
+        f.write("\n")
+    print("wrote reference_contract.json", {k: len(v) for k, v in doc["param_tables"].items()})
+
+
 if __name__ == "__main__":
+    if "--contract-only" in sys.argv:       # reference_contract.json alone
+        gen_reference_contract()
+        sys.exit(0)
     if "--streaming-cap-only" in sys.argv:
         gen_generate_streaming(custom=[("streaming_cap_on_text.npz", 23, 35, 191019, 0.0)])
         sys.exit(0)
@@ -709,3 +776,4 @@ if __name__ == "__main__":
     gen_lm()
     gen_generate()
     gen_generate_streaming()
+    gen_reference_contract()

@@ -473,6 +473,47 @@ def test_bench_algorithmic_bytes_match_the_survey_figures():
     assert abs(gb("7b", 20, 32000, 75) - 42.65) < 0.3
 
 
+def test_bench_plain_run_is_lean_and_dump_outputs_writes_what_generate_returned(tmp_path, monkeypatch):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` measures the headline figure only (--full adds the rest), and --dump-outputs DIR
+    writes what the timed generate() returned -- token sequences, waveforms, the last timed step's frame -- as float64 / float32 .npy
+    files, within 64 MB in all (a fixed seeded sample of the waveform columns beyond that, the same on every run)."""
+    import importlib.util
+    import types
+    spec = importlib.util.spec_from_file_location("bench_dump", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    plain = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert plain.full is False and plain.dump_outputs is None and plain.steps == 7 and plain.warmup == 2
+    assert bench.parse_args(["--full", "--dump-outputs", str(tmp_path)]).full is True
+    F = bench.FRAME_SAMPLES
+    g = torch.Generator().manual_seed(0)
+    wav = [torch.randn(1, 5 * F, generator=g).to(torch.bfloat16) for _ in range(2)]
+    seq = torch.randint(0, 1000, (2, 40), generator=g)
+    out = types.SimpleNamespace(sequences=seq, speech_outputs=wav)
+    got = bench.returned_arrays([out], last_frame=3)
+    args = types.SimpleNamespace(dump_outputs=str(tmp_path / "a"))
+    res = {"value": 1.0, "_outputs": got}
+    bench.dump_outputs(args, 0, res)
+    assert "_outputs" not in res                                     # never part of the JSON line
+    ld = lambda d, n: np.load(os.path.join(str(tmp_path / d), n + ".npy"))
+    assert ld("a", "sequences").dtype == np.float64 and np.array_equal(ld("a", "sequences"), seq.numpy().astype(np.float64))
+    sp = ld("a", "speech_outputs")
+    assert sp.dtype == np.float32 and sp.shape == (2, 5 * F)
+    assert np.array_equal(sp, torch.cat(wav).float().numpy())
+    assert np.array_equal(ld("a", "last_step_audio"), sp[:, 3 * F:4 * F])
+    assert list(ld("a", "speech_lengths")) == [5 * F, 5 * F]
+    # over the budget: a seeded sample of the columns, identical from run to run, and the whole dump within the limit
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 48 * 1024)
+    for d in ("b", "c"):
+        bench.dump_outputs(types.SimpleNamespace(dump_outputs=str(tmp_path / d)), 0, {"_outputs": got})
+    total = sum(os.path.getsize(os.path.join(str(tmp_path / "b"), f)) for f in os.listdir(str(tmp_path / "b")))
+    assert total <= 48 * 1024 + 128 * len(os.listdir(str(tmp_path / "b")))       # + the .npy headers
+    idx = ld("b", "speech_sample_index").astype(np.int64)
+    assert 0 < len(idx) < 5 * F and np.array_equal(ld("b", "speech_outputs"), sp[:, idx])
+    for n in os.listdir(str(tmp_path / "b")):
+        assert np.array_equal(ld("b", n[:-4]), ld("c", n[:-4]))
+
+
 def test_host_generate_sampling_keeps_the_reference_rng_stream(monkeypatch):
     """do_sample=True, nothing injected: tokens come from torch.multinomial, prefill and diffusion noise from torch.randn,
     all on the global generator.  Seeded like the reference run that produced generate_sampled_b1.npz, the product's host
@@ -610,7 +651,7 @@ def test_host_generate_reports_a_row_whose_valid_tokens_were_all_filtered(monkey
 
 
 def test_recorded_bench_line_keeps_the_driver_contract():
-    """profiles/r06_bench_default.json is the stdout of `python bench.py` on an MI355X: the one JSON line the driver parses.  Its fields
+    """profiles/r06_bench_default.json is the stdout of `python bench.py --full` on an MI355X: the one JSON line the driver parses.  Its fields
     are the contract (metric / unit = BASELINE.json's, whole-job value, workload named in config, `roofline` with algorithmic bytes over
     measured launch time against the 8 TB/s HBM peak, `cpu_baseline` on a bounded sample AT THE TIMED KV LENGTH), the north-star target
     configuration rides under extra.configs with its own roofline and batch parity, and the numbers must be self-consistent."""

@@ -2,7 +2,7 @@
 # memset / memcpy nodes were replaced by kernels (build/variants/libvvhip_memsetnodes.so = commit ad5f27a's sources), then with the library
 # at HEAD, then the sampler's stage probe resetting its records through a memset node (VVHIP_NAN_PROBE=2) and through a kernel (=1)
 cd ${GRAFT_REPO_ROOT:-.}; O=gpurun_out/${1:-r06z}; mkdir -p $O
-A="--no-config3"
+A="--full --no-config3"
 run() { env $2 timeout 600 python bench.py $A $3 > $O/$1.json 2> $O/$1.err; }
 chk() { python - <<PY
 import json,sys

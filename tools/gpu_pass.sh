@@ -2,7 +2,7 @@
 # One GPU pass under gpurun:  gpurun --timeout T -- 'bash tools/gpu_pass.sh <tag> <step> [<step> ...]'
 # Steps (each writes under gpurun_out/<tag>/ and prints a short digest to stdout, which is what gpurun hands back):
 #   pytest:<expr>      python -m pytest -m gpu -q <expr words, '+' for spaces>     e.g.  pytest:tests/test_gpu_kernels.py+-k+ragged%or%kv_move
-#   bench:<name>:<args>  python bench.py <args, '+' for spaces>  -> <name>.json     e.g.  bench:default:   bench:1p5b:--workload+1p5b
+#   bench:<name>:<args>  python bench.py <args, '+' for spaces>  -> <name>.json     e.g.  bench:default:--full   bench:1p5b:--full+--workload+1p5b
 #   trace:<name>:<args>  rocprofv3 --kernel-trace of bench.py <args> + tools/rocprof_summary.py -> <name>_top.txt, _kernel_stats.csv, _gaps.txt
 #   pmc:<name>:<counters>:<args>  rocprofv3 --pmc <counters> --kernel-trace of bench.py <args> (its own pass, no other trace domain)
 #   py:<script>:<args>   python <script> <args>  (stdout -> <script basename>.log)
@@ -10,7 +10,7 @@
 #   smoke              python __graft_entry__.py smoke
 R=${GRAFT_REPO_ROOT:-$(pwd)}; TAG=$1; shift
 O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R; export TMPDIR=/tmp
-Q="--no-cpu-baseline --no-eager-baseline --skip-extra"
+Q="--full --no-cpu-baseline --no-eager-baseline --skip-extra"
 for step in "$@"; do
   kind=${step%%:*}; rest=${step#*:}
   case $kind in

@@ -4,7 +4,7 @@
 # no other trace domain).  $1 = tag (r03), $2 = directory with the bench JSON lines of the same build (optional).
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/pmc; mkdir -p $O; cd $R; export TMPDIR=/tmp
 TAG=${1:-r03}; B=${2:-$R/gpurun_out/final}
-Q="--skip-extra --no-cpu-baseline --no-eager-baseline --no-roofline"
+Q="--full --skip-extra --no-cpu-baseline --no-eager-baseline --no-roofline"
 run() {   # key, bench args, bench json
   timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/p_$1 -o f -- python bench.py $Q $2 > /dev/null 2> $O/pmc_$1.err
   python tools/rocprof_summary.py $O/p_$1/f_results.db $O/${TAG}_$1_pmc_fetch --pmc > $O/${TAG}_$1_pmc_fetch_top.txt 2>&1; rm -rf $O/p_$1

@@ -4,7 +4,7 @@
 # Everything lands under gpurun_out/<tag>_final/ with the file names profiles/ uses (<tag>_*); copy what is to be judged into profiles/.
 R=${GRAFT_REPO_ROOT:-$(pwd)}; TAG=${1:-r06}; shift; PARTS=${*:-tests bench configs traces pmc dist lanes cpuwin}
 O=$R/gpurun_out/${TAG}_final; mkdir -p $O; cd $R; export TMPDIR=/tmp
-Q="--no-cpu-baseline --no-eager-baseline --skip-extra --no-parity"
+Q="--full --no-cpu-baseline --no-eager-baseline --skip-extra --no-parity"
 has() { [[ " $PARTS " == *" $1 "* ]]; }
 say() { echo "== $*"; }
 if has tests; then
@@ -12,12 +12,12 @@ if has tests; then
   timeout 300 python __graft_entry__.py smoke > $O/${TAG}_smoke.log 2>&1; tail -1 $O/${TAG}_smoke.log
 fi
 if has bench; then
-  say "bench.py (the driver's command)"; timeout 900 python bench.py > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err; head -c 400 $O/${TAG}_bench_default.json; echo
+  say "bench.py --full (every leg of the line)"; timeout 900 python bench.py --full > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err; head -c 400 $O/${TAG}_bench_default.json; echo
 fi
 if has configs; then
   say "the other configurations"
   timeout 300 python bench.py --workload 1p5b --steps 60 --warmup 10 $Q > $O/${TAG}_1p5b.json 2> $O/e1.err
-  timeout 300 python bench.py --workload streaming --steps 60 > $O/${TAG}_streaming.json 2> $O/e2.err
+  timeout 300 python bench.py --full --workload streaming --steps 60 > $O/${TAG}_streaming.json 2> $O/e2.err
   timeout 600 python bench.py --batch 8 --speakers 4 --text-tokens 10569 --steps 20 --warmup 5 $Q > $O/${TAG}_7b_4spk_batch8_32k.json 2> $O/e3.err
   timeout 300 python bench.py --workload 1p5b --batch 8 --steps 100 --warmup 10 $Q > $O/${TAG}_1p5b_batch8.json 2> $O/e4.err
   timeout 300 python bench.py --workload 1p5b --solver-steps 20 --kv-start 64000 --steps 60 --warmup 5 $Q > $O/${TAG}_1p5b_64k_n20.json 2> $O/e5.err
@@ -74,5 +74,5 @@ if has cpuwin; then
   say "CPU baseline windows (SURVEY 8d): 16 frames at three KV lengths"; timeout 1200 python bench.py --cpu-windows --cpu-frames 16 > $O/${TAG}_cpu_baseline.json 2> $O/cpuwin.err; tail -4 $O/cpuwin.err; head -c 600 $O/${TAG}_cpu_baseline.json; echo
 fi
 if has utterance; then
-  say "one whole utterance (configs[2] to the reference's length cap: ~3 minutes)"; timeout 900 python bench.py --full-utterance > $O/${TAG}_full_utterance.json 2> $O/utt.err; head -c 500 $O/${TAG}_full_utterance.json; echo
+  say "one whole utterance (configs[2] to the reference's length cap: ~3 minutes)"; timeout 900 python bench.py --full --full-utterance > $O/${TAG}_full_utterance.json 2> $O/utt.err; head -c 500 $O/${TAG}_full_utterance.json; echo
 fi

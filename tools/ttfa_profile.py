@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Where the host spends the time to first audio: bench.py's own first-audio trials (same request, same streamer consumer) with
-cProfile around the generate() call of the later trials.  Usage: python tools/ttfa_profile.py [bench.py arguments] 2> report.txt"""
+cProfile around the generate() call of the later trials.  Usage: python tools/ttfa_profile.py [bench.py arguments] 2> report.txt
+(the trials are part of a --full run: the flag is added when it is not given)"""
 import cProfile
 import io
 import os
@@ -57,4 +58,6 @@ def trials(fn, n_trials):
 
 bench.first_audio_trials = trials
 if __name__ == "__main__":
+    if "--full" not in sys.argv:
+        sys.argv.append("--full")
     bench.main()
