@@ -724,10 +724,11 @@ def test_bench_checkpoint_hook_resolves_model_directories(tmp_path, monkeypatch)
     assert bench.find_checkpoint("1.5b") == str(tmp_path) and bench.find_checkpoint("0.5b-streaming") is None
 
 
-def test_engine_sync_refuses_captured_graphs_that_hold_memset_nodes(monkeypatch):
+def test_engine_sync_refuses_memset_nodes_even_with_the_retired_escape_set(monkeypatch):
     """Round 6: a memset node of a replayed hipGraph filled with stale words on this runtime, so the library captures kernel
-    launches only and Engine.sync() -- where every generate() ends -- raises when vv_stat(ctx, 5) says otherwise.  Host logic only: the
-    engine object is built around a stub of the C library."""
+    launches only and Engine.sync() -- where every generate() ends -- raises when vv_stat(ctx, 5) says otherwise.  The A/B escape
+    VVHIP_ALLOW_FOREIGN_NODES=1 is retired: with it set, sync() still raises.  Host logic only: the engine object is built around a stub of
+    the C library."""
     import pytest
     from vibevoice_amd.engine import Engine
 
@@ -758,5 +759,6 @@ def test_engine_sync_refuses_captured_graphs_that_hold_memset_nodes(monkeypatch)
     make(0).sync()
     with pytest.raises(RuntimeError, match="memset / memcpy node"):
         make(2).sync()
-    monkeypatch.setenv("VVHIP_ALLOW_FOREIGN_NODES", "1")          # the escape for A/B runs against library builds from before round 6
-    make(2).sync()
+    monkeypatch.setenv("VVHIP_ALLOW_FOREIGN_NODES", "1")          # the retired escape for A/B runs: no longer honoured
+    with pytest.raises(RuntimeError, match="memset / memcpy node"):
+        make(2).sync()

@@ -623,33 +623,22 @@ extern "C" int vv_rope_table_launch(const float* inv_freq, void* tab, int n_pos,
 
 // Decode-step attention in one launch; requires every row to own a different cache (the new token of row r must not
 // be visible to -- or needed by -- another row of the same launch).
-// waves: 4, or 8 (the caller's choice for contexts that fit ONE split but are several 32-position blocks long: twice the
-// K/V requests in flight at once, half the dependent load -> consume iterations per wave)
-template <int D, int XS, int W>
+template <int D, int XS>
 static void attn_fused_go(dim3 grid, hipStream_t s, const float* qkv, const VVRow* rows, const void* rope_tab, void* kc, void* vc,
                           int Hq, int Hkv, int64_t cache_stride, int64_t head_stride, float scale, float* pm, float* pl, float* po, float* out, void* out_packed) {
-    constexpr size_t smem = (size_t)W * (D / 16) * 64 * 16 + (size_t)2 * W * 16 * 4 + (size_t)2 * D * 2;
-    static bool attr = false;
-    if (!attr) {
-        if (smem > 64 * 1024)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vv_attn_fused_kernel<D, XS, W>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        attr = true;
-    }
+    constexpr int W = 4;                 // waves per workgroup
+    constexpr size_t smem = (size_t)W * (D / 16) * 64 * 16 + (size_t)2 * W * 16 * 4 + (size_t)2 * D * 2;      // <= 33 KiB
     hipLaunchKernelGGL((vv_attn_fused_kernel<D, XS, W>), grid, dim3(W * 64), smem, s, qkv, rows, (const float2*)rope_tab, (__bf16*)kc, (__bf16*)vc,
                        Hq, Hkv, cache_stride, head_stride, scale, pm, pl, po, out, (unsigned char*)out_packed);
 }
 extern "C" int vv_attn_fused_launch(int D, int xs, const float* qkv, const VVRow* rows, const void* rope_tab, void* kc, void* vc,
-                                    int R, int Hq, int Hkv, int64_t cache_stride, int64_t head_stride, int S, int waves,
+                                    int R, int Hq, int Hkv, int64_t cache_stride, int64_t head_stride, int S,
                                     float* pm, float* pl, float* po, float* out, void* out_packed, hipStream_t s) {
-    if (Hq % Hkv != 0 || Hq / Hkv > 16 || (waves != 4 && waves != 8)) return -1;
+    if (Hq % Hkv != 0 || Hq / Hkv > 16) return -1;
     if (out_packed && (R > 16 || ((Hq * D) & 31))) return -1;
     const float scale = 1.0f / sqrtf((float)D);
     const dim3 grid(S, Hkv, R);
-#define VV_F(D_, XS_)                                                                                                                   \
-    do {                                                                                                                                \
-        if (waves == 8) attn_fused_go<D_, XS_, 8>(grid, s, qkv, rows, rope_tab, kc, vc, Hq, Hkv, cache_stride, head_stride, scale, pm, pl, po, out, out_packed); \
-        else attn_fused_go<D_, XS_, 4>(grid, s, qkv, rows, rope_tab, kc, vc, Hq, Hkv, cache_stride, head_stride, scale, pm, pl, po, out, out_packed);            \
-    } while (0)
+#define VV_F(D_, XS_) attn_fused_go<D_, XS_>(grid, s, qkv, rows, rope_tab, kc, vc, Hq, Hkv, cache_stride, head_stride, scale, pm, pl, po, out, out_packed)
     if (D == 128) { if (xs == 1) VV_F(128, 1); else if (xs == 2) VV_F(128, 2); else VV_F(128, 3); }
     else if (D == 64) { if (xs == 1) VV_F(64, 1); else if (xs == 2) VV_F(64, 2); else VV_F(64, 3); }
     else return -1;

@@ -26,7 +26,7 @@ int vv_rope_append_launch(int D, const float* qkv, const VVRow* rows, const floa
                           void* vc, int R, int Hq, int Hkv, int64_t cache_stride, int64_t head_stride, hipStream_t s);
 int vv_rope_table_launch(const float* inv_freq, void* tab, int n_pos, int half, hipStream_t s);
 int vv_attn_fused_launch(int D, int xs, const float* qkv, const VVRow* rows, const void* rope_tab, void* kc, void* vc,
-                         int R, int Hq, int Hkv, int64_t cache_stride, int64_t head_stride, int S, int waves,
+                         int R, int Hq, int Hkv, int64_t cache_stride, int64_t head_stride, int S,
                          float* pm, float* pl, float* po, float* out, void* out_packed, hipStream_t s);
 int vv_attn_launch(int D, int xs, const float* q, const VVRow* rows, const void* kc, const void* vc, int R, int Hq,
                    int Hkv, int64_t cache_stride, int64_t head_stride, int S, float* pm, float* pl, float* po,
@@ -89,7 +89,8 @@ int vv_gemv16p_launch(const void* W, const void* W2, const void* Xp, float* Y, v
                       int T, int N, int K, int ldy, int ld_gate, int epi, hipStream_t s);
 int vv_gemv16p_launch2(const VVGemv16p* a, int epi, int flags, hipStream_t s);
 int vv_head_tail_ok(const VVTail* a);
-int vv_head_tail_launch(const VVTail* a, int tiles_per_wg, hipStream_t s);
+int vv_head_tail_init();
+int vv_head_tail_launch(const VVTail* a, hipStream_t s);
 int vv_pack16_tiles_launch(const float* x, int ldx, int64_t stride_outer, int n_inner, int64_t stride_inner, void* xp, int64_t tile_bytes,
                            int T, int K, int n_tiles, hipStream_t s);
 int vv_ada_pack_launch(const float* cproj, const float* temb, void* xp, int rows, int n_steps, int H, hipStream_t s);
@@ -218,14 +219,10 @@ struct vv_ctx {
     void *xp = nullptr, *actp = nullptr;               // prefill (prefill.hip): activations as packed bf16 MFMA fragments
     bool tile3_ok = false, attn2_ok = false;
     VVGemmWs gws = {nullptr, nullptr, nullptr, nullptr, 0};         // K-split workspace of the long-prompt GEMM (null: never split)
-    bool fold_normdw = true;      // one-row tokenizer stages: norm + depthwise conv inside FFN1's prologue (VVHIP_FOLD_NORMDW=0: separate launch)
-    // batch decode (5..16 rows, bf16 mode): activations packed once per op into one 16-row fragment tile (gemv16p.hip)
-    void *p16_x = nullptr, *p16_act = nullptr; bool p16_ok = false;
-    // round 6: the producer's residual epilogue packs the next projection's operand (x * norm weight, un-normalised) and leaves per-tile
-    // partial sums of squares; the consumer applies 1/rms to its accumulator rows (gemv16p.hip RS / PK / SH).  VVHIP_P16_FUSE=0: the
-    // separate vv_pack16 launches of round 3.
-    void *p16_y = nullptr, *p16_shift = nullptr; float *ssq_a = nullptr, *ssq_b = nullptr; bool p16_fuse = false;
-    bool p16_head_sh = false;       // the head's layers 1.. take the two-operand (x, shift) form; off: they keep their vv_pack16 launch
+    // batch decode (5..16 rows, bf16 mode): activations as one 16-row packed fragment tile (gemv16p.hip).  The producer's residual
+    // epilogue packs the next projection's operand (x * norm weight, un-normalised) and leaves per-tile partial sums of squares; the
+    // consumer applies 1/rms to its accumulator rows (gemv16p.hip RS / PK / SH)
+    void *p16_x = nullptr, *p16_act = nullptr, *p16_y = nullptr, *p16_shift = nullptr; float *ssq_a = nullptr, *ssq_b = nullptr; bool p16_ok = false;
     size_t p16_shift_tile = 0;      // bytes of one packed [16][H] tile of the head's shift rows
     float *pm = nullptr, *pl = nullptr, *po = nullptr;
     // head
@@ -242,7 +239,7 @@ struct vv_ctx {
     float *cproj = nullptr, *mod = nullptr, *zz = nullptr, *x0p = nullptr, *xh = nullptr, *hact = nullptr, *eps = nullptr;
     // second generation of the sampler's state (headtail.hip: a solver step reads one generation and writes the other)
     float *zz2 = nullptr, *x0p2 = nullptr, *xh2 = nullptr;
-    int head_tail_tpw = 0;          // in-projection tiles per workgroup of the fused seam; 0 = off (VVHIP_HEAD_TAIL=0 / exact modes)
+    bool head_tail = false;         // the fused seam (headtail.hip); off in the exact modes or when its LDS size is refused
     float *tmp1 = nullptr, *tmp2 = nullptr;
     // connectors
     struct Conn { void *fc1, *fc2; float *b1, *b2, *norm; } ac_conn, sem_conn;
@@ -265,8 +262,8 @@ struct vv_ctx {
     // tokenizer state, graphs, staging) is the child's own, so two contexts decode concurrently on two streams over one weight copy
     vv_ctx* parent = nullptr; int n_children = 0; bool zombie = false, creating = false;
     // VVHIP_NAN_PROBE=1 (debugging): scan kernels behind the sampler's launches, inside the captured graph as well; the first stage whose
-    // output holds a non-finite value is printed after the call (nan_probe())
-    unsigned* probe_rec = nullptr; std::vector<std::string> probe_names; int probe_on = -1; int probe_calls = 0;
+    // output holds a non-finite value is printed after the call (nan_probe()).  The record buffer is allocated by vv_create
+    unsigned* probe_rec = nullptr; std::vector<std::string> probe_names; bool probe_on = false; int probe_calls = 0;
     int64_t foreign_nodes = 0;        // nodes of captured graphs that are not kernel launches (memset / memcpy nodes: none must exist, see misc.hip's copy kernels)
     int64_t capture_fallbacks = 0; char last_capture_issue[256] = "";     // stream captures that fell back to an eager run (graphed())
     std::vector<std::pair<void*, size_t>> wallocs; size_t wshare_i = 0;
@@ -317,26 +314,21 @@ static __global__ void vv_nan_probe_kernel(const float* __restrict__ p, int n, u
 }
 constexpr int PROBE_MAX = 1024;
 static void nan_probe(vv_ctx* ctx, hipStream_t st, const char* name, const void* p, size_t n) {
-    if (ctx->probe_on < 0) { const char* e = getenv("VVHIP_NAN_PROBE"); ctx->probe_on = (e && (e[0] == '1' || e[0] == '2')) ? 1 : 0; }
     if (!ctx->probe_on || !p || n == 0) return;
-    if (!ctx->probe_rec) { if (hipMalloc(&ctx->probe_rec, PROBE_MAX * 16) != hipSuccess) { ctx->probe_on = 0; return; } hipMemset(ctx->probe_rec, 0, PROBE_MAX * 16); }
     const int id = (int)ctx->probe_names.size();
     if (id >= PROBE_MAX) return;
     ctx->probe_names.push_back(name);
-    if (id == 0) {       // VVHIP_NAN_PROBE=2: reset the records with a MEMSET NODE (the form that showed the stale-pattern fills); 1: with a kernel
-        const char* e = getenv("VVHIP_NAN_PROBE");
-        if (e && e[0] == '2') (void)hipMemsetAsync(ctx->probe_rec, 0, PROBE_MAX * 16, st); else (void)vv_zero_launch(ctx->probe_rec, PROBE_MAX * 16, st);
-    }
+    if (id == 0) (void)vv_zero_launch(ctx->probe_rec, PROBE_MAX * 16, st);      // a kernel, like every fill of a captured sequence
     hipLaunchKernelGGL(vv_nan_probe_kernel, dim3(64), dim3(256), 0, st, (const float*)p, (int)n, ctx->probe_rec + 4 * id);
 }
 static void nan_probe_report(vv_ctx* ctx, hipStream_t st, const char* what) {
-    if (ctx->probe_on != 1 || !ctx->probe_rec) return;
+    if (!ctx->probe_on) return;
     std::vector<unsigned> h(PROBE_MAX * 4);
     const hipError_t e1 = hipStreamSynchronize(st);
     const hipError_t e2 = hipMemcpy(h.data(), ctx->probe_rec, PROBE_MAX * 16, hipMemcpyDeviceToHost);
     const int call = ctx->probe_calls++;
     if (e1 != hipSuccess || e2 != hipSuccess) { fprintf(stderr, "[nan_probe] %s call %d: sync %d copy %d\n", what, call, (int)e1, (int)e2); (void)hipGetLastError(); return; }
-    { const size_t ns = ctx->probe_names.size(); bool tail_dirty = false;      // the words past the last stage must still be the memset's zeros
+    { const size_t ns = ctx->probe_names.size(); bool tail_dirty = false;      // the words past the last stage must still be zeros
       for (size_t i = 4 * ns; i < (size_t)PROBE_MAX * 4; ++i) if (h[i]) { tail_dirty = true; break; }
       if (tail_dirty) fprintf(stderr, "[nan_probe] %s call %d (prof %d): record buffer %p holds words nobody wrote: %08x %08x %08x %08x | %08x %08x %08x %08x (last 4 words)\n",
                               what, call, (int)ctx->prof_on, (void*)ctx->probe_rec, h[0], h[1], h[2], h[3], h[4092], h[4093], h[4094], h[4095]); }
@@ -629,9 +621,8 @@ static int ksplit_parts(const vv_ctx* ctx, VVGemm& g, float* parts, int part_str
     const int n_tiles = (g.N + 15) / 16, k_tiles = (g.K + 31) / 32;
     // few tiles x long K only: at 7B widths (224 tiles for 256 CUs) three K columns put 672 workgroups on the chip, i.e. the SAME 87.5 %
     // balance (2.625 per CU against 3) as 224 workgroups on 256 CUs, and the consumer reads two more part tensors -- measured, not shipped
-    // (profiles/r06_down_ksplit_7b_ab.json; VVHIP_KSPLIT_MAX_TILES raises the limit for that A/B)
-    static int max_tiles = -1;
-    if (max_tiles < 0) { const char* e = getenv("VVHIP_KSPLIT_MAX_TILES"); max_tiles = e ? atoi(e) : 128; }
+    // (profiles/r06_down_ksplit_7b_ab.json)
+    constexpr int max_tiles = 128;
     if (g.T > 4 || n_tiles > max_tiles || k_tiles < 96) return 0;
     const int ks = 3;
     g.kgrid = ks; g.yparts = parts; g.part_stride = part_stride;
@@ -747,7 +738,7 @@ static int run_codec(vv_ctx* ctx, CodecNet& net, int sl, int F, float* out, hipS
         }
         float* xo = s.pp ? s.xs2 + (size_t)s.hist * s.C : x;       // pp stages: each block's norm+conv writes the other buffer
         for (auto& b : s.blocks) {
-            if (s.pp && T == 1 && ctx->fold_normdw && vv_normdw_sliced_ok(T, s.C)) {
+            if (s.pp && T == 1 && vv_normdw_sliced_ok(T, s.C)) {
                 // one-row stages (C = 2048: 8 blocks per net): the block's norm + depthwise conv + layer scale + residual run in
                 // FFN1's prologue (VV_PRO_NORMDW) -- one launch less per block on a chain where every launch is a latency link
                 VVGemm g1 = mk_gemm(b.w1, x, net.u[sl], T, 4 * s.C, s.C, s.C, 4 * s.C);
@@ -977,7 +968,6 @@ static int create_impl(const vv_config* cfg, vv_ctx* parent, vv_ctx** out) {
     vv_ctx* ctx = new vv_ctx();
     ctx->c = *cfg; ctx->err[0] = 0;
     ctx->parent = parent; ctx->creating = true;
-    { const char* e = getenv("VVHIP_FOLD_NORMDW"); if (e && e[0] == '0') ctx->fold_normdw = false; }
     vv_config& c = ctx->c;
     if (c.max_rows < 1 || c.max_rows > 16384) { delete ctx; return fail(nullptr, "max_rows must be in [1,16384]"); }
     if (c.lm_head_dim != 64 && c.lm_head_dim != 128) { delete ctx; return fail(nullptr, "head_dim must be 64 or 128"); }
@@ -1072,16 +1062,10 @@ static int create_impl(const vv_config* cfg, vv_ctx* parent, vv_ctx** out) {
         const int kx = std::max(H, Hq * D), ka = std::max(I, c.head_ffn);
         ctx->p16_x = dalloc(ctx, (size_t)vv_packed_elems(16, kx) * 2);
         ctx->p16_act = dalloc(ctx, (size_t)vv_packed_elems(16, ka + 32) * 2);
-        ctx->p16_ok = ctx->p16_x && ctx->p16_act;
-        const char* fz = getenv("VVHIP_P16_FUSE");
-        if (ctx->p16_ok && !(fz && fz[0] == '0') && (H % 16) == 0) {
-            ctx->p16_y = dalloc(ctx, (size_t)vv_packed_elems(16, kx) * 2);
-            ctx->ssq_a = (float*)dalloc(ctx, (size_t)(H / 16) * 16 * 4);
-            ctx->ssq_b = (float*)dalloc(ctx, (size_t)(H / 16) * 16 * 4);
-            ctx->p16_fuse = ctx->p16_y && ctx->ssq_a && ctx->ssq_b;
-            const char* hs = getenv("VVHIP_P16_HEAD_SH");
-            ctx->p16_head_sh = hs && hs[0] == '1';
-        }
+        ctx->p16_y = dalloc(ctx, (size_t)vv_packed_elems(16, kx) * 2);
+        ctx->ssq_a = (float*)dalloc(ctx, (size_t)(H / 16) * 16 * 4);
+        ctx->ssq_b = (float*)dalloc(ctx, (size_t)(H / 16) * 16 * 4);
+        ctx->p16_ok = ctx->p16_x && ctx->p16_act && ctx->p16_y && ctx->ssq_a && ctx->ssq_b;
     }
     ctx->rope_tab = dalloc(ctx, (size_t)c.max_ctx * (D / 2) * 8, false);
     // split-attention partials exist for decode rows and short ragged launches only (prompt chunks use the prefill kernel)
@@ -1117,10 +1101,11 @@ static int create_impl(const vv_config* cfg, vv_ctx* parent, vv_ctx** out) {
     ctx->zz2 = (float*)dalloc(ctx, (size_t)R2 * L * 4);
     ctx->x0p2 = (float*)dalloc(ctx, (size_t)R2 * L * 4);
     ctx->xh2 = (float*)dalloc(ctx, (size_t)R2 * H * 4);
-    {   // decode rows of the bf16 mode: final layer + solver update + next in-projection as one launch (headtail.hip)
-        const char* e = getenv("VVHIP_HEAD_TAIL");
-        const int tpw = e ? atoi(e) : 4;
-        ctx->head_tail_tpw = (c.xsplit == 1 && L == 64 && (H % 32) == 0 && (tpw == 1 || tpw == 2 || tpw == 4 || tpw == 8)) ? tpw : 0;
+    // decode rows of the bf16 mode: final layer + solver update + next in-projection as one launch (headtail.hip)
+    ctx->head_tail = c.xsplit == 1 && L == 64 && (H % 32) == 0 && vv_head_tail_init() == 0;
+    if (const char* e = getenv("VVHIP_NAN_PROBE"); e && e[0] == '1') {
+        ctx->probe_rec = (unsigned*)dalloc(ctx, PROBE_MAX * 16);
+        ctx->probe_on = ctx->probe_rec != nullptr;
     }
     ctx->xh_parts = (float*)dalloc(ctx, (size_t)4 * R2 * H * 4);      // two generations: a layer reads one while writing the other
     ctx->hact = (float*)dalloc(ctx, (size_t)R2 * HF * 4);
@@ -1374,7 +1359,7 @@ static int set_schedule(vv_ctx* ctx, int n_steps, const float* t, const float* c
             ctx->ada_p = (ctx->c.xsplit == 1 && (ctx->H & 7) == 0) ? dalloc(ctx, (size_t)vv_packed_elems(n_steps * 16, ctx->H) * 2, false) : nullptr;
             ctx->mod_all_bytes = (ctx->mod_all && ctx->ada_in) ? need : 0;
             dfree(ctx, ctx->p16_shift); ctx->p16_shift = nullptr;
-            if (ctx->p16_fuse) {          // the adaLN shift rows of every (solver step, layer) as packed bf16 operand tiles
+            if (ctx->p16_ok) {            // the adaLN shift rows of every (solver step, layer) as packed bf16 operand tiles
                 ctx->p16_shift_tile = (size_t)vv_packed_elems(16, ctx->H) * 2;
                 ctx->p16_shift = dalloc(ctx, (size_t)n_steps * (ctx->c.head_layers + 1) * ctx->p16_shift_tile);
             }
@@ -1416,7 +1401,7 @@ static VVGemv16p p16_args(const void* W, const void* W2, const void* Xp, float* 
 }
 
 static int lm_body(vv_ctx* ctx, hipStream_t st, int R, const float* x_in, float* hidden_out, int l0, int l1, int final_norm, bool fused_attn, bool contiguous,
-                   int attn_S, int64_t kv_positions = 0, int attn_W = 4) {
+                   int attn_S, int64_t kv_positions = 0) {
     const vv_config& c = ctx->c;
     const int H = ctx->H, D = ctx->D, Hq = ctx->Hq, Hkv = ctx->Hkv, I = ctx->I, QKV = ctx->QKV;
     VVCHK(vv_copy_launch(ctx->h, x_in, (size_t)R * H * 4, st));        // copies / fills inside captured sequences are kernels, never memcpy / memset nodes (misc.hip)
@@ -1461,7 +1446,7 @@ static int lm_body(vv_ctx* ctx, hipStream_t st, int R, const float* x_in, float*
     const bool p16 = R > 4 && R <= 16 && ctx->p16_ok && fused_attn;      // batch decode rows: packed-activation projections
     for (int l = l0; l < l1; ++l) {
         auto& L = ctx->layers[l];
-        if (p16 && ctx->p16_fuse && l > l0) {
+        if (p16 && l > l0) {
             // the previous layer's down projection left x * ln1 packed in p16_x and the rows' partial sums of squares in ssq_b
             ctx->launches += 1;
             VVGemv16p a = p16_args(L.wqkv, nullptr, ctx->p16_x, ctx->qkv, nullptr, R, QKV, H, QKV);
@@ -1486,14 +1471,14 @@ static int lm_body(vv_ctx* ctx, hipStream_t st, int R, const float* x_in, float*
                 // algorithmic bytes: every cached position of every row once, K and V (bf16) + the row's q / new k, v / output
                 const double by = (double)kv_positions * Hkv * D * 2.0 * 2.0 + (double)R * (QKV + Hq * D) * 4.0;
                 const int xs = c.xsplit; vv_ctx* cx = ctx;
-                void* opk = (p16 && ctx->p16_fuse) ? ctx->p16_y : nullptr;
+                void* opk = p16 ? ctx->p16_y : nullptr;
                 ctx->prof_other.push_back({2, by, [=](hipStream_t s) {
                     return vv_attn_fused_launch(D, xs, cx->qkv, cx->rows_dev, cx->rope_tab, kl, vl, R, Hq, Hkv, cx->cache_stride,
-                                                cx->head_stride, attn_S, attn_W, cx->pm, cx->pl, cx->po, cx->attn, opk, s); }});
+                                                cx->head_stride, attn_S, cx->pm, cx->pl, cx->po, cx->attn, opk, s); }});
             }
             // batch decode: the attention (or its merge) writes the o-projection's packed bf16 operand itself
             VVCHK(vv_attn_fused_launch(D, c.xsplit, ctx->qkv, ctx->rows_dev, ctx->rope_tab, kl, vl, R, Hq, Hkv, ctx->cache_stride,
-                                       ctx->head_stride, attn_S, attn_W, ctx->pm, ctx->pl, ctx->po, ctx->attn, (p16 && ctx->p16_fuse) ? ctx->p16_y : nullptr, st));
+                                       ctx->head_stride, attn_S, ctx->pm, ctx->pl, ctx->po, ctx->attn, p16 ? ctx->p16_y : nullptr, st));
         } else {
             // rows of one launch share caches (prefill chunks): every append must land before any row attends
             ctx->launches += 3;
@@ -1512,7 +1497,7 @@ static int lm_body(vv_ctx* ctx, hipStream_t st, int R, const float* x_in, float*
                 }
             }
         }
-        if (p16 && ctx->p16_fuse) {
+        if (p16) {
             ctx->launches += 3;
             // o-projection: h += Wo . attn; its epilogue packs h * ln2 (-> p16_x) and the rows' partial sums of squares (-> ssq_a)
             VVGemv16p ao = p16_args(L.wo, nullptr, ctx->p16_y, ctx->h, ctx->p16_x, R, H, Hq * D, H);
@@ -1527,16 +1512,6 @@ static int lm_body(vv_ctx* ctx, hipStream_t st, int R, const float* x_in, float*
                 ad.Yp = (unsigned char*)ctx->p16_x; ad.pk_nw = ctx->layers[l + 1].ln1; ad.ssq_out = ctx->ssq_b;
                 VVCHK(p16_go(ctx, st, ad, VV_EPI_RESID, 4));
             } else VVCHK(p16_go(ctx, st, ad, VV_EPI_RESID, 0));
-            continue;
-        }
-        if (p16) {
-            ctx->launches += 2;
-            VVCHK(vv_pack16_launch(ctx->attn, Hq * D, 0, nullptr, 0.f, nullptr, nullptr, 0, ctx->p16_x, R, Hq * D, st));
-            VVCHK(p16_gemv(ctx, st, L.wo, nullptr, ctx->p16_x, ctx->h, nullptr, nullptr, nullptr, R, H, Hq * D, H, 0, VV_EPI_RESID));
-            ctx->launches += 3;
-            VVCHK(vv_pack16_launch(ctx->h, H, 1, L.ln2, c.lm_eps, nullptr, nullptr, 0, ctx->p16_x, R, H, st));
-            VVCHK(p16_gemv(ctx, st, L.wg, L.wu, ctx->p16_x, nullptr, ctx->p16_act, nullptr, nullptr, R, I, H, 0, 0, VV_EPI_SWIGLU));
-            VVCHK(p16_gemv(ctx, st, L.wd, nullptr, ctx->p16_act, ctx->h, nullptr, nullptr, nullptr, R, H, I, H, 0, VV_EPI_RESID));
             continue;
         }
         VVGemm go = mk_gemm(L.wo, ctx->attn, ctx->h, R, H, Hq * D, Hq * D, H);
@@ -1615,33 +1590,25 @@ extern "C" int vv_lm_forward_range(vv_ctx* ctx, void* stream, int n_rows, const 
         if (rows[i].cache != rows[0].cache || rows[i].pos != rows[0].pos + i) contiguous = false;
     if (!contiguous && n_rows > ctx->ws_rows)
         return fail(ctx, "a launch of %d rows must be consecutive positions of one cache (decode / ragged launches take <= %d rows)", n_rows, ctx->ws_rows);
-    // decode attention geometry: one split (workgroup column) per 1024 positions of the longest row, at most attn_splits; the
-    // 8-wave form once the KV stream dominates.  Both are grid / template choices, so they are part of the graph key: a
-    // growing context re-captures the step graph every 512 positions.
+    // decode attention geometry: one split (workgroup column) per 1024 positions of the longest row, at most attn_splits.  A grid
+    // choice, so it is part of the graph key: a growing context re-captures the step graph when the split count changes.
     int max_len = 1;
     for (int i = 0; i < n_rows; ++i) max_len = std::max(max_len, rows[i].pos + 1);
     // ... and no more splits than it takes to put ~256 workgroups on the chip: with eight 32K-context utterances in flight the
     // rows themselves are the parallelism (8 splits of 4096 positions: 122 us per layer against 162 us with 32 splits).
-    // Measured and left alone: 512 / 256 positions per split (no gain once the merge is its own launch), 8-wave workgroups.
+    // Measured and left alone: 512 / 256 positions per split (no gain once the merge is its own launch), 8-wave workgroups (three
+    // times, slower than 4 waves: round 4, 8.90 vs 8.28 us per unit at 400 positions, 1.5B; 5.84 vs 5.78 at 250, 0.5B).
     constexpr int split_pos = 1024;
-    static int target_wgs = -1;            // workgroups a launch of long rows aims for (VVHIP_ATTN_TARGET_WGS: A/B of round 6)
-    if (target_wgs < 0) { const char* e = getenv("VVHIP_ATTN_TARGET_WGS"); target_wgs = e ? std::max(64, atoi(e)) : 256; }
+    constexpr int target_wgs = 256;        // workgroups a launch of long rows aims for
     int n_long = 0;
     for (int i = 0; i < n_rows; ++i) if (rows[i].pos + 1 > split_pos) ++n_long;
     const int by_wgs = std::max(1, (target_wgs + std::max(1, n_long) * ctx->Hkv - 1) / (std::max(1, n_long) * ctx->Hkv));
     const int attn_S = std::min(std::min(ctx->c.attn_splits, by_wgs), std::max(1, (max_len + split_pos - 1) / split_pos));
-    // one split, but several 32-position blocks per wave: the 8-wave form (all K/V requests of a <= 512-position context in
-    // flight at once).  Measured three times now, the third with every wave combining its share of the output tiles: slower than
-    // 4 waves (round 4: 8.90 vs 8.28 us per unit at 400 positions, 1.5B; 5.84 vs 5.78 at 250, 0.5B) -- off unless
-    // VVHIP_ATTN_W8_MIN = positions from which to use it
-    static int w8_min = -1;
-    if (w8_min < 0) { const char* e = getenv("VVHIP_ATTN_W8_MIN"); w8_min = e ? atoi(e) : 0; }
-    const int attn_W = (fused && attn_S == 1 && w8_min > 0 && max_len >= w8_min) ? 8 : 4;
     char key[160]; snprintf(key, 160, "lm:%d:%p:%p:%d:%d:%d:%d:%d", n_rows, (const void*)x_in_dev, (void*)hidden_out_dev, l0, l1, final_norm,
-                            fused ? 1 : (contiguous ? 2 : 0), (contiguous && ctx->attn2_ok) ? 0 : attn_S * 16 + attn_W);
+                            fused ? 1 : (contiguous ? 2 : 0), (contiguous && ctx->attn2_ok) ? 0 : attn_S);
     int64_t kv_positions = 0;
     for (int i = 0; i < n_rows; ++i) kv_positions += rows[i].pos + 1;
-    return graphed(ctx, key, st, [&]() { return lm_body(ctx, st, n_rows, x_in_dev, hidden_out_dev, l0, l1, final_norm, fused, contiguous, attn_S, kv_positions, attn_W); });
+    return graphed(ctx, key, st, [&]() { return lm_body(ctx, st, n_rows, x_in_dev, hidden_out_dev, l0, l1, final_norm, fused, contiguous, attn_S, kv_positions); });
 }
 
 extern "C" int vv_kv_import_at(vv_ctx* ctx, void* stream, int cache, int layer, int pos0, int n_pos, const void* k_dev, const void* v_dev, int src_dtype) {
@@ -1763,34 +1730,12 @@ static int head_eval(vv_ctx* ctx, hipStream_t st, int rows, const float* zrows, 
     const int xps = 16 * H;
     for (int l = 0; l < HL; ++l) {
         const float* base = mod + (size_t)l * 3 * H;
-        if (rows > 4 && rows <= 16 && ctx->p16_ok && (HF % 32) == 0 && ctx->p16_fuse && sh_tiles && coef && ctx->p16_head_sh) {
-            // batch rows, round 6: layer 0 packs its operand (the in-projection is not a packed-activation launch); every later layer
-            // finds x * w * (1 + scale) packed by the previous down projection's epilogue, the rows' sums of squares beside it, and the
-            // shift rows of this (step, layer) packed once per frame: y = rs * W.xm + W.shift
-            if (l == 0) {
-                ctx->launches += 1;
-                VVCHK(vv_pack16_launch(xh, H, 2, ctx->hl[l].norm, c.head_eps, base + H, base, MODW, ctx->p16_x, rows, H, st));
-                VVCHK(p16_gemv(ctx, st, ctx->hl[l].wg, ctx->hl[l].wu, ctx->p16_x, nullptr, ctx->p16_act, nullptr, nullptr, rows, HF, H, 0, 0, VV_EPI_SWIGLU));
-            } else {
-                VVGemv16p ag = p16_args(ctx->hl[l].wg, ctx->hl[l].wu, ctx->p16_x, nullptr, ctx->p16_act, rows, HF, H, 0);
-                ag.ssq_in = ctx->ssq_a; ag.ssq_tiles = H / 16; ag.eps = c.head_eps;
-                ag.Xs = (const u32x4*)(sh_tiles + (size_t)l * ctx->p16_shift_tile);
-                VVCHK(p16_go(ctx, st, ag, VV_EPI_SWIGLU, 3));
-            }
-            ctx->launches += 2;
-            VVGemv16p ad = p16_args(ctx->hl[l].wd, nullptr, ctx->p16_act, xh, ctx->p16_x, rows, H, HF, H);
-            ad.gate = base + 2 * H; ad.ld_gate = MODW; ad.ssq_out = ctx->ssq_a;
-            ad.pk_nw = (l + 1 < HL) ? ctx->hl[l + 1].norm : nullptr;
-            ad.pk_sc = mod + (size_t)(l + 1) * 3 * H + H; ad.ld_pk = MODW;          // layer l + 1's scale rows (l + 1 == HL: the final layer's)
-            VVCHK(p16_go(ctx, st, ad, VV_EPI_GATED_RESID, 4));
-            continue;
-        }
         if (rows > 4 && rows <= 16 && ctx->p16_ok && (HF % 32) == 0) {
             // batch rows: normalise + modulate + pack ONCE, then both projections stream weights against packed fragments
             ctx->launches += 3;
             VVCHK(vv_pack16_launch(xh, H, 2, ctx->hl[l].norm, c.head_eps, base + H, base, MODW, ctx->p16_x, rows, H, st));
             VVCHK(p16_gemv(ctx, st, ctx->hl[l].wg, ctx->hl[l].wu, ctx->p16_x, nullptr, ctx->p16_act, nullptr, nullptr, rows, HF, H, 0, 0, VV_EPI_SWIGLU));
-            if (l + 1 == HL && ctx->p16_fuse && sh_tiles && coef) {
+            if (l + 1 == HL && sh_tiles && coef) {
                 // the last layer's down projection leaves the FINAL layer's operand (x * (1 + scale), un-normalised) packed and the rows' sums of squares
                 VVGemv16p ad = p16_args(ctx->hl[l].wd, nullptr, ctx->p16_act, xh, ctx->p16_x, rows, H, HF, H);
                 ad.gate = base + 2 * H; ad.ld_gate = MODW; ad.ssq_out = ctx->ssq_a;
@@ -1811,15 +1756,15 @@ static int head_eval(vv_ctx* ctx, hipStream_t st, int rows, const float* zrows, 
         g2.epi = VV_EPI_GATED_RESID; g2.gate = base + 2 * H; g2.ld_gate = MODW; g2.nt = 1;
         g2.ya = cur; g2.n_ya = xp; g2.part_stride = xps;
         xp = ksplit_parts(ctx, g2, nxt, xps);
-        if (ctx->probe_on == 1) { char nm[64]; snprintf(nm, 64, "layer %d hact (parts in %d)", l, g1.n_xa); nan_probe(ctx, st, nm, ctx->hact, (size_t)rows * HF); }
+        if (ctx->probe_on) { char nm[64]; snprintf(nm, 64, "layer %d hact (parts in %d)", l, g1.n_xa); nan_probe(ctx, st, nm, ctx->hact, (size_t)rows * HF); }
         GEMM(g2);
-        if (ctx->probe_on == 1) {
+        if (ctx->probe_on) {
             char nm[64]; snprintf(nm, 64, "layer %d xh", l); nan_probe(ctx, st, nm, xh, (size_t)rows * H);
             for (int q = 0; q < xp; ++q) { snprintf(nm, 64, "layer %d part %d", l, q); nan_probe(ctx, st, nm, nxt + (size_t)q * xps, (size_t)rows * H); }
         }
     }
     const float* fb = mod + (size_t)HL * 3 * H;
-    if (rows > 4 && rows <= 16 && ctx->p16_ok && (HF % 32) == 0 && ctx->p16_fuse && sh_tiles && coef && HL > 0) {
+    if (rows > 4 && rows <= 16 && ctx->p16_ok && (HF % 32) == 0 && sh_tiles && coef && HL > 0) {
         // the sampler's final layer over the packed operand the last down projection left (4 workgroups that only stream: the 16-row
         // vv_gemv form staged 16 x H modulated rows in each of its 4 workgroups, 21 us), CFG + DPM-Solver++ update in the epilogue
         ctx->launches += 1;
@@ -1830,7 +1775,7 @@ static int head_eval(vv_ctx* ctx, hipStream_t st, int rows, const float* zrows, 
         VVCHK(p16_go(ctx, st, af, VV_EPI_CFG_DPM, 3));
         return 0;
     }
-    if (seam && coef && rows == 2 && ctx->head_tail_tpw > 0) {
+    if (seam && coef && rows == 2 && ctx->head_tail) {
         VVTail t{};
         t.Wout = (const u32x4*)ctx->h_out; t.Win = (const u32x4*)ctx->h_in; t.bin = nullptr;
         t.X = xh; t.xa = ctx->xh_parts + (size_t)(HL & 1) * 2 * xps; t.n_xa = xp; t.part_stride = xps;
@@ -1842,11 +1787,11 @@ static int head_eval(vv_ctx* ctx, hipStream_t st, int rows, const float* zrows, 
         if (vv_head_tail_ok(&t)) {
             ctx->launches++;
             if (ctx->prof_on) {
-                const VVTail tc = t; const int tpw = ctx->head_tail_tpw;
+                const VVTail tc = t;
                 ctx->prof_other.push_back({3, (double)vv_packed_elems(L, H) * 2.0 + (double)vv_packed_elems(H, L) * 2.0 + (double)rows * H * 8.0,
-                                           [=](hipStream_t s2) { return vv_head_tail_launch(&tc, tpw, s2); }});
+                                           [=](hipStream_t s2) { return vv_head_tail_launch(&tc, s2); }});
             }
-            VVCHK(vv_head_tail_launch(&t, ctx->head_tail_tpw, st));
+            VVCHK(vv_head_tail_launch(&t, st));
             return 1;          // the next step's in-projection is done (generation gen ^ 1)
         }
     }
@@ -1901,10 +1846,10 @@ static int sample_body(vv_ctx* ctx, hipStream_t st, int n, const float* cond, co
     }
     nan_probe(ctx, st, "cproj", ctx->cproj, (size_t)rows * H);
     if (batch_ada) nan_probe(ctx, st, "mod_all", ctx->mod_all, (size_t)rows * ctx->n_steps * MODW);
-    const bool sh_ok = batch_ada && rows > 4 && rows <= 16 && ctx->p16_fuse && ctx->p16_shift;
+    const bool sh_ok = batch_ada && rows > 4 && rows <= 16 && ctx->p16_shift;
     if (sh_ok) {
         // the shift rows of every (solver step, layer) -- and the final layer's -- as packed bf16 tiles, one launch per frame:
-        // tile (i, l) = rows [i * rows, (i + 1) * rows) of mod_all, columns [l * 3H, l * 3H + H)
+        // tile (i, l) = rows [i * rows, (i + 1) * rows) of mod_all, columns [l * 3H, l * 3H + H).  Only the final layer's tile (l == HL) is read
         ctx->launches++;
         VVCHK(vv_pack16_tiles_launch(ctx->mod_all, MODW, (int64_t)rows * MODW, ctx->c.head_layers + 1, (int64_t)3 * H, ctx->p16_shift,
                                      (int64_t)ctx->p16_shift_tile, rows, H, ctx->n_steps * (ctx->c.head_layers + 1), st));
@@ -1916,11 +1861,11 @@ static int sample_body(vv_ctx* ctx, hipStream_t st, int n, const float* cond, co
         const unsigned char* sht = sh_ok ? (const unsigned char*)ctx->p16_shift + (size_t)i * (ctx->c.head_layers + 1) * ctx->p16_shift_tile : nullptr;
         // decode rows, bf16 mode: every step but the last ends with the fused seam (final layer + CFG + solver update + the next step's
         // in-projection, headtail.hip), which leaves the next step's state in the other generation of (xh, zz, x0p)
-        const bool seam = (i + 1 < ctx->n_steps) && rows == 2 && ctx->head_tail_tpw > 0;
+        const bool seam = (i + 1 < ctx->n_steps) && rows == 2 && ctx->head_tail;
         const int hr = head_eval(ctx, st, rows, gen ? ctx->zz2 : ctx->zz, ctx->temb + (size_t)i * H, ctx->eps, ctx->coef + i * 6, cfg, mod_i, sn, sht,
                                  gen, have_x, seam);
         if (hr < 0) return -1;
-        if (ctx->probe_on == 1) {
+        if (ctx->probe_on) {
             char nm[64];
             snprintf(nm, 64, "step %d z%s", i, hr == 1 ? " (seam, next gen)" : ""); nan_probe(ctx, st, nm, (gen ^ (hr == 1)) ? ctx->zz2 : ctx->zz, (size_t)rows * L);
             snprintf(nm, 64, "step %d x0p", i); nan_probe(ctx, st, nm, (gen ^ (hr == 1)) ? ctx->x0p2 : ctx->x0p, (size_t)n * L);

@@ -73,11 +73,8 @@ constexpr int U = 8;       // k-steps per batch (256 k = one float4 per lane per
 
 // adaLN-modulated norm, decode rows (MR <= 4): the shift rows ride in the SAME B tile as the modulated activation rows, as columns
 // MR..2MR-1 of the MFMA's 16 (a decode launch uses 2..4 of them) -- one operand, one accumulator set, half the ds_reads and MFMAs
-// per k-step; the epilogue adds column r + MR to column r with one DPP row shift.  -DVV_MOD_FOLD=0 restores the two-operand form
-// (A/B: profiles/r06_mod_fold_ab.json); the 16-row batch form has no spare columns and keeps two operands.
-#ifndef VV_MOD_FOLD
-#define VV_MOD_FOLD 1
-#endif
+// per k-step; the epilogue adds column r + MR to column r with one DPP row shift (A/B against the two-operand form:
+// profiles/r06_mod_fold_ab.json); the 16-row batch form has no spare columns and keeps two operands.
 
 // PRO / EPI are compile-time: a launch executes only the code of its own prologue/epilogue (the runtime-
 // switched version spent a third of a small launch fetching and skipping code it never needed).
@@ -103,7 +100,7 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemv_kernel(const u32x4* __restri
     // LDS: [wave][XS][U][4][MR] x 16 B staging tiles, then [wave][NM][64] f32x4 partials, then [wave][MR] ssq
     // adaLN-modulated norm: y = rs * W.(x*nw*(1+scale)) + W.shift -- two B operands and two accumulator sets, so the
     // 1/rms of the row is only needed in the epilogue (as for plain RMSNorm) and no pre-pass over x exists
-    constexpr bool FOLD = VV_MOD_FOLD && (PRO == VV_PRO_RMS_MOD) && MR <= 4;
+    constexpr bool FOLD = (PRO == VV_PRO_RMS_MOD) && MR <= 4;
     constexpr int NOP = (PRO == VV_PRO_RMS_MOD && !FOLD) ? 2 : 1;
     constexpr int MRS = FOLD ? 2 * MR : MR;         // staged B columns: activation rows, then (folded form) their shift rows
     // one (k-step, k-group) plane of the staging tile = MR rows x 16 B; the 16-row form pads it by 16 B so that the planes

@@ -34,7 +34,7 @@ __device__ __forceinline__ float p16_wave_sum(float v) {
     return v;
 }
 
-// MODE 0: plain conversion;  MODE 1: RMSNorm with weight nw;  MODE 2: adaLN-modulated RMSNorm (scale / shift rows, stride ld_mod).
+// MODE 1: RMSNorm with weight nw;  MODE 2: adaLN-modulated RMSNorm (scale / shift rows, stride ld_mod).
 // grid = 16 * ceil(T / 16) workgroups (rows >= T are written as zeros), 256 threads; K % 32 == 0, K <= 8192.
 template <int MODE>
 __global__ __launch_bounds__(256) void vv_pack16_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ nw, float eps,
@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256) void vv_pack16_kernel(const float* __restrict_
     ssq = p16_wave_sum(ssq);
     if (lane == 0) red[wave] = ssq;
     __syncthreads();
-    const float rs = (MODE == 0) ? 1.0f : rsqrtf(((red[0] + red[1]) + (red[2] + red[3])) / (float)K + eps);
+    const float rs = rsqrtf(((red[0] + red[1]) + (red[2] + red[3])) / (float)K + eps);
 #pragma unroll
     for (int i = 0; i < MAXQ; ++i) {
         const int q = tid + i * 256;
@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256) void vv_pack16_kernel(const float* __restrict_
         const int k = q * 4;
         float o[4] = {0.f, 0.f, 0.f, 0.f};
         if (t < T) {
-            const float4 w4 = (MODE != 0 && nw) ? *reinterpret_cast<const float4*>(nw + k) : float4{1.f, 1.f, 1.f, 1.f};
+            const float4 w4 = nw ? *reinterpret_cast<const float4*>(nw + k) : float4{1.f, 1.f, 1.f, 1.f};
             o[0] = v[i].x * rs * w4.x; o[1] = v[i].y * rs * w4.y; o[2] = v[i].z * rs * w4.z; o[3] = v[i].w * rs * w4.w;
             if constexpr (MODE == 2) {
                 const float4 s4 = *reinterpret_cast<const float4*>(sc + (int64_t)t * ld_mod + k);
@@ -327,15 +327,14 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemv16p_kernel(const VVGemv16p a)
 
 extern "C" {
 
-// rows [T][K] fp32 (T <= 16) -> one packed 16-row tile.  mode 0: plain conversion; 1: RMSNorm (nw may be null: no affine);
-// 2: adaLN-modulated RMSNorm (sc / sh rows)
+// rows [T][K] fp32 (T <= 16) -> one packed 16-row tile.  mode 1: RMSNorm (nw may be null: no affine); 2: adaLN-modulated RMSNorm
+// (sc / sh rows)
 int vv_pack16_launch(const float* x, int ldx, int mode, const float* nw, float eps, const float* sc, const float* sh, int ld_mod,
                      void* xp, int T, int K, hipStream_t s) {
-    if (T < 1 || T > 16 || (K & 31) || K > 8192 || (ldx & 3) || (((uintptr_t)x) & 15) || mode < 0 || mode > 2 ||
+    if (T < 1 || T > 16 || (K & 31) || K > 8192 || (ldx & 3) || (((uintptr_t)x) & 15) || mode < 1 || mode > 2 ||
         (mode == 2 && ((ld_mod & 3) || !sc || !sh))) return -1;
     if (mode == 2) hipLaunchKernelGGL((vv_pack16_kernel<2>), dim3(16), dim3(256), 0, s, x, ldx, nw, eps, sc, sh, ld_mod, (unsigned char*)xp, T, K);
-    else if (mode == 1) hipLaunchKernelGGL((vv_pack16_kernel<1>), dim3(16), dim3(256), 0, s, x, ldx, nw, eps, sc, sh, ld_mod, (unsigned char*)xp, T, K);
-    else hipLaunchKernelGGL((vv_pack16_kernel<0>), dim3(16), dim3(256), 0, s, x, ldx, nw, eps, sc, sh, ld_mod, (unsigned char*)xp, T, K);
+    else hipLaunchKernelGGL((vv_pack16_kernel<1>), dim3(16), dim3(256), 0, s, x, ldx, nw, eps, sc, sh, ld_mod, (unsigned char*)xp, T, K);
     return vv_launch_rc(0);
 }
 

@@ -246,27 +246,23 @@ extern "C" int vv_head_tail_ok(const VVTail* a) {
     return 1;
 }
 
-// tiles_per_wg: in-projection feature tiles per workgroup (1, 2, 4 or 8): fewer workgroups = fewer redundant passes over W_out
-extern "C" int vv_head_tail_launch(const VVTail* ap, int tiles_per_wg, hipStream_t s) {
+// 4 in-projection feature tiles per workgroup (measured against 1, 2 and 8: fewer workgroups = fewer redundant passes over W_out)
+constexpr int HT_TPW = 4;
+constexpr size_t HT_SMEM = 8 * KMAX * 4 * 128 + 2 * 1024 + 8 * 4 * sizeof(float);
+
+// the kernel's dynamic LDS is above the 64 KiB default: 0 once it is granted, -1 if refused (the caller then keeps the two launches)
+extern "C" int vv_head_tail_init() {
+    for (const void* k : {reinterpret_cast<const void*>(&vv_head_tail_kernel<HT_TPW, 1, 2>), reinterpret_cast<const void*>(&vv_head_tail_kernel<HT_TPW, 0, 2>)})
+        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HT_SMEM) != hipSuccess) { (void)hipGetLastError(); return -1; }
+    return 0;
+}
+
+// vv_head_tail_init() must have succeeded
+extern "C" int vv_head_tail_launch(const VVTail* ap, hipStream_t s) {
     if (!vv_head_tail_ok(ap)) return -3;
     const VVTail& a = *ap;
-    const int n_tiles = a.H / 16;
-    constexpr size_t smem = 8 * KMAX * 4 * 128 + 2 * 1024 + 8 * 4 * sizeof(float);
-#define VV_T(TPW_)                                                                                                   \
-    do { const dim3 grid((n_tiles + TPW_ - 1) / TPW_);                                                                \
-         static bool attr = false;                                                                                    \
-         if (!attr) {                                                                                                 \
-             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vv_head_tail_kernel<TPW_, 1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
-             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vv_head_tail_kernel<TPW_, 0, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
-             attr = true;                                                                                             \
-         }                                                                                                            \
-         if (a.n_xa) hipLaunchKernelGGL((vv_head_tail_kernel<TPW_, 1, 2>), grid, dim3(512), smem, s, a);              \
-         else hipLaunchKernelGGL((vv_head_tail_kernel<TPW_, 0, 2>), grid, dim3(512), smem, s, a);                     \
-         return vv_launch_rc(0); } while (0)
-    if (tiles_per_wg == 1) VV_T(1);
-    if (tiles_per_wg == 2) VV_T(2);
-    if (tiles_per_wg == 4) VV_T(4);
-    if (tiles_per_wg == 8) VV_T(8);
-#undef VV_T
-    return -3;
+    const dim3 grid((a.H / 16 + HT_TPW - 1) / HT_TPW);
+    if (a.n_xa) hipLaunchKernelGGL((vv_head_tail_kernel<HT_TPW, 1, 2>), grid, dim3(512), HT_SMEM, s, a);
+    else hipLaunchKernelGGL((vv_head_tail_kernel<HT_TPW, 0, 2>), grid, dim3(512), HT_SMEM, s, a);
+    return vv_launch_rc(0);
 }

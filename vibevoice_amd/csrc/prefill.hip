@@ -23,7 +23,6 @@
 //                           ring; 8 waves = 4 units x 2 row halves in anti-phase (matrix segment / softmax segment), one
 //                           lazy-rescaled softmax step per stage, row sums through the matrix pipe; the result leaves as the
 //                           o-projection's packed operand.
-#include <cstdlib>
 #include <cstring>
 #include <type_traits>
 #include "vv_common.h"
@@ -1139,22 +1138,18 @@ int vv_gemm3_launch(const void* W, const void* W2, const void* Xp, float* Y, voi
     // Short prompts (a 330-token request: 36 tiles for the o / down projections of a 1.5B layer, 48 for QKV): a few dozen workgroups
     // stream the whole matrix -- 170 us for the 27.5 MB down projection.  K is split over grid.y (each part >= 4 of the 64-wide
     // steps) until ~192 workgroups pull on HBM; the parts go to dense fp32 tensors and vv_g3_reduce_kernel sums them in part order
-    // with the bias / residual: deterministic, no hand-off inside a launch.  VVHIP_G3_KSPLIT=0 switches it off.
+    // with the bias / residual: deterministic, no hand-off inside a launch.
     int ks = 1;
     if (epi != VV_EPI_SWIGLU && ws && ws->g3_partials && grid.x < 128 && (N & 3) == 0 && Y) {
-        static int on = -1;
-        if (on < 0) { const char* e = getenv("VVHIP_G3_KSPLIT"); on = (e && e[0] == '0') ? 0 : 1; }
         const int n_steps = (((K + 31) >> 5) + 1) >> 1;
-        ks = on ? (int)((192 + grid.x - 1) / grid.x) : 1;
+        ks = (int)((192 + grid.x - 1) / grid.x);
         if (ks > 8) ks = 8;
         if (ks > n_steps / 4) ks = n_steps / 4;
         if (ks < 2 || (size_t)ks * T * N * 4 > ws->g3_bytes) ks = 1;
     }
     const float* bias_r = bias; const int resid_r = (epi == VV_EPI_RESID) ? 1 : 0;
     if (ks > 1) { grid.y = (unsigned)ks; a.ws = ws->g3_partials; a.split = ks; }
-    static int db_on = -1;
-    if (db_on < 0) { const char* e = getenv("VVHIP_G3_DB"); db_on = (e && e[0] == '0') ? 0 : 1; }
-    const bool db = db_on && tr == 4 && (int64_t)grid.x * (ks > 1 ? ks : 1) <= 512;      // at most ~2 workgroups per CU: nothing else hides a stage's latency
+    const bool db = tr == 4 && (int64_t)grid.x * (ks > 1 ? ks : 1) <= 512;      // at most ~2 workgroups per CU: nothing else hides a stage's latency
 #define VV_G3(E_) do { if (tr == 8) hipLaunchKernelGGL((vv_gemm3_kernel<E_, 8>), grid, dim3(256), 0, s, a); \
                        else if (db) hipLaunchKernelGGL((vv_gemm3_kernel<E_, 4, 1>), grid, dim3(256), 0, s, a); \
                        else hipLaunchKernelGGL((vv_gemm3_kernel<E_, 4>), grid, dim3(256), 0, s, a); } while (0)

@@ -12,7 +12,6 @@
 //     one per row tile: 4x the arithmetic per weight byte of the GEMV, 4x fewer weight passes per prompt;
 //   * RMSNorm: sum(x^2) per row is gathered while staging and applied to the accumulators in the epilogue.
 // Prologues NONE / RMS; epilogues STORE / BIAS / BIAS_GELU / SWIGLU / RESID (what the LM and the tokenizer stages issue).
-#include <cstdlib>
 #include "vv_common.h"
 
 namespace {
@@ -246,12 +245,10 @@ extern "C" int vv_tile_ok(const VVGemm* a, int xs) {
     {   // enough workgroups to occupy the chip; smaller problems (tokenizer stages at decode) stay on the row-tiled GEMV
         const int per_wg = 4 * (a->epi == VV_EPI_SWIGLU ? 1 : 2);
         const int64_t wgs = (int64_t)(((a->N + 15) / 16 + per_wg - 1) / per_wg) * ((a->T + BM - 1) / BM);
-        static int min_sl = -1;
-        if (min_sl < 0) { const char* e = getenv("VVHIP_TILE_MIN_WGS_SLOTS"); min_sl = e ? atoi(e) : 40; }
         // slot-batched tokenizer stages (several utterances' frames in one launch): the 16-row GEMV form re-normalises and
         // re-stages its 16 rows in every one of its (feature tiles x row tiles) workgroups -- 87 us for the C = 256 FFN1 of eight
         // utterances (1600 rows x 1024 features x 256: 0.8 GFLOP) -- so the tile form takes over much earlier there
-        const int min_wgs = a->sl_n > 0 ? min_sl : 48;
+        const int min_wgs = a->sl_n > 0 ? 40 : 48;
         if (wgs < min_wgs) return 0;
     }
     if (a->sl_n > 0) {
