@@ -241,7 +241,10 @@ int vv_profile_replay_family(vv_ctx* ctx, void* stream, int family, int reps, in
  * timings of the last profile window; 4: stream captures that did not close cleanly and were run eagerly instead (seen when
  * several host threads drive several contexts: another thread's activity can invalidate a capture; the result is unaffected);
  * 5: nodes of the captured graphs that are not kernel launches -- 0 by construction: copies and fills inside captured sequences are
- * kernels of the library, because a memset node of a replayed graph was seen to fill with stale words */
+ * kernels of the library, because a memset node of a replayed graph was seen to fill with stale words;
+ * 6: head-tail seam launches (headtail.hip: final layer + CFG + solver update + the next step's in-projection in one launch) that
+ * the last recorded sampler body issued -- n_steps - 1 for one utterance in bf16 mode, 0 where the two-launch form ran; a graph
+ * replay keeps the count of its capture */
 int64_t vv_stat(vv_ctx* ctx, int what);
 
 #pragma GCC visibility pop

@@ -54,7 +54,7 @@ def build_small(lmcfg=None, xsplit=3, use_graph=False, n_slots=2, max_ctx=512, t
     ac_conn = synth.connector_weights(64, H, 4)
     sem_conn = synth.connector_weights(128, H, 8)
     ecfg = EngineConfig(lm_hidden=H, lm_layers=lmcfg.layers, lm_heads=lmcfg.heads, lm_kv_heads=lmcfg.kv_heads,
-                        lm_inter=lmcfg.inter, lm_vocab=lmcfg.vocab, lm_eps=lmcfg.eps, rope_theta=lmcfg.theta,
+                        lm_head_dim=lmcfg.head_dim, lm_inter=lmcfg.inter, lm_vocab=lmcfg.vocab, lm_eps=lmcfg.eps, rope_theta=lmcfg.theta,
                         head_layers=hc.layers, head_ffn_ratio=hc.ffn_ratio, head_eps=hc.eps,
                         n_filters=cc.n_filters, ratios=cc.ratios, enc_depths=cc.enc_depths, sem_dim=128,
                         codec_eps=cc.eps, n_slots=n_slots, max_ctx=max_ctx, xsplit=xsplit, use_graph=use_graph, max_rows=max_rows,

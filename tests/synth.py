@@ -14,7 +14,7 @@ re-randomised -- otherwise outputs are identically 0 and tests are vacuous
 (SURVEY.md 7(f)).
 """
 from dataclasses import dataclass, field
-from typing import List
+from typing import List, Optional
 
 import numpy as np
 import torch
@@ -178,10 +178,11 @@ class LMCfg:
     theta: float = 1e6
     eps: float = 1e-6
     max_pos: int = 4096
+    head_dim_override: Optional[int] = None     # explicit head dim (heads * head_dim != hidden); None = hidden // heads
 
     @property
     def head_dim(self):
-        return self.hidden // self.heads
+        return self.head_dim_override or self.hidden // self.heads
 
 
 def lm_weights(cfg: LMCfg, seed=5):

@@ -569,6 +569,105 @@ def test_prefill_attention_ignores_cache_slots_past_the_prompt():
         eng.close()
 
 
+def _fill_past(eng, cfg, cache, pos0, poison):
+    """cache positions [pos0, max_ctx) of every layer: NaN with every third position Inf (poison), or zeros"""
+    n, kvh, hd = eng.max_ctx - pos0, cfg.kv_heads, cfg.head_dim
+    if poison:
+        bad = torch.full((kvh, n, hd), float("nan"), device=eng.device)
+        bad[:, ::3] = float("inf")
+    else:
+        bad = torch.zeros((kvh, n, hd), device=eng.device)
+    for layer in range(cfg.layers):
+        eng.kv_import_at(cache, layer, pos0, bad, bad)
+
+
+def _clean_and_dirty(run):
+    clean, dirty = run(False), run(True)
+    return bool(torch.isfinite(dirty).all()) and torch.equal(clean, dirty)
+
+
+@pytest.mark.parametrize("xs", [1, 3])
+def test_short_prompt_spans_ignore_cache_slots_past_their_end(xs):
+    """Prompt spans shorter than the 64-position stage of the prefill attention: 8..63 rows of one cache take vv_attn_prefill4 in the
+    bf16 mode (through the per-layer GEMMs, not the packed-activation pass), whose V tail past the span must be zeroed as well;
+    2..7 rows take the split + merge pair, as do all of them in the exact mode.  Then a chunked prompt: 128 rows, and a trailing
+    span of 20 rows at position 128 (the last chunk of a longer prompt).  NaN / Inf in every cache slot past the prompt, every
+    layer: the hidden states must be the clean run's, bit for bit."""
+    s = build_small(LM_CASES["gqa"], xsplit=xs, max_ctx=512, max_rows=256)
+    eng = s.eng
+    try:
+        cfg = s.lmcfg
+        H = cfg.hidden
+        g = synth.Gen(709)
+        bad = []
+        for L0 in (2, 5, 7, 8, 20, 48, 63):
+            x = dev(g.normal((L0, H), 1.0, mat=False), eng)
+
+            def run(poison):
+                hid = eng.new(L0, H)
+                with torch.cuda.stream(eng.stream):
+                    _fill_past(eng, cfg, 0, L0, poison)
+                    eng.lm_forward_span(0, 0, L0, x, hid)
+                eng.sync()
+                return hid.clone()
+            if not _clean_and_dirty(run):
+                bad.append(L0)
+        x = dev(g.normal((148, H), 1.0, mat=False), eng)
+
+        def chunked(poison):
+            hid = eng.new(148, H)
+            with torch.cuda.stream(eng.stream):
+                _fill_past(eng, cfg, 0, 128, poison)
+                eng.lm_forward_span(0, 0, 128, x[:128], hid[:128])
+                eng.lm_forward_span(0, 128, 20, x[128:], hid[128:])
+            eng.sync()
+            return hid.clone()
+        if not _clean_and_dirty(chunked):
+            bad.append("128 + 20")
+        assert not bad, f"prompt lengths whose hidden states the stale cache slots reached: {bad}"
+    finally:
+        eng.close()
+
+
+@pytest.mark.parametrize("xs", [1, 3])
+@pytest.mark.parametrize("case", ["1", "6", "16", "long"])
+def test_decode_batches_ignore_cache_slots_past_each_row(xs, case):
+    """Decode rows over caches of different lengths in one launch: a single row, 6 and 16 rows (the bf16 mode's packed-activation
+    batch forms, vv_gemv16p, with the attention writing the packed o-projection operand) and one row at position 1100 (two
+    flash-decoding splits: the merge kernel runs).  Every cache holds random K/V up to its own length and NaN / Inf (or, for the
+    clean run, zeros) past it in every layer; three decode steps must give the clean run's hidden states bit for bit."""
+    s = build_small(LM_CASES["gqa"], xsplit=xs, max_ctx=1280, max_rows=16, n_slots=8)
+    eng = s.eng
+    try:
+        cfg = s.lmcfg
+        H, kvh, hd = cfg.hidden, cfg.kv_heads, cfg.head_dim
+        lens = {"1": [37], "6": [1, 31, 32, 33, 64, 90], "16": [1, 2, 7, 16, 31, 32, 33, 40, 63, 64, 65, 70, 95, 96, 97, 127],
+                "long": [1100]}[case]
+        gk = torch.Generator().manual_seed(710 + len(lens))
+        kv = [tuple(torch.randn(cfg.layers, kvh, n, hd, generator=gk).to(torch.bfloat16) for _ in "kv") for n in lens]
+        g = synth.Gen(711)
+        x = dev(g.normal((3, len(lens), H), 1.0, mat=False), eng)
+
+        def run(poison):
+            outs = []
+            with torch.cuda.stream(eng.stream):
+                for c, n in enumerate(lens):
+                    for layer in range(cfg.layers):
+                        eng.kv_import_at(c, layer, 0, kv[c][0][layer].to(eng.device), kv[c][1][layer].to(eng.device))
+                    _fill_past(eng, cfg, c, n, poison)
+                for step in range(3):
+                    hid = eng.new(len(lens), H)
+                    eng.lm_forward([(c, n + step) for c, n in enumerate(lens)], x[step], hid)
+                    outs.append(hid)
+            eng.sync()
+            return torch.cat(outs)
+        clean, dirty = run(False), run(True)
+        assert bool(torch.isfinite(dirty).all())
+        assert torch.equal(clean, dirty)
+    finally:
+        eng.close()
+
+
 LM_CASES = {"d64": synth.LMCfg(), "d128": synth.LMCfg(hidden=256, heads=2, kv_heads=1, inter=384),
             "gqa": synth.LMCfg(hidden=256, heads=4, kv_heads=2, inter=320, layers=3)}
 
@@ -671,9 +770,9 @@ def test_bf16_activation_mode_tolerance():
 @pytest.mark.parametrize("n", [1, 3, 8])
 def test_bf16_mode_batched_sampler_rows(n):
     """8 utterances diffusing together = 16 head rows: the 16-row adaLN / gated-residual / CFG+DPM GEMV forms (bench mode
-    only) against the oracle sampler, SURVEY 8d tolerance for bf16 activations.  n = 1 (two rows): the decode forms of the bf16 mode,
-    i.e. the folded shift operand and the solver-step seam launch (headtail.hip) over its double-buffered state, deterministic and
-    stochastic solver."""
+    only) against the oracle sampler, SURVEY 8d tolerance for bf16 activations.  n = 1 (two rows): the two-launch decode form of the
+    bf16 mode (the folded-shift final layer, then the in-projection), deterministic and stochastic solver.  The solver-step seam
+    (headtail.hip) does not run here -- it needs H >= 256, this head is 128 wide -- tests/test_gpu_head_seam.py covers it."""
     s = build_small(synth.LMCfg(), xsplit=1, n_slots=8)
     eng = s.eng
     try:

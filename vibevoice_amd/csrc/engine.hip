@@ -268,6 +268,7 @@ struct vv_ctx {
     int64_t capture_fallbacks = 0; char last_capture_issue[256] = "";     // stream captures that fell back to an eager run (graphed())
     std::vector<std::pair<void*, size_t>> wallocs; size_t wshare_i = 0;
     int64_t launches = 0;
+    int64_t seam_launches = 0;        // head-tail seam launches the last recorded sampler body issued (vv_stat 6; a replay keeps its capture's count)
     // optional per-GEMM-launch hipEvent timing (vv_profile_begin/end)
     bool prof_on = false;
     std::vector<hipEvent_t> prof_ev;
@@ -1444,6 +1445,12 @@ static int lm_body(vv_ctx* ctx, hipStream_t st, int R, const float* x_in, float*
         return 0;
     }
     const bool p16 = R > 4 && R <= 16 && ctx->p16_ok && fused_attn;      // batch decode rows: packed-activation projections
+    if (contiguous && ctx->attn2_ok) {
+        // short prompt chunks reach vv_attn_prefill4 as well: the same V tail past the chunk, zeroed once for every layer of this pass
+        ctx->launches++;
+        VVCHK(vv_kv_zero_v_tail_launch((char*)ctx->vc + (size_t)l0 * ctx->layer_stride * 2, ctx->rows_dev, R, l1 - l0, Hkv, D, ctx->cache_stride,
+                                       ctx->layer_stride, ctx->head_stride, ctx->c.max_ctx, st));
+    }
     for (int l = l0; l < l1; ++l) {
         auto& L = ctx->layers[l];
         if (p16 && l > l0) {
@@ -1786,6 +1793,7 @@ static int head_eval(vv_ctx* ctx, hipStream_t st, int rows, const float* zrows, 
         t.T = rows; t.H = H; t.L = L; t.eps = c.head_eps;
         if (vv_head_tail_ok(&t)) {
             ctx->launches++;
+            ctx->seam_launches++;
             if (ctx->prof_on) {
                 const VVTail tc = t;
                 ctx->prof_other.push_back({3, (double)vv_packed_elems(L, H) * 2.0 + (double)vv_packed_elems(H, L) * 2.0 + (double)rows * H * 8.0,
@@ -1811,6 +1819,7 @@ static int sample_body(vv_ctx* ctx, hipStream_t st, int n, const float* cond, co
     const vv_config& c = ctx->c;
     const int H = ctx->H, L = c.latent_dim;
     const int rows = 2 * n;
+    ctx->seam_launches = 0;
     ctx->probe_names.clear();
     nan_probe(ctx, st, "cond (input)", cond, (size_t)rows * H);
     nan_probe(ctx, st, "noise (input)", noise, (size_t)n * L);
@@ -2235,6 +2244,7 @@ extern "C" int64_t vv_stat(vv_ctx* ctx, int what) {
         case 3: return ctx->prof_ev_over_ns;      // last profile: time of an empty event pair
         case 5: return ctx->foreign_nodes;        // nodes of the captured graphs that are not kernel launches (expected: 0)
         case 4: return ctx->capture_fallbacks;    // stream captures that did not close and ran eagerly instead (multi-threaded lanes)
+        case 6: return ctx->seam_launches;        // head-tail seam launches of the last recorded sampler body
         default: return (int64_t)ctx->graphs.size();
     }
 }
