@@ -133,6 +133,26 @@ int vv_kv_import_at(vv_ctx* ctx, void* stream, int cache, int layer, int pos0, i
  * correction of a non-diffusing batch row that holds exactly one valid entry (modeling_vibevoice_inference.py:594-624: the mask
  * shifts, :603, and the K/V does not, :613 -- the entry appended at that step stays, the older one is masked out). */
 int vv_kv_move(vv_ctx* ctx, void* stream, int cache, int src_pos, int dst_pos);
+/* The exact inverse of vv_kv_import_at: positions [pos0, pos0 + n_pos) of one layer of `cache` written out in HF layout
+ * k/v [kv_heads][n_pos][head_dim], keys as cached (rotated); dst_dtype 0 fp32, 1 bf16 (both exact: the cache holds bf16).  Outputs
+ * 16-byte aligned.  What makes a prompt prefix storable on disk independent of the tile layout, and how the tests read a cache.
+ * New surface; closest reference counterpart: reading past_key_values[layer] of the DynamicCache generate() carries
+ * (modeling_vibevoice_inference.py:480-482), which the reference can slice because its cache is a list of plain tensors. */
+int vv_kv_export(vv_ctx* ctx, void* stream, int cache, int layer, int pos0, int n_pos, void* k_out_dev, void* v_out_dev,
+                 int dst_dtype);
+/* A prompt prefix as data (voice presets for the non-streaming class): positions [0, n_pos) of EVERY layer and kv head of `cache`
+ * copied to two compact buffers in the cache's own tile layouts (K tiles [pos/16][d/32][lane][8], V blocks [pos/32][d/16][lane][8],
+ * DESIGN.md section 2), each [layer][kv_head][ceil32(n_pos) * head_dim] bf16 = vv_kv_snapshot_bytes bytes, 16-byte aligned.  The
+ * buffer does not depend on max_ctx: a context created with another max_ctx over the same model (a vv_create_shared child) restores
+ * it.  Slots of positions >= n_pos inside the last 32-position block are written as ZERO whatever the source holds there (V: the
+ * prefill attention multiplies whole stages and 0 x NaN = NaN; K: so that a snapshot is a function of the n_pos positions alone).
+ * vv_kv_restore is the inverse, into positions [0, ceil32(n_pos)) of `cache`; the caller then appends behind n_pos with
+ * vv_lm_forward.  One eager launch each (K, V and all layers), never part of a captured sequence.  New surface; closest reference
+ * counterpart: the Streaming class's prefilled presets, copy.deepcopy(all_prefilled_outputs) at the head of its generate()
+ * (modeling_vibevoice_streaming_inference.py) -- the non-streaming generate() re-runs the prompt on every call (:467-482). */
+int64_t vv_kv_snapshot_bytes(vv_ctx* ctx, int n_pos);
+int vv_kv_snapshot(vv_ctx* ctx, void* stream, int cache, int n_pos, void* k_out_dev, void* v_out_dev);
+int vv_kv_restore(vv_ctx* ctx, void* stream, int cache, int n_pos, const void* k_dev, const void* v_dev);
 /* y[t][:] = x[t][:] + tts_input_types[type]  (forward_tts_lm, :293) */
 int vv_add_type_embedding(vv_ctx* ctx, void* stream, int n, const float* x_dev, int type, float* out_dev);
 /* tts_eos_classifier: fc2(relu(fc1(h))) -> out_dev[n] logits (BinaryClassifier, modeling_vibevoice_streaming.py:42-53) */

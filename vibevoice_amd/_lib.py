@@ -55,6 +55,10 @@ _SIGS = {
     "vv_acoustic_encode": (C.c_int, [_P, _P, C.c_int, _P, _P]),
     "vv_acoustic_encode_ragged": (C.c_int, [_P, _P, C.c_int, C.c_longlong, _P, _P]),
     "vv_kv_move": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int]),
+    "vv_kv_export": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int]),
+    "vv_kv_snapshot_bytes": (C.c_int64, [_P, C.c_int]),
+    "vv_kv_snapshot": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
+    "vv_kv_restore": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     "vv_set_enc_pass_frames": (C.c_int, [_P, C.c_int]),
     "vv_audio_to_pcm16": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     "vv_codec_reset": (C.c_int, [_P, _P, C.c_int]),

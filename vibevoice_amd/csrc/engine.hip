@@ -78,6 +78,10 @@ int vv_kv_import_launch(const void* k, const void* v, int src_bf16, void* kc, vo
 int vv_kv_move_launch(void* kc, void* vc, int layers, int Hkv, int D, int64_t layer_stride, int64_t head_stride, int src, int dst, hipStream_t s);
 int vv_kv_zero_v_tail_launch(void* vc, const VVRow* rows, int R, int layers, int Hkv, int D, int64_t cache_stride, int64_t layer_stride,
                              int64_t head_stride, int max_ctx, hipStream_t s);
+int vv_kv_span_copy_launch(void* kc, void* vc, void* ks, void* vs, int to_cache, int layers, int Hkv, int D, int64_t layer_stride,
+                           int64_t head_stride, int n_pos, hipStream_t s);
+int vv_kv_export_launch(const void* kc, const void* vc, void* k, void* v, int dst_bf16, int L, int Hkv, int D, int64_t head_stride, int pos0,
+                        hipStream_t s);
 int vv_pcm16_launch(const float* x, short* out, int n, int samples, hipStream_t s);
 int vv_cvt_launch(const void* src, void* dst, int64_t n, int to_bf16, hipStream_t s);
 int vv_dw_transpose_launch(const float* src, float* dst, int C, hipStream_t s);
@@ -1644,6 +1648,45 @@ extern "C" int vv_kv_move(vv_ctx* ctx, void* stream, int cache, int src_pos, int
 }
 extern "C" int vv_kv_import(vv_ctx* ctx, void* stream, int cache, int layer, int n_pos, const void* k_dev, const void* v_dev, int src_dtype) {
     return vv_kv_import_at(ctx, stream, cache, layer, 0, n_pos, k_dev, v_dev, src_dtype);
+}
+extern "C" int vv_kv_export(vv_ctx* ctx, void* stream, int cache, int layer, int pos0, int n_pos, void* k_out_dev, void* v_out_dev, int dst_dtype) {
+    VV_SHARED;
+    hipStream_t st = (hipStream_t)stream;
+    if (cache < 0 || cache >= 2 * ctx->c.n_slots) return fail(ctx, "cache id %d out of range", cache);
+    if (layer < 0 || layer >= ctx->c.lm_layers) return fail(ctx, "layer %d out of range", layer);
+    if (pos0 < 0 || n_pos < 0 || (int64_t)pos0 + n_pos > ctx->c.max_ctx)
+        return fail(ctx, "vv_kv_export: positions [%d, %lld) exceed max_ctx %d", pos0, (long long)pos0 + n_pos, ctx->c.max_ctx);
+    if (dst_dtype != 0 && dst_dtype != 1) return fail(ctx, "vv_kv_export: dst_dtype %d (0 = fp32, 1 = bf16)", dst_dtype);
+    if (n_pos == 0) return 0;
+    if (!k_out_dev || !v_out_dev) return fail(ctx, "vv_kv_export: null output");
+    if (((uintptr_t)k_out_dev | (uintptr_t)v_out_dev) & 15) return fail(ctx, "vv_kv_export: outputs must be 16-byte aligned");
+    const size_t off = ((size_t)cache * ctx->cache_stride + (size_t)layer * ctx->layer_stride) * 2;
+    VVCHK(vv_kv_export_launch((char*)ctx->kc + off, (char*)ctx->vc + off, k_out_dev, v_out_dev, dst_dtype, n_pos, ctx->Hkv, ctx->D, ctx->head_stride, pos0, st));
+    return 0;
+}
+extern "C" int64_t vv_kv_snapshot_bytes(vv_ctx* ctx, int n_pos) {
+    if (n_pos < 0 || n_pos > ctx->c.max_ctx) return fail(ctx, "vv_kv_snapshot_bytes: %d positions outside [0, max_ctx %d]", n_pos, ctx->c.max_ctx);
+    return (int64_t)ctx->c.lm_layers * ctx->Hkv * ((n_pos + 31) & ~31) * ctx->D * 2;
+}
+// snapshot (to_cache = 0) and restore (1): one eager launch over K, V and every layer
+static int kv_span_copy(vv_ctx* ctx, void* stream, const char* who, int cache, int n_pos, void* k_dev, void* v_dev, int to_cache) {
+    VV_SHARED;
+    hipStream_t st = (hipStream_t)stream;
+    if (cache < 0 || cache >= 2 * ctx->c.n_slots) return fail(ctx, "%s: cache id %d out of range", who, cache);
+    if (n_pos < 0 || n_pos > ctx->c.max_ctx) return fail(ctx, "%s: %d positions outside [0, max_ctx %d]", who, n_pos, ctx->c.max_ctx);
+    if (n_pos == 0) return 0;
+    if (!k_dev || !v_dev) return fail(ctx, "%s: null snapshot buffer", who);
+    if (((uintptr_t)k_dev | (uintptr_t)v_dev) & 15) return fail(ctx, "%s: snapshot buffers must be 16-byte aligned", who);
+    const size_t off = (size_t)cache * ctx->cache_stride * 2;
+    VVCHK(vv_kv_span_copy_launch((char*)ctx->kc + off, (char*)ctx->vc + off, k_dev, v_dev, to_cache, ctx->c.lm_layers, ctx->Hkv, ctx->D,
+                                 ctx->layer_stride, ctx->head_stride, n_pos, st));
+    return 0;
+}
+extern "C" int vv_kv_snapshot(vv_ctx* ctx, void* stream, int cache, int n_pos, void* k_out_dev, void* v_out_dev) {
+    return kv_span_copy(ctx, stream, "vv_kv_snapshot", cache, n_pos, k_out_dev, v_out_dev, 0);
+}
+extern "C" int vv_kv_restore(vv_ctx* ctx, void* stream, int cache, int n_pos, const void* k_dev, const void* v_dev) {
+    return kv_span_copy(ctx, stream, "vv_kv_restore", cache, n_pos, (void*)k_dev, (void*)v_dev, 1);
 }
 
 extern "C" int vv_audio_to_pcm16(vv_ctx* ctx, void* stream, int n, int samples, const float* audio_dev, int16_t* pcm_out_dev) {

@@ -347,6 +347,45 @@ class Engine:
         self._chk(self.lib.vv_kv_import_at(self._ctx, self._s, cache, layer, int(pos0), k.shape[1], self._p(k), self._p(v),
                                            1 if k.dtype == torch.bfloat16 else 0), "vv_kv_import_at")
 
+    def kv_export(self, cache: int, layer: int, pos0: int, n_pos: int, dtype=torch.bfloat16):
+        """positions [pos0, pos0 + n_pos) of one layer of `cache` in HF layout: (k, v), each [kv_heads, n_pos, head_dim] (keys as
+        cached, rotated), fp32 or bf16 -- the exact inverse of kv_import_at."""
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise EngineError(f"kv_export: dtype {dtype} (torch.float32 or torch.bfloat16)")
+        with torch.cuda.stream(self.stream):
+            k = torch.empty(self.cfg.lm_kv_heads, max(0, int(n_pos)), self.cfg.lm_head_dim, dtype=dtype, device=self.device)
+            v = torch.empty_like(k)
+        self._chk(self.lib.vv_kv_export(self._ctx, self._s, int(cache), int(layer), int(pos0), int(n_pos), self._p(k), self._p(v),
+                                        1 if dtype == torch.bfloat16 else 0), "vv_kv_export")
+        return k, v
+
+    def kv_snapshot_numel(self, n_pos: int) -> int:
+        """bf16 elements of ONE of the two snapshot buffers (K or V) for n_pos positions"""
+        nb = int(self.lib.vv_kv_snapshot_bytes(self._ctx, int(n_pos)))
+        if nb < 0:
+            raise EngineError(f"vv_kv_snapshot_bytes failed: {self._err()}")
+        return nb // 2
+
+    def kv_snapshot(self, cache: int, n_pos: int):
+        """positions [0, n_pos) of every layer of `cache` as two compact bf16 device tensors (k, v), each
+        [layers, kv_heads, ceil32(n_pos) * head_dim] in the cache's tile layouts; slots past n_pos are zero.  Independent of max_ctx:
+        any engine over the same model (a fork() with another max_ctx) restores it."""
+        n = self.kv_snapshot_numel(n_pos)
+        per_head = n // (self.cfg.lm_layers * self.cfg.lm_kv_heads)
+        with torch.cuda.stream(self.stream):
+            k = torch.empty(self.cfg.lm_layers, self.cfg.lm_kv_heads, per_head, dtype=torch.bfloat16, device=self.device)
+            v = torch.empty_like(k)
+        self._chk(self.lib.vv_kv_snapshot(self._ctx, self._s, int(cache), int(n_pos), self._p(k), self._p(v)), "vv_kv_snapshot")
+        return k, v
+
+    def kv_restore(self, cache: int, n_pos: int, k: torch.Tensor, v: torch.Tensor):
+        """the inverse of kv_snapshot, into positions [0, ceil32(n_pos)) of `cache`, every layer; append behind n_pos afterwards"""
+        n = self.kv_snapshot_numel(n_pos)
+        for t in (k, v):
+            if t.dtype != torch.bfloat16 or not t.is_contiguous() or t.numel() != n or t.device != self.device:
+                raise EngineError(f"kv_restore: a snapshot of {n_pos} positions is a contiguous bf16 tensor of {n} elements on {self.device}")
+        self._chk(self.lib.vv_kv_restore(self._ctx, self._s, int(cache), int(n_pos), self._p(k), self._p(v)), "vv_kv_restore")
+
     def add_type_embedding(self, n: int, x: torch.Tensor, type_id: int, out: torch.Tensor):
         self._chk(self.lib.vv_add_type_embedding(self._ctx, self._s, n, self._p(x), int(type_id), self._p(out)),
                   "vv_add_type_embedding")

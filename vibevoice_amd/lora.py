@@ -182,4 +182,6 @@ def load_lora_assets(model, checkpoint_dir: str, base_state: Optional[Callable[[
         model.engine.upload(name, tensor)
         setattr(rep, kind, True)
         rep.merged_tensors += 1
+    if rep.merged_tensors and hasattr(model, "_bump_weights_epoch"):
+        model._bump_weights_epoch()              # prompt prefixes computed under the unmerged weights are stale
     return rep

@@ -193,6 +193,8 @@ class WeightHandle:
                 continue
             eng.upload(name, v)
             seen.add(k)
+        if seen and hasattr(self._owner, "_bump_weights_epoch"):
+            self._owner._bump_weights_epoch()        # prompt prefixes computed under the old weights are stale
         missing = [k for k in self.expected_keys() if k not in seen]
         if strict and (missing or unexpected):
             raise RuntimeError(f"load_state_dict({self._ref_prefix}): missing {missing[:4]}, unexpected {unexpected[:4]}")
@@ -318,6 +320,86 @@ class _LaneStreamer:
             self.inner.end(torch.tensor(ids))
 
 
+class PromptPrefix:
+    """The K/V of a prompt head that many requests share -- system prompt, ` Voice input:`, the speakers' voice blocks -- computed
+    once (model.build_prompt_prefix) and copied in front of every request that starts with it (generate(prompt_prefix=...)): the
+    voice samples are not encoded again and the LM runs over the rest of the prompt only.  Holds the engine's snapshot of positions
+    [0, n_pos) of the positive cache (device resident, independent of max_ctx: a fork()ed lane restores it), the n_pos token ids
+    and the speech positions it was computed from (a request is checked against both), the model geometry and the weights epoch
+    of the model that built it (a prefix is refused after the weights changed).  The voice latents' noise is ONE draw, fixed when
+    the prefix was built -- the reference draws it per call (_process_speech_inputs); the Streaming presets fix it the same way."""
+    FORMAT = "vibevoice_amd.prompt_prefix.v1"
+
+    def __init__(self, k, v, n_pos, ids, speech_pos, geometry, epoch, weights_token=None, model=None):
+        self.k, self.v = k, v
+        self.n_pos = int(n_pos)
+        self.ids = [int(i) for i in ids]
+        self.speech_pos = sorted(int(p) for p in speech_pos)
+        self.geometry = tuple(int(g) for g in geometry)       # (layers, kv heads, head dim)
+        self.epoch = int(epoch)
+        self._weights_token = weights_token                   # identity of the weight copy (shared by a model and its forks)
+        self._model = model
+        if len(self.ids) != self.n_pos:
+            raise ValueError(f"a prefix of {self.n_pos} positions holds {len(self.ids)} token ids")
+
+    def __repr__(self):
+        return f"PromptPrefix(n_pos={self.n_pos}, speech_positions={len(self.speech_pos)}, geometry={self.geometry}, epoch={self.epoch})"
+
+    def save(self, path):
+        """One torch.save file: per-layer bf16 K/V in HF layout [kv_heads, n_pos, head_dim] (keys rotated, as cached) plus the
+        metadata -- independent of the tile layout of the build that wrote it.  Goes through KV cache 0 of the model that built the
+        prefix as scratch (restore, then export layer by layer): not while that model generates."""
+        m = self._model
+        if m is None:
+            raise RuntimeError("PromptPrefix.save: the prefix is not attached to a model (build_prompt_prefix / load attach it)")
+        m._check_prefix(self)
+        e = m.engine
+        with torch.cuda.stream(e.stream):
+            e.kv_restore(0, self.n_pos, self.k, self.v)
+            layers = [e.kv_export(0, l, 0, self.n_pos, dtype=torch.bfloat16) for l in range(self.geometry[0])]
+        e.sync()
+        torch.save({"format": self.FORMAT, "n_pos": self.n_pos, "ids": list(self.ids), "speech_pos": list(self.speech_pos),
+                    "geometry": list(self.geometry), "k": [k.cpu() for k, _ in layers], "v": [v.cpu() for _, v in layers]}, path)
+
+    @classmethod
+    def load(cls, path, model):
+        """Read a saved prefix into `model`: kv_import_at into KV cache 0 (scratch; not while the model generates), then a snapshot.
+        The file does not say which weights it was computed with: loading one under other weights is the caller's mistake, as with
+        the Streaming presets."""
+        d = torch.load(path, map_location="cpu", weights_only=True)
+        if not isinstance(d, dict) or d.get("format") != cls.FORMAT:
+            raise ValueError(f"{path} is not a saved PromptPrefix")
+        geo = tuple(int(g) for g in d["geometry"])
+        if geo != model._kv_geometry():
+            raise ValueError(f"the prefix was saved for (layers, kv heads, head dim) = {geo}; this model has {model._kv_geometry()}")
+        n = int(d["n_pos"])
+        e = model.engine
+        with torch.cuda.stream(e.stream):
+            for l in range(geo[0]):
+                e.kv_import_at(0, l, 0, d["k"][l].to(e.device), d["v"][l].to(e.device))
+            k, v = e.kv_snapshot(0, n)
+        e.sync()
+        return cls(k, v, n, d["ids"], d["speech_pos"], geo, model.weights_epoch, model._epoch_box, model)
+
+
+def _speakers_of_rows(need, have):
+    """Voice sample i contributes have[i] speech rows; the batch rows consume them in order, need[b] each (_process_speech_inputs +
+    the masked scatter, :149-163,470-474).  -> the sample indices of every row, or None when a sample spans two rows."""
+    out, i = [], 0
+    for nb in need:
+        got, mine = 0, []
+        while got < nb:
+            if i >= len(have):
+                return None
+            mine.append(i)
+            got += have[i]
+            i += 1
+        if got != nb:
+            return None
+        out.append(mine)
+    return out
+
+
 class _Utt:
     """One utterance in flight: its engine slot (KV caches 2*slot / 2*slot+1, codec states), lengths and outputs."""
     __slots__ = ("idx", "slot", "ids", "seq_len0", "init_len", "max_length", "max_steps", "max_step_sample", "step", "pos_len",
@@ -404,6 +486,9 @@ class VibeVoiceForConditionalGenerationInference:
         self.batched_codecs = hasattr(engine, "codec_chain_batch")
         self.speculate_sampling = True
         self.last_stats = {}
+        # weights epoch: [count of parameter updates since construction]; one box per weight copy (forks share their parent's).  A
+        # PromptPrefix remembers the value it was computed under
+        self._epoch_box = [0]
 
     # ------------------------------------------------------------------ construction
     @classmethod
@@ -533,6 +618,149 @@ class VibeVoiceForConditionalGenerationInference:
 
     def set_ddpm_inference_steps(self, num_steps=None):
         self.ddpm_inference_steps = num_steps or self.config_dict["diffusion_head_config"].get("ddpm_num_inference_steps", 20)
+
+    # ------------------------------------------------------------------ parameter updates on a live model
+    @property
+    def weights_epoch(self) -> int:
+        return self._epoch_box[0]
+
+    def _bump_weights_epoch(self):
+        self._epoch_box[0] += 1
+
+    def upload(self, name: str, tensor):
+        """One parameter by its ENGINE name ("lm.layers.0.self_attn.q_proj.weight", include/vvhip.h); K/V computed before it is stale."""
+        self.engine.upload(name, tensor)
+        self._bump_weights_epoch()
+
+    def load_state_dict(self, state_dict, strict: bool = True):
+        """A (partial) state dict keyed like the reference checkpoint, uploaded into the live engine (which re-packs); returns
+        (missing_keys, unexpected_keys) like nn.Module.  Prompt prefixes built before it are refused afterwards."""
+        eng = self.engine
+        exp = eng.expected_weights()
+        seen, unexpected = set(), []
+        scaling = bias = None
+        for k, v in state_dict.items():
+            if k == "model.speech_scaling_factor":
+                scaling = float(v)
+                continue
+            if k == "model.speech_bias_factor":
+                bias = float(v)
+                continue
+            name = map_param_name(k)
+            if name is None or name not in exp:
+                unexpected.append(k)
+                continue
+            eng.upload(name, v)
+            seen.add(name)
+        self._bump_weights_epoch()
+        if scaling is not None and bias is not None:
+            self.set_speech_factors(scaling, bias)
+        missing = [_engine_name_to_reference(n) or n for n in exp if n not in seen and n != "lm.rope.inv_freq"]
+        if strict and (missing or unexpected):
+            raise RuntimeError(f"load_state_dict: missing {missing[:4]}, unexpected {unexpected[:4]}")
+        import collections
+        return collections.namedtuple("IncompatibleKeys", "missing_keys unexpected_keys")(missing, unexpected)
+
+    # ------------------------------------------------------------------ prompt prefixes (voice presets for this class)
+    def _kv_geometry(self):
+        c = self.engine.cfg
+        return (int(c.lm_layers), int(c.lm_kv_heads), int(c.lm_head_dim))
+
+    def _check_prefix(self, prefix):
+        if not isinstance(prefix, PromptPrefix):
+            raise TypeError(f"prompt_prefix takes a PromptPrefix (model.build_prompt_prefix / PromptPrefix.load), not {type(prefix).__name__}")
+        if prefix.geometry != self._kv_geometry():
+            raise ValueError(f"the prompt prefix was built for (layers, kv heads, head dim) = {prefix.geometry}; this model has {self._kv_geometry()}")
+        if prefix._weights_token is not self._epoch_box:
+            raise RuntimeError("the prompt prefix was built by another model (not this one or a fork() of it): its K/V belongs to other weights")
+        if prefix.epoch != self.weights_epoch:
+            raise RuntimeError(f"the prompt prefix is stale: it was built at weights epoch {prefix.epoch} and the model's parameters have been "
+                               f"updated since (epoch {self.weights_epoch}: load_state_dict / upload / load_lora_assets); build it again")
+
+    def _prefix_plan(self, prefix, ids: List[int], speech_pos: Optional[List[int]]) -> int:
+        """How many leading positions of the prompt `ids` come from `prefix`: r = min(prefix.n_pos, len(ids) - 1) -- at least one row goes
+        through the LM, its hidden state starts the loop -- after checking that the prompt really starts with the prefix (token ids and
+        speech positions below r; a mismatch raises: a silent fallback would hide a wrong voice).  0 = prefill the row in full: no
+        prefix, or a speech position of the row at or beyond r (its voice rows are not in the prefix).  speech_pos None: the call
+        carries no speech mask, the prefix's own positions are taken."""
+        if prefix is None:
+            return 0
+        self._check_prefix(prefix)
+        r = min(prefix.n_pos, len(ids) - 1)
+        if r < 1:
+            return 0
+        if ids[:r] != prefix.ids[:r]:
+            p = next(i for i in range(r) if ids[i] != prefix.ids[i])
+            raise ValueError(f"prompt_prefix does not match the prompt: token {ids[p]} at position {p}, the prefix holds {prefix.ids[p]}")
+        if speech_pos is None:
+            if any(p >= r for p in prefix.speech_pos):
+                raise ValueError(f"the prompt ends at position {len(ids) - 1}, inside the prefix's voice block, and the call carries no speech inputs")
+            return r
+        mine, theirs = set(p for p in speech_pos if p < r), set(p for p in prefix.speech_pos if p < r)
+        if mine != theirs:
+            raise ValueError(f"prompt_prefix does not match the prompt: position {min(mine ^ theirs)} is a speech position in one of them only")
+        if any(p >= r for p in speech_pos):
+            return 0
+        return r
+
+    @staticmethod
+    def _prefix_list(prompt_prefix, n_rows):
+        if prompt_prefix is None or isinstance(prompt_prefix, PromptPrefix):
+            return [prompt_prefix] * n_rows
+        if not isinstance(prompt_prefix, (list, tuple)):
+            raise TypeError(f"prompt_prefix takes a PromptPrefix or a list of them (None for a row without one), not {type(prompt_prefix).__name__}")
+        lst = list(prompt_prefix)
+        if len(lst) != n_rows:
+            raise ValueError(f"prompt_prefix: {len(lst)} entries for {n_rows} rows (one PromptPrefix for all rows, or one entry or None per row)")
+        return lst
+
+    @torch.no_grad()
+    def build_prompt_prefix(self, input_ids, speech_tensors=None, speech_masks=None, speech_input_mask=None, attention_mask=None,
+                            n_prefix: Optional[int] = None, **kw) -> PromptPrefix:
+        """Compute the K/V of the first n_prefix positions of ONE row of processor output and keep it as a PromptPrefix: the voice
+        samples go through the acoustic encoder and the connector, the LM runs over the head (engine slot 0), the positive cache is
+        snapshotted.  n_prefix defaults to one past the last True of speech_input_mask (the whole voice block); without a speech
+        mask it is required.  _prefill_noise=(r1, r2) fixes the voice latents' noise as in generate(); without it the draw comes from
+        the device generator -- either way the prefix holds ONE draw for every request that uses it, where the reference draws per
+        call (_process_speech_inputs), exactly as the Streaming presets do.  Not while the model generates."""
+        e = self.engine
+        prefill_noise = kw.pop("_prefill_noise", None)
+        input_ids = input_ids.cpu()
+        if input_ids.dim() == 1:
+            input_ids = input_ids[None]
+        if input_ids.shape[0] != 1:
+            raise ValueError("build_prompt_prefix takes one row of processor output")
+        am = torch.ones_like(input_ids) if attention_mask is None else attention_mask.cpu().reshape(1, -1)
+        keep = am[0].bool()
+        ids = input_ids[0][keep].tolist()
+        sp_all = []
+        if speech_input_mask is not None:
+            sp_all = speech_input_mask.cpu().reshape(1, -1)[0][keep].to(torch.bool).nonzero().squeeze(1).tolist()
+        if n_prefix is None:
+            if not sp_all:
+                raise ValueError("build_prompt_prefix: n_prefix is required when the row has no speech positions")
+            n_prefix = sp_all[-1] + 1
+        n_prefix = int(n_prefix)
+        if not 1 <= n_prefix <= len(ids):
+            raise ValueError(f"n_prefix = {n_prefix} outside [1, {len(ids)}] (the row's unpadded prompt)")
+        if n_prefix > e.max_ctx:
+            raise ValueError(f"n_prefix = {n_prefix} exceeds the engine's max_ctx {e.max_ctx}")
+        sp = [p for p in sp_all if p < n_prefix]
+        with torch.cuda.stream(e.stream):
+            rows = pos = None
+            if sp:
+                if speech_tensors is None or speech_masks is None:
+                    raise ValueError("build_prompt_prefix: the row has speech positions; speech_tensors and speech_masks are required")
+                pos = torch.tensor(sp, dtype=torch.long).to(self.device)
+                _, emb = self._process_speech_inputs(speech_tensors, speech_masks, prefill_noise)
+                if emb.shape[0] < len(sp):
+                    raise ValueError("speech_masks hold fewer frames than speech_input_mask marks")
+                rows = emb[:len(sp)]
+            u = _Utt(0, 0, ids[:n_prefix], n_prefix, n_prefix, 2, 0)
+            self._prefill_checked([(u, u.ids, rows, pos, 0, None)])
+            k, v = e.kv_snapshot(0, n_prefix)
+        e.sync()               # complete before any other stream (a lane's) reads it
+        return PromptPrefix(k, v, n_prefix, ids[:n_prefix], sp, self._kv_geometry(), self.weights_epoch, self._epoch_box, self)
 
     def warmup(self, prompt_rows: Optional[Sequence[int]] = None, voice_frames: int = 75):
         """Touch everything the first request needs, so that its time to first audio is a warm process's: the first launch of
@@ -791,10 +1019,16 @@ class VibeVoiceForConditionalGenerationInference:
 
     # ------------------------------------------------------------------ prompt prefill of one utterance
     def _prefill(self, u: _Utt, ids: List[int], speech_rows: Optional[torch.Tensor], speech_pos: Optional[torch.Tensor],
-                 kv_start: int = 0, kv_fill_fn=None):
-        """LM prefill of one utterance's prompt into KV cache 2*slot; the last row's hidden state -> _hid_fresh[slot]."""
+                 kv_start: int = 0, kv_fill_fn=None, prefix: Optional[PromptPrefix] = None, pos0: int = 0):
+        """LM prefill of one utterance's prompt into KV cache 2*slot; the last row's hidden state -> _hid_fresh[slot].
+        prefix / pos0 (_prefix_plan): the first pos0 positions are restored from the prefix's snapshot and the LM runs over ids[pos0:]
+        only, appended behind them (speech rows all lie below pos0 then)."""
         e = self.engine
         H = e.cfg.lm_hidden
+        if prefix is not None:
+            e.kv_restore(2 * u.slot, prefix.n_pos, prefix.k, prefix.v)
+            ids = ids[pos0:]
+            speech_rows = speech_pos = None
         n = len(ids)
         CH = e.cfg.max_rows          # prompt rows per weight pass
         if n <= CH:
@@ -820,14 +1054,14 @@ class VibeVoiceForConditionalGenerationInference:
         for i0 in range(0, n, CH):
             k = min(CH, n - i0)
             if hasattr(e, "lm_forward_span"):
-                e.lm_forward_span(2 * u.slot, i0, k, emb[i0:i0 + k], hid)
+                e.lm_forward_span(2 * u.slot, pos0 + i0, k, emb[i0:i0 + k], hid)
             else:
-                e.lm_forward([(2 * u.slot, i0 + j) for j in range(k)], emb[i0:i0 + k], hid)
+                e.lm_forward([(2 * u.slot, pos0 + i0 + j) for j in range(k)], emb[i0:i0 + k], hid)
         self._hid_fresh[u.slot].copy_(hid[(n - 1) % CH])
         if timed:
             e.sync(); torch.cuda.current_stream(self.device).synchronize()
             self._t_lm_pass = getattr(self, "_t_lm_pass", 0.0) + (time.perf_counter() - t_emb)
-        u.pos_len = n
+        n = u.pos_len = pos0 + n
         if kv_start > n:             # bench hook: decode measured at a long context (kv_fill_fn supplies the cache contents)
             if kv_fill_fn is not None:
                 timed = os.environ.get("VVHIP_TIME_PREFILL") is not None
@@ -1246,6 +1480,7 @@ class VibeVoiceForConditionalGenerationInference:
         kwargs.pop("all_speakers_list", None)
         max_length_times = kwargs.pop("max_length_times", 2)
         prefill_noise = kwargs.pop("_prefill_noise", None)
+        prompt_prefix = kwargs.pop("prompt_prefix", None)      # PromptPrefix (every row) or a list with one entry / None per row
         hooks = kwargs.pop("_bench_hooks", None) or BenchHooks()  # measurement harness only (bench.py): see BenchHooks
         step_cb, kv_start, kv_fill_fn = hooks.step_callback, hooks.kv_start, hooks.kv_fill_fn
         input_ids = kwargs["input_ids"] if inputs is None else inputs
@@ -1261,7 +1496,9 @@ class VibeVoiceForConditionalGenerationInference:
             # output form
             return self._generate_queued(input_ids, attention_mask, tokenizer, generation_config, cfg_scale, audio_streamer,
                                          speech_tensors, speech_masks, speech_input_mask, is_prefill, return_speech, stop_check_fn,
-                                         max_length_times, prefill_noise, step_cb, kwargs)
+                                         max_length_times, prefill_noise, step_cb, kwargs, prompt_prefix=prompt_prefix)
+        prefixes = self._prefix_list(prompt_prefix, B)
+        pf_stats = {"prefix_rows_reused": 0, "prompt_rows_computed": 0}
         S = self._session(tokenizer, generation_config, cfg_scale, kwargs, audio_streamer, B)
         S["sample_rows"] = lambda order: list(range(B))
         self._frame_w = B                                 # frame-store rows are as wide as this call's batch
@@ -1313,12 +1550,33 @@ class VibeVoiceForConditionalGenerationInference:
                     # lazy kernel-module load (~20 ms) on its first use and a sync on every use), uploaded while the stream is
                     # still idle -- behind the encoder a pageable copy would hold the host until the encoder has finished
                     sp_pos = {}
-                    if with_voice and speech_input_mask is not None:
+                    sp_host = {}
+                    if speech_input_mask is not None and (with_voice or any(p is not None for p in prefixes)):
                         for u in utts:
                             sm_cpu = speech_input_mask[u.idx].cpu()[attention_mask[u.idx].bool().cpu()]
                             idx = sm_cpu.to(torch.bool).nonzero().squeeze(1)
-                            if idx.numel():
+                            sp_host[u.idx] = idx.tolist()
+                            if with_voice and idx.numel():
                                 sp_pos[u.idx] = (int(idx.numel()), idx.to(self.device))
+                    # rows that start with a prompt prefix: r leading positions come from its snapshot (0: today's full prefill)
+                    reuse = {u.idx: self._prefix_plan(prefixes[u.idx], u.ids, sp_host.get(u.idx)) for u in utts}
+                    if with_voice and any(reuse.values()):
+                        # the voice samples of a prefixed row are in the prefix: only the other rows' samples are encoded (none: no
+                        # encoder call at all).  A sample that spans two rows cannot be told apart: then every sample is encoded.
+                        need = [sp_pos[u.idx][0] if u.idx in sp_pos else 0 for u in utts]
+                        spk = _speakers_of_rows(need, [int(speech_masks[i].sum()) for i in range(speech_masks.shape[0])])
+                        if spk is not None:
+                            keep_spk = [i for u in utts if not reuse[u.idx] for i in spk[u.idx]]
+                            for u in utts:
+                                if reuse[u.idx]:
+                                    sp_pos.pop(u.idx, None)
+                            if keep_spk:
+                                sel = torch.tensor(keep_spk, dtype=torch.long)
+                                speech_tensors, speech_masks = speech_tensors.cpu()[sel], speech_masks.cpu()[sel]
+                                if prefill_noise is not None:
+                                    prefill_noise = tuple(t.cpu()[sel] for t in prefill_noise)
+                            else:
+                                with_voice = False
                     if with_voice:
                         _, sp_embeds = self._process_speech_inputs(speech_tensors, speech_masks, prefill_noise)
                     if time_prefill:
@@ -1331,7 +1589,12 @@ class VibeVoiceForConditionalGenerationInference:
                             cnt, pos = sp_pos[u.idx]
                             rows = sp_embeds[sp_off:sp_off + cnt]
                             sp_off += cnt
-                        jobs.append((u, u.ids, rows, pos, kv_start, kv_fill_fn))
+                        if reuse[u.idx]:
+                            jobs.append((u, u.ids, None, None, kv_start, kv_fill_fn, prefixes[u.idx], reuse[u.idx]))
+                        else:
+                            jobs.append((u, u.ids, rows, pos, kv_start, kv_fill_fn))
+                        pf_stats["prefix_rows_reused"] += reuse[u.idx]
+                        pf_stats["prompt_rows_computed"] += len(u.ids) - reuse[u.idx]
                     self._prefill_checked(jobs)
                     if time_prefill:
                         e.sync(); t_pf.append(time.perf_counter())
@@ -1351,14 +1614,14 @@ class VibeVoiceForConditionalGenerationInference:
                     seq[u.idx, L0:L0 + len(u.tokens)] = torch.tensor(u.tokens, dtype=torch.long)
         e.sync()
         self._release_frames()
-        self.last_stats = {"frames": S["n_frames"], "steps": n_steps}
+        self.last_stats = {"frames": S["n_frames"], "steps": n_steps, **pf_stats}
         return VibeVoiceGenerationOutput(
             sequences=seq.to(self.device), speech_outputs=outs if return_speech else None,
             reach_max_step_sample=torch.tensor([u.reach_max for u in utts], dtype=torch.bool).to(self.device))
 
     def _generate_queued(self, input_ids, attention_mask, tokenizer, generation_config, cfg_scale, audio_streamer, speech_tensors,
                          speech_masks, speech_input_mask, is_prefill, return_speech, stop_check_fn, max_length_times, prefill_noise,
-                         step_cb, kwargs):
+                         step_cb, kwargs, prompt_prefix=None):
         """generate() for a batch of more than MAX_BATCH rows (the reference's batch is unbounded, :393-394): every row becomes a
         one-utterance request of generate_continuous() -- up to n_slots of them in flight, a finished row's slot refilled at once --
         and the results are assembled into ONE VibeVoiceGenerationOutput as the batched loop returns it (sequences [B, L0 + steps]
@@ -1373,6 +1636,7 @@ class VibeVoiceForConditionalGenerationInference:
         order instead of the batch's lock-step order.  Loop lengths follow the batch: every row's cap uses the batch's padded
         width L0 (:421-422)."""
         B, L0 = input_ids.shape
+        prefixes = self._prefix_list(prompt_prefix, B)
         if prefill_noise is not None:
             raise NotImplementedError("_prefill_noise (test hook) is per call; not supported for batches above MAX_BATCH")
         forced = kwargs.pop("_forced_tokens", None)
@@ -1391,17 +1655,11 @@ class VibeVoiceForConditionalGenerationInference:
         if is_prefill and speech_tensors is not None and speech_masks is not None and speech_input_mask is not None:
             need = [int((speech_input_mask[b].cpu() & attention_mask[b].bool()).sum()) for b in range(B)]
             have = [int(speech_masks[i].sum()) for i in range(speech_masks.shape[0])]
-            i = 0
-            for b in range(B):
-                got = 0
-                while got < need[b]:
-                    if i >= len(have):
-                        raise ValueError("speech_masks hold fewer frames than speech_input_mask marks")
-                    spk_of_row[b].append(i)
-                    got += have[i]
-                    i += 1
-                if got != need[b]:
-                    raise ValueError("a voice prompt spans two batch rows: the rows' speech positions must consume whole speakers")
+            if sum(have) < sum(need):
+                raise ValueError("speech_masks hold fewer frames than speech_input_mask marks")
+            spk_of_row = _speakers_of_rows(need, have)
+            if spk_of_row is None:
+                raise ValueError("a voice prompt spans two batch rows: the rows' speech positions must consume whole speakers")
         reqs = []
         for b in range(B):
             r = {"input_ids": input_ids[b:b + 1], "attention_mask": attention_mask[b:b + 1]}
@@ -1410,6 +1668,10 @@ class VibeVoiceForConditionalGenerationInference:
                 r["speech_tensors"] = speech_tensors[idx]
                 r["speech_masks"] = speech_masks[idx]
                 r["speech_input_mask"] = speech_input_mask[b:b + 1]
+            elif prefixes[b] is not None and speech_input_mask is not None:
+                r["speech_input_mask"] = speech_input_mask[b:b + 1]
+            if prefixes[b] is not None:
+                r["prompt_prefix"] = prefixes[b]
             if forced is not None:
                 r["_forced_tokens"] = forced[b]
             if noise_fn is not None:
@@ -1435,6 +1697,7 @@ class VibeVoiceForConditionalGenerationInference:
         context -- KV caches, tokenizer state, graphs, stream -- and its own host-side buffers.  runtime: n_slots / max_ctx / max_rows
         overrides.  generate() on the fork and on the original may run at the same time from two host threads."""
         m = type(self)(self.config_dict, self.engine.fork(**runtime), self.dtype, self.requested_attn_implementation)
+        m._epoch_box = self._epoch_box          # one weight copy, one epoch: a prefix built on either model serves both
         m.set_speech_factors(self._scaling, self._bias)
         m.set_ddpm_inference_steps(self.ddpm_inference_steps)
         m._sched_cfg = dict(self._sched_cfg)
@@ -1501,6 +1764,8 @@ class VibeVoiceForConditionalGenerationInference:
             audio_streamer.end()
         self.last_stats = {"lanes": lanes, "frames": sum(m.last_stats.get("frames", 0) for m in models),
                            "capture_fallbacks": [m.engine.stat(4) if hasattr(m.engine, "stat") else 0 for m in models],
+                           "prefix_rows_reused": sum(m.last_stats.get("prefix_rows_reused", 0) for m in models),
+                           "prompt_rows_computed": sum(m.last_stats.get("prompt_rows_computed", 0) for m in models),
                            "per_lane": [dict(m.last_stats) for m in models], "shards": shards}
         return outs
 
@@ -1545,7 +1810,7 @@ class VibeVoiceForConditionalGenerationInference:
         done = [None] * n_req
         active: List[_Utt] = []
         it = 0
-        stats = {"iterations": 0, "admissions": [], "max_in_flight": 0}
+        stats = {"iterations": 0, "admissions": [], "max_in_flight": 0, "prefix_rows_reused": 0, "prompt_rows_computed": 0}
         with torch.cuda.stream(e.stream), _end_streamer_on_error(audio_streamer):
             e.embed([S["start_id"]], self._start_emb)
             while queue or active:
@@ -1605,7 +1870,12 @@ class VibeVoiceForConditionalGenerationInference:
                     u.t_admit = it
                     e.codec_reset(slot)
                     rows = pos = None
-                    if is_prefill and r.get("speech_tensors") is not None and r.get("speech_masks") is not None:
+                    reuse = 0
+                    if r.get("prompt_prefix") is not None:      # the request starts with a prompt prefix: its voice rows are in the snapshot
+                        sim = r.get("speech_input_mask")
+                        sp_host = None if sim is None else sim[0].cpu()[am[0].bool().cpu()].to(torch.bool).nonzero().squeeze(1).tolist()
+                        reuse = self._prefix_plan(r["prompt_prefix"], u.ids, sp_host)
+                    if not reuse and is_prefill and r.get("speech_tensors") is not None and r.get("speech_masks") is not None:
                         _, sp = self._process_speech_inputs(r["speech_tensors"], r["speech_masks"], r.get("_prefill_noise"), dev_gen=S.get("dev_gen"))
                         sim = r.get("speech_input_mask")
                         if sim is not None:
@@ -1613,7 +1883,12 @@ class VibeVoiceForConditionalGenerationInference:
                             if idx.numel():
                                 pos = idx.to(self.device)
                                 rows = sp[:int(idx.numel())]
-                    self._prefill_checked([(u, u.ids, rows, pos, 0, None)])
+                    if reuse:
+                        self._prefill_checked([(u, u.ids, None, None, 0, None, r["prompt_prefix"], reuse)])
+                    else:
+                        self._prefill_checked([(u, u.ids, rows, pos, 0, None)])
+                    stats["prefix_rows_reused"] += reuse
+                    stats["prompt_rows_computed"] += len(u.ids) - reuse
                     done[ri] = u
                     stats["admissions"].append((it, ri, slot))
                     if u.max_steps > 0 and u.seq_len0 < u.max_length:
