@@ -232,6 +232,30 @@ int vv_gemm_raw(void* stream, const void* w_packed_dev, const void* w2_packed_de
                 float* y_dev, int T, int N, int K, int ldx, int ldy, int pro, int epi,
                 const float* nw_dev, float eps, const float* bias_dev, const float* nscale_dev,
                 int xsplit, int ksplit, int nontemporal);
+/* Exactly ONE launch of the decode GEMV kernel (gemv.hip: vv_gemv_kernel), or a refusal -- never another kernel in its place
+ * (vv_gemm_raw goes through the dispatcher, which answers a shape the GEMV refuses with the tile or the general kernel).  The
+ * struct carries every operand of the kernel (field meanings: VVGemm in csrc/vv_common.h); unused ones are 0 / NULL.  W / W2 are
+ * vv_pack_matrix outputs.  Returns 0 after the launch, VV_GEMV_REFUSED (nothing was launched: the eligibility check said no, or
+ * there is no instantiation for this pair / row count / xsplit), < 0 on a bad xsplit or a launch error.  form_out (optional)
+ * receives {XS, MR rows, WPB waves, PARTS (0 none, 1 activation side, 2 residual side), SL (1 = slot-batched)} of the instantiation
+ * that ran, as decided by the launcher itself.  The caller vouches for the sizes of every buffer (Engine.gemv_case checks them).
+ * New surface (tests); the reference has no native code. */
+#define VV_GEMV_REFUSED 1
+typedef struct vv_gemv_case_args {
+    const void* W; const void* W2; const float* X; float* Y;
+    int T, N, K, ldx, ldy;
+    int pro, epi;
+    const float* nw; float eps; const float* bias; const float* nscale;
+    const float* mod_scale; const float* mod_shift; int ld_mod;
+    const float* addvec; int x_row_mod, add_rows_per_vec;
+    const float* gate; int ld_gate;
+    float* z; float* x0p; const float* coef; float cfg; int n_cfg; const float* sde_noise;
+    int kgrid; float* yparts; const float* xa; int n_xa; const float* ya; int n_ya; int part_stride;
+    int sl_n, sl_T, sl_x, sl_y; int sl_id[8];
+    const float* dw_hist; const float* dw_w; const float* dw_b; const float* dw_gamma; const float* dw_nw;
+    float* dw_xout; float* dw_hnew;
+} vv_gemv_case_args;
+int vv_gemv_case(void* stream, const vv_gemv_case_args* args, int xsplit, int* form_out);
 /* The prompt-prefill GEMM (bf16-activation mode): x_dev fp32 [T][K] is packed (RMS-normalised when nw_dev != NULL) into
  * xp_scratch (vv_packed_bytes(T, K)); epi 0/1/4 (store / bias / residual) -> fp32 y_dev [T][N]; epi 3 (SwiGLU: w = gate,
  * w2 = up) -> packed bf16 in yp_scratch (vv_packed_bytes(T, N), zero-initialised), unpacked into y_dev.  K % 8 == 0, N % 4 == 0.

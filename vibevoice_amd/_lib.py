@@ -25,6 +25,26 @@ class VVRow(C.Structure):
 
 
 _P = C.c_void_p
+
+
+class VVGemvCase(C.Structure):
+    """vv_gemv_case_args (include/vvhip.h): every operand of one decode-GEMV launch"""
+    _fields_ = [
+        ("W", _P), ("W2", _P), ("X", _P), ("Y", _P),
+        ("T", C.c_int), ("N", C.c_int), ("K", C.c_int), ("ldx", C.c_int), ("ldy", C.c_int),
+        ("pro", C.c_int), ("epi", C.c_int),
+        ("nw", _P), ("eps", C.c_float), ("bias", _P), ("nscale", _P),
+        ("mod_scale", _P), ("mod_shift", _P), ("ld_mod", C.c_int),
+        ("addvec", _P), ("x_row_mod", C.c_int), ("add_rows_per_vec", C.c_int),
+        ("gate", _P), ("ld_gate", C.c_int),
+        ("z", _P), ("x0p", _P), ("coef", _P), ("cfg", C.c_float), ("n_cfg", C.c_int), ("sde_noise", _P),
+        ("kgrid", C.c_int), ("yparts", _P), ("xa", _P), ("n_xa", C.c_int), ("ya", _P), ("n_ya", C.c_int), ("part_stride", C.c_int),
+        ("sl_n", C.c_int), ("sl_T", C.c_int), ("sl_x", C.c_int), ("sl_y", C.c_int), ("sl_id", C.c_int * 8),
+        ("dw_hist", _P), ("dw_w", _P), ("dw_b", _P), ("dw_gamma", _P), ("dw_nw", _P), ("dw_xout", _P), ("dw_hnew", _P),
+    ]
+
+
+GEMV_REFUSED = 1     # VV_GEMV_REFUSED
 _SIGS = {
     "vv_create": (C.c_int, [C.POINTER(VVConfig), C.POINTER(_P)]),
     "vv_create_shared": (C.c_int, [C.POINTER(VVConfig), _P, C.POINTER(_P)]),
@@ -67,6 +87,7 @@ _SIGS = {
     "vv_pack_matrix": (C.c_int, [_P, _P, _P, C.c_int, C.c_int]),
     "vv_gemm_raw": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                               _P, C.c_float, _P, _P, C.c_int, C.c_int, C.c_int]),
+    "vv_gemv_case": (C.c_int, [_P, C.POINTER(VVGemvCase), C.c_int, C.POINTER(C.c_int)]),
     "vv_gemm3_raw": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_float, _P, _P, _P, _P]),
     "vv_profile_begin": (C.c_int, [_P]),
     "vv_profile_end": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -2171,6 +2171,29 @@ extern "C" int vv_gemm_raw(void* stream, const void* w, const void* w2, const fl
     if (g.dbg) g.nscale = nullptr;
     return vv_gemm_launch(g, xsplit, (hipStream_t)stream);
 }
+// tests: one launch of the decode GEMV kernel in the form its own launcher picks, or a refusal; no dispatcher, no stand-in kernel
+extern "C" int vv_gemv_launch(VVGemm a, int xs, hipStream_t s, int* form);
+extern "C" int vv_gemv_case(void* stream, const vv_gemv_case_args* c, int xsplit, int* form_out) {
+    if (!c || xsplit < 1 || xsplit > 3) return -1;
+    VVGemm g = mk_gemm(c->W, c->X, c->Y, c->T, c->N, c->K, c->ldx, c->ldy);
+    g.W2 = (const u32x4*)c->W2; g.pro = c->pro; g.epi = c->epi; g.nw = c->nw; g.eps = c->eps; g.bias = c->bias; g.nscale = c->nscale;
+    g.mod_scale = c->mod_scale; g.mod_shift = c->mod_shift; g.ld_mod = c->ld_mod;
+    g.addvec = c->addvec; g.x_row_mod = c->x_row_mod; g.add_rows_per_vec = c->add_rows_per_vec;
+    g.gate = c->gate; g.ld_gate = c->ld_gate;
+    g.z = c->z; g.x0p = c->x0p; g.coef = c->coef; g.cfg = c->cfg; g.n_cfg = c->n_cfg; g.sde_noise = c->sde_noise;
+    g.kgrid = c->kgrid; g.yparts = c->yparts; g.xa = c->xa; g.n_xa = c->n_xa; g.ya = c->ya; g.n_ya = c->n_ya; g.part_stride = c->part_stride;
+    g.sl_n = c->sl_n; g.sl_T = c->sl_T; g.sl_x = c->sl_x; g.sl_y = c->sl_y;
+    for (int j = 0; j < 8; ++j) g.sl_id[j] = c->sl_id[j];
+    g.dw_hist = c->dw_hist; g.dw_w = c->dw_w; g.dw_b = c->dw_b; g.dw_gamma = c->dw_gamma; g.dw_nw = c->dw_nw;
+    g.dw_xout = c->dw_xout; g.dw_hnew = c->dw_hnew;
+    g.nt = 1;
+    if (!vv_gemv_ok(&g)) return VV_GEMV_REFUSED;
+    int form[5] = {0, 0, 0, 0, 0};
+    const int r = vv_gemv_launch(g, xsplit, (hipStream_t)stream, form);
+    if (r == -3) return VV_GEMV_REFUSED;
+    if (r == 0 && form_out) for (int j = 0; j < 5; ++j) form_out[j] = form[j];
+    return r;
+}
 // tests: Y = f(X) . W^T through the prefill GEMM (prefill.hip): X fp32 [T][K] is packed (optionally RMS-normalised) into xp_scratch,
 // epi STORE/BIAS/RESID write fp32 Y [T][N]; epi SWIGLU (W = gate, W2 = up) writes packed bf16 into yp_scratch, unpacked to Y.
 extern "C" int vv_gemm3_raw(vv_ctx* ctx, void* stream, const void* w, const void* w2, const float* x_dev, int T, int N, int K, int epi,

@@ -478,7 +478,7 @@ static void launch_t(const VVGemm& a, dim3 grid, size_t smem, hipStream_t s) {
 static int pow2_floor(int v) { int p = 1; while (p * 2 <= v) p *= 2; return p; }
 
 extern "C" int vv_gemv_ok(const VVGemm* a);
-extern "C" int vv_gemv_launch(VVGemm a, int xs, hipStream_t s);
+extern "C" int vv_gemv_launch(VVGemm a, int xs, hipStream_t s, int* form);
 
 // Chooses the kernel and its decomposition.  `xs` in {1,2,3}.
 extern "C" int vv_tile_ok(const VVGemm* a, int xs);
@@ -490,7 +490,7 @@ extern "C" int vv_gemm_launch(VVGemm a, int xs, hipStream_t s) {
             if (r != -3) return r;
         }
         if (xs > 2 || !vv_gemv_ok(&a)) return -4;
-        const int r = vv_gemv_launch(a, xs, s);
+        const int r = vv_gemv_launch(a, xs, s, nullptr);
         return r == -3 ? -4 : r;
     }
     if (vv_tile_ok(&a, xs)) {      // tall activations: MFMA tile GEMM (tile.hip)
@@ -498,7 +498,7 @@ extern "C" int vv_gemm_launch(VVGemm a, int xs, hipStream_t s) {
         if (r != -3) return r;
     }
     if (a.ksplit <= 0 && vv_gemv_ok(&a) && (a.T <= 4 || xs <= 2)) {
-        const int r = vv_gemv_launch(a, xs, s);
+        const int r = vv_gemv_launch(a, xs, s, nullptr);
         if (r != -3) return r;                 // -3: no instantiation for this (pair, rows, split mode): general kernel
     }
     if (a.kgrid > 1 || a.n_xa > 0 || a.n_ya > 0) return -4;      // part tensors exist only on the decode GEMV path

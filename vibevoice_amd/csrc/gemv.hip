@@ -498,6 +498,9 @@ extern "C" int vv_gemv_ok(const VVGemm* a) {
                 (int64_t)a->sl_id[j] * a->sl_y + (int64_t)a->sl_T * a->ldy >= (1LL << 30)) return 0;
     }
     if ((a->x_row_mod > 0 || a->add_rows_per_vec > 0) && a->pro != VV_PRO_ADD_SILU) return 0;
+    // CFG + solver epilogue: row r (cond) meets row r + n_cfg (uncond) by a lane shuffle inside ONE 16-row tile, and z / x0p are
+    // indexed by the tile-local row -- so the launch is exactly the 2 * n_cfg rows of one tile (decode forms: n_cfg <= 2)
+    if (a->epi == VV_EPI_CFG_DPM && (a->n_cfg < 1 || a->T != 2 * a->n_cfg || a->T > 16 || !a->z || !a->x0p || !a->coef)) return 0;
     if (a->pro == VV_PRO_NORMDW) {     // one row, whole K inside every workgroup, every operand present and 16-B aligned
         if (a->T != 1 || a->sl_n > 0 || a->kgrid > 1 || a->n_xa || a->n_ya || !a->dw_hist || !a->dw_w || !a->dw_b || !a->dw_gamma ||
             !a->dw_nw || !a->dw_xout || !a->dw_hnew || a->dw_xout == a->X) return 0;
@@ -569,12 +572,15 @@ static bool gemv_parts_ok(int pro, int epi, bool xside) {
     return false;
 }
 
-extern "C" int vv_gemv_launch(VVGemm a, int xs, hipStream_t s) {
+// form (optional, tests): receives {XS, MR, WPB, PARTS, SL} of the instantiation this call launches -- written by the launch
+// macros themselves, so it IS the dispatch decision, not a restatement of it.  The engine passes nullptr.
+#define VV_FORM(XS_, MR_, WP_, PT_, SL_) do { if (form) { form[0] = XS_; form[1] = MR_; form[2] = WP_; form[3] = PT_; form[4] = SL_; } } while (0)
+extern "C" int vv_gemv_launch(VVGemm a, int xs, hipStream_t s, int* form) {
     const int n_tiles = (a.N + 15) / 16, k_tiles = (a.K + 31) / 32;
     if (a.epi == VV_EPI_SWIGLU && !a.W2) return -1;
     dim3 grid(n_tiles);
 #define VV_GO(XS_, P, E, MR_, WP_)                                                                      \
-    do { hipLaunchKernelGGL((vv_gemv_kernel<XS_, P, E, MR_, WP_>), grid, dim3(WP_ * 64), 0, s, a.W, a.W2, a.X, a.Y, a.nw, a.T, a.N, a.K, a.ldx, a.ldy, a);       \
+    do { VV_FORM(XS_, MR_, WP_, 0, 0); hipLaunchKernelGGL((vv_gemv_kernel<XS_, P, E, MR_, WP_>), grid, dim3(WP_ * 64), 0, s, a.W, a.W2, a.X, a.Y, a.nw, a.T, a.N, a.K, a.ldx, a.ldy, a);       \
          return vv_launch_rc(0); } while (0)
     if (a.T > 4 || a.sl_n > 0) {
         if (xs > 2) return -3;       // 16-row staging tiles of the exact mode exceed the LDS: general kernel
@@ -585,7 +591,7 @@ extern "C" int vv_gemv_launch(VVGemm a, int xs, hipStream_t s) {
         // thresholds 64..128 vs 512 (DESIGN.md section 8 lists the sweep).
         if (a.sl_n > 0) {
 #define VV_GOSL(XS_, P, E, WP_)                                                                         \
-    do { hipLaunchKernelGGL((vv_gemv_kernel<XS_, P, E, 16, WP_, 0, 1>), grid, dim3(WP_ * 64), 0, s, a.W, a.W2, a.X, a.Y, a.nw, a.T, a.N, a.K, a.ldx, a.ldy, a);   \
+    do { VV_FORM(XS_, 16, WP_, 0, 1); hipLaunchKernelGGL((vv_gemv_kernel<XS_, P, E, 16, WP_, 0, 1>), grid, dim3(WP_ * 64), 0, s, a.W, a.W2, a.X, a.Y, a.nw, a.T, a.N, a.K, a.ldx, a.ldy, a);   \
          return vv_launch_rc(0); } while (0)
 #define X(P, E) if (a.pro == P && a.epi == E) { if (xs == 2) VV_GOSL(2, P, E, 8); else if ((int64_t)n_tiles * grid.y > wide4_wgs) VV_GOSL(1, P, E, 4); else VV_GOSL(1, P, E, 8); }
             VV_GEMV_SL(X)
@@ -609,10 +615,10 @@ extern "C" int vv_gemv_launch(VVGemm a, int xs, hipStream_t s) {
     if (a.n_xa > 0 || a.n_ya > 0) {           // consumers of a K-split tensor (decode rows only)
         if (a.kgrid > 1) grid.y = a.kgrid;
 #define VV_GOP(XS_, P, E, WP_, S_)                                                                      \
-    do { hipLaunchKernelGGL((vv_gemv_kernel<XS_, P, E, 4, WP_, S_>), grid, dim3(WP_ * 64), 0, s, a.W, a.W2, a.X, a.Y, a.nw, a.T, a.N, a.K, a.ldx, a.ldy, a);     \
+    do { VV_FORM(XS_, 4, WP_, S_, 0); hipLaunchKernelGGL((vv_gemv_kernel<XS_, P, E, 4, WP_, S_>), grid, dim3(WP_ * 64), 0, s, a.W, a.W2, a.X, a.Y, a.nw, a.T, a.N, a.K, a.ldx, a.ldy, a);     \
          return vv_launch_rc(0); } while (0)
 #define VV_GOP2(P, E)   /* two rows, wide output: the 2-row form of the K-split consumer (7B-width A/B of the column split, round 6) */ \
-    do { hipLaunchKernelGGL((vv_gemv_kernel<1, P, E, 2, 4, 1>), grid, dim3(256), 0, s, a.W, a.W2, a.X, a.Y, a.nw, a.T, a.N, a.K, a.ldx, a.ldy, a);     \
+    do { VV_FORM(1, 2, 4, 1, 0); hipLaunchKernelGGL((vv_gemv_kernel<1, P, E, 2, 4, 1>), grid, dim3(256), 0, s, a.W, a.W2, a.X, a.Y, a.nw, a.T, a.N, a.K, a.ldx, a.ldy, a);     \
          return vv_launch_rc(0); } while (0)
 #define X(P, E)                                                                                         \
     if (a.pro == P && a.epi == E) {                                                                     \
@@ -658,5 +664,6 @@ extern "C" int vv_gemv_launch(VVGemm a, int xs, hipStream_t s) {
     VV_GEMV_COMBOS(X)
 #undef X
 #undef VV_GO
+#undef VV_FORM
     return -3;
 }

@@ -530,3 +530,130 @@ class Engine:
                                   self._p(nscale), xsplit or self.cfg.xsplit, ksplit, nontemporal)
         if rc != 0:
             raise EngineError(f"vv_gemm_raw failed ({rc})")
+
+    # prologue / epilogue ids of csrc/vv_common.h
+    PRO_NONE, PRO_RMS, PRO_RMS_MOD, PRO_ADD_SILU, PRO_NORMDW = 0, 1, 2, 3, 4
+    EPI_STORE, EPI_BIAS, EPI_BIAS_GELU, EPI_SWIGLU, EPI_RESID, EPI_GATED_RESID, EPI_CFG_DPM = 0, 1, 2, 3, 4, 5, 6
+
+    def gemv_case(self, wp, x, y, T, N, K, *, ldx=None, ldy=None, pro=0, epi=0, w2p=None, nw=None, eps=1e-6, bias=None, nscale=None,
+                  mod_scale=None, mod_shift=None, ld_mod=0, addvec=None, x_row_mod=0, add_rows_per_vec=0, gate=None, ld_gate=0,
+                  z=None, x0p=None, coef=None, cfg=0.0, n_cfg=0, sde_noise=None,
+                  kgrid=0, yparts=None, xa=None, n_xa=0, ya=None, n_ya=0, part_stride=0,
+                  sl_n=0, sl_T=0, sl_x=0, sl_y=0, sl_id=(),
+                  dw_hist=None, dw_w=None, dw_b=None, dw_gamma=None, dw_nw=None, dw_xout=None, dw_hnew=None,
+                  xsplit=None, unaligned_ok=()):
+        """One launch of the decode GEMV kernel (vv_gemv_case), or a refusal.  Returns the form the launcher chose,
+        (XS, MR, WPB, PARTS, SL), or None when nothing was launched (the kernel's eligibility check or its launcher refused).
+
+        Every tensor is checked BEFORE the call -- device, dtype (fp32; packed weights uint8), contiguity, 16-byte alignment and a
+        size that covers every address the kernel can form from T, N, K and the strides -- and a mismatch raises ValueError: a
+        wrong argument must fail here, not as an out-of-bounds access on the GPU.  unaligned_ok names tensors whose alignment
+        check is waived, for callers that test the refusal of a misaligned operand (their size is still checked).
+        Asynchronous: the caller syncs."""
+        ldx = K if ldx is None else ldx
+        ldy = N if ldy is None else ldy
+        xs = self.cfg.xsplit if xsplit is None else xsplit
+        ints = dict(T=T, N=N, K=K, ldx=ldx, ldy=ldy, pro=pro, epi=epi, ld_mod=ld_mod, x_row_mod=x_row_mod, add_rows_per_vec=add_rows_per_vec,
+                    ld_gate=ld_gate, n_cfg=n_cfg, kgrid=kgrid, n_xa=n_xa, n_ya=n_ya, part_stride=part_stride, sl_n=sl_n, sl_T=sl_T,
+                    sl_x=sl_x, sl_y=sl_y, xsplit=xs)
+        for k, v in ints.items():
+            if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v < 0 or v >= (1 << 30):
+                raise ValueError(f"gemv_case: {k} = {v!r} is not an int in [0, 2^30)")
+        if T < 1 or N < 1 or K < 1:
+            raise ValueError(f"gemv_case: T, N, K = {T}, {N}, {K} must be positive")
+        if xs not in (1, 2, 3):
+            raise ValueError(f"gemv_case: xsplit = {xs}")
+        if not 0 <= pro <= 4 or not 0 <= epi <= 6:
+            raise ValueError(f"gemv_case: pro = {pro}, epi = {epi}")
+        if ldx < K or ldy < N:
+            raise ValueError(f"gemv_case: ldx = {ldx} < K = {K} or ldy = {ldy} < N = {N}")
+        sl_id = [int(v) for v in sl_id]
+        if sl_n > 8 or len(sl_id) < sl_n or len(sl_id) > 8 or any(v < 0 or v >= (1 << 20) for v in sl_id):
+            raise ValueError(f"gemv_case: sl_n = {sl_n}, sl_id = {sl_id}")
+        if sl_n > 0 and (sl_T < 1 or T != sl_n * sl_T):
+            raise ValueError(f"gemv_case: T = {T} is not sl_n * sl_T = {sl_n} * {sl_T}")
+        if sl_n == 0 and (sl_T or sl_x or sl_y or sl_id):
+            raise ValueError("gemv_case: slot fields without sl_n")
+
+        def need(name, t, numel, dtype=torch.float32, required=True):
+            if t is None:
+                if required:
+                    raise ValueError(f"gemv_case: {name} is required here")
+                return
+            if not isinstance(t, torch.Tensor) or t.device != self.device:
+                raise ValueError(f"gemv_case: {name} is not a tensor on {self.device}")
+            if t.dtype != dtype:
+                raise ValueError(f"gemv_case: {name} is {t.dtype}, expected {dtype}")
+            if not t.is_contiguous():
+                raise ValueError(f"gemv_case: {name} is not contiguous")
+            if t.data_ptr() % 16 and name not in unaligned_ok:
+                raise ValueError(f"gemv_case: {name} is not 16-byte aligned")
+            if t.numel() < numel:
+                raise ValueError(f"gemv_case: {name} holds {t.numel()} elements, the launch addresses {numel}")
+
+        def extent(rows, ld, width, slot_stride):
+            """elements from the base pointer to the end of the last addressable row"""
+            if sl_n > 0 and slot_stride > 0:
+                return max(sl_id[:sl_n]) * slot_stride + (sl_T - 1) * ld + width
+            return (rows - 1) * ld + width
+        x_rows = x_row_mod if x_row_mod > 0 else T
+        x_need = extent(x_rows, ldx, K, sl_x)
+        y_need = extent(T, ldy, N, sl_y)
+        wbytes = int(self.lib.vv_packed_bytes(N, K))
+        need("wp", wp, wbytes, torch.uint8)
+        need("w2p", w2p, wbytes, torch.uint8, required=epi == self.EPI_SWIGLU)
+        need("x", x, x_need)
+        need("y", y, y_need, required=epi != self.EPI_CFG_DPM)
+        need("nw", nw, K, required=False)
+        need("bias", bias, N, required=False)
+        need("nscale", nscale, N, required=False)
+        is_mod = pro == self.PRO_RMS_MOD
+        if is_mod and ld_mod < K:
+            raise ValueError(f"gemv_case: ld_mod = {ld_mod} < K = {K}")
+        need("mod_scale", mod_scale, (T - 1) * ld_mod + K, required=is_mod)
+        need("mod_shift", mod_shift, (T - 1) * ld_mod + K, required=is_mod)
+        n_vec = (T - 1) // add_rows_per_vec + 1 if add_rows_per_vec > 0 else 1
+        need("addvec", addvec, n_vec * K, required=pro == self.PRO_ADD_SILU)
+        is_gated = epi == self.EPI_GATED_RESID
+        if is_gated and ld_gate < N:
+            raise ValueError(f"gemv_case: ld_gate = {ld_gate} < N = {N}")
+        need("gate", gate, (T - 1) * ld_gate + N, required=is_gated)
+        is_cfg = epi == self.EPI_CFG_DPM
+        if is_cfg and n_cfg < 1:
+            raise ValueError("gemv_case: the CFG epilogue needs n_cfg >= 1")
+        need("z", z, 2 * n_cfg * N, required=is_cfg)       # dense [2 n_cfg][N]: the epilogue addresses them by n_cfg, not by T or ldy
+        need("x0p", x0p, n_cfg * N, required=is_cfg)
+        need("coef", coef, 6, required=is_cfg)
+        need("sde_noise", sde_noise, n_cfg * N, required=False)
+        if (kgrid > 1 or n_xa or n_ya) and part_stride < max(x_need if n_xa else 0, y_need if (kgrid > 1 or n_ya) else 0):
+            raise ValueError(f"gemv_case: part_stride = {part_stride} is smaller than one part tensor")
+        need("yparts", yparts, (kgrid - 2) * part_stride + y_need if kgrid > 1 else 0, required=kgrid > 1)
+        need("xa", xa, (max(n_xa, 2) - 1) * part_stride + x_need, required=n_xa > 0)
+        need("ya", ya, (max(n_ya, 2) - 1) * part_stride + y_need, required=n_ya > 0)
+        is_dw = pro == self.PRO_NORMDW
+        for name, t, rows in (("dw_hist", dw_hist, 6), ("dw_w", dw_w, 7), ("dw_b", dw_b, 1), ("dw_gamma", dw_gamma, 1), ("dw_nw", dw_nw, 1),
+                              ("dw_xout", dw_xout, 1), ("dw_hnew", dw_hnew, 1)):
+            need(name, t, rows * K, required=is_dw)
+
+        a = _lib.VVGemvCase()
+        p = lambda t: t.data_ptr() if t is not None else None
+        a.W, a.W2, a.X, a.Y = p(wp), p(w2p), p(x), p(y)
+        a.T, a.N, a.K, a.ldx, a.ldy, a.pro, a.epi = T, N, K, ldx, ldy, pro, epi
+        a.nw, a.eps, a.bias, a.nscale = p(nw), float(eps), p(bias), p(nscale)
+        a.mod_scale, a.mod_shift, a.ld_mod = p(mod_scale), p(mod_shift), ld_mod
+        a.addvec, a.x_row_mod, a.add_rows_per_vec = p(addvec), x_row_mod, add_rows_per_vec
+        a.gate, a.ld_gate = p(gate), ld_gate
+        a.z, a.x0p, a.coef, a.cfg, a.n_cfg, a.sde_noise = p(z), p(x0p), p(coef), float(cfg), n_cfg, p(sde_noise)
+        a.kgrid, a.yparts, a.xa, a.n_xa, a.ya, a.n_ya, a.part_stride = kgrid, p(yparts), p(xa), n_xa, p(ya), n_ya, part_stride
+        a.sl_n, a.sl_T, a.sl_x, a.sl_y = sl_n, sl_T, sl_x, sl_y
+        for j, v in enumerate(sl_id):
+            a.sl_id[j] = v
+        a.dw_hist, a.dw_w, a.dw_b, a.dw_gamma, a.dw_nw = p(dw_hist), p(dw_w), p(dw_b), p(dw_gamma), p(dw_nw)
+        a.dw_xout, a.dw_hnew = p(dw_xout), p(dw_hnew)
+        form = (C.c_int * 5)()
+        rc = self.lib.vv_gemv_case(self._s, C.byref(a), xs, form)
+        if rc == _lib.GEMV_REFUSED:
+            return None
+        if rc != 0:
+            raise EngineError(f"vv_gemv_case failed ({rc})")
+        return tuple(form)
