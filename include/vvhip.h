@@ -179,6 +179,12 @@ int vv_diffusion_sample(vv_ctx* ctx, void* stream, int n, const float* cond_dev,
  * Needs a table from vv_set_schedule_sde; vv_diffusion_sample refuses to run on a stochastic table. */
 int vv_diffusion_sample_sde(vv_ctx* ctx, void* stream, int n, const float* cond_dev, const float* noise_dev,
                             const float* step_noise_dev, float cfg_scale, float* latent_out_dev);
+/* vv_diffusion_sample / vv_diffusion_sample_sde with one guidance scale per utterance: cfg_rows_dev [n] fp32, read by the
+ * kernels at run time (the values are NOT part of the graph key; rewriting the buffer between calls needs no re-capture).
+ * step_noise_dev == NULL: deterministic table required; non-NULL: stochastic table required (the same guard rails as the two
+ * scalar entry points).  New surface: the reference's sample_speech_tokens takes one cfg_scale for the whole batch. */
+int vv_diffusion_sample_rows(vv_ctx*, void* stream, int n, const float* cond_dev, const float* noise_dev,
+                             const float* step_noise_dev, const float* cfg_rows_dev, float* latent_out_dev);
 /* one prediction_head forward (modular_vibevoice_diffusion_head.py:254-280) for tests:
  * noisy [n][latent], t[n] (host), cond [n][H] -> out [n][latent].  Synchronous. */
 int vv_head_forward(vv_ctx* ctx, void* stream, int n, const float* noisy_dev, const float* t_host,
@@ -254,6 +260,7 @@ typedef struct vv_gemv_case_args {
     int sl_n, sl_T, sl_x, sl_y; int sl_id[8];
     const float* dw_hist; const float* dw_w; const float* dw_b; const float* dw_gamma; const float* dw_nw;
     float* dw_xout; float* dw_hnew;
+    const float* cfg_rows;      /* VV_EPI_CFG_DPM: [n_cfg] one guidance scale per utterance row, or NULL (cfg for every row) */
 } vv_gemv_case_args;
 int vv_gemv_case(void* stream, const vv_gemv_case_args* args, int xsplit, int* form_out);
 /* The prompt-prefill GEMM (bf16-activation mode): x_dev fp32 [T][K] is packed (RMS-normalised when nw_dev != NULL) into

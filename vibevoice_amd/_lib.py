@@ -41,6 +41,7 @@ class VVGemvCase(C.Structure):
         ("kgrid", C.c_int), ("yparts", _P), ("xa", _P), ("n_xa", C.c_int), ("ya", _P), ("n_ya", C.c_int), ("part_stride", C.c_int),
         ("sl_n", C.c_int), ("sl_T", C.c_int), ("sl_x", C.c_int), ("sl_y", C.c_int), ("sl_id", C.c_int * 8),
         ("dw_hist", _P), ("dw_w", _P), ("dw_b", _P), ("dw_gamma", _P), ("dw_nw", _P), ("dw_xout", _P), ("dw_hnew", _P),
+        ("cfg_rows", _P),
     ]
 
 
@@ -68,6 +69,7 @@ _SIGS = {
     "vv_lm_logits_full": (C.c_int, [_P, _P, C.c_int, _P, _P]),
     "vv_diffusion_sample": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_float, _P]),
     "vv_diffusion_sample_sde": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_float, _P]),
+    "vv_diffusion_sample_rows": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P]),
     "vv_head_forward": (C.c_int, [_P, _P, C.c_int, _P, C.POINTER(C.c_float), _P, _P]),
     "vv_codec_decode": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int]),
     "vv_semantic_encode": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),

@@ -63,7 +63,8 @@ int vv_stem_conv_launch(const float* in, const void* wp, const float* bias, floa
 int vv_head_conv1_launch(const float* x, const void* wp, const float* bias, float* out, int T, int Cin, hipStream_t s);
 int vv_shift_rows_launch(const void* tab, int n_entries, int maxC, hipStream_t s);
 int vv_zero_hist_launch(const void* tab, int n_entries, hipStream_t s);
-int vv_cfg_dpm_launch(const float* eps, float* x, float* x0_prev, const float* coef, float cfg, int n, int L, const float* sde_noise, hipStream_t s);
+int vv_cfg_dpm_launch(const float* eps, float* x, float* x0_prev, const float* coef, float cfg, int n, int L, const float* sde_noise,
+                      const float* cfg_rows, hipStream_t s);
 int vv_affine_launch(const float* x, float* y, float mul, float add, int n, hipStream_t s);
 int vv_copy_launch(void* dst, const void* src, size_t bytes, hipStream_t s);
 int vv_zero_launch(void* dst, size_t bytes, hipStream_t s);
@@ -1371,7 +1372,8 @@ static int set_schedule(vv_ctx* ctx, int n_steps, const float* t, const float* c
         }
     }
     for (auto it = ctx->graphs.begin(); it != ctx->graphs.end();) {
-        if (it->first.rfind("samp", 0) == 0 || it->first.rfind("sde:", 0) == 0) { hipGraphExecDestroy(it->second.exec); it = ctx->graphs.erase(it); } else ++it;
+        // every sampler key family: a captured sample_body holds the step count, the table offsets and the buffers reallocated above
+        if (it->first.rfind("samp", 0) == 0 || it->first.rfind("sde:", 0) == 0 || it->first.rfind("rows:", 0) == 0) { hipGraphExecDestroy(it->second.exec); it = ctx->graphs.erase(it); } else ++it;
     }
     return 0;
 }
@@ -1756,7 +1758,9 @@ extern "C" int vv_lm_logits(vv_ctx* ctx, void* stream, int n, const float* hidde
 // one head evaluation on 2n rows; mod/xh/hact/eps are ctx scratch. temb = t-embedding row for this step.
 static int head_eval(vv_ctx* ctx, hipStream_t st, int rows, const float* zrows, const float* temb_row, float* eps_out,
                      const float* coef = nullptr, float cfg = 0.f, const float* mod_ready = nullptr, const float* sde_noise = nullptr,
-                     const unsigned char* sh_tiles = nullptr, int gen = 0, bool have_x = false, bool seam = false) {
+                     const unsigned char* sh_tiles = nullptr, int gen = 0, bool have_x = false, bool seam = false,
+                     const float* cfg_rows = nullptr) {
+    // cfg_rows: [rows / 2] one guidance scale per utterance on the device, read by the final layer's epilogue in place of cfg (null: cfg)
     // gen / have_x / seam (sampler, decode rows, bf16 mode): the step's state is generation `gen` (xh / zz / x0p or their second copies);
     // have_x: the previous step's seam launch already produced this step's in-projection; seam: end this step with the fused launch
     // (final layer + CFG + solver update + the NEXT step's in-projection, written to the other generation) instead of the final layer
@@ -1822,6 +1826,7 @@ static int head_eval(vv_ctx* ctx, hipStream_t st, int rows, const float* zrows, 
         af.ssq_in = ctx->ssq_a; af.ssq_tiles = H / 16; af.eps = c.head_eps;
         af.Xs = (const u32x4*)(sh_tiles + (size_t)HL * ctx->p16_shift_tile);
         af.z = zcur; af.x0p = x0cur; af.coef = coef; af.cfg = cfg; af.n_cfg = rows / 2; af.sde_noise = sde_noise;
+        af.cfg_rows = cfg_rows;
         VVCHK(p16_go(ctx, st, af, VV_EPI_CFG_DPM, 3));
         return 0;
     }
@@ -1832,7 +1837,7 @@ static int head_eval(vv_ctx* ctx, hipStream_t st, int rows, const float* zrows, 
         t.sc = fb + H; t.sh = fb; t.ld_mod = MODW;
         t.Xout = gen ? ctx->xh : ctx->xh2;
         t.z_in = zcur; t.x0p_in = x0cur; t.z_out = gen ? ctx->zz : ctx->zz2; t.x0p_out = gen ? ctx->x0p : ctx->x0p2;
-        t.coef = coef; t.cfg = cfg; t.n_cfg = rows / 2; t.sde_noise = sde_noise;
+        t.coef = coef; t.cfg = cfg; t.n_cfg = rows / 2; t.sde_noise = sde_noise; t.cfg_rows = cfg_rows;
         t.T = rows; t.H = H; t.L = L; t.eps = c.head_eps;
         if (vv_head_tail_ok(&t)) {
             ctx->launches++;
@@ -1851,14 +1856,14 @@ static int head_eval(vv_ctx* ctx, hipStream_t st, int rows, const float* zrows, 
     gf.xa = ctx->xh_parts + (size_t)(HL & 1) * 2 * xps; gf.n_xa = xp; gf.part_stride = xps;
     if (coef) {   // CFG + DPM-Solver++ update fused into the epilogue: the noisy latent is rewritten in place
         gf.epi = VV_EPI_CFG_DPM; gf.z = zcur; gf.x0p = x0cur; gf.coef = coef; gf.cfg = cfg; gf.n_cfg = rows / 2;
-        gf.sde_noise = sde_noise;
+        gf.sde_noise = sde_noise; gf.cfg_rows = cfg_rows;
     }
     GEMM(gf);
     return 0;
 }
 
 static int sample_body(vv_ctx* ctx, hipStream_t st, int n, const float* cond, const float* noise, float cfg, float* latent_out,
-                       const float* step_noise = nullptr) {
+                       const float* step_noise = nullptr, const float* cfg_rows = nullptr) {
     const vv_config& c = ctx->c;
     const int H = ctx->H, L = c.latent_dim;
     const int rows = 2 * n;
@@ -1915,7 +1920,7 @@ static int sample_body(vv_ctx* ctx, hipStream_t st, int n, const float* cond, co
         // in-projection, headtail.hip), which leaves the next step's state in the other generation of (xh, zz, x0p)
         const bool seam = (i + 1 < ctx->n_steps) && rows == 2 && ctx->head_tail;
         const int hr = head_eval(ctx, st, rows, gen ? ctx->zz2 : ctx->zz, ctx->temb + (size_t)i * H, ctx->eps, ctx->coef + i * 6, cfg, mod_i, sn, sht,
-                                 gen, have_x, seam);
+                                 gen, have_x, seam, cfg_rows);
         if (hr < 0) return -1;
         if (ctx->probe_on) {
             char nm[64];
@@ -1955,6 +1960,24 @@ extern "C" int vv_diffusion_sample_sde(vv_ctx* ctx, void* stream, int n, const f
     char key[160]; snprintf(key, 160, "sde:%d:%p:%p:%p:%p:%a", n, (const void*)cond_dev, (const void*)noise_dev, (const void*)step_noise_dev,
                             (void*)latent_out_dev, cfg_scale);
     return graphed(ctx, key, st, [&]() { return sample_body(ctx, st, n, cond_dev, noise_dev, cfg_scale, latent_out_dev, step_noise_dev); });
+}
+
+// Either sampler with one guidance scale per utterance, cfg_rows_dev [n] fp32.  The kernels read the values at run time: the graph key
+// holds the POINTER, so rewriting the buffer between calls replays the same captured graph.
+extern "C" int vv_diffusion_sample_rows(vv_ctx* ctx, void* stream, int n, const float* cond_dev, const float* noise_dev,
+                                        const float* step_noise_dev, const float* cfg_rows_dev, float* latent_out_dev) {
+    hipStream_t st = (hipStream_t)stream;
+    if (ctx->n_steps < 1) return fail(ctx, "vv_set_schedule / vv_set_schedule_sde has not been called");
+    if (n < 1 || n > 8) return fail(ctx, "vv_diffusion_sample_rows: n must be in [1,8]");
+    if (!cfg_rows_dev) return fail(ctx, "vv_diffusion_sample_rows: cfg_rows is null");
+    if (ctx->sde_on && !step_noise_dev) return fail(ctx, "the schedule is stochastic (vv_set_schedule_sde): vv_diffusion_sample_rows needs its per-step noise");
+    if (!ctx->sde_on && step_noise_dev) return fail(ctx, "the schedule is deterministic (vv_set_schedule): vv_diffusion_sample_rows takes no step noise");
+    ctx->launches = 0;
+    char key[192]; snprintf(key, 192, "rows:%d:%p:%p:%p:%p:%p", n, (const void*)cond_dev, (const void*)noise_dev, (const void*)step_noise_dev,
+                            (const void*)cfg_rows_dev, (void*)latent_out_dev);
+    const int rc = graphed(ctx, key, st, [&]() { return sample_body(ctx, st, n, cond_dev, noise_dev, 0.f, latent_out_dev, step_noise_dev, cfg_rows_dev); });
+    nan_probe_report(ctx, st, key);
+    return rc;
 }
 
 extern "C" int vv_head_forward(vv_ctx* ctx, void* stream, int n, const float* noisy_dev, const float* t_host, const float* cond_dev, float* out_dev) {
@@ -2181,6 +2204,7 @@ extern "C" int vv_gemv_case(void* stream, const vv_gemv_case_args* c, int xsplit
     g.addvec = c->addvec; g.x_row_mod = c->x_row_mod; g.add_rows_per_vec = c->add_rows_per_vec;
     g.gate = c->gate; g.ld_gate = c->ld_gate;
     g.z = c->z; g.x0p = c->x0p; g.coef = c->coef; g.cfg = c->cfg; g.n_cfg = c->n_cfg; g.sde_noise = c->sde_noise;
+    g.cfg_rows = c->cfg_rows;
     g.kgrid = c->kgrid; g.yparts = c->yparts; g.xa = c->xa; g.n_xa = c->n_xa; g.ya = c->ya; g.n_ya = c->n_ya; g.part_stride = c->part_stride;
     g.sl_n = c->sl_n; g.sl_T = c->sl_T; g.sl_x = c->sl_x; g.sl_y = c->sl_y;
     for (int j = 0; j < 8; ++j) g.sl_id[j] = c->sl_id[j];

@@ -358,6 +358,8 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemm_kernel(const VVGemm a) {
     if (frow >= Tt) return;
     float rs = 1.0f;
     if (a.pro == VV_PRO_RMS) rs = rsqrtf(my_ssq / (float)a.K + a.eps);
+    float cfg = a.cfg;
+    if (a.epi == VV_EPI_CFG_DPM && a.cfg_rows && frow < a.n_cfg) cfg = a.cfg_rows[frow];     // one guidance scale per utterance row
 #pragma unroll
     for (int i = 0; i < NT; ++i) {
         const int n0 = (tile0 + i) * 16 + fq * 4;
@@ -375,7 +377,7 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemm_kernel(const VVGemm a) {
                 const float vu = __shfl(o4[r], lane + nc);
                 const int n = n0 + r;
                 if (frow < nc && n < a.N) {
-                    const float v = vu + a.cfg * (o4[r] - vu);
+                    const float v = vu + cfg * (o4[r] - vu);
                     const int64_t zi = (int64_t)frow * a.N + n;
                     const float zo = a.z[zi];
                     const float x0 = ca * zo - cs_ * v;

@@ -116,7 +116,7 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemv_kernel(const u32x4* __restri
     asm volatile("" ::"s"(a.ld_mod), "s"(a.ld_gate), "s"(a.x_row_mod), "s"(a.add_rows_per_vec),
                  "s"(a.eps), "s"(a.z), "s"(a.x0p), "s"(a.coef), "s"(a.cfg), "s"(a.n_cfg));
     asm volatile("" ::"s"(a.yparts), "s"(a.xa), "s"(a.ya), "s"(a.n_xa), "s"(a.n_ya), "s"(a.part_stride));
-    if constexpr (EPI == VV_EPI_CFG_DPM) asm volatile("" ::"s"(a.sde_noise));
+    if constexpr (EPI == VV_EPI_CFG_DPM) asm volatile("" ::"s"(a.sde_noise), "s"(a.cfg_rows));
     VV_STAMP(0);
     VV_BSTAMP(0);
     const int lane = threadIdx.x & 63;
@@ -451,12 +451,14 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemv_kernel(const u32x4* __restri
         const int nc = a.n_cfg;
         const float ca = a.coef[0], cs_ = a.coef[1], csx = a.coef[2], c0 = a.coef[3], c1 = a.coef[4];
         const float cn = a.sde_noise ? a.coef[5] : 0.f;          // sde-dpmsolver++: + cn * eps_i (dpm_solver.py:680-686, 785-793)
+        float cfg = a.cfg;
+        if (a.cfg_rows && frow < nc) cfg = a.cfg_rows[frow];     // one guidance scale per utterance row
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float vu = __shfl(o[r], lane + nc);
             const int n = n0 + r;
             if (frow < nc && n < pN) {
-                const float v = vu + a.cfg * (o[r] - vu);
+                const float v = vu + cfg * (o[r] - vu);
                 const unsigned zi = (unsigned)(frow * pN + n);
                 const float zo = a.z[zi];
                 const float x0 = ca * zo - cs_ * v;

@@ -280,13 +280,15 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemv16p_kernel(const VVGemv16p a)
         const int nc = a.n_cfg;
         const float ca = a.coef[0], cs_ = a.coef[1], csx = a.coef[2], c0 = a.coef[3], c1 = a.coef[4];
         const float cn = a.sde_noise ? a.coef[5] : 0.f;
+        float cfg = a.cfg;
+        if (a.cfg_rows && frow < nc) cfg = a.cfg_rows[frow];     // one guidance scale per utterance row
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float oc = acc[0][r];
             const float vu = __shfl(oc, lane + nc);
             const int n = n0 + r;
             if (frow < nc && n < a.N) {
-                const float v = vu + a.cfg * (oc - vu);
+                const float v = vu + cfg * (oc - vu);
                 const unsigned zi = (unsigned)(frow * a.N + n);
                 const float zo = a.z[zi];
                 const float x0 = ca * zo - cs_ * v;

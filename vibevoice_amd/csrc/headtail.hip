@@ -47,7 +47,7 @@ __global__ __launch_bounds__(512) void vv_head_tail_kernel(const VVTail a) {
     const unsigned kper = (k_tiles + WPB - 1) / WPB;
     const unsigned kt0 = wave * kper, kt1 = min(k_tiles, kt0 + kper);
     const unsigned nk = (kt1 > kt0) ? kt1 - kt0 : 0u;
-    asm volatile("" ::"s"(a.coef), "s"(a.z_in), "s"(a.x0p_in), "s"(a.sde_noise), "s"(a.z_out), "s"(a.x0p_out), "s"(a.Xout), "s"(a.cfg));
+    asm volatile("" ::"s"(a.coef), "s"(a.z_in), "s"(a.x0p_in), "s"(a.sde_noise), "s"(a.z_out), "s"(a.x0p_out), "s"(a.Xout), "s"(a.cfg), "s"(a.cfg_rows));
     // ---- first weight batches go out before anything else (L2-resident: 4 latent tiles per k-step) ----
     u32x4 wA[WB][NT], wB[WB][NT];
     auto w_load = [&](unsigned kb, u32x4 (&w)[WB][NT]) {
@@ -72,10 +72,12 @@ __global__ __launch_bounds__(512) void vv_head_tail_kernel(const VVTail a) {
     const int nc = a.n_cfg;
     float4 pz = {0.f, 0.f, 0.f, 0.f}, px = {0.f, 0.f, 0.f, 0.f}, pn = {0.f, 0.f, 0.f, 0.f};
     float cf[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float cfg = a.cfg;
     if (wave < NT) {
 #pragma unroll
         for (int i = 0; i < 6; ++i) cf[i] = a.coef[i];
         if (frow < nc) {
+            if (a.cfg_rows) cfg = a.cfg_rows[frow];                 // one guidance scale per utterance row
             const unsigned zi = (unsigned)(frow * a.L + wave * 16 + fq * 4);
             pz = *reinterpret_cast<const float4*>(a.z_in + zi);
             px = *reinterpret_cast<const float4*>(a.x0p_in + zi);
@@ -197,7 +199,7 @@ __global__ __launch_bounds__(512) void vv_head_tail_kernel(const VVTail a) {
             const int d = nt * 16 + fq * 4 + r;
             float zn = 0.f;
             if (frow < nc) {
-                const float v = vu + a.cfg * (o - vu);
+                const float v = vu + cfg * (o - vu);
                 const unsigned zi = (unsigned)(frow * a.L + d);
                 const float zo = reinterpret_cast<const float*>(&pz)[r];
                 const float x0 = ca * zo - cs_ * v;

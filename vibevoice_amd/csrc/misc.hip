@@ -349,9 +349,11 @@ __global__ void vv_zero_hist_kernel(const VVShift* __restrict__ tab) {
 //   x' = cs x + c0 x0 + c1 (x0 - x0_prev)       (c1 = 0 on first-order steps)
 // coef = {a, s, cs, c0, c1} for this step.
 __global__ void vv_cfg_dpm_kernel(const float* __restrict__ eps, float* __restrict__ x, float* __restrict__ x0_prev,
-                                  const float* __restrict__ coef, float cfg, int n, int L, const float* __restrict__ sde_noise) {
+                                  const float* __restrict__ coef, float cfg, int n, int L, const float* __restrict__ sde_noise,
+                                  const float* __restrict__ cfg_rows) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n * L) return;
+    if (cfg_rows) cfg = cfg_rows[i / L];                       // one guidance scale per utterance row (null: cfg for every row)
     const float a = coef[0], s = coef[1], cs = coef[2], c0 = coef[3], c1 = coef[4];
     const float vc = eps[i], vu = eps[i + n * L];
     const float v = vu + cfg * (vc - vu);
@@ -698,8 +700,9 @@ int vv_zero_hist_launch(const void* tab, int n_entries, hipStream_t s) {
     hipLaunchKernelGGL(vv_zero_hist_kernel, dim3(n_entries, 8), dim3(256), 0, s, (const VVShift*)tab);
     return okk();
 }
-int vv_cfg_dpm_launch(const float* eps, float* x, float* x0_prev, const float* coef, float cfg, int n, int L, const float* sde_noise, hipStream_t s) {
-    hipLaunchKernelGGL(vv_cfg_dpm_kernel, dim3((n * L + 255) / 256), dim3(256), 0, s, eps, x, x0_prev, coef, cfg, n, L, sde_noise);
+int vv_cfg_dpm_launch(const float* eps, float* x, float* x0_prev, const float* coef, float cfg, int n, int L, const float* sde_noise,
+                      const float* cfg_rows, hipStream_t s) {
+    hipLaunchKernelGGL(vv_cfg_dpm_kernel, dim3((n * L + 255) / 256), dim3(256), 0, s, eps, x, x0_prev, coef, cfg, n, L, sde_noise, cfg_rows);
     return okk();
 }
 int vv_affine_launch(const float* x, float* y, float mul, float add, int n, hipStream_t s) {

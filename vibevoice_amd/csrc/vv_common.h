@@ -70,6 +70,7 @@ struct VVGemm {
     const float* coef;     // {a, s, cs, c0, c1, cn}: one 6-float row of the schedule table per solver step
     float cfg;
     int n_cfg;
+    const float* cfg_rows; // [n_cfg] one guidance scale per utterance row, read in place of cfg; null = cfg for every row
     const float* sde_noise; // stochastic solver (sde-dpmsolver++): this step's variance noise [n][N], added as cn * eps; null = off
     unsigned long long* dbg;   // optional phase timestamps (VV_GEMM_TIMING builds only)
     // row t reads activation row (t % x_row_mod) and, for PRO_ADD_SILU, the add-vector (t / add_rows_per_vec)
@@ -127,6 +128,7 @@ struct VVGemv16p {
     float* ssq_out;        // [N / 16][16]
     // VV_EPI_CFG_DPM (the sampler's final layer): rows [0, n) cond, [n, 2n) uncond -> CFG + DPM-Solver++ update of z in place (gemv.hip)
     float* z; float* x0p; const float* coef; float cfg; int n_cfg; const float* sde_noise;
+    const float* cfg_rows; // [n_cfg] per-row guidance scale or null (VVGemm::cfg_rows)
 };
 
 // ---- the seam between two solver steps of the diffusion head (headtail.hip): final layer + CFG + DPM-Solver++ update + in-projection ----
@@ -141,6 +143,7 @@ struct VVTail {
     const float* z_in; const float* x0p_in;            // [2n][L], [n][L]: this step's state
     float* z_out; float* x0p_out;                      // the next step's state (different buffers)
     const float* coef; float cfg; int n_cfg; const float* sde_noise;
+    const float* cfg_rows; // [n_cfg] per-row guidance scale or null (VVGemm::cfg_rows)
     int T, H, L; float eps;
 };
 

@@ -411,10 +411,20 @@ class Engine:
         assert logits_out.dtype == torch.float32 and logits_out.is_contiguous() and logits_out.numel() >= n * self.cfg.lm_vocab
         self._chk(self.lib.vv_lm_logits_full(self._ctx, self._s, n, self._p(hidden), self._p(logits_out)), "vv_lm_logits_full")
 
-    def diffusion_sample(self, n: int, cond: torch.Tensor, noise: torch.Tensor, cfg_scale: float, latent_out: torch.Tensor,
+    def diffusion_sample(self, n: int, cond: torch.Tensor, noise: torch.Tensor, cfg_scale, latent_out: torch.Tensor,
                          step_noise: Optional[torch.Tensor] = None):
-        """step_noise [n_steps, n, latent] fp32 (contiguous, on the device): the per-step variance noise of the stochastic solver."""
-        if step_noise is None:
+        """step_noise [n_steps, n, latent] fp32 (contiguous, on the device): the per-step variance noise of the stochastic solver.
+        cfg_scale: one float for every row, or a 1-D fp32 device tensor of n guidance scales, one per utterance row.  The kernels read
+        the tensor at run time and the graph is keyed by its address: rewrite the same buffer between calls and nothing is re-captured."""
+        if isinstance(cfg_scale, torch.Tensor):
+            if (cfg_scale.dim() != 1 or cfg_scale.shape[0] != n or cfg_scale.dtype != torch.float32 or cfg_scale.device != self.device
+                    or not cfg_scale.is_contiguous()):
+                raise ValueError(f"diffusion_sample: a per-row cfg_scale is a contiguous 1-D fp32 tensor of n = {n} entries on {self.device}")
+            if step_noise is not None:
+                assert step_noise.dtype == torch.float32 and step_noise.is_contiguous() and step_noise.shape[1] == n
+            self._chk(self.lib.vv_diffusion_sample_rows(self._ctx, self._s, n, self._p(cond), self._p(noise), self._p(step_noise),
+                                                        self._p(cfg_scale), self._p(latent_out)), "vv_diffusion_sample_rows")
+        elif step_noise is None:
             self._chk(self.lib.vv_diffusion_sample(self._ctx, self._s, n, self._p(cond), self._p(noise),
                                                    float(cfg_scale), self._p(latent_out)), "vv_diffusion_sample")
         else:
@@ -537,7 +547,7 @@ class Engine:
 
     def gemv_case(self, wp, x, y, T, N, K, *, ldx=None, ldy=None, pro=0, epi=0, w2p=None, nw=None, eps=1e-6, bias=None, nscale=None,
                   mod_scale=None, mod_shift=None, ld_mod=0, addvec=None, x_row_mod=0, add_rows_per_vec=0, gate=None, ld_gate=0,
-                  z=None, x0p=None, coef=None, cfg=0.0, n_cfg=0, sde_noise=None,
+                  z=None, x0p=None, coef=None, cfg=0.0, n_cfg=0, sde_noise=None, cfg_rows=None,
                   kgrid=0, yparts=None, xa=None, n_xa=0, ya=None, n_ya=0, part_stride=0,
                   sl_n=0, sl_T=0, sl_x=0, sl_y=0, sl_id=(),
                   dw_hist=None, dw_w=None, dw_b=None, dw_gamma=None, dw_nw=None, dw_xout=None, dw_hnew=None,
@@ -625,6 +635,7 @@ class Engine:
         need("x0p", x0p, n_cfg * N, required=is_cfg)
         need("coef", coef, 6, required=is_cfg)
         need("sde_noise", sde_noise, n_cfg * N, required=False)
+        need("cfg_rows", cfg_rows, n_cfg, required=False)
         if (kgrid > 1 or n_xa or n_ya) and part_stride < max(x_need if n_xa else 0, y_need if (kgrid > 1 or n_ya) else 0):
             raise ValueError(f"gemv_case: part_stride = {part_stride} is smaller than one part tensor")
         need("yparts", yparts, (kgrid - 2) * part_stride + y_need if kgrid > 1 else 0, required=kgrid > 1)
@@ -650,6 +661,7 @@ class Engine:
             a.sl_id[j] = v
         a.dw_hist, a.dw_w, a.dw_b, a.dw_gamma, a.dw_nw = p(dw_hist), p(dw_w), p(dw_b), p(dw_gamma), p(dw_nw)
         a.dw_xout, a.dw_hnew = p(dw_xout), p(dw_hnew)
+        a.cfg_rows = p(cfg_rows)
         form = (C.c_int * 5)()
         rc = self.lib.vv_gemv_case(self._s, C.byref(a), xs, form)
         if rc == _lib.GEMV_REFUSED:

@@ -400,11 +400,51 @@ def _speakers_of_rows(need, have):
     return out
 
 
+def _cfg_scale_values(cfg_scale, n, what):
+    """cfg_scale of one call -> n finite Python floats, one per utterance.  A real number stands for every row; a sequence or 1-D
+    tensor / array carries one value per row.  ValueError on a wrong length, a non-finite value or anything that is not a real
+    number -- on the host, before anything is enqueued."""
+    import math
+    import numbers
+    if isinstance(cfg_scale, (torch.Tensor, np.ndarray)):
+        if cfg_scale.ndim > 1:
+            raise ValueError(f"{what}: cfg_scale has {cfg_scale.ndim} dimensions; a number or one value per utterance ({n}) is expected")
+        vals = cfg_scale.tolist()
+        seq = cfg_scale.ndim == 1
+        vals = vals if seq else [vals]
+    elif isinstance(cfg_scale, (list, tuple)):
+        vals, seq = list(cfg_scale), True
+    else:
+        vals, seq = [cfg_scale], False
+    out = []
+    for v in vals:
+        if isinstance(v, torch.Tensor) and v.ndim == 0:
+            v = v.item()
+        if isinstance(v, bool) or not isinstance(v, numbers.Real):
+            raise ValueError(f"{what}: cfg_scale {v!r} is not a real number")
+        v = float(v)
+        if not math.isfinite(v):
+            raise ValueError(f"{what}: cfg_scale {v!r} is not finite")
+        out.append(v)
+    if not seq:
+        return out * n
+    if len(out) != n:
+        raise ValueError(f"{what}: cfg_scale holds {len(out)} values for {n} utterances")
+    return out
+
+
+def _request_cfg_scales(requests, cfg_scale, what):
+    """the guidance scale of every request of a queue: its own "cfg_scale" key, else the call's argument"""
+    default = _cfg_scale_values(cfg_scale, 1, what)[0]
+    return [_cfg_scale_values(r["cfg_scale"], 1, f"{what}, request {i}")[0] if r.get("cfg_scale") is not None else default
+            for i, r in enumerate(requests)]
+
+
 class _Utt:
     """One utterance in flight: its engine slot (KV caches 2*slot / 2*slot+1, codec states), lengths and outputs."""
     __slots__ = ("idx", "slot", "ids", "seq_len0", "init_len", "max_length", "max_steps", "max_step_sample", "step", "pos_len",
                  "neg_len", "have_embeds", "finished", "reach_max", "tokens", "chunks", "last", "forced", "noise_fn", "req",
-                 "t_admit", "t_done", "neg_book")
+                 "t_admit", "t_done", "neg_book", "cfg_scale")
 
     def __init__(self, idx, slot, ids, seq_len0, max_length, max_length_times, start_id):
         self.idx, self.slot, self.ids = idx, slot, ids
@@ -421,6 +461,7 @@ class _Utt:
         self.last = ids[-1] if ids else start_id
         self.forced = self.noise_fn = self.req = None
         self.t_admit = self.t_done = None
+        self.cfg_scale = None                         # this utterance's guidance scale (a session with mixed scales; else the session's)
         # the reference's bookkeeping of this row's negative cache, without the tensors: [attention mask incl. the next token's slot,
         # entries ever appended, corrections so far (correct_cnt)] -- to recognise the one correction that keeps THIS step's entry (vv_kv_move)
         self.neg_book = [[1], 0, 0]
@@ -474,6 +515,12 @@ class VibeVoiceForConditionalGenerationInference:
         self._logits_pin = torch.empty(2 * NB * 16, dtype=torch.float32).pin_memory()
         self._noise_pin = [torch.empty(NB, engine.cfg.latent_dim, dtype=torch.float32).pin_memory() for _ in range(4)]
         self._noise_i = 0
+        # per-row guidance scales of a sampler call: ONE device buffer (its address is in the sampler's graph key), written from a
+        # ring of pinned rows; _cfg_staged = what the device buffer holds once the stream gets there
+        self._cfg_dev = e.new(NB)
+        self._cfg_pin = torch.empty(4, NB, dtype=torch.float32).pin_memory()
+        self._cfg_i = 0
+        self._cfg_staged = []
         self._lg_event = torch.cuda.Event()
         self._fork_ev = torch.cuda.Event()
         self._join_ev = torch.cuda.Event()
@@ -851,6 +898,23 @@ class VibeVoiceForConditionalGenerationInference:
         pin[:n].copy_(nz[:n])
         self._noise[:n].copy_(pin[:n], non_blocking=True)
 
+    def _cfg_arg(self, S, utts):
+        """cfg_scale of one sampler call over `utts` (in the order of its condition rows): the session's float when every request of
+        the session has the same scale -- the scalar kernels and graphs -- else a view of the one staging buffer holding each row's own
+        scale.  The values travel host -> pinned -> device on the engine stream without a sync; nothing is copied while the rows and
+        their scales are what the buffer already holds."""
+        if not S["cfg_rows"]:
+            return S["cfg_scale"]
+        vals = [u.cfg_scale for u in utts]
+        n = len(vals)
+        if self._cfg_staged[:n] != vals:
+            pin = self._cfg_pin[self._cfg_i]
+            self._cfg_i = (self._cfg_i + 1) % self._cfg_pin.shape[0]
+            pin[:n] = torch.tensor(vals, dtype=torch.float32)
+            self._cfg_dev[:n].copy_(pin[:n], non_blocking=True)
+            self._cfg_staged[:n] = vals
+        return self._cfg_dev[:n]
+
     def _process_speech_inputs(self, speech_tensors, speech_masks, prefill_noise=None, dev_gen=None):
         """_process_speech_inputs (:149-163): encode voice prompts, sample, scale, connect.
         dev_gen: a lane's own device generator (generate_interleaved); None = the device's global generator, as the reference.
@@ -1118,7 +1182,7 @@ class VibeVoiceForConditionalGenerationInference:
         e = self.engine
         nv, valid_t = S["nv"], S["valid_t"]
         start_id, end_id, diff_id, eos_id = S["start_id"], S["end_id"], S["diff_id"], S["eos_id"]
-        cfg_scale, trace, audio_streamer, verbose = S["cfg_scale"], S["trace"], S["audio_streamer"], S["verbose"]
+        trace, audio_streamer, verbose = S["trace"], S["audio_streamer"], S["verbose"]
         run = [u for u in act if u.have_embeds]
         fresh = [u for u in act if not u.have_embeds]
         order = run + fresh
@@ -1168,7 +1232,7 @@ class VibeVoiceForConditionalGenerationInference:
                 nz = torch.randn(2 * nR, e.cfg.latent_dim, generator=cg)
             self._stage_noise(nz, nR)
             # all active rows diffusing, in order: cond rows == [hidden[:nR]; hidden[nR:2nR]]
-            e.diffusion_sample(nR, self._hidden, self._noise, cfg_scale, self._latent)
+            e.diffusion_sample(nR, self._hidden, self._noise, self._cfg_arg(S, run), self._latent)
             spec_sample = True
         self._lg_event.synchronize()
         logits = self._logits_pin[:nA * nv].view(nA, nv).clone()
@@ -1297,6 +1361,7 @@ class VibeVoiceForConditionalGenerationInference:
             if nz is None:
                 nz = torch.randn(2 * n, e.cfg.latent_dim, generator=S.get("cpu_gen"))      # CPU global RNG, as the reference (:701), unless the session has its own
             self._stage_noise(nz, n)
+            cfg_scale = self._cfg_arg(S, diff)
             if S["sde"]:
                 e.diffusion_sample(n, self._cond, self._noise, cfg_scale, self._latent, step_noise=self._sde_draws(S, n))
             else:
@@ -1439,7 +1504,8 @@ class VibeVoiceForConditionalGenerationInference:
             return S["noise_fn"](S["step"], 2 * len(utts))
         return None
 
-    def _session(self, tokenizer, generation_config, cfg_scale, kwargs, audio_streamer, n_rows):
+    def _session(self, tokenizer, generation_config, cfg_scales, kwargs, audio_streamer, n_rows):
+        """cfg_scales: the validated guidance scale of every utterance of the call (_cfg_scale_values)"""
         e = self.engine
         if tokenizer is None:
             raise ValueError("generate() needs tokenizer= (speech_start_id / speech_end_id / speech_diffusion_id / eos_token_id)")
@@ -1455,7 +1521,7 @@ class VibeVoiceForConditionalGenerationInference:
         e.set_num_steps(self.ddpm_inference_steps, t_cast_bf16=(self.dtype == torch.bfloat16 and kwargs.get("_t_cast", True)),
                         **({} if algo == "dpmsolver++" else {"algorithm_type": algo}))
         return dict(sde=(algo == "sde-dpmsolver++"), sde_noise_fn=kwargs.pop("_sde_noise_fn", None), nv=len(valid), valid_t=torch.tensor(valid, dtype=torch.long), start_id=start_id, end_id=end_id, diff_id=diff_id,
-                    eos_id=eos_id, cfg_scale=cfg_scale, do_sample=do_sample, temperature=temperature, warp=warp,
+                    eos_id=eos_id, cfg_scale=cfg_scales[0] if cfg_scales else 1.0, cfg_rows=len(set(cfg_scales)) > 1, do_sample=do_sample, temperature=temperature, warp=warp,
                     pad_id=getattr(tokenizer, "pad_token_id", None),
                     trace=kwargs.pop("_trace", None), audio_streamer=audio_streamer, verbose=kwargs.get("verbose", False),
                     forced=kwargs.pop("_forced_tokens", None), noise_fn=kwargs.pop("_noise_fn", None), n_rows=n_rows,
@@ -1490,16 +1556,17 @@ class VibeVoiceForConditionalGenerationInference:
             attention_mask = torch.ones_like(input_ids)
         attention_mask = attention_mask.cpu()
         B, L0 = input_ids.shape
+        cfg_scales = _cfg_scale_values(cfg_scale, B, "generate()")      # a float, or one guidance scale per row
         if B > MAX_BATCH or B > e.cfg.n_slots or 2 * B > e.cfg.max_rows:
             # the reference's batch is unbounded (:393-394); one engine pass carries MAX_BATCH utterances (and this engine was created with
             # n_slots / max_rows), so a larger batch is decoded through the continuous-admission queue and handed back in the batch's own
             # output form
-            return self._generate_queued(input_ids, attention_mask, tokenizer, generation_config, cfg_scale, audio_streamer,
+            return self._generate_queued(input_ids, attention_mask, tokenizer, generation_config, cfg_scales, audio_streamer,
                                          speech_tensors, speech_masks, speech_input_mask, is_prefill, return_speech, stop_check_fn,
                                          max_length_times, prefill_noise, step_cb, kwargs, prompt_prefix=prompt_prefix)
         prefixes = self._prefix_list(prompt_prefix, B)
         pf_stats = {"prefix_rows_reused": 0, "prompt_rows_computed": 0}
-        S = self._session(tokenizer, generation_config, cfg_scale, kwargs, audio_streamer, B)
+        S = self._session(tokenizer, generation_config, cfg_scales, kwargs, audio_streamer, B)
         S["sample_rows"] = lambda order: list(range(B))
         self._frame_w = B                                 # frame-store rows are as wide as this call's batch
         if kwargs.get("max_new_tokens", None) is None:
@@ -1511,6 +1578,7 @@ class VibeVoiceForConditionalGenerationInference:
         for b in range(B):
             m = attention_mask[b].bool()
             utts.append(_Utt(b, b, input_ids[b][m].tolist(), L0, max_length, max_length_times, S["start_id"]))
+            utts[-1].cfg_scale = cfg_scales[b]
         max_steps = min(max_length - L0, int(max_length_times * L0))
         time_prefill = os.environ.get("VVHIP_TIME_PREFILL") is not None     # debug: sync + time the two prefill phases
         if tqdm_class is not None and kwargs.get("show_progress_bar", True):
@@ -1619,7 +1687,7 @@ class VibeVoiceForConditionalGenerationInference:
             sequences=seq.to(self.device), speech_outputs=outs if return_speech else None,
             reach_max_step_sample=torch.tensor([u.reach_max for u in utts], dtype=torch.bool).to(self.device))
 
-    def _generate_queued(self, input_ids, attention_mask, tokenizer, generation_config, cfg_scale, audio_streamer, speech_tensors,
+    def _generate_queued(self, input_ids, attention_mask, tokenizer, generation_config, cfg_scales, audio_streamer, speech_tensors,
                          speech_masks, speech_input_mask, is_prefill, return_speech, stop_check_fn, max_length_times, prefill_noise,
                          step_cb, kwargs, prompt_prefix=None):
         """generate() for a batch of more than MAX_BATCH rows (the reference's batch is unbounded, :393-394): every row becomes a
@@ -1676,9 +1744,10 @@ class VibeVoiceForConditionalGenerationInference:
                 r["_forced_tokens"] = forced[b]
             if noise_fn is not None:
                 r["_noise_fn"] = noise_fn                # per utterance here: noise_fn(its own step, 2) -> [2, latent]
+            r["cfg_scale"] = cfg_scales[b]               # the row's own guidance scale (all equal when generate() got a float)
             reqs.append(r)
         kw = {k: v for k, v in kwargs.items() if k in ("verbose", "refresh_negative", "_trace", "_teacher_embeds", "_t_cast", "_sde_noise_fn")}
-        outs = self.generate_continuous(reqs, tokenizer=tokenizer, generation_config=generation_config, cfg_scale=cfg_scale,
+        outs = self.generate_continuous(reqs, tokenizer=tokenizer, generation_config=generation_config, cfg_scale=cfg_scales[0],
                                         audio_streamer=audio_streamer, is_prefill=is_prefill, return_speech=return_speech,
                                         max_new_tokens=kwargs.get("max_new_tokens"), max_length_times=max_length_times,
                                         stop_check_fn=stop_check_fn, _bench_hooks=BenchHooks(step_callback=step_cb), _batch_exit=True, **kw)
@@ -1716,6 +1785,7 @@ class VibeVoiceForConditionalGenerationInference:
         created on first use (each owns KV caches for its n_slots) and kept: `model.close_lanes()` releases them."""
         import threading
         from .parallel import shard_utterances
+        _request_cfg_scales(requests, kwargs.get("cfg_scale", 1.0), "generate_interleaved()")      # refused here, before any lane starts
         lanes = max(1, min(int(lanes), len(requests)))
         if lanes == 1:
             return self.generate_continuous(requests, audio_streamer=audio_streamer, **kwargs)
@@ -1789,6 +1859,7 @@ class VibeVoiceForConditionalGenerationInference:
         sample index = request index."""
         e = self.engine
         n_req = len(requests)
+        cfg_scales = _request_cfg_scales(requests, cfg_scale, "generate_continuous()")      # a request's own "cfg_scale" key, else the call's
         cap = min(max_concurrent or e.cfg.n_slots, e.cfg.n_slots, MAX_BATCH, e.cfg.max_rows // 2)
         if cap < 1:
             raise ValueError("no engine slot available")
@@ -1800,7 +1871,8 @@ class VibeVoiceForConditionalGenerationInference:
             # step (the correction of :590-624): defined for the lock-step batch of generate(), not for a queue of requests
             raise NotImplementedError("refresh_negative=False is a rule over the rows of one lock-step batch: use generate() with at "
                                       f"most {MAX_BATCH} rows (continuous admission / larger batches refuse it)")
-        S = self._session(tokenizer, generation_config, cfg_scale, kwargs, audio_streamer, n_req)
+        S = self._session(tokenizer, generation_config, cfg_scales or _cfg_scale_values(cfg_scale, 1, "generate_continuous()"), kwargs,
+                          audio_streamer, n_req)
         S["lockstep"] = False                   # independent requests: no cross-row tokenizer-cache coupling (see _iterate)
         S["sample_rows"] = lambda order: [u.idx for u in order]
         self._frame_w = cap
@@ -1867,6 +1939,7 @@ class VibeVoiceForConditionalGenerationInference:
                     mnt = self.max_position_embeddings - L0 if mnt is None else mnt
                     u = _Utt(ri, slot, ids_t[0][am[0].bool()].tolist(), L0, min(L0 + mnt, e.max_ctx), max_length_times, S["start_id"])
                     u.forced, u.noise_fn, u.req = r.get("_forced_tokens"), r.get("_noise_fn"), r
+                    u.cfg_scale = cfg_scales[ri]
                     u.t_admit = it
                     e.codec_reset(slot)
                     rows = pos = None
