@@ -166,6 +166,18 @@ int vv_lm_logits(vv_ctx* ctx, void* stream, int n, const float* hidden_dev, floa
  * Needed only when a full-vocabulary logits processor is requested (top-k / top-p / min-p / repetition penalty run before the
  * valid-id constraint in the reference's processor list, :310-319); the default path evaluates the valid rows only. */
 int vv_lm_logits_full(vv_ctx* ctx, void* stream, int n, const float* hidden_dev, float* logits_out_dev);
+/* The full-vocabulary logits processors of :310-319 (HF's order: repetition penalty; with do_sample temperature, top-k, top-p,
+ * min-p with min_tokens_to_keep = 1) followed by the valid-id constraint of :416-419, evaluated for the valid ids only: each
+ * processor is a reduction over the row, nothing is sorted and nothing of size lm_vocab is written.  logits_dev [n][lm_vocab] fp32
+ * as vv_lm_logits_full wrote them (read only); seen_dev [n][lm_vocab] bytes, non-zero where the id occurs in the row's input_ids
+ * (NULL when repetition_penalty == 1); top_k 0 = off (HF: k = min(top_k, lm_vocab)), top_p 1 = off, min_p 0 = off; temperature and
+ * the three filters apply only with do_sample.  out_dev [n][n_valid] fp32 in the order given to vv_set_valid_tokens: the processed
+ * score, bit-equal to torch's fp32 arithmetic, or -inf where a filter removed the id; survivors_dev [n]: finite entries per row
+ * (0: the reference would fail in torch.multinomial).  1 <= n <= 16.  One eager launch on `stream`, never captured; bit-identical
+ * run to run. */
+int vv_lm_warp_valid(vv_ctx* ctx, void* stream, int n, const float* logits_dev, const unsigned char* seen_dev,
+                     float repetition_penalty, float temperature, int do_sample, int top_k, float top_p, float min_p,
+                     float* out_dev, int* survivors_dev);
 
 /* sample_speech_tokens (:697-710): cond_dev [2n][H] = n positive then n negative
  * conditions, noise_dev [n][latent], -> latent_out_dev [n][latent] */

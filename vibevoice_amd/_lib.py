@@ -67,6 +67,7 @@ _SIGS = {
     "vv_embed": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), _P]),
     "vv_lm_logits": (C.c_int, [_P, _P, C.c_int, _P, _P]),
     "vv_lm_logits_full": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "vv_lm_warp_valid": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P]),
     "vv_diffusion_sample": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_float, _P]),
     "vv_diffusion_sample_sde": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_float, _P]),
     "vv_diffusion_sample_rows": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P]),

@@ -33,6 +33,8 @@ int vv_attn_launch(int D, int xs, const float* q, const VVRow* rows, const void*
                    float* out, hipStream_t s);
 int vv_embed_launch(const void* table, const int* ids, float* out, int n, int H, hipStream_t s);
 int vv_logits_full_launch(const void* table, const float* hidden, float* out, int n, int V, int H, hipStream_t s);
+int vv_warp_valid_launch(const float* logits, const unsigned char* seen, float* out, int* survivors, int n, int V, const int* ids,
+                         int n_valid, float pen, float temp, int do_sample, int top_k, float top_p, float min_p, hipStream_t s);
 int vv_rmsnorm_rows_launch(const float* x, int ldx, float* y, int ldy, const float* w, int T, int C, float eps, hipStream_t s);
 int vv_dwconv_res_launch(const float* nb, const float* x, float* xo, const float* w, const float* b, const float* gamma, int T, int C, hipStream_t s);
 int vv_normdw_sliced_ok(int T, int C);
@@ -210,6 +212,7 @@ struct vv_ctx {
     void *embed = nullptr, *lm_head = nullptr;
     bool lm_head_loaded = false;
     void* valid_w = nullptr; int n_valid = 0;
+    int valid_ids[16] = {0};               // the ids themselves (vv_lm_warp_valid reads their columns of the full logits)
     // LM runtime
     void *kc = nullptr, *vc = nullptr;
     int64_t cache_stride = 0, head_stride = 0, layer_stride = 0;
@@ -1307,6 +1310,7 @@ extern "C" int vv_set_valid_tokens(vv_ctx* ctx, const int* ids, int n) {
     HIPCHK(ctx, hipDeviceSynchronize());
     dfree(ctx, rows);
     ctx->n_valid = n;
+    for (int i = 0; i < n; ++i) ctx->valid_ids[i] = ids[i];
     return 0;
 }
 
@@ -1743,6 +1747,24 @@ extern "C" int vv_lm_logits_full(vv_ctx* ctx, void* stream, int n, const float* 
     if (n < 1 || n > 16) return fail(ctx, "vv_lm_logits_full: n must be in [1,16]");
     if (ctx->H & 7) return fail(ctx, "vv_lm_logits_full: hidden size %d is not a multiple of 8", ctx->H);
     VVCHK(vv_logits_full_launch(table, hidden_dev, logits_out_dev, n, ctx->c.lm_vocab, ctx->H, (hipStream_t)stream));
+    return 0;
+}
+extern "C" int vv_lm_warp_valid(vv_ctx* ctx, void* stream, int n, const float* logits_dev, const unsigned char* seen_dev,
+                                float repetition_penalty, float temperature, int do_sample, int top_k, float top_p, float min_p,
+                                float* out_dev, int* survivors_dev) {
+    VV_SHARED;
+    if (n < 1 || n > 16) return fail(ctx, "vv_lm_warp_valid: n must be in [1,16]");
+    if (!ctx->valid_w || ctx->n_valid < 1) return fail(ctx, "vv_lm_warp_valid: vv_set_valid_tokens has not been called");
+    if (!(repetition_penalty > 0.f)) return fail(ctx, "vv_lm_warp_valid: repetition_penalty %g must be > 0", (double)repetition_penalty);
+    if (!(temperature > 0.f)) return fail(ctx, "vv_lm_warp_valid: temperature %g must be > 0", (double)temperature);
+    if (top_k < 0) return fail(ctx, "vv_lm_warp_valid: top_k %d must be >= 0", top_k);
+    if (!(top_p >= 0.f && top_p <= 1.f)) return fail(ctx, "vv_lm_warp_valid: top_p %g must be in [0,1]", (double)top_p);
+    if (!(min_p >= 0.f && min_p <= 1.f)) return fail(ctx, "vv_lm_warp_valid: min_p %g must be in [0,1]", (double)min_p);
+    if (!seen_dev && repetition_penalty != 1.f) return fail(ctx, "vv_lm_warp_valid: a repetition_penalty other than 1 needs the seen mask");
+    if (!logits_dev || !out_dev || !survivors_dev) return fail(ctx, "vv_lm_warp_valid: null logits / out / survivors pointer");
+    ctx->launches++;
+    VVCHK(vv_warp_valid_launch(logits_dev, seen_dev, out_dev, survivors_dev, n, ctx->c.lm_vocab, ctx->valid_ids, ctx->n_valid,
+                               repetition_penalty, temperature, do_sample, top_k, top_p, min_p, (hipStream_t)stream));
     return 0;
 }
 extern "C" int vv_lm_logits(vv_ctx* ctx, void* stream, int n, const float* hidden_dev, float* logits_out_dev) {

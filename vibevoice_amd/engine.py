@@ -411,6 +411,21 @@ class Engine:
         assert logits_out.dtype == torch.float32 and logits_out.is_contiguous() and logits_out.numel() >= n * self.cfg.lm_vocab
         self._chk(self.lib.vv_lm_logits_full(self._ctx, self._s, n, self._p(hidden), self._p(logits_out)), "vv_lm_logits_full")
 
+    def lm_warp_valid(self, n: int, logits: torch.Tensor, seen: Optional[torch.Tensor], out: torch.Tensor, survivors: torch.Tensor, *,
+                      repetition_penalty: float = 1.0, temperature: float = 1.0, do_sample: bool = False, top_k: int = 0,
+                      top_p: float = 1.0, min_p: float = 0.0):
+        """The full-vocabulary logits processors + the valid-id constraint for n <= 16 rows of lm_logits_full's output (read only):
+        out[:n * n_valid] = the processed scores of the valid ids, -inf where a filter removed one; survivors[:n] = finite entries per
+        row.  seen: [n, lm_vocab] uint8, non-zero where the id is in the row's input_ids (None when repetition_penalty == 1)."""
+        V = self.cfg.lm_vocab
+        assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.numel() >= n * V
+        assert seen is None or (seen.dtype == torch.uint8 and seen.is_contiguous() and seen.numel() >= n * V)
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= n * max(1, getattr(self, "n_valid", 0) or 0)
+        assert survivors.dtype == torch.int32 and survivors.is_contiguous() and survivors.numel() >= n
+        self._chk(self.lib.vv_lm_warp_valid(self._ctx, self._s, int(n), self._p(logits), self._p(seen), float(repetition_penalty),
+                                            float(temperature), int(bool(do_sample)), int(top_k), float(top_p), float(min_p),
+                                            self._p(out), self._p(survivors)), "vv_lm_warp_valid")
+
     def diffusion_sample(self, n: int, cond: torch.Tensor, noise: torch.Tensor, cfg_scale, latent_out: torch.Tensor,
                          step_noise: Optional[torch.Tensor] = None):
         """step_noise [n_steps, n, latent] fp32 (contiguous, on the device): the per-step variance noise of the stochastic solver.

@@ -532,6 +532,9 @@ class VibeVoiceForConditionalGenerationInference:
         self.concurrent_codecs = True
         self.batched_codecs = hasattr(engine, "codec_chain_batch")
         self.speculate_sampling = True
+        # the full-vocabulary logits processors (repetition penalty, top-k / top-p / min-p) as ONE kernel over lm_logits_full's output
+        # (vv_lm_warp_valid) instead of the chain of torch ops in _full_vocab_scores; engines without the entry take the torch path
+        self.warp_on_device = True
         self.last_stats = {}
         # weights epoch: [count of parameter updates since construction]; one box per weight copy (forks share their parent's).  A
         # PromptPrefix remembers the value it was computed under
@@ -1081,6 +1084,59 @@ class VibeVoiceForConditionalGenerationInference:
                 scores = scores.masked_fill(srt_remove.scatter(1, idx, srt_remove), float("-inf"))
         return scores
 
+    def _warp_valid_scores(self, hidden: torch.Tensor, order, S) -> torch.Tensor:
+        """[n, n_valid] scores of the valid ids of the given positive rows after the same processors as _full_vocab_scores and the
+        valid-token constraint (-inf where a filter removed an id), from vv_lm_warp_valid: no [n, V] clone and no torch op over the
+        vocabulary.  Raises when a row keeps no valid id."""
+        e, w = self.engine, S["warp"]
+        n, V, nv = hidden.shape[0], e.cfg.lm_vocab, S["nv"]
+        if getattr(self, "_full_logits", None) is None or self._full_logits.numel() < 16 * V:
+            self._full_logits = torch.empty(16 * V, dtype=torch.float32, device=self.device)
+        if getattr(self, "_warp_out", None) is None or self._warp_out.numel() < n * 16:
+            self._warp_out = torch.empty(max(16, n) * 16, dtype=torch.float32, device=self.device)
+            self._warp_surv = torch.empty(max(16, n), dtype=torch.int32, device=self.device)
+        hidden = hidden.to(torch.float32).contiguous()
+        pen = w["repetition_penalty"]
+        if pen != 1.0:
+            # the rows' "seen" sets (RepetitionPenaltyLogitsProcessor: left padding, prompt, generated tokens) are rows of one
+            # [slots][V] byte buffer on the device, one per engine slot, extended by the tokens generated since the last step --
+            # the same ids in the same order as the dict of bool masks of _full_vocab_scores
+            n_rows = max(int(getattr(e.cfg, "n_slots", 1)), max(u.slot for u in order) + 1)
+            if getattr(self, "_seen_buf", None) is None or self._seen_buf.shape[0] < n_rows or self._seen_buf.shape[1] != V:
+                self._seen_buf = torch.zeros(n_rows, V, dtype=torch.uint8, device=self.device)
+                S.pop("_seen_dev", None)
+            done = S.setdefault("_seen_dev", {})
+            flat = []                                 # every row's new ids as positions of the flat buffer: one upload, one scatter per step
+            for u in order:
+                if u.idx not in done:
+                    self._seen_buf[u.slot].zero_()    # once per utterance: the slot's previous owner
+                    fresh_tok = list(u.ids) + ([S["pad_id"]] if (u.seq_len0 > u.init_len and S["pad_id"] is not None) else [])
+                    done[u.idx] = 0
+                else:
+                    fresh_tok = []
+                flat += [u.slot * V + int(t) for t in fresh_tok + list(u.tokens[done[u.idx]:]) if 0 <= int(t) < V]
+                done[u.idx] = len(u.tokens)
+            if flat:
+                self._seen_buf.view(-1)[torch.tensor(flat, dtype=torch.long, device=self.device)] = 1
+        for i0 in range(0, n, 16):
+            k = min(16, n - i0)
+            e.lm_logits_full(k, hidden[i0:i0 + k], self._full_logits)
+            # the kernel takes dense rows: one launch per run of consecutive slots (one launch unless an earlier row has finished)
+            j0 = 0
+            while j0 < k:
+                j1 = k if pen == 1.0 else j0 + 1
+                while j1 < k and order[i0 + j1].slot == order[i0 + j1 - 1].slot + 1:
+                    j1 += 1
+                e.lm_warp_valid(j1 - j0, self._full_logits[j0 * V:], self._seen_buf[order[i0 + j0].slot:].reshape(-1) if pen != 1.0 else None,
+                                self._warp_out[(i0 + j0) * nv:], self._warp_surv[i0 + j0:], repetition_penalty=pen,
+                                temperature=S["temperature"], do_sample=S["do_sample"], top_k=w["top_k"], top_p=w["top_p"], min_p=w["min_p"])
+                j0 = j1
+        if int(self._warp_surv[:n].min()) < 1:
+            raise RuntimeError("the full-vocabulary logits processors (top_k / top_p / min_p) removed every valid speech token "
+                               "of a row: nothing is left to sample from (the reference fails in torch.multinomial here: "
+                               "'probability tensor contains either `inf`, `nan` or element < 0')")
+        return self._warp_out[:n * nv].view(n, nv)
+
     # ------------------------------------------------------------------ prompt prefill of one utterance
     def _prefill(self, u: _Utt, ids: List[int], speech_rows: Optional[torch.Tensor], speech_pos: Optional[torch.Tensor],
                  kv_start: int = 0, kv_fill_fn=None, prefix: Optional[PromptPrefix] = None, pos0: int = 0):
@@ -1256,6 +1312,8 @@ class VibeVoiceForConditionalGenerationInference:
             full[:, vt] = 0.0                              # finished rows: any proper distribution, the draw is discarded
             if S["warp"] is None:
                 lg = self._logits[:nA * nv].view(nA, nv).float() / S["temperature"]
+            elif self.warp_on_device and hasattr(e, "lm_warp_valid"):
+                lg = self._warp_valid_scores(torch.cat([pos_hidden(i) for i in range(nA)]), order, S)
             else:
                 # full-vocabulary processors, then the constraint: what survives of the valid ids (-inf where a filter removed one;
                 # a row that loses ALL its valid ids has NaN probabilities in the reference too -- torch.multinomial raises)
@@ -1305,6 +1363,10 @@ class VibeVoiceForConditionalGenerationInference:
             for u in order:
                 if u.finished:
                     S["_seen"].pop(u.idx, None)       # the repetition-penalty mask of a finished utterance ([V] bools on the device)
+        if S.get("_seen_dev"):
+            for u in order:
+                if u.finished:
+                    S["_seen_dev"].pop(u.idx, None)
         for u in order:
             if u.last == end_id:
                 e.codec_reset(u.slot)
@@ -1771,6 +1833,7 @@ class VibeVoiceForConditionalGenerationInference:
         m.set_ddpm_inference_steps(self.ddpm_inference_steps)
         m._sched_cfg = dict(self._sched_cfg)
         m.concurrent_codecs, m.batched_codecs, m.speculate_sampling = self.concurrent_codecs, self.batched_codecs, self.speculate_sampling
+        m.warp_on_device = self.warp_on_device
         return m
 
     def generate_interleaved(self, requests: List[dict], lanes: int = 2, audio_streamer=None, **kwargs) -> List[VibeVoiceGenerationOutput]:
