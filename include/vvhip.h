@@ -178,6 +178,15 @@ int vv_lm_logits_full(vv_ctx* ctx, void* stream, int n, const float* hidden_dev,
 int vv_lm_warp_valid(vv_ctx* ctx, void* stream, int n, const float* logits_dev, const unsigned char* seen_dev,
                      float repetition_penalty, float temperature, int do_sample, int top_k, float top_p, float min_p,
                      float* out_dev, int* survivors_dev);
+/* The normals of seeded requests (vibevoice_amd/noise.py defines them: Philox4x32-10, key = the seed, counter = (element / 4, t,
+ * stream id, aux), Box-Muller on the four output words): one request's draws are a function of its own key and counters only.
+ * out[s][r][f][j], s < n_streams (stream id stream0 + s), r < n, f < n_t (counter word t = keys[r].t0 + f), j < width: the j-th
+ * normal of row r.  keys_host: n keys in HOST memory, passed to the kernel by value.  1 <= n <= 16, n_t >= 1, 1 <= n_streams <= 65,
+ * width a positive multiple of 4, total elements < 2^31, out_dev 16-byte aligned; anything else: negative return + vv_last_error,
+ * nothing launched.  One eager launch on `stream`, never captured; no device-side state. */
+typedef struct vv_noise_key { uint32_t seed_lo, seed_hi, t0, aux; } vv_noise_key;
+int vv_noise_rows(vv_ctx* ctx, void* stream, int n, const vv_noise_key* keys_host, uint32_t stream0, int n_streams,
+                  int n_t, int width, float* out_dev);
 
 /* sample_speech_tokens (:697-710): cond_dev [2n][H] = n positive then n negative
  * conditions, noise_dev [n][latent], -> latent_out_dev [n][latent] */

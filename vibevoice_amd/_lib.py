@@ -45,6 +45,11 @@ class VVGemvCase(C.Structure):
     ]
 
 
+class VVNoiseKey(C.Structure):
+    """vv_noise_key (include/vvhip.h): the seed's two halves, the first counter word t and aux of one row of vv_noise_rows"""
+    _fields_ = [("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("t0", C.c_uint32), ("aux", C.c_uint32)]
+
+
 GEMV_REFUSED = 1     # VV_GEMV_REFUSED
 _SIGS = {
     "vv_create": (C.c_int, [C.POINTER(VVConfig), C.POINTER(_P)]),
@@ -68,6 +73,7 @@ _SIGS = {
     "vv_lm_logits": (C.c_int, [_P, _P, C.c_int, _P, _P]),
     "vv_lm_logits_full": (C.c_int, [_P, _P, C.c_int, _P, _P]),
     "vv_lm_warp_valid": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P]),
+    "vv_noise_rows": (C.c_int, [_P, _P, C.c_int, C.POINTER(VVNoiseKey), C.c_uint32, C.c_int, C.c_int, C.c_int, _P]),
     "vv_diffusion_sample": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_float, _P]),
     "vv_diffusion_sample_sde": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_float, _P]),
     "vv_diffusion_sample_rows": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P]),

@@ -35,6 +35,7 @@ int vv_embed_launch(const void* table, const int* ids, float* out, int n, int H,
 int vv_logits_full_launch(const void* table, const float* hidden, float* out, int n, int V, int H, hipStream_t s);
 int vv_warp_valid_launch(const float* logits, const unsigned char* seen, float* out, int* survivors, int n, int V, const int* ids,
                          int n_valid, float pen, float temp, int do_sample, int top_k, float top_p, float min_p, hipStream_t s);
+int vv_noise_rows_launch(float* out, int n, const uint32_t* keys, uint32_t stream0, int n_streams, int n_t, int width, hipStream_t s);
 int vv_rmsnorm_rows_launch(const float* x, int ldx, float* y, int ldy, const float* w, int T, int C, float eps, hipStream_t s);
 int vv_dwconv_res_launch(const float* nb, const float* x, float* xo, const float* w, const float* b, const float* gamma, int T, int C, hipStream_t s);
 int vv_normdw_sliced_ok(int T, int C);
@@ -1765,6 +1766,22 @@ extern "C" int vv_lm_warp_valid(vv_ctx* ctx, void* stream, int n, const float* l
     ctx->launches++;
     VVCHK(vv_warp_valid_launch(logits_dev, seen_dev, out_dev, survivors_dev, n, ctx->c.lm_vocab, ctx->valid_ids, ctx->n_valid,
                                repetition_penalty, temperature, do_sample, top_k, top_p, min_p, (hipStream_t)stream));
+    return 0;
+}
+extern "C" int vv_noise_rows(vv_ctx* ctx, void* stream, int n, const vv_noise_key* keys_host, uint32_t stream0, int n_streams, int n_t,
+                             int width, float* out_dev) {
+    VV_SHARED;
+    if (n < 1 || n > 16) return fail(ctx, "vv_noise_rows: n = %d must be in [1,16]", n);
+    if (n_t < 1) return fail(ctx, "vv_noise_rows: n_t = %d must be >= 1", n_t);
+    if (n_streams < 1 || n_streams > 65) return fail(ctx, "vv_noise_rows: n_streams = %d must be in [1,65]", n_streams);
+    if (width < 4 || (width & 3)) return fail(ctx, "vv_noise_rows: width = %d must be a positive multiple of 4", width);
+    if ((int64_t)n_streams * n * n_t * width >= ((int64_t)1 << 31))
+        return fail(ctx, "vv_noise_rows: %d x %d x %d x %d elements: the total must stay below 2^31", n_streams, n, n_t, width);
+    if (!keys_host || !out_dev) return fail(ctx, "vv_noise_rows: null keys / out pointer");
+    if ((uintptr_t)out_dev & 15u) return fail(ctx, "vv_noise_rows: out_dev must be 16-byte aligned");
+    static_assert(sizeof(vv_noise_key) == 16, "vv_noise_key is four uint32 words");
+    ctx->launches++;
+    VVCHK(vv_noise_rows_launch(out_dev, n, reinterpret_cast<const uint32_t*>(keys_host), stream0, n_streams, n_t, width, (hipStream_t)stream));
     return 0;
 }
 extern "C" int vv_lm_logits(vv_ctx* ctx, void* stream, int n, const float* hidden_dev, float* logits_out_dev) {

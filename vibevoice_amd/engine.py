@@ -426,6 +426,24 @@ class Engine:
                                             float(temperature), int(bool(do_sample)), int(top_k), float(top_p), float(min_p),
                                             self._p(out), self._p(survivors)), "vv_lm_warp_valid")
 
+    def noise_rows(self, keys: Sequence[tuple], stream0: int, n_streams: int, n_t: int, width: int, out: torch.Tensor):
+        """The normals of seeded requests (vibevoice_amd/noise.py), on the device: out[s][r][f][j] for stream ids stream0 + s
+        (s < n_streams), rows r = keys[r] = (seed, t0, aux), counter words t = t0 + f (f < n_t), j < width.  out: contiguous fp32 on
+        the engine device with at least n_streams * len(keys) * n_t * width elements; nothing else is written."""
+        from . import noise as _noise
+        n = len(keys)
+        arr = (_lib.VVNoiseKey * max(1, n))()
+        for i, (seed, t0, aux) in enumerate(keys):
+            seed = _noise.check_seed(seed)
+            arr[i].seed_lo, arr[i].seed_hi, arr[i].t0, arr[i].aux = seed & 0xffffffff, seed >> 32, int(t0) & 0xffffffff, int(aux) & 0xffffffff
+        if out is not None:
+            if out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+                raise ValueError(f"noise_rows: out is a contiguous fp32 tensor on {self.device}")
+            if n >= 1 and n_streams >= 1 and n_t >= 1 and width >= 1 and out.numel() < int(n_streams) * n * int(n_t) * int(width):
+                raise ValueError(f"noise_rows: out holds {out.numel()} elements, {int(n_streams) * n * int(n_t) * int(width)} are written")
+        self._chk(self.lib.vv_noise_rows(self._ctx, self._s, n, arr, int(stream0) & 0xffffffff, int(n_streams), int(n_t), int(width),
+                                         self._p(out)), "vv_noise_rows")
+
     def diffusion_sample(self, n: int, cond: torch.Tensor, noise: torch.Tensor, cfg_scale, latent_out: torch.Tensor,
                          step_noise: Optional[torch.Tensor] = None):
         """step_noise [n_steps, n, latent] fp32 (contiguous, on the device): the per-step variance noise of the stochastic solver.

@@ -42,6 +42,7 @@ from typing import Callable, List, Optional, Sequence
 import numpy as np
 import torch
 
+from . import noise as _noise
 from .engine import Engine, EngineConfig, map_param_name
 
 _WARNED_QUEUED_RNG = False
@@ -440,11 +441,46 @@ def _request_cfg_scales(requests, cfg_scale, what):
             for i, r in enumerate(requests)]
 
 
+def _seed_values(seed, n, what):
+    """seed of one generate() call -> n entries, each an int in [0, 2**64) or None (a row without a seed of its own).  One int stands
+    for a one-row call only: a row's draws must not depend on its batch index, so several rows take one seed each."""
+    if seed is None:
+        return [None] * n
+    if isinstance(seed, (list, tuple)):
+        if len(seed) != n:
+            raise ValueError(f"{what}: seed holds {len(seed)} entries for {n} rows (one int or None per row)")
+        return [None if v is None else _noise.check_seed(v, f"{what}: seed[{i}]") for i, v in enumerate(seed)]
+    seed = _noise.check_seed(seed, f"{what}: seed")
+    if n != 1:
+        raise ValueError(f"{what}: one seed for {n} rows -- pass one seed per row (a list with an int or None for every row): a row's "
+                         "result must not depend on its batch index")
+    return [seed]
+
+
+def _resolve_seeds(seeds, cpu_gen=None):
+    """The seeds of a call's requests (ints or None) -> None when no request carries one (the call takes the torch generators' path,
+    draw for draw), else one seed per request: the requests without one get theirs from ONE torch.randint on the session's CPU
+    generator, in request order."""
+    if all(v is None for v in seeds):
+        return None
+    out = list(seeds)
+    miss = [i for i, v in enumerate(out) if v is None]
+    if miss:
+        drawn = torch.randint(0, 2 ** 63 - 1, (len(miss),), dtype=torch.int64, generator=cpu_gen).tolist()
+        for i, v in zip(miss, drawn):
+            out[i] = int(v)
+    return out
+
+
+def _request_seeds(requests, what):
+    return [None if r.get("seed") is None else _noise.check_seed(r["seed"], f"{what}, request {i}: seed") for i, r in enumerate(requests)]
+
+
 class _Utt:
     """One utterance in flight: its engine slot (KV caches 2*slot / 2*slot+1, codec states), lengths and outputs."""
     __slots__ = ("idx", "slot", "ids", "seq_len0", "init_len", "max_length", "max_steps", "max_step_sample", "step", "pos_len",
                  "neg_len", "have_embeds", "finished", "reach_max", "tokens", "chunks", "last", "forced", "noise_fn", "req",
-                 "t_admit", "t_done", "neg_book", "cfg_scale")
+                 "t_admit", "t_done", "neg_book", "cfg_scale", "seed", "n_lat")
 
     def __init__(self, idx, slot, ids, seq_len0, max_length, max_length_times, start_id):
         self.idx, self.slot, self.ids = idx, slot, ids
@@ -462,6 +498,8 @@ class _Utt:
         self.forced = self.noise_fn = self.req = None
         self.t_admit = self.t_done = None
         self.cfg_scale = None                         # this utterance's guidance scale (a session with mixed scales; else the session's)
+        self.seed = None                              # the request's seed (a call on the counter path, noise.py); else None
+        self.n_lat = 0                                # latents accepted so far: counter word t of the seeded solver noise
         # the reference's bookkeeping of this row's negative cache, without the tensors: [attention mask incl. the next token's slot,
         # entries ever appended, corrections so far (correct_cnt)] -- to recognise the one correction that keeps THIS step's entry (vv_kv_move)
         self.neg_book = [[1], 0, 0]
@@ -775,6 +813,9 @@ class VibeVoiceForConditionalGenerationInference:
         call (_process_speech_inputs), exactly as the Streaming presets do.  Not while the model generates."""
         e = self.engine
         prefill_noise = kw.pop("_prefill_noise", None)
+        seed = kw.pop("seed", None)                # the voice draws of the prefix as a function of this seed (noise.py); None: the device generator
+        if seed is not None:
+            seed = _noise.check_seed(seed, "build_prompt_prefix(): seed")
         input_ids = input_ids.cpu()
         if input_ids.dim() == 1:
             input_ids = input_ids[None]
@@ -802,7 +843,8 @@ class VibeVoiceForConditionalGenerationInference:
                 if speech_tensors is None or speech_masks is None:
                     raise ValueError("build_prompt_prefix: the row has speech positions; speech_tensors and speech_masks are required")
                 pos = torch.tensor(sp, dtype=torch.long).to(self.device)
-                _, emb = self._process_speech_inputs(speech_tensors, speech_masks, prefill_noise)
+                _, emb = self._process_speech_inputs(speech_tensors, speech_masks, prefill_noise,
+                                                     seeds=None if seed is None else [(seed, i) for i in range(speech_tensors.shape[0])])
                 if emb.shape[0] < len(sp):
                     raise ValueError("speech_masks hold fewer frames than speech_input_mask marks")
                 rows = emb[:len(sp)]
@@ -918,9 +960,26 @@ class VibeVoiceForConditionalGenerationInference:
             self._cfg_staged[:n] = vals
         return self._cfg_dev[:n]
 
-    def _process_speech_inputs(self, speech_tensors, speech_masks, prefill_noise=None, dev_gen=None):
+    def _voice_normals(self, seeds, frames):
+        """(r1 [n_spk], r2 [n_spk, frames, latent]) of seeded voice samples on the device: seeds[i] = (the request's seed, the sample's
+        speaker index within its request).  r2 = stream 0x80000001 (rows = speakers, t = frame, aux = speaker) through vv_noise_rows;
+        r1 = normal 0 of quad 0 of stream 0x80000002 (aux = speaker), on the host: n_spk numbers per request."""
+        e = self.engine
+        L, n_spk = e.cfg.latent_dim, len(seeds)
+        r1 = torch.stack([_noise.normals(sd, 0, 1, _noise.STREAM_VOICE_SCALE, 1, spk, 4)[0, 0, 0] for sd, spk in seeds])
+        if hasattr(e, "noise_rows") and L % 4 == 0:
+            r2 = torch.empty(n_spk, frames, L, dtype=torch.float32, device=self.device)
+            for i0 in range(0, n_spk, 16):
+                e.noise_rows([(sd, 0, spk) for sd, spk in seeds[i0:i0 + 16]], _noise.STREAM_VOICE, 1, frames, L, r2[i0:])
+        else:
+            r2 = torch.cat([_noise.normals(sd, 0, frames, _noise.STREAM_VOICE, 1, spk, L) for sd, spk in seeds])
+        return r1.to(self.device, torch.float32), r2.to(self.device, torch.float32)
+
+    def _process_speech_inputs(self, speech_tensors, speech_masks, prefill_noise=None, dev_gen=None, seeds=None):
         """_process_speech_inputs (:149-163): encode voice prompts, sample, scale, connect.
         dev_gen: a lane's own device generator (generate_interleaved); None = the device's global generator, as the reference.
+        seeds: one (seed, speaker index within its request) per voice sample of a call on the counter path (noise.py) -- no generator
+        is touched then; an explicit prefill_noise keeps precedence.
         Every host -> device copy of the call (waveform, frame selection, explicit noise) goes out BEFORE the encoder is enqueued:
         a pageable copy blocks the host until the stream has drained, and a boolean-mask gather synchronises to count its rows --
         behind the encoder either one keeps the prompt pass from being enqueued while the encoder runs."""
@@ -947,6 +1006,10 @@ class VibeVoiceForConditionalGenerationInference:
         sel_idx = speech_masks.reshape(-1).to(torch.bool).cpu().nonzero().squeeze(1).to(self.device)
         if prefill_noise is not None:
             prefill_noise = tuple(t.to(self.device, torch.float32) for t in prefill_noise)
+        elif seeds is not None and self.std_dist_type in ("gaussian", "fix"):
+            if len(seeds) != n_spk:
+                raise ValueError(f"{len(seeds)} seeds for {n_spk} voice samples")
+            prefill_noise = self._voice_normals(list(seeds), frames)
         mean = e.new(n_spk, frames, e.cfg.latent_dim)
         for i in range(n_spk):
             e.acoustic_encode(frames, wav[i], mean[i], valid_samples=valid)
@@ -1275,20 +1338,28 @@ class VibeVoiceForConditionalGenerationInference:
         # leaving the GPU idle; if the guess is wrong the latent is discarded and the RNG state restored.
         spec_sample, rng_state = False, None
         do_sample = S["do_sample"]
-        if (run and not fresh and self.speculate_sampling and not S["sde"]      # a discarded guess would spend device-RNG draws
-                and not (do_sample and S["noise_fn"] is None and S["forced"] is None)   # keep the reference's RNG draw order
+        seeded = S["seeds"] is not None         # the counter path: a discarded guess spends nothing, there is no state to restore
+        if (run and not fresh and self.speculate_sampling
+                and (seeded or (not S["sde"]      # a discarded guess would spend device-RNG draws
+                                and not (do_sample and S["noise_fn"] is None and S["forced"] is None)))   # keep the reference's RNG draw order
                 and all(u.last in (diff_id, start_id) for u in run)):
             nz = self._draw_noise(S, run)
-            if nz is None:
+            if nz is None and seeded:
+                self._seeded_noise(run)
+            elif nz is None:
                 # the draw is undone if the guess is wrong: on the session's OWN generator when it has one (a lane of
                 # generate_interleaved) -- rewinding the process-global generator from one lane would hand another lane draws it has
                 # already consumed
                 cg = S.get("cpu_gen")
                 rng_state = cg.get_state() if cg is not None else torch.get_rng_state()
                 nz = torch.randn(2 * nR, e.cfg.latent_dim, generator=cg)
-            self._stage_noise(nz, nR)
+            if nz is not None:
+                self._stage_noise(nz, nR)
             # all active rows diffusing, in order: cond rows == [hidden[:nR]; hidden[nR:2nR]]
-            e.diffusion_sample(nR, self._hidden, self._noise, self._cfg_arg(S, run), self._latent)
+            if S["sde"]:
+                e.diffusion_sample(nR, self._hidden, self._noise, self._cfg_arg(S, run), self._latent, step_noise=self._sde_draws(S, nR, run))
+            else:
+                e.diffusion_sample(nR, self._hidden, self._noise, self._cfg_arg(S, run), self._latent)
             spec_sample = True
         self._lg_event.synchronize()
         logits = self._logits_pin[:nA * nv].view(nA, nv).clone()
@@ -1301,6 +1372,22 @@ class VibeVoiceForConditionalGenerationInference:
             for u in order:
                 f = u.forced if u.forced is not None else S["forced"][u.idx]
                 u.last = int(f[u.step]) if u.step < len(f) else eos_id
+        elif seeded and do_sample:
+            # the counter path: one uniform per (request, token index) and the inverse CDF of the float64 softmax over the row's
+            # valid-id scores, per row on the host -- no [rows, lm_vocab] tensor, no generator; finished rows draw nothing
+            if S["warp"] is None:
+                lg = logits / S["temperature"]
+            elif self.warp_on_device and hasattr(e, "lm_warp_valid"):
+                lg = self._warp_valid_scores(torch.cat([pos_hidden(i) for i in range(nA)]), order, S).cpu()
+            else:
+                lg = self._full_vocab_scores(torch.cat([pos_hidden(i) for i in range(nA)]), order, S)[:, valid_t.to(self.device)].cpu()
+            if not bool(torch.isfinite(lg).any(dim=-1).all()):
+                raise RuntimeError("the full-vocabulary logits processors (top_k / top_p / min_p) removed every valid speech token "
+                                   "of a row: nothing is left to sample from (the reference fails in torch.multinomial here: "
+                                   "'probability tensor contains either `inf`, `nan` or element < 0')")
+            lg = lg.numpy()
+            for i, u in enumerate(order):
+                u.last = int(valid_t[_noise.choose(lg[i], _noise.uniform(u.seed, len(u.tokens)))])
         elif do_sample or S["warp"] is not None:
             # the reference samples torch.multinomial(softmax(scores)) over the FULL vocabulary rows of the WHOLE batch (-inf
             # outside the valid ids, :490-496; finished rows included, their draw is overwritten by eos, :499) on the model's
@@ -1420,12 +1507,15 @@ class VibeVoiceForConditionalGenerationInference:
                 u.neg_len += 1
             # ---- diffusion sampling (:697-710) ----
             nz = self._draw_noise(S, diff)
-            if nz is None:
-                nz = torch.randn(2 * n, e.cfg.latent_dim, generator=S.get("cpu_gen"))      # CPU global RNG, as the reference (:701), unless the session has its own
-            self._stage_noise(nz, n)
+            if nz is None and seeded:
+                self._seeded_noise(diff)
+            else:
+                if nz is None:
+                    nz = torch.randn(2 * n, e.cfg.latent_dim, generator=S.get("cpu_gen"))      # CPU global RNG, as the reference (:701), unless the session has its own
+                self._stage_noise(nz, n)
             cfg_scale = self._cfg_arg(S, diff)
             if S["sde"]:
-                e.diffusion_sample(n, self._cond, self._noise, cfg_scale, self._latent, step_noise=self._sde_draws(S, n))
+                e.diffusion_sample(n, self._cond, self._noise, cfg_scale, self._latent, step_noise=self._sde_draws(S, n, diff))
             else:
                 e.diffusion_sample(n, self._cond, self._noise, cfg_scale, self._latent)
         if diff and S.get("lockstep", True):
@@ -1482,6 +1572,12 @@ class VibeVoiceForConditionalGenerationInference:
             if audio_streamer is not None:
                 audio_streamer.put(chunk[:n, None, :].to(self.dtype), torch.tensor([u.idx for u in diff]))
             S["n_frames"] += n
+            if trace is not None and hasattr(trace, "noise"):
+                nz_host = self._noise[:n].cpu()                   # (request, t, start noise) of every ACCEPTED latent
+                for j, u in enumerate(diff):
+                    trace.noise.append((u.idx, u.n_lat, nz_host[j].clone()))
+            for u in diff:
+                u.n_lat += 1
             if trace is not None:
                 trace.neg_hidden.append(cond_used[n:2 * n].cpu())
                 trace.latents.append(self._latent[:n].cpu())
@@ -1539,7 +1635,18 @@ class VibeVoiceForConditionalGenerationInference:
             mask[cnt] = 0
             u.neg_book[2] = cnt + 1
 
-    def _sde_draws(self, S, n):
+    def _seeded_noise(self, utts):
+        """start noise of one sampler call over seeded utterances -> self._noise[:n]: row j is stream 0 of utts[j]'s seed at t = the
+        latents it has accepted (noise.py).  One vv_noise_rows launch: no host draw, no staging copy."""
+        e = self.engine
+        L = e.cfg.latent_dim
+        if hasattr(e, "noise_rows") and L % 4 == 0:
+            e.noise_rows([(u.seed, u.n_lat, 0) for u in utts], _noise.STREAM_START, 1, 1, L, self._noise)
+        else:
+            for j, u in enumerate(utts):
+                self._noise[j].copy_(_noise.normals(u.seed, u.n_lat, 1, _noise.STREAM_START, 1, 0, L)[0, 0])
+
+    def _sde_draws(self, S, n, utts=None):
         """The variance noise of one frame's solver steps, [N, n, latent] fp32 on the device.  scheduler.step() draws
         randn(model_output.shape = [2n, latent], device=model_output.device, float32) once per solver step on the device's
         global generator (dpm_solver.py:994-997; generate() passes no generator); only the first n rows survive the next step's
@@ -1551,6 +1658,13 @@ class VibeVoiceForConditionalGenerationInference:
         buf = self._sde_flat[:N * n * L].view(N, n, L)
         if S["sde_noise_fn"] is not None:                     # test hook: the recorded draws, [N, 2n, latent]
             buf.copy_(S["sde_noise_fn"](S["step"], N, 2 * n)[:, :n].to(buf.device, torch.float32))
+            return buf
+        if S["seeds"] is not None:                            # the counter path: streams 1 .. N of every row's seed, at its own t
+            if hasattr(e, "noise_rows") and L % 4 == 0:
+                e.noise_rows([(u.seed, u.n_lat, 0) for u in utts], _noise.STREAM_START + 1, N, 1, L, buf)
+            else:
+                for j, u in enumerate(utts):
+                    buf[:, j].copy_(_noise.normals(u.seed, u.n_lat, 1, _noise.STREAM_START + 1, N, 0, L)[:, 0])
             return buf
         for i in range(N):
             buf[i].copy_(torch.randn(2 * n, L, device=self.device, dtype=torch.float32, generator=S.get("dev_gen"))[:n])
@@ -1589,6 +1703,7 @@ class VibeVoiceForConditionalGenerationInference:
                     forced=kwargs.pop("_forced_tokens", None), noise_fn=kwargs.pop("_noise_fn", None), n_rows=n_rows,
                     teacher=kwargs.pop("_teacher_embeds", None), refresh_negative=bool(kwargs.get("refresh_negative", True)),
                     frame_rows=0, n_frames=0, step=0, sample_rows=None,
+                    seeds=None,               # one seed per request when the call runs the counter path (noise.py), set by the caller
                     # a session's own generators (generate_interleaved gives every lane a pair): None = the process-global CPU / device
                     # generators, i.e. the reference's RNG streams
                     cpu_gen=(kwargs.get("_generators") or (None, None))[0], dev_gen=(kwargs.pop("_generators", None) or (None, None))[1])
@@ -1601,9 +1716,14 @@ class VibeVoiceForConditionalGenerationInference:
                  speech_masks=None, speech_input_mask=None, is_prefill=True, return_speech=True,
                  cfg_scale=1.0, stop_check_fn: Optional[Callable[[], bool]] = None, tqdm_class=None, **kwargs):
         """logits_processor / stopping_criteria are accepted and unused, as in the reference (its generate() overwrites the
-        arguments with the lists it builds itself, :375-377)."""
+        arguments with the lists it builds itself, :375-377).
+        seed (keyword): an int for a one-row call, or a list with one int or None per row.  With at least one seed the call runs the
+        counter path (vibevoice_amd/noise.py): every draw of a row -- solver noise, token choice, voice latents -- is a function of
+        the row's seed and its own counters, whatever it shares the batch or the queue with; rows without a seed get one from ONE
+        torch.randint on the CPU generator.  No seed: the torch generators, as the reference, draw for draw."""
         e = self.engine
         tokenizer = kwargs.pop("tokenizer", None)
+        seeds_in = _seed_values(kwargs.pop("seed", None), (kwargs["input_ids"] if inputs is None else inputs).shape[0], "generate()")
         kwargs.pop("parsed_scripts", None)
         kwargs.pop("all_speakers_list", None)
         max_length_times = kwargs.pop("max_length_times", 2)
@@ -1625,11 +1745,12 @@ class VibeVoiceForConditionalGenerationInference:
             # output form
             return self._generate_queued(input_ids, attention_mask, tokenizer, generation_config, cfg_scales, audio_streamer,
                                          speech_tensors, speech_masks, speech_input_mask, is_prefill, return_speech, stop_check_fn,
-                                         max_length_times, prefill_noise, step_cb, kwargs, prompt_prefix=prompt_prefix)
+                                         max_length_times, prefill_noise, step_cb, kwargs, prompt_prefix=prompt_prefix, seeds=seeds_in)
         prefixes = self._prefix_list(prompt_prefix, B)
         pf_stats = {"prefix_rows_reused": 0, "prompt_rows_computed": 0}
         S = self._session(tokenizer, generation_config, cfg_scales, kwargs, audio_streamer, B)
         S["sample_rows"] = lambda order: list(range(B))
+        S["seeds"] = _resolve_seeds(seeds_in, S.get("cpu_gen"))
         self._frame_w = B                                 # frame-store rows are as wide as this call's batch
         if kwargs.get("max_new_tokens", None) is None:
             max_new_tokens = self.max_position_embeddings - L0
@@ -1641,6 +1762,8 @@ class VibeVoiceForConditionalGenerationInference:
             m = attention_mask[b].bool()
             utts.append(_Utt(b, b, input_ids[b][m].tolist(), L0, max_length, max_length_times, S["start_id"]))
             utts[-1].cfg_scale = cfg_scales[b]
+            if S["seeds"] is not None:
+                utts[-1].seed = S["seeds"][b]
         max_steps = min(max_length - L0, int(max_length_times * L0))
         time_prefill = os.environ.get("VVHIP_TIME_PREFILL") is not None     # debug: sync + time the two prefill phases
         if tqdm_class is not None and kwargs.get("show_progress_bar", True):
@@ -1690,6 +1813,21 @@ class VibeVoiceForConditionalGenerationInference:
                                 sp_pos[u.idx] = (int(idx.numel()), idx.to(self.device))
                     # rows that start with a prompt prefix: r leading positions come from its snapshot (0: today's full prefill)
                     reuse = {u.idx: self._prefix_plan(prefixes[u.idx], u.ids, sp_host.get(u.idx)) for u in utts}
+                    spk_seeds = None
+                    if with_voice and S["seeds"] is not None and prefill_noise is None:
+                        # every voice sample draws from the seed of the row it belongs to, under its index within that row
+                        need = [sp_pos[u.idx][0] if u.idx in sp_pos else 0 for u in utts]
+                        spk = _speakers_of_rows(need, [int(speech_masks[i].sum()) for i in range(speech_masks.shape[0])])
+                        if spk is None:
+                            raise ValueError("generate(seed=...): a voice sample spans two batch rows; with seeds the rows' speech "
+                                             "positions must consume whole voice samples")
+                        spk_seeds = [None] * speech_masks.shape[0]
+                        for u in utts:
+                            for k, i in enumerate(spk[u.idx]):
+                                spk_seeds[i] = (u.seed, k)
+                        for i in range(len(spk_seeds)):          # samples no row consumes: their latents are never read
+                            if spk_seeds[i] is None:
+                                spk_seeds[i] = (utts[-1].seed, i)
                     if with_voice and any(reuse.values()):
                         # the voice samples of a prefixed row are in the prefix: only the other rows' samples are encoded (none: no
                         # encoder call at all).  A sample that spans two rows cannot be told apart: then every sample is encoded.
@@ -1705,10 +1843,12 @@ class VibeVoiceForConditionalGenerationInference:
                                 speech_tensors, speech_masks = speech_tensors.cpu()[sel], speech_masks.cpu()[sel]
                                 if prefill_noise is not None:
                                     prefill_noise = tuple(t.cpu()[sel] for t in prefill_noise)
+                                if spk_seeds is not None:
+                                    spk_seeds = [spk_seeds[i] for i in keep_spk]
                             else:
                                 with_voice = False
                     if with_voice:
-                        _, sp_embeds = self._process_speech_inputs(speech_tensors, speech_masks, prefill_noise)
+                        _, sp_embeds = self._process_speech_inputs(speech_tensors, speech_masks, prefill_noise, seeds=spk_seeds)
                     if time_prefill:
                         e.sync(); torch.cuda.current_stream(self.device).synchronize(); t_pf.append(time.perf_counter())
                     sp_off = 0
@@ -1751,7 +1891,7 @@ class VibeVoiceForConditionalGenerationInference:
 
     def _generate_queued(self, input_ids, attention_mask, tokenizer, generation_config, cfg_scales, audio_streamer, speech_tensors,
                          speech_masks, speech_input_mask, is_prefill, return_speech, stop_check_fn, max_length_times, prefill_noise,
-                         step_cb, kwargs, prompt_prefix=None):
+                         step_cb, kwargs, prompt_prefix=None, seeds=None):
         """generate() for a batch of more than MAX_BATCH rows (the reference's batch is unbounded, :393-394): every row becomes a
         one-utterance request of generate_continuous() -- up to n_slots of them in flight, a finished row's slot refilled at once --
         and the results are assembled into ONE VibeVoiceGenerationOutput as the batched loop returns it (sequences [B, L0 + steps]
@@ -1772,7 +1912,8 @@ class VibeVoiceForConditionalGenerationInference:
         forced = kwargs.pop("_forced_tokens", None)
         noise_fn = kwargs.pop("_noise_fn", None)
         global _WARNED_QUEUED_RNG
-        if not _WARNED_QUEUED_RNG and (noise_fn is None or self._generation_options(generation_config)[0]):
+        all_seeded = seeds is not None and all(v is not None for v in seeds)      # every draw is the row's own: nothing follows the queue
+        if not _WARNED_QUEUED_RNG and not all_seeded and (noise_fn is None or self._generation_options(generation_config)[0]):
             _WARNED_QUEUED_RNG = True
             import warnings
             warnings.warn(f"generate(): a batch of {B} rows exceeds one engine pass ({min(MAX_BATCH, self.engine.cfg.n_slots, self.engine.cfg.max_rows // 2)} "
@@ -1807,6 +1948,8 @@ class VibeVoiceForConditionalGenerationInference:
             if noise_fn is not None:
                 r["_noise_fn"] = noise_fn                # per utterance here: noise_fn(its own step, 2) -> [2, latent]
             r["cfg_scale"] = cfg_scales[b]               # the row's own guidance scale (all equal when generate() got a float)
+            if seeds is not None and seeds[b] is not None:
+                r["seed"] = seeds[b]
             reqs.append(r)
         kw = {k: v for k, v in kwargs.items() if k in ("verbose", "refresh_negative", "_trace", "_teacher_embeds", "_t_cast", "_sde_noise_fn")}
         outs = self.generate_continuous(reqs, tokenizer=tokenizer, generation_config=generation_config, cfg_scale=cfg_scales[0],
@@ -1844,14 +1987,22 @@ class VibeVoiceForConditionalGenerationInference:
         noise every request ends exactly as generate() on it alone (the lanes share nothing but read-only weights).  Random draws:
         every lane owns a CPU and a device torch.Generator seeded from the process-global CPU generator when the call starts, so a
         seeded call is reproducible and no lane consumes (or, undoing a speculative draw, rewinds) another lane's stream -- but the
-        noise a request sees is its lane's, not what the same request would draw on the global generators through generate().  Returns the outputs in request order.  The lanes are
+        noise a request sees is its lane's, not what the same request would draw on the global generators through generate().  Requests
+        with a "seed" key (generate_continuous) draw from their own counters instead: the lane generators are not used for them and the
+        lane a request lands in does not matter.  Returns the outputs in request order.  The lanes are
         created on first use (each owns KV caches for its n_slots) and kept: `model.close_lanes()` releases them."""
         import threading
         from .parallel import shard_utterances
         _request_cfg_scales(requests, kwargs.get("cfg_scale", 1.0), "generate_interleaved()")      # refused here, before any lane starts
+        seeds = _request_seeds(requests, "generate_interleaved()")
         lanes = max(1, min(int(lanes), len(requests)))
         if lanes == 1:
             return self.generate_continuous(requests, audio_streamer=audio_streamer, **kwargs)
+        # seeds are settled here, on the caller's thread (a request without one in a call that has some: one randint on the
+        # process-global CPU generator, in request order), so which lane a request lands in does not matter
+        seeds = _resolve_seeds(seeds)
+        if seeds is not None:
+            requests = [dict(r, seed=sd) for r, sd in zip(requests, seeds)]
         pool = getattr(self, "_lanes", None) or []
         while len(pool) < lanes - 1:
             pool.append(self.fork())
@@ -1919,7 +2070,10 @@ class VibeVoiceForConditionalGenerationInference:
         in flight share every LM / diffusion-head weight pass.  Each request ends exactly as generate() on it alone would
         (greedy / forced decoding; with do_sample the draws interleave on the global generator).  Returns one
         VibeVoiceGenerationOutput per request, in request order; `audio_streamer` (batch_size = len(requests)) sees
-        sample index = request index."""
+        sample index = request index.
+        A request's "seed" key (an int in [0, 2**64)) makes every draw of that request a function of the seed and the request's own
+        counters (vibevoice_amd/noise.py): the same take in any slot, behind any queue.  One seeded request puts the whole call on that
+        path -- the others get a seed from ONE torch.randint on the session's CPU generator, in request order."""
         e = self.engine
         n_req = len(requests)
         cfg_scales = _request_cfg_scales(requests, cfg_scale, "generate_continuous()")      # a request's own "cfg_scale" key, else the call's
@@ -1938,6 +2092,7 @@ class VibeVoiceForConditionalGenerationInference:
                           audio_streamer, n_req)
         S["lockstep"] = False                   # independent requests: no cross-row tokenizer-cache coupling (see _iterate)
         S["sample_rows"] = lambda order: [u.idx for u in order]
+        S["seeds"] = _resolve_seeds(_request_seeds(requests, "generate_continuous()"), S.get("cpu_gen"))
         self._frame_w = cap
         self._first_row = {}
         queue = list(range(n_req))
@@ -2003,6 +2158,8 @@ class VibeVoiceForConditionalGenerationInference:
                     u = _Utt(ri, slot, ids_t[0][am[0].bool()].tolist(), L0, min(L0 + mnt, e.max_ctx), max_length_times, S["start_id"])
                     u.forced, u.noise_fn, u.req = r.get("_forced_tokens"), r.get("_noise_fn"), r
                     u.cfg_scale = cfg_scales[ri]
+                    if S["seeds"] is not None:
+                        u.seed = S["seeds"][ri]
                     u.t_admit = it
                     e.codec_reset(slot)
                     rows = pos = None
@@ -2012,7 +2169,8 @@ class VibeVoiceForConditionalGenerationInference:
                         sp_host = None if sim is None else sim[0].cpu()[am[0].bool().cpu()].to(torch.bool).nonzero().squeeze(1).tolist()
                         reuse = self._prefix_plan(r["prompt_prefix"], u.ids, sp_host)
                     if not reuse and is_prefill and r.get("speech_tensors") is not None and r.get("speech_masks") is not None:
-                        _, sp = self._process_speech_inputs(r["speech_tensors"], r["speech_masks"], r.get("_prefill_noise"), dev_gen=S.get("dev_gen"))
+                        _, sp = self._process_speech_inputs(r["speech_tensors"], r["speech_masks"], r.get("_prefill_noise"), dev_gen=S.get("dev_gen"),
+                                                            seeds=None if u.seed is None else [(u.seed, k) for k in range(r["speech_tensors"].shape[0])])
                         sim = r.get("speech_input_mask")
                         if sim is not None:
                             idx = sim[0].cpu()[am[0].bool().cpu()].to(torch.bool).nonzero().squeeze(1)      # host data: no device count

@@ -16,6 +16,7 @@ import os
 
 import numpy as np
 
+from . import noise as _noise
 from .engine import Engine, EngineConfig
 from .modeling import VibeVoiceGenerationOutput, WeightHandle, _Ns, _SchedulerView, engine_config_from_reference
 
@@ -244,8 +245,13 @@ class VibeVoiceStreamingForConditionalGenerationInference:
 
     @torch.no_grad()
     def generate(self, inputs=None, generation_config=None, audio_streamer=None, tts_text_ids=None,
-                 return_speech=True, cfg_scale=1.0, stop_check_fn: Optional[Callable[[], bool]] = None, **kwargs):
+                 return_speech=True, cfg_scale=1.0, stop_check_fn: Optional[Callable[[], bool]] = None, seed: Optional[int] = None,
+                 **kwargs):
+        """seed: an int in [0, 2**64) makes the session's start noise a function of (seed, frame index) alone (vibevoice_amd/noise.py,
+        stream 0, generated on the device by vv_noise_rows); None: torch.randn on the CPU generator, as the reference."""
         e = self.engine
+        if seed is not None:
+            seed = _noise.check_seed(seed, "generate(seed=...)")
         all_pre = kwargs.pop("all_prefilled_outputs")
         # the processor's prompt ids (vibevoice_streaming_processor.py:180-325): the preset's caches already hold them; the
         # reference returns them in front of the generated ids (`sequences=tts_lm_input_ids`, :722)
@@ -302,8 +308,14 @@ class VibeVoiceStreamingForConditionalGenerationInference:
                     tts_len += k
                     self._cond[0].copy_(self._hid[k - 1])
                 for i in range(TTS_SPEECH_WINDOW_SIZE):
-                    nz = noise_fn(frame, 2) if noise_fn is not None else torch.randn(2, e.cfg.latent_dim)
-                    self._noise[0].copy_(nz[0].to(torch.float32))
+                    if noise_fn is None and seed is not None:
+                        if hasattr(e, "noise_rows"):
+                            e.noise_rows([(seed, frame, 0)], _noise.STREAM_START, 1, 1, e.cfg.latent_dim, self._noise)
+                        else:
+                            self._noise[0].copy_(_noise.normals(seed, frame, 1, _noise.STREAM_START, 1, 0, e.cfg.latent_dim)[0, 0])
+                    else:
+                        nz = noise_fn(frame, 2) if noise_fn is not None else torch.randn(2, e.cfg.latent_dim)
+                        self._noise[0].copy_(nz[0].to(torch.float32))
                     e.diffusion_sample(1, self._cond, self._noise, cfg_scale, self._latent)
                     own_latent = None
                     if teacher is not None:
