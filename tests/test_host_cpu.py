@@ -596,7 +596,7 @@ def test_full_vocabulary_processors_equal_the_transformers_classes(monkeypatch):
     from test_oracle_golden import _oracle_small
     from transformers.generation.logits_process import (MinPLogitsWarper, RepetitionPenaltyLogitsProcessor, TemperatureLogitsWarper,
                                                         TopKLogitsWarper, TopPLogitsWarper)
-    from vibevoice_amd.modeling import VibeVoiceForConditionalGenerationInference
+    from vibevoice_amd.modeling import VibeVoiceForConditionalGenerationInference, _Session
     om = _oracle_small()
     with fake_engine.cpu_cuda_shims(monkeypatch):
         eng = fake_engine.FakeEngine(om, n_slots=1)
@@ -613,7 +613,7 @@ def test_full_vocabulary_processors_equal_the_transformers_classes(monkeypatch):
             order.append(_types.SimpleNamespace(idx=i, ids=ids, tokens=torch.randint(0, V, (4,), generator=g).tolist(),
                                                 seq_len0=40 if i % 2 else len(ids), init_len=len(ids)))
         warp = dict(top_k=180, top_p=0.9, min_p=0.003, repetition_penalty=1.25)
-        got = m._full_vocab_scores(hid, order, dict(warp=warp, do_sample=True, temperature=0.6, pad_id=V - 2))
+        got = m._full_vocab_scores(hid, order, _Session(warp=warp, do_sample=True, temperature=0.6, pad_id=V - 2))
     want = torch.nn.functional.linear(hid, om.lm_head)
     for i, u in enumerate(order):
         row = ([V - 2] if u.seq_len0 > u.init_len else []) + u.ids + u.tokens

@@ -51,11 +51,12 @@ def summarise(us):
 
 
 def measure(model, n, sde, iters, warmup):
+    from vibevoice_amd.modeling import _Session
     e = model.engine
     L = e.cfg.latent_dim
     utts = [types.SimpleNamespace(seed=0x9e3779b97f4a7c15 + i, n_lat=0) for i in range(n)]
-    S_torch = dict(seeds=None, sde_noise_fn=None, step=0, dev_gen=None, cpu_gen=None)
-    S_seed = dict(seeds=[u.seed for u in utts], sde_noise_fn=None, step=0)
+    S_torch = _Session(seeds=None, sde_noise_fn=None, step=0, dev_gen=None, cpu_gen=None)
+    S_seed = _Session(seeds=[u.seed for u in utts], sde_noise_fn=None, step=0)
 
     def arm_torch():
         model._stage_noise(torch.randn(2 * n, L), n)

@@ -58,6 +58,7 @@ def summarise(us):
 
 
 def measure(model, n, iters, warmup):
+    from vibevoice_amd.modeling import _Session
     e = model.engine
     V, H = e.cfg.lm_vocab, e.cfg.lm_hidden
     g = torch.Generator().manual_seed(11)
@@ -70,8 +71,8 @@ def measure(model, n, iters, warmup):
     e.set_valid_tokens(valid)
     vt = torch.tensor(valid, dtype=torch.long, device=e.device)
     hist = torch.randint(0, V, (n, 64 + warmup + iters), generator=g).tolist()
-    S = dict(warp=dict(top_k=GEN_CFG["top_k"], top_p=GEN_CFG["top_p"], min_p=0.0, repetition_penalty=GEN_CFG["repetition_penalty"]),
-             do_sample=True, temperature=1.0, pad_id=None, nv=len(valid))
+    S = _Session(warp=dict(top_k=GEN_CFG["top_k"], top_p=GEN_CFG["top_p"], min_p=0.0, repetition_penalty=GEN_CFG["repetition_penalty"]),
+                 do_sample=True, temperature=1.0, pad_id=None, nv=len(valid))
     order = [types.SimpleNamespace(idx=i, slot=i, ids=hist[i][:64], tokens=[], seq_len0=64, init_len=64, finished=False) for i in range(n)]
 
     def arm_torch():
@@ -81,7 +82,10 @@ def measure(model, n, iters, warmup):
         return lg
 
     def arm_device():
-        return model._warp_valid_scores(hid, order, S)
+        lg = model._warp_valid_scores(hid, order, S)
+        if int(model._warp_surv[:n].min()) < 1:
+            raise SystemExit("device arm: a row lost every valid token")
+        return lg
 
     def arm_logits():
         e.lm_logits_full(n, hid, scratch)

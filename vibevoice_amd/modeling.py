@@ -35,9 +35,11 @@ no cross-sample arithmetic, :393-394,549,573,594).
 import json
 import contextlib
 import os
+import threading
 import time
-from dataclasses import dataclass
-from typing import Callable, List, Optional, Sequence
+import warnings
+from dataclasses import dataclass, field
+from typing import Any, Callable, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -401,6 +403,12 @@ def _speakers_of_rows(need, have):
     return out
 
 
+def _speech_positions(speech_input_mask_row, attention_mask_row):
+    """positions of a row's speech tokens within its unpadded prompt: an int64 index tensor on the host (the masks are the
+    processor's host data: no device count)"""
+    return speech_input_mask_row.cpu()[attention_mask_row.bool().cpu()].to(torch.bool).nonzero().squeeze(1)
+
+
 def _cfg_scale_values(cfg_scale, n, what):
     """cfg_scale of one call -> n finite Python floats, one per utterance.  A real number stands for every row; a sequence or 1-D
     tensor / array carries one value per row.  ValueError on a wrong length, a non-finite value or anything that is not a real
@@ -474,6 +482,54 @@ def _resolve_seeds(seeds, cpu_gen=None):
 
 def _request_seeds(requests, what):
     return [None if r.get("seed") is None else _noise.check_seed(r["seed"], f"{what}, request {i}: seed") for i, r in enumerate(requests)]
+
+
+_NO_VALID_TOKEN_LEFT = ("the full-vocabulary logits processors (top_k / top_p / min_p) removed every valid speech token "
+                        "of a row: nothing is left to sample from (the reference fails in torch.multinomial here: "
+                        "'probability tensor contains either `inf`, `nan` or element < 0')")
+
+
+@dataclass(slots=True)
+class _Session:
+    """What one generate() / generate_continuous() call holds beside its utterances (_session builds it; every field has a default, so
+    a caller of one stage -- a test, a tool -- names only what that stage reads)."""
+    sde: bool = False                              # the stochastic solver ('sde-dpmsolver++')
+    sde_noise_fn: Optional[Callable] = None        # test hook: the recorded variance draws
+    nv: int = 0                                    # number of valid ids
+    valid_t: Optional[torch.Tensor] = None         # the valid ids in the engine's order (host, int64)
+    start_id: Optional[int] = None
+    end_id: Optional[int] = None
+    diff_id: Optional[int] = None
+    eos_id: Optional[int] = None
+    pad_id: Optional[int] = None
+    cfg_scale: float = 1.0                         # the call's guidance scale
+    cfg_rows: bool = False                         # the utterances carry different scales (_cfg_arg)
+    do_sample: bool = False
+    temperature: float = 1.0
+    warp: Optional[dict] = None                    # the full-vocabulary processors' settings (_generation_options); None: none asked for
+    trace: Any = None
+    audio_streamer: Any = None
+    verbose: bool = False
+    forced: Any = None                             # test / bench hooks: token plan per row, noise_fn(step, rows), teacher(step, rows)
+    noise_fn: Optional[Callable] = None
+    teacher: Optional[Callable] = None
+    n_rows: int = 0
+    refresh_negative: bool = True
+    lockstep: bool = True                          # the rows are one batch of the reference's loop (False: independent requests)
+    sample_rows: Optional[Callable] = None         # order -> the row ids of the torch.multinomial call (_choose_tokens)
+    seeds: Optional[List[int]] = None              # one seed per request when the call runs the counter path (noise.py)
+    cpu_gen: Optional[torch.Generator] = None      # the session's own generators (generate_interleaved gives every lane a pair); None: the
+    dev_gen: Optional[torch.Generator] = None      # process-global CPU / device generators, i.e. the reference's RNG streams
+    frame_rows: int = 0                            # rows of the frame store written so far
+    n_frames: int = 0
+    step: int = 0                                  # the caller's loop iteration
+    _seen: dict = field(default_factory=dict)      # repetition penalty, torch path: {idx: [seen mask [V], tokens folded in]}
+    _seen_dev: dict = field(default_factory=dict)  # ... device path: {idx: tokens folded in} (the masks are rows of the model's _seen_buf)
+
+    @property
+    def seeded(self) -> bool:
+        """the call is on the counter path: no draw touches a torch generator"""
+        return self.seeds is not None
 
 
 class _Utt:
@@ -565,6 +621,12 @@ class VibeVoiceForConditionalGenerationInference:
         self._side_streams = [torch.cuda.Stream(device=self.device) for _ in range(min(NB, engine.cfg.n_slots))] if engine.cfg.n_slots > 1 else []
         self._audio_blocks = []                                       # output frames, FRAME_BLOCK steps per block (no per-step allocation)
         self.frame_block = 64
+        self._frame_w = min(NB, max(1, engine.cfg.n_slots))           # utterances per row of the frame store (the call's batch / slots)
+        self._first_row = None                                        # generate_continuous: {id(utterance): its first frame-store row}
+        # allocated on first use: the one-pass prompt buffers, the processors' [16, V] logits, the warp kernel's outputs, its seen rows
+        self._pf_buf = self._full_logits = self._warp_out = self._warp_surv = self._seen_buf = None
+        self._t_lm_pass = self._t_kv_fill = 0.0                       # VVHIP_TIME_PREFILL: seconds inside the LM launches / the bench's cache fill
+        self._lanes = []                                              # generate_interleaved: the fork()ed models, kept until close_lanes()
         # plain attributes (tests flip them): per-utterance tokenizer chains on forked streams; several utterances' chains of a step
         # as ONE engine call (vv_codec_chain_batch); the sampler enqueued speculatively behind the LM pass
         self.concurrent_codecs = True
@@ -635,8 +697,7 @@ class VibeVoiceForConditionalGenerationInference:
             try:
                 m.warmup()
             except Exception as ex:         # a failed warm-up costs the first request its latency, never the model load --
-                import warnings             # unless the device itself is gone: then the load fails here, with the cause
-                try:
+                try:                        # unless the device itself is gone: then the load fails here, with the cause
                     torch.cuda.synchronize(m.device)
                     m.engine.sync()
                 except Exception as dead:
@@ -826,7 +887,7 @@ class VibeVoiceForConditionalGenerationInference:
         ids = input_ids[0][keep].tolist()
         sp_all = []
         if speech_input_mask is not None:
-            sp_all = speech_input_mask.cpu().reshape(1, -1)[0][keep].to(torch.bool).nonzero().squeeze(1).tolist()
+            sp_all = _speech_positions(speech_input_mask.reshape(1, -1)[0], keep).tolist()
         if n_prefix is None:
             if not sp_all:
                 raise ValueError("build_prompt_prefix: n_prefix is required when the row has no speech positions")
@@ -948,8 +1009,8 @@ class VibeVoiceForConditionalGenerationInference:
         the session has the same scale -- the scalar kernels and graphs -- else a view of the one staging buffer holding each row's own
         scale.  The values travel host -> pinned -> device on the engine stream without a sync; nothing is copied while the rows and
         their scales are what the buffer already holds."""
-        if not S["cfg_rows"]:
-            return S["cfg_scale"]
+        if not S.cfg_rows:
+            return S.cfg_scale
         vals = [u.cfg_scale for u in utts]
         n = len(vals)
         if self._cfg_staged[:n] != vals:
@@ -1097,9 +1158,9 @@ class VibeVoiceForConditionalGenerationInference:
         (generation/utils.py `_get_logits_processor`): repetition penalty over the row's input_ids (left padding, prompt and
         generated tokens), then -- with do_sample -- temperature, top-k, top-p, min-p (min_tokens_to_keep = 1).  The valid-token
         constraint comes after them (the caller)."""
-        e, w = self.engine, S["warp"]
+        e, w = self.engine, S.warp
         n, V = hidden.shape[0], e.cfg.lm_vocab
-        if getattr(self, "_full_logits", None) is None or self._full_logits.numel() < 16 * V:
+        if self._full_logits is None or self._full_logits.numel() < 16 * V:
             self._full_logits = torch.empty(16 * V, dtype=torch.float32, device=self.device)
         hidden = hidden.to(torch.float32).contiguous()
         parts = []
@@ -1113,11 +1174,11 @@ class VibeVoiceForConditionalGenerationInference:
             # penalised once.  The row's "seen" set is a [V] mask kept on the device for the session and extended by the tokens
             # generated since the last step: O(1) per step, not O(history) (a 90-minute utterance has ~40 K of them).
             pen = w["repetition_penalty"]
-            seen = S.setdefault("_seen", {})
+            seen = S._seen
             for i, u in enumerate(order):
                 ent = seen.get(u.idx)
                 if ent is None:
-                    base = list(u.ids) + ([S["pad_id"]] if (u.seq_len0 > u.init_len and S["pad_id"] is not None) else [])
+                    base = list(u.ids) + ([S.pad_id] if (u.seq_len0 > u.init_len and S.pad_id is not None) else [])
                     mask = torch.zeros(V, dtype=torch.bool, device=scores.device)
                     mask[torch.tensor([int(t) for t in base if 0 <= int(t) < V], dtype=torch.long, device=scores.device)] = True
                     ent = seen[u.idx] = [mask, 0]
@@ -1127,9 +1188,9 @@ class VibeVoiceForConditionalGenerationInference:
                 ent[1] = len(u.tokens)
                 sc = scores[i]
                 scores[i] = torch.where(ent[0], torch.where(sc < 0, sc * pen, sc / pen), sc)
-        if S["do_sample"]:
-            if S["temperature"] != 1.0:
-                scores = scores / S["temperature"]
+        if S.do_sample:
+            if S.temperature != 1.0:
+                scores = scores / S.temperature
             if w["top_k"] > 0:
                 kth = torch.topk(scores, min(w["top_k"], V))[0][..., -1, None]
                 scores = scores.masked_fill(scores < kth, float("-inf"))
@@ -1150,12 +1211,12 @@ class VibeVoiceForConditionalGenerationInference:
     def _warp_valid_scores(self, hidden: torch.Tensor, order, S) -> torch.Tensor:
         """[n, n_valid] scores of the valid ids of the given positive rows after the same processors as _full_vocab_scores and the
         valid-token constraint (-inf where a filter removed an id), from vv_lm_warp_valid: no [n, V] clone and no torch op over the
-        vocabulary.  Raises when a row keeps no valid id."""
-        e, w = self.engine, S["warp"]
-        n, V, nv = hidden.shape[0], e.cfg.lm_vocab, S["nv"]
-        if getattr(self, "_full_logits", None) is None or self._full_logits.numel() < 16 * V:
+        vocabulary.  _warp_surv[:n] holds how many valid ids every row keeps (_valid_scores refuses a row without one)."""
+        e, w = self.engine, S.warp
+        n, V, nv = hidden.shape[0], e.cfg.lm_vocab, S.nv
+        if self._full_logits is None or self._full_logits.numel() < 16 * V:
             self._full_logits = torch.empty(16 * V, dtype=torch.float32, device=self.device)
-        if getattr(self, "_warp_out", None) is None or self._warp_out.numel() < n * 16:
+        if self._warp_out is None or self._warp_out.numel() < n * 16:
             self._warp_out = torch.empty(max(16, n) * 16, dtype=torch.float32, device=self.device)
             self._warp_surv = torch.empty(max(16, n), dtype=torch.int32, device=self.device)
         hidden = hidden.to(torch.float32).contiguous()
@@ -1165,15 +1226,15 @@ class VibeVoiceForConditionalGenerationInference:
             # [slots][V] byte buffer on the device, one per engine slot, extended by the tokens generated since the last step --
             # the same ids in the same order as the dict of bool masks of _full_vocab_scores
             n_rows = max(int(getattr(e.cfg, "n_slots", 1)), max(u.slot for u in order) + 1)
-            if getattr(self, "_seen_buf", None) is None or self._seen_buf.shape[0] < n_rows or self._seen_buf.shape[1] != V:
+            if self._seen_buf is None or self._seen_buf.shape[0] < n_rows or self._seen_buf.shape[1] != V:
                 self._seen_buf = torch.zeros(n_rows, V, dtype=torch.uint8, device=self.device)
-                S.pop("_seen_dev", None)
-            done = S.setdefault("_seen_dev", {})
+                S._seen_dev = {}
+            done = S._seen_dev
             flat = []                                 # every row's new ids as positions of the flat buffer: one upload, one scatter per step
             for u in order:
                 if u.idx not in done:
                     self._seen_buf[u.slot].zero_()    # once per utterance: the slot's previous owner
-                    fresh_tok = list(u.ids) + ([S["pad_id"]] if (u.seq_len0 > u.init_len and S["pad_id"] is not None) else [])
+                    fresh_tok = list(u.ids) + ([S.pad_id] if (u.seq_len0 > u.init_len and S.pad_id is not None) else [])
                     done[u.idx] = 0
                 else:
                     fresh_tok = []
@@ -1192,12 +1253,8 @@ class VibeVoiceForConditionalGenerationInference:
                     j1 += 1
                 e.lm_warp_valid(j1 - j0, self._full_logits[j0 * V:], self._seen_buf[order[i0 + j0].slot:].reshape(-1) if pen != 1.0 else None,
                                 self._warp_out[(i0 + j0) * nv:], self._warp_surv[i0 + j0:], repetition_penalty=pen,
-                                temperature=S["temperature"], do_sample=S["do_sample"], top_k=w["top_k"], top_p=w["top_p"], min_p=w["min_p"])
+                                temperature=S.temperature, do_sample=S.do_sample, top_k=w["top_k"], top_p=w["top_p"], min_p=w["min_p"])
                 j0 = j1
-        if int(self._warp_surv[:n].min()) < 1:
-            raise RuntimeError("the full-vocabulary logits processors (top_k / top_p / min_p) removed every valid speech token "
-                               "of a row: nothing is left to sample from (the reference fails in torch.multinomial here: "
-                               "'probability tensor contains either `inf`, `nan` or element < 0')")
         return self._warp_out[:n * nv].view(n, nv)
 
     # ------------------------------------------------------------------ prompt prefill of one utterance
@@ -1217,7 +1274,7 @@ class VibeVoiceForConditionalGenerationInference:
         if n <= CH:
             # one-pass prompts (the common case) reuse two persistent [max_rows, H] buffers: a fresh 2 x 150 MB allocation per
             # request is milliseconds of hipMalloc; every row is overwritten by the embedding lookup, no zero fill needed
-            if getattr(self, "_pf_buf", None) is None or self._pf_buf.shape[1] < n:
+            if self._pf_buf is None or self._pf_buf.shape[1] < n:
                 with torch.cuda.stream(e.stream):
                     self._pf_buf = torch.empty(2, CH, H, dtype=torch.float32, device=self.device)
             emb = self._pf_buf[0, :n]
@@ -1243,7 +1300,7 @@ class VibeVoiceForConditionalGenerationInference:
         self._hid_fresh[u.slot].copy_(hid[(n - 1) % CH])
         if timed:
             e.sync(); torch.cuda.current_stream(self.device).synchronize()
-            self._t_lm_pass = getattr(self, "_t_lm_pass", 0.0) + (time.perf_counter() - t_emb)
+            self._t_lm_pass += time.perf_counter() - t_emb
         n = u.pos_len = pos0 + n
         if kv_start > n:             # bench hook: decode measured at a long context (kv_fill_fn supplies the cache contents)
             if kv_fill_fn is not None:
@@ -1253,7 +1310,7 @@ class VibeVoiceForConditionalGenerationInference:
                 kv_fill_fn(e, 2 * u.slot, n, kv_start)
                 if timed:
                     e.sync(); torch.cuda.current_stream(self.device).synchronize()
-                    self._t_kv_fill = getattr(self, "_t_kv_fill", 0.0) + (time.perf_counter() - t0)
+                    self._t_kv_fill += time.perf_counter() - t0
             u.pos_len = kv_start
 
     def _prefill_checked(self, jobs):
@@ -1274,13 +1331,12 @@ class VibeVoiceForConditionalGenerationInference:
             except RuntimeError as ex:
                 if attempt or "K-split" not in str(ex):
                     raise
-                import warnings
                 warnings.warn(f"vibevoice_amd: {ex}; repeating the prompt pass once", RuntimeWarning)
 
     def _block_rows(self, i: int):
         """row i of the frame store: [utterances in flight, hop] fp32, frame_block rows per block"""
         b, r = divmod(i, self.frame_block)
-        w = getattr(self, "_frame_w", min(MAX_BATCH, max(1, self.engine.cfg.n_slots)))
+        w = self._frame_w
         if any(t is not None and t.shape[1] != w for t in self._audio_blocks):
             self._audio_blocks = []
         while len(self._audio_blocks) <= b:
@@ -1298,15 +1354,69 @@ class VibeVoiceForConditionalGenerationInference:
     # ------------------------------------------------------------------ one iteration of the hot loop over the active utterances
     def _iterate(self, S, act: List[_Utt]):
         """modeling_vibevoice_inference.py:466-672 for the utterances in `act`; returns the utterances still live."""
-        e = self.engine
-        nv, valid_t = S["nv"], S["valid_t"]
-        start_id, end_id, diff_id, eos_id = S["start_id"], S["end_id"], S["diff_id"], S["eos_id"]
-        trace, audio_streamer, verbose = S["trace"], S["audio_streamer"], S["verbose"]
         run = [u for u in act if u.have_embeds]
         fresh = [u for u in act if not u.have_embeds]
         order = run + fresh
-        nR, nA = len(run), len(order)
-        # ---------------- positive (+ speculative negative) LM pass ----------------
+        nR = len(run)
+        self._lm_pass(S, run, fresh)
+
+        def hidden_of(i):                       # hidden state of order[i]'s positive row, [1, H]
+            return self._hidden[i:i + 1] if i < nR else self._hid_fresh[order[i].slot:order[i].slot + 1]
+        # ---- speculative sampling: a row that has just emitted <speech_diffusion>/<speech_start> almost always
+        # emits <speech_diffusion> next.  The sampler (stateless: cond + noise -> latent) is enqueued behind the LM
+        # pass BEFORE the host waits for the logits, so the token decision below overlaps GPU work instead of
+        # leaving the GPU idle; if the guess is wrong the latent is discarded and the RNG state restored.
+        # (the counter path: a discarded guess spends nothing, there is no state to restore)
+        speculated = bool(run and not fresh and self.speculate_sampling
+                          and (S.seeded or (not S.sde      # a discarded guess would spend device-RNG draws
+                                            and not (S.do_sample and S.noise_fn is None and S.forced is None)))   # keep the reference's RNG draw order
+                          and all(u.last in (S.diff_id, S.start_id) for u in run))
+        # all active rows diffusing, in order: cond rows == [hidden[:nR]; hidden[nR:2nR]]
+        rng_state = self._sample(S, run, self._hidden, undoable=True) if speculated else None
+        logits = self._await_logits(S, order, hidden_of)
+        self._choose_tokens(S, order, logits, hidden_of)
+        self._retire(S, order)
+        # ---------------- next input embeddings (:569) ----------------
+        live = [u for u in order if not u.finished]
+        diff = [u for u in live if u.last == S.diff_id]
+        plain = [u for u in live if u.last != S.diff_id]
+        if plain:
+            self._embed_ids([u.last for u in plain], self._tmp_emb)
+            for i, u in enumerate(plain):
+                self._nxt_x[live.index(u)].copy_(self._tmp_emb[i])      # rows re-packed to the next step's active order
+        if speculated and diff != order:
+            speculated = False                                   # wrong guess: drop the latent, undo the draw
+            if rng_state is not None:
+                (S.cpu_gen.set_state if S.cpu_gen is not None else torch.set_rng_state)(rng_state)
+        if S.lockstep and len(order) > 1:
+            self._negative_bookkeeping(S, order, live, diff)
+        if not S.refresh_negative and not diff:
+            # the entry the negative pass appended at this step stays for a live row that does not diffuse, unless some row of the
+            # batch does: then the reference's correction of :590-624 shifts it back out (pinned by generate_norefresh_b2.npz)
+            for u in plain:
+                u.neg_len += 1
+        if diff and speculated:
+            for u in diff:
+                u.neg_len += 1
+        elif diff:
+            self._negative_conditions(S, order, diff, nR, hidden_of)
+            self._sample(S, diff, self._cond)
+        direct = False
+        if diff:
+            self._tokenizer_chain(S, diff)
+            direct = self._emit_frames(S, live, diff, self._hidden if speculated else self._cond)
+        if live:
+            self._next_inputs(S, live, direct)
+        for u in order:
+            u.step += 1
+        for u in live:
+            u.have_embeds = True
+        return live
+
+    def _lm_pass(self, S, run, fresh):
+        """The positive (+ speculative negative) LM pass over `run`, the valid-id logits of every row (`fresh` rows from their prompt's
+        last hidden state), their copy to the host with its event, and -- refresh_negative=False -- the step-0 negative rows."""
+        e, nv, nR = self.engine, S.nv, len(run)
         if run:
             rows = [(2 * u.slot, u.pos_len) for u in run] + [(2 * u.slot + 1, u.neg_len) for u in run]
             self._x_in[nR:2 * nR].copy_(self._x_in[:nR])
@@ -1322,98 +1432,96 @@ class VibeVoiceForConditionalGenerationInference:
                     e.lm_logits(1, self._hid_fresh[u.slot:u.slot + 1], self._logits[(nR + i) * nv:])
         self._logits_pin.copy_(self._logits, non_blocking=True)      # whole (contiguous) buffer: a true async D2H
         self._lg_event.record(e.stream)
-        refresh = S["refresh_negative"]
-        if not refresh:
+        if not S.refresh_negative:
             # refresh_negative=False (:503-516): the negative pass runs at EVERY step for every row on the input the positive pass
             # consumed -- the speculative rows above for `run`; at step 0 (inputs_embeds still None, :395) the lone <speech_start>
             # prompt token
             for i, u in enumerate(fresh):
                 e.lm_forward([(2 * u.slot + 1, u.neg_len)], self._start_emb, self._neg_hidden[i:i + 1])
 
-        def pos_hidden(i):                      # hidden state of order[i]'s positive row, [1, H]
-            return self._hidden[i:i + 1] if i < nR else self._hid_fresh[order[i].slot:order[i].slot + 1]
-        # ---- speculative sampling: a row that has just emitted <speech_diffusion>/<speech_start> almost always
-        # emits <speech_diffusion> next.  The sampler (stateless: cond + noise -> latent) is enqueued behind the LM
-        # pass BEFORE the host waits for the logits, so the token decision below overlaps GPU work instead of
-        # leaving the GPU idle; if the guess is wrong the latent is discarded and the RNG state restored.
-        spec_sample, rng_state = False, None
-        do_sample = S["do_sample"]
-        seeded = S["seeds"] is not None         # the counter path: a discarded guess spends nothing, there is no state to restore
-        if (run and not fresh and self.speculate_sampling
-                and (seeded or (not S["sde"]      # a discarded guess would spend device-RNG draws
-                                and not (do_sample and S["noise_fn"] is None and S["forced"] is None)))   # keep the reference's RNG draw order
-                and all(u.last in (diff_id, start_id) for u in run)):
-            nz = self._draw_noise(S, run)
-            if nz is None and seeded:
-                self._seeded_noise(run)
-            elif nz is None:
-                # the draw is undone if the guess is wrong: on the session's OWN generator when it has one (a lane of
-                # generate_interleaved) -- rewinding the process-global generator from one lane would hand another lane draws it has
-                # already consumed
-                cg = S.get("cpu_gen")
-                rng_state = cg.get_state() if cg is not None else torch.get_rng_state()
-                nz = torch.randn(2 * nR, e.cfg.latent_dim, generator=cg)
-            if nz is not None:
-                self._stage_noise(nz, nR)
-            # all active rows diffusing, in order: cond rows == [hidden[:nR]; hidden[nR:2nR]]
-            if S["sde"]:
-                e.diffusion_sample(nR, self._hidden, self._noise, self._cfg_arg(S, run), self._latent, step_noise=self._sde_draws(S, nR, run))
-            else:
-                e.diffusion_sample(nR, self._hidden, self._noise, self._cfg_arg(S, run), self._latent)
-            spec_sample = True
+    def _sample(self, S, utts, cond, *, undoable=False):
+        """Diffusion sampling (:697-710) of `utts` from the condition rows cond[:2n] into self._latent[:n]: the start noise (a hook's,
+        the counter path's, or torch.randn on the CPU generator, as the reference, :701), the guidance scales, the solver.
+        undoable: returns the state of the generator the draw came from, taken before the draw (None when nothing was drawn from one)
+        -- on the session's OWN generator when it has one (a lane of generate_interleaved): rewinding the process-global generator from
+        one lane would hand another lane draws it has already consumed."""
+        e, n = self.engine, len(utts)
+        nz = rng_state = None
+        if any(u.noise_fn is not None for u in utts):         # explicit noise (test / bench hooks), per utterance or per call
+            rows = [u.noise_fn(u.step, 2)[:1].to(torch.float32) for u in utts]
+            nz = torch.cat(rows + rows)
+        elif S.noise_fn is not None:
+            nz = S.noise_fn(S.step, 2 * n)
+        if nz is None and S.seeded:
+            self._seeded_noise(utts)
+        else:
+            if nz is None:
+                if undoable:
+                    rng_state = S.cpu_gen.get_state() if S.cpu_gen is not None else torch.get_rng_state()
+                nz = torch.randn(2 * n, e.cfg.latent_dim, generator=S.cpu_gen)
+            self._stage_noise(nz, n)
+        cfg_scale = self._cfg_arg(S, utts)
+        sde = {"step_noise": self._sde_draws(S, n, utts)} if S.sde else {}
+        e.diffusion_sample(n, cond, self._noise, cfg_scale, self._latent, **sde)
+        return rng_state
+
+    def _await_logits(self, S, order, hidden_of):
+        """wait for the step's logits on the host -> [rows, n_valid] (a copy); the trace's positive hidden states and scores"""
+        nA, nv = len(order), S.nv
         self._lg_event.synchronize()
         logits = self._logits_pin[:nA * nv].view(nA, nv).clone()
-        if trace is not None:
-            trace.pos_hidden.append(torch.cat([pos_hidden(i) for i in range(nA)]).cpu())
-            if hasattr(trace, "logits"):
-                trace.logits.append(logits.clone())               # [rows, n_valid]: the scores the token decision is taken from
-        # ---------------- token selection (:488-501) ----------------
-        if S["forced"] is not None or any(u.forced is not None for u in order):
+        if S.trace is not None:
+            S.trace.pos_hidden.append(torch.cat([hidden_of(i) for i in range(nA)]).cpu())
+            if hasattr(S.trace, "logits"):
+                S.trace.logits.append(logits.clone())             # [rows, n_valid]: the scores the token decision is taken from
+        return logits
+
+    def _valid_scores(self, S, order, hidden_of, plain):
+        """[n, n_valid] scores of the rows' valid ids the token is drawn from: `plain` (the LM's own, on the host or the device, as the
+        caller holds them) over the temperature, or -- full-vocabulary processors -- what survives of the valid ids after them and the
+        constraint (-inf where a filter removed one), from the kernel or from the torch ops.  A row that loses ALL its valid ids has
+        NaN probabilities in the reference too -- torch.multinomial raises there; here the one place that says why."""
+        if S.warp is None:
+            return plain / S.temperature
+        hidden = torch.cat([hidden_of(i) for i in range(len(order))])
+        if self.warp_on_device and hasattr(self.engine, "lm_warp_valid"):
+            lg = self._warp_valid_scores(hidden, order, S)
+            alive = int(self._warp_surv[:len(order)].min()) >= 1
+        else:
+            lg = self._full_vocab_scores(hidden, order, S)[:, S.valid_t.to(self.device)]
+            alive = bool(torch.isfinite(lg).any(dim=-1).all())
+        if not alive:
+            raise RuntimeError(_NO_VALID_TOKEN_LEFT)
+        return lg
+
+    def _choose_tokens(self, S, order, logits, hidden_of):
+        """token selection (:488-501): u.last and u.tokens of every row of `order`; logits: the host copy of their valid-id scores"""
+        e, valid_t = self.engine, S.valid_t
+        nA, nv = len(order), S.nv
+        if S.forced is not None or any(u.forced is not None for u in order):
             for u in order:
-                f = u.forced if u.forced is not None else S["forced"][u.idx]
-                u.last = int(f[u.step]) if u.step < len(f) else eos_id
-        elif seeded and do_sample:
+                f = u.forced if u.forced is not None else S.forced[u.idx]
+                u.last = int(f[u.step]) if u.step < len(f) else S.eos_id
+        elif S.seeded and S.do_sample:
             # the counter path: one uniform per (request, token index) and the inverse CDF of the float64 softmax over the row's
             # valid-id scores, per row on the host -- no [rows, lm_vocab] tensor, no generator; finished rows draw nothing
-            if S["warp"] is None:
-                lg = logits / S["temperature"]
-            elif self.warp_on_device and hasattr(e, "lm_warp_valid"):
-                lg = self._warp_valid_scores(torch.cat([pos_hidden(i) for i in range(nA)]), order, S).cpu()
-            else:
-                lg = self._full_vocab_scores(torch.cat([pos_hidden(i) for i in range(nA)]), order, S)[:, valid_t.to(self.device)].cpu()
-            if not bool(torch.isfinite(lg).any(dim=-1).all()):
-                raise RuntimeError("the full-vocabulary logits processors (top_k / top_p / min_p) removed every valid speech token "
-                                   "of a row: nothing is left to sample from (the reference fails in torch.multinomial here: "
-                                   "'probability tensor contains either `inf`, `nan` or element < 0')")
-            lg = lg.numpy()
+            lg = self._valid_scores(S, order, hidden_of, logits).cpu().numpy()
             for i, u in enumerate(order):
                 u.last = int(valid_t[_noise.choose(lg[i], _noise.uniform(u.seed, len(u.tokens)))])
-        elif do_sample or S["warp"] is not None:
+        elif S.do_sample or S.warp is not None:
             # the reference samples torch.multinomial(softmax(scores)) over the FULL vocabulary rows of the WHOLE batch (-inf
             # outside the valid ids, :490-496; finished rows included, their draw is overwritten by eos, :499) on the model's
             # device.  One-sample multinomial spends one exponential variate per (row, category), so the same call on the
             # same-shaped tensor keeps a seeded run on the reference's RNG stream (pinned on CPU by generate_sampled_b1.npz)
-            rows_of = S["sample_rows"](order)            # batch mode: every batch row; continuous mode: one row per utterance
+            rows_of = S.sample_rows(order)               # batch mode: every batch row; continuous mode: one row per utterance
             full = torch.full((len(rows_of), e.cfg.lm_vocab), float("-inf"), device=self.device, dtype=torch.float32)
             vt = valid_t.to(self.device)
             full[:, vt] = 0.0                              # finished rows: any proper distribution, the draw is discarded
-            if S["warp"] is None:
-                lg = self._logits[:nA * nv].view(nA, nv).float() / S["temperature"]
-            elif self.warp_on_device and hasattr(e, "lm_warp_valid"):
-                lg = self._warp_valid_scores(torch.cat([pos_hidden(i) for i in range(nA)]), order, S)
-            else:
-                # full-vocabulary processors, then the constraint: what survives of the valid ids (-inf where a filter removed one;
-                # a row that loses ALL its valid ids has NaN probabilities in the reference too -- torch.multinomial raises)
-                scores = self._full_vocab_scores(torch.cat([pos_hidden(i) for i in range(nA)]), order, S)
-                lg = scores[:, vt]
-                if not bool(torch.isfinite(lg).any(dim=-1).all()):
-                    raise RuntimeError("the full-vocabulary logits processors (top_k / top_p / min_p) removed every valid speech token "
-                                       "of a row: nothing is left to sample from (the reference fails in torch.multinomial here: "
-                                       "'probability tensor contains either `inf`, `nan` or element < 0')")
+            lg = self._valid_scores(S, order, hidden_of, self._logits[:nA * nv].view(nA, nv).float())
             for i, u in enumerate(order):
                 full[rows_of.index(u.idx), vt] = lg[i]
-            if do_sample:
-                pick_ids = torch.multinomial(torch.softmax(full, dim=-1), num_samples=1, generator=S.get("dev_gen")).squeeze(1).cpu()
+            if S.do_sample:
+                pick_ids = torch.multinomial(torch.softmax(full, dim=-1), num_samples=1, generator=S.dev_gen).squeeze(1).cpu()
             else:
                 pick_ids = torch.argmax(full, dim=-1).cpu()
             for u in order:
@@ -1424,182 +1532,138 @@ class VibeVoiceForConditionalGenerationInference:
                 u.last = int(valid_t[pick[i]])
         for u in order:
             u.tokens.append(u.last)
-        if trace is not None:
-            nxt = torch.full((S["n_rows"],), eos_id, dtype=torch.long)
+        if S.trace is not None:
+            nxt = torch.full((S.n_rows,), S.eos_id, dtype=torch.long)
             for u in order:
                 nxt[u.idx] = u.last
-            trace.tokens.append(nxt)
-        # ---------------- bookkeeping (:518-539) ----------------
-        new_eos = [u for u in order if u.last == eos_id]
-        if new_eos:
-            for u in new_eos:
-                u.finished = True
-            if verbose:
-                print(f"Samples {sorted(u.idx for u in new_eos)} reached EOS token at step {new_eos[0].step + 1}.", flush=True)
-            if audio_streamer is not None:
-                audio_streamer.end(torch.tensor(sorted(u.idx for u in new_eos)))
-        hit = [u for u in order if not u.finished and u.step >= u.max_step_sample]
-        if hit:
-            for u in hit:
-                u.finished = u.reach_max = True
-            if verbose:
-                print(f"Samples {sorted(u.idx for u in hit)} reached max generation length at step {hit[0].step + 1}.", flush=True)
-            if audio_streamer is not None:
-                audio_streamer.end(torch.tensor(sorted(u.idx for u in hit)))
-        if S.get("_seen"):
-            for u in order:
-                if u.finished:
-                    S["_seen"].pop(u.idx, None)       # the repetition-penalty mask of a finished utterance ([V] bools on the device)
-        if S.get("_seen_dev"):
-            for u in order:
-                if u.finished:
-                    S["_seen_dev"].pop(u.idx, None)
+            S.trace.tokens.append(nxt)
+
+    def _retire(self, S, order):
+        """bookkeeping (:518-539): rows ended by <eos> or by their cap, and what a control token does to a row's engine state"""
+        e, audio_streamer = self.engine, S.audio_streamer
+        def end(rows, what, reach_max):
+            for u in rows:
+                u.finished, u.reach_max = True, reach_max
+            if rows and S.verbose:
+                print(f"Samples {sorted(u.idx for u in rows)} reached {what} at step {rows[0].step + 1}.", flush=True)
+            if rows and audio_streamer is not None:
+                audio_streamer.end(torch.tensor(sorted(u.idx for u in rows)))
+        end([u for u in order if u.last == S.eos_id], "EOS token", False)
+        end([u for u in order if not u.finished and u.step >= u.max_step_sample], "max generation length", True)
         for u in order:
-            if u.last == end_id:
+            if u.finished:                            # the repetition-penalty mask of a finished utterance ([V] bools on the device)
+                S._seen.pop(u.idx, None)
+                S._seen_dev.pop(u.idx, None)
+        for u in order:
+            if u.last == S.end_id:
                 e.codec_reset(u.slot)
-            if refresh and not u.finished and u.last == start_id:
+            if S.refresh_negative and not u.finished and u.last == S.start_id:
                 # :549-565 -- the reference masks the whole negative cache and un-masks only the slot of the NEXT token, so the
                 # negative context restarts empty and the next negative pass re-feeds <speech_start> at position 0
                 # (pinned against the reference's generate(): tests/golden/generate_forced_*.npz)
                 u.neg_len = 0
-        # ---------------- next input embeddings (:569) ----------------
-        live = [u for u in order if not u.finished]
-        diff = [u for u in live if u.last == diff_id]
-        nxt_x = self._nxt_x                     # rows re-packed to the next step's active order
-        plain = [u for u in live if u.last != diff_id]
-        if plain:
-            self._embed_ids([u.last for u in plain], self._tmp_emb)
-            for i, u in enumerate(plain):
-                nxt_x[live.index(u)].copy_(self._tmp_emb[i])
-        if spec_sample and diff != order:
-            spec_sample = False                                  # wrong guess: drop the latent, undo the draw
-            if rng_state is not None:
-                if S.get("cpu_gen") is not None:
-                    S["cpu_gen"].set_state(rng_state)
-                else:
-                    torch.set_rng_state(rng_state)
-        cond_used = self._hidden if spec_sample else self._cond
-        n = len(diff)
-        if S.get("lockstep", True) and len(order) > 1:
-            self._negative_bookkeeping(S, order, live, diff, refresh, start_id)
-        if not refresh:
-            # the entry the negative pass appended at this step stays for a live row that does not diffuse, unless some row of the
-            # batch does: then the reference's correction of :590-624 shifts it back out (pinned by generate_norefresh_b2.npz)
-            for u in plain:
-                if not diff:
-                    u.neg_len += 1
-        if diff and spec_sample:
-            for u in diff:
-                u.neg_len += 1
-        elif diff:
-            # ---- negative condition ----
-            for j, u in enumerate(diff):
-                oi = order.index(u)
-                self._cond[j].copy_(pos_hidden(oi)[0])
-                if u.have_embeds:
-                    self._cond[n + j].copy_(self._hidden[nR + oi])
-                elif not refresh:
-                    self._cond[n + j].copy_(self._neg_hidden[oi - nR])
-                else:
-                    # first negative step of a fresh utterance: the lone <speech_start> prompt token (:379-386)
-                    e.lm_forward([(2 * u.slot + 1, u.neg_len)], self._start_emb, self._neg_hidden[j:j + 1])
-                    self._cond[n + j].copy_(self._neg_hidden[j])
-                u.neg_len += 1
-            # ---- diffusion sampling (:697-710) ----
-            nz = self._draw_noise(S, diff)
-            if nz is None and seeded:
-                self._seeded_noise(diff)
+
+    def _negative_conditions(self, S, order, diff, nR, hidden_of):
+        """condition rows of the sampler call over `diff` -> self._cond: [positive hidden states; negative hidden states]"""
+        e, n = self.engine, len(diff)
+        for j, u in enumerate(diff):
+            oi = order.index(u)
+            self._cond[j].copy_(hidden_of(oi)[0])
+            if u.have_embeds:
+                self._cond[n + j].copy_(self._hidden[nR + oi])
+            elif not S.refresh_negative:
+                self._cond[n + j].copy_(self._neg_hidden[oi - nR])
             else:
-                if nz is None:
-                    nz = torch.randn(2 * n, e.cfg.latent_dim, generator=S.get("cpu_gen"))      # CPU global RNG, as the reference (:701), unless the session has its own
-                self._stage_noise(nz, n)
-            cfg_scale = self._cfg_arg(S, diff)
-            if S["sde"]:
-                e.diffusion_sample(n, self._cond, self._noise, cfg_scale, self._latent, step_noise=self._sde_draws(S, n, diff))
-            else:
-                e.diffusion_sample(n, self._cond, self._noise, cfg_scale, self._latent)
-        if diff and S.get("lockstep", True):
+                # first negative step of a fresh utterance: the lone <speech_start> prompt token (:379-386)
+                e.lm_forward([(2 * u.slot + 1, u.neg_len)], self._start_emb, self._neg_hidden[j:j + 1])
+                self._cond[n + j].copy_(self._neg_hidden[j])
+            u.neg_len += 1
+
+    def _tokenizer_chain(self, S, diff):
+        """codec decode and semantic re-encode (:636-672) of self._latent[:n] -> self._audio[:n], self._sem[:n]"""
+        e, n = self.engine, len(diff)
+        started = [u for u in diff if u.chunks]
+        if S.lockstep and started and len(started) < n:
             # The reference's VibeVoiceTokenizerStreamingCache.get (modular_vibevoice_tokenizer.py:198-207) answers "no history" for
             # EVERY row of a decode / encode call as soon as ONE of its rows has no entry yet: in a lock-step batch, a row that
             # diffuses for the first time costs the rows decoded with it their conv history for that frame (both tokenizers).  It
             # cannot fire on processor-built prompts (every row takes its first frame at step 0); pinned by
             # tests/golden/generate_late_start_b2*.npz.  A queue of independent requests (generate_continuous) keeps every row's own
             # history instead -- each request ends as generate() on it alone would.
-            started = [u for u in diff if u.chunks]
-            if started and len(started) < len(diff):
-                for u in started:
-                    e.codec_reset(u.slot)
-        if diff:
-            # ---- codec decode, semantic encode, connectors (:636-672) ----
-            if self.batched_codecs:
-                # the reference decodes / re-encodes the step's diffusion rows as one batch (:636-672): one engine call, the
-                # weight-heavy tokenizer stages read their weights once for all rows; one utterance's chain too (one captured
-                # sequence instead of two: a graph-to-graph transition costs ~7 us against ~1.5 us between two kernels of one graph)
-                e.codec_chain_batch([u.slot for u in diff], self._latent[:n], self._audio[:n],
-                                    self._sem[:n] if e.cfg.sem_dim > 0 else None)
-            elif len(diff) > 1 and self.concurrent_codecs and self._side_streams:
-                # each utterance's tokenizer chain (decode -> semantic re-encode) is an independent, launch-latency
-                # bound graph: fork them onto side streams so they overlap, join before the connectors
-                self._fork_ev.record(e.stream)
-                for j, u in enumerate(diff):
-                    ss = self._side_streams[j % len(self._side_streams)]
-                    ss.wait_event(self._fork_ev)
-                    e.codec_decode(u.slot, self._latent[j:j + 1], self._audio[j], stream=ss)
-                    if e.cfg.sem_dim > 0:
-                        e.semantic_encode(u.slot, self._audio[j], self._sem[j], stream=ss)
-                for ss in self._side_streams[:min(len(diff), len(self._side_streams))]:
-                    self._join_ev.record(ss)
-                    e.stream.wait_event(self._join_ev)
-            else:
-                for j, u in enumerate(diff):
-                    e.codec_decode(u.slot, self._latent[j:j + 1], self._audio[j])
-                    if e.cfg.sem_dim > 0:
-                        e.semantic_encode(u.slot, self._audio[j], self._sem[j])
-            # every live row diffuses, in order (the steady state of a speech segment): the connectors write the next step's LM input
-            # rows in place -- no staging through _emb_out / nxt_x, two device copies fewer on the step's dependency line
-            direct = diff == live and S["teacher"] is None
-            e.connect(n, self._latent, self._sem if e.cfg.sem_dim > 0 else None, self._x_in if direct else self._emb_out)
-            chunk = self._block_rows(S["frame_rows"])
-            S["frame_rows"] += 1
-            chunk[:n].copy_(self._audio[:n])
-            fr = getattr(self, "_first_row", None)
+            for u in started:
+                e.codec_reset(u.slot)
+        if self.batched_codecs:
+            # the reference decodes / re-encodes the step's diffusion rows as one batch (:636-672): one engine call, the
+            # weight-heavy tokenizer stages read their weights once for all rows; one utterance's chain too (one captured
+            # sequence instead of two: a graph-to-graph transition costs ~7 us against ~1.5 us between two kernels of one graph)
+            e.codec_chain_batch([u.slot for u in diff], self._latent[:n], self._audio[:n],
+                                self._sem[:n] if e.cfg.sem_dim > 0 else None)
+        elif len(diff) > 1 and self.concurrent_codecs and self._side_streams:
+            # each utterance's tokenizer chain (decode -> semantic re-encode) is an independent, launch-latency
+            # bound graph: fork them onto side streams so they overlap, join before the connectors
+            self._fork_ev.record(e.stream)
             for j, u in enumerate(diff):
-                if fr is not None and not u.chunks:
-                    fr[id(u)] = S["frame_rows"] - 1
-                u.chunks.append(chunk[j])
-                if not direct:
-                    nxt_x[live.index(u)].copy_(self._emb_out[j])
-            if audio_streamer is not None:
-                audio_streamer.put(chunk[:n, None, :].to(self.dtype), torch.tensor([u.idx for u in diff]))
-            S["n_frames"] += n
-            if trace is not None and hasattr(trace, "noise"):
-                nz_host = self._noise[:n].cpu()                   # (request, t, start noise) of every ACCEPTED latent
-                for j, u in enumerate(diff):
-                    trace.noise.append((u.idx, u.n_lat, nz_host[j].clone()))
-            for u in diff:
-                u.n_lat += 1
-            if trace is not None:
-                trace.neg_hidden.append(cond_used[n:2 * n].cpu())
-                trace.latents.append(self._latent[:n].cpu())
-                trace.semantic.append(self._sem[:n].cpu())
-        if live:
-            if S["teacher"] is not None:
-                # test hook (SURVEY 8d "teacher-forced per step"): the next step consumes the embeddings the oracle fed its LM at
-                # this step, so a bf16-mode run is compared step by step without the autoregressive feedback compounding
-                te = S["teacher"](S["step"], [u.idx for u in live])
-                if te is not None:
-                    nxt_x[:len(live)].copy_(te.to(self.device, torch.float32))
-            if not (diff and direct):
-                self._x_in[:len(live)].copy_(nxt_x[:len(live)])
-            if trace is not None:
-                trace.next_embeds.append(self._x_in[:len(live)].cpu())
-        for u in order:
-            u.step += 1
-        for u in live:
-            u.have_embeds = True
-        return live
+                ss = self._side_streams[j % len(self._side_streams)]
+                ss.wait_event(self._fork_ev)
+                e.codec_decode(u.slot, self._latent[j:j + 1], self._audio[j], stream=ss)
+                if e.cfg.sem_dim > 0:
+                    e.semantic_encode(u.slot, self._audio[j], self._sem[j], stream=ss)
+            for ss in self._side_streams[:min(len(diff), len(self._side_streams))]:
+                self._join_ev.record(ss)
+                e.stream.wait_event(self._join_ev)
+        else:
+            for j, u in enumerate(diff):
+                e.codec_decode(u.slot, self._latent[j:j + 1], self._audio[j])
+                if e.cfg.sem_dim > 0:
+                    e.semantic_encode(u.slot, self._audio[j], self._sem[j])
 
-    def _negative_bookkeeping(self, S, order, live, diff, refresh, start_id):
+    def _emit_frames(self, S, live, diff, cond_used):
+        """connectors (:636-672), the frame store, the streamer and the trace for the step's frames; -> True when the connectors wrote
+        the next step's LM input rows in place"""
+        e, n = self.engine, len(diff)
+        # every live row diffuses, in order (the steady state of a speech segment): the connectors write the next step's LM input
+        # rows in place -- no staging through _emb_out / _nxt_x, two device copies fewer on the step's dependency line
+        direct = diff == live and S.teacher is None
+        e.connect(n, self._latent, self._sem if e.cfg.sem_dim > 0 else None, self._x_in if direct else self._emb_out)
+        chunk = self._block_rows(S.frame_rows)
+        S.frame_rows += 1
+        chunk[:n].copy_(self._audio[:n])
+        for j, u in enumerate(diff):
+            if self._first_row is not None and not u.chunks:
+                self._first_row[id(u)] = S.frame_rows - 1
+            u.chunks.append(chunk[j])
+            if not direct:
+                self._nxt_x[live.index(u)].copy_(self._emb_out[j])
+        if S.audio_streamer is not None:
+            S.audio_streamer.put(chunk[:n, None, :].to(self.dtype), torch.tensor([u.idx for u in diff]))
+        S.n_frames += n
+        trace = S.trace
+        if trace is not None and hasattr(trace, "noise"):
+            nz_host = self._noise[:n].cpu()                   # (request, t, start noise) of every ACCEPTED latent
+            for j, u in enumerate(diff):
+                trace.noise.append((u.idx, u.n_lat, nz_host[j].clone()))
+        for u in diff:
+            u.n_lat += 1
+        if trace is not None:
+            trace.neg_hidden.append(cond_used[n:2 * n].cpu())
+            trace.latents.append(self._latent[:n].cpu())
+            trace.semantic.append(self._sem[:n].cpu())
+        return direct
+
+    def _next_inputs(self, S, live, direct):
+        """self._x_in[:len(live)] = the next step's LM input rows (already there when the connectors wrote them in place)"""
+        if S.teacher is not None:
+            # test hook (SURVEY 8d "teacher-forced per step"): the next step consumes the embeddings the oracle fed its LM at
+            # this step, so a bf16-mode run is compared step by step without the autoregressive feedback compounding
+            te = S.teacher(S.step, [u.idx for u in live])
+            if te is not None:
+                self._nxt_x[:len(live)].copy_(te.to(self.device, torch.float32))
+        if not direct:
+            self._x_in[:len(live)].copy_(self._nxt_x[:len(live)])
+        if S.trace is not None:
+            S.trace.next_embeds.append(self._x_in[:len(live)].cpu())
+
+    def _negative_bookkeeping(self, S, order, live, diff):
         """The reference's array bookkeeping of the negative branch (oracle.generate.NegativeRow restates it with the tensors), masks
         and counters only.  Its correction of a non-diffusing row (:594-624) guards the mask shift and the K/V shift differently
         (:603 vs :613): for a row holding exactly one valid entry the mask moves and the K/V does not, so the reference KEEPS the entry
@@ -1611,11 +1675,12 @@ class VibeVoiceForConditionalGenerationInference:
                 b = u.neg_book
                 b[1] += 1
                 b[0].append(1)
+        refresh = S.refresh_negative
         if not refresh:
             fwd()
         else:
             for u in live:
-                if u.last == start_id:
+                if u.last == S.start_id:
                     u.neg_book[0] = [0] * (len(u.neg_book[0]) - 1) + [1]
         if not diff:
             return
@@ -1656,10 +1721,10 @@ class VibeVoiceForConditionalGenerationInference:
         if self._sde_flat is None:
             self._sde_flat = e.new(64 * MAX_BATCH * L)
         buf = self._sde_flat[:N * n * L].view(N, n, L)
-        if S["sde_noise_fn"] is not None:                     # test hook: the recorded draws, [N, 2n, latent]
-            buf.copy_(S["sde_noise_fn"](S["step"], N, 2 * n)[:, :n].to(buf.device, torch.float32))
+        if S.sde_noise_fn is not None:                        # test hook: the recorded draws, [N, 2n, latent]
+            buf.copy_(S.sde_noise_fn(S.step, N, 2 * n)[:, :n].to(buf.device, torch.float32))
             return buf
-        if S["seeds"] is not None:                            # the counter path: streams 1 .. N of every row's seed, at its own t
+        if S.seeded:                                          # the counter path: streams 1 .. N of every row's seed, at its own t
             if hasattr(e, "noise_rows") and L % 4 == 0:
                 e.noise_rows([(u.seed, u.n_lat, 0) for u in utts], _noise.STREAM_START + 1, N, 1, L, buf)
             else:
@@ -1667,21 +1732,12 @@ class VibeVoiceForConditionalGenerationInference:
                     buf[:, j].copy_(_noise.normals(u.seed, u.n_lat, 1, _noise.STREAM_START + 1, N, 0, L)[:, 0])
             return buf
         for i in range(N):
-            buf[i].copy_(torch.randn(2 * n, L, device=self.device, dtype=torch.float32, generator=S.get("dev_gen"))[:n])
+            buf[i].copy_(torch.randn(2 * n, L, device=self.device, dtype=torch.float32, generator=S.dev_gen)[:n])
         return buf
 
-    @staticmethod
-    def _draw_noise(S, utts):
-        """explicit noise for `utts` (test / bench hooks), or None: draw torch.randn as the reference does"""
-        if any(u.noise_fn is not None for u in utts):
-            rows = [u.noise_fn(u.step, 2)[:1].to(torch.float32) for u in utts]
-            return torch.cat(rows + rows)
-        if S["noise_fn"] is not None:
-            return S["noise_fn"](S["step"], 2 * len(utts))
-        return None
-
-    def _session(self, tokenizer, generation_config, cfg_scales, kwargs, audio_streamer, n_rows):
-        """cfg_scales: the validated guidance scale of every utterance of the call (_cfg_scale_values)"""
+    def _session(self, tokenizer, generation_config, cfg_scales, kwargs, audio_streamer, n_rows, *, seeds, sample_rows, lockstep=True):
+        """cfg_scales: the validated guidance scale of every utterance of the call (_cfg_scale_values); seeds: the requests' seeds as
+        given (ints or None, _resolve_seeds settles them on the session's CPU generator)"""
         e = self.engine
         if tokenizer is None:
             raise ValueError("generate() needs tokenizer= (speech_start_id / speech_end_id / speech_diffusion_id / eos_token_id)")
@@ -1696,17 +1752,15 @@ class VibeVoiceForConditionalGenerationInference:
         algo = self._sched_cfg["algorithm_type"]
         e.set_num_steps(self.ddpm_inference_steps, t_cast_bf16=(self.dtype == torch.bfloat16 and kwargs.get("_t_cast", True)),
                         **({} if algo == "dpmsolver++" else {"algorithm_type": algo}))
-        return dict(sde=(algo == "sde-dpmsolver++"), sde_noise_fn=kwargs.pop("_sde_noise_fn", None), nv=len(valid), valid_t=torch.tensor(valid, dtype=torch.long), start_id=start_id, end_id=end_id, diff_id=diff_id,
-                    eos_id=eos_id, cfg_scale=cfg_scales[0] if cfg_scales else 1.0, cfg_rows=len(set(cfg_scales)) > 1, do_sample=do_sample, temperature=temperature, warp=warp,
-                    pad_id=getattr(tokenizer, "pad_token_id", None),
-                    trace=kwargs.pop("_trace", None), audio_streamer=audio_streamer, verbose=kwargs.get("verbose", False),
-                    forced=kwargs.pop("_forced_tokens", None), noise_fn=kwargs.pop("_noise_fn", None), n_rows=n_rows,
-                    teacher=kwargs.pop("_teacher_embeds", None), refresh_negative=bool(kwargs.get("refresh_negative", True)),
-                    frame_rows=0, n_frames=0, step=0, sample_rows=None,
-                    seeds=None,               # one seed per request when the call runs the counter path (noise.py), set by the caller
-                    # a session's own generators (generate_interleaved gives every lane a pair): None = the process-global CPU / device
-                    # generators, i.e. the reference's RNG streams
-                    cpu_gen=(kwargs.get("_generators") or (None, None))[0], dev_gen=(kwargs.pop("_generators", None) or (None, None))[1])
+        cpu_gen, dev_gen = kwargs.pop("_generators", None) or (None, None)
+        return _Session(sde=(algo == "sde-dpmsolver++"), sde_noise_fn=kwargs.pop("_sde_noise_fn", None), nv=len(valid),
+                        valid_t=torch.tensor(valid, dtype=torch.long), start_id=start_id, end_id=end_id, diff_id=diff_id, eos_id=eos_id,
+                        pad_id=getattr(tokenizer, "pad_token_id", None), cfg_scale=cfg_scales[0] if cfg_scales else 1.0,
+                        cfg_rows=len(set(cfg_scales)) > 1, do_sample=do_sample, temperature=temperature, warp=warp,
+                        trace=kwargs.pop("_trace", None), audio_streamer=audio_streamer, verbose=kwargs.get("verbose", False),
+                        forced=kwargs.pop("_forced_tokens", None), noise_fn=kwargs.pop("_noise_fn", None),
+                        teacher=kwargs.pop("_teacher_embeds", None), n_rows=n_rows, refresh_negative=bool(kwargs.get("refresh_negative", True)),
+                        lockstep=lockstep, sample_rows=sample_rows, seeds=_resolve_seeds(seeds, cpu_gen), cpu_gen=cpu_gen, dev_gen=dev_gen)
 
     # ------------------------------------------------------------------ generate
     @torch.no_grad()
@@ -1748,24 +1802,19 @@ class VibeVoiceForConditionalGenerationInference:
                                          max_length_times, prefill_noise, step_cb, kwargs, prompt_prefix=prompt_prefix, seeds=seeds_in)
         prefixes = self._prefix_list(prompt_prefix, B)
         pf_stats = {"prefix_rows_reused": 0, "prompt_rows_computed": 0}
-        S = self._session(tokenizer, generation_config, cfg_scales, kwargs, audio_streamer, B)
-        S["sample_rows"] = lambda order: list(range(B))
-        S["seeds"] = _resolve_seeds(seeds_in, S.get("cpu_gen"))
+        S = self._session(tokenizer, generation_config, cfg_scales, kwargs, audio_streamer, B, seeds=seeds_in,
+                          sample_rows=lambda order: list(range(B)))
         self._frame_w = B                                 # frame-store rows are as wide as this call's batch
-        if kwargs.get("max_new_tokens", None) is None:
-            max_new_tokens = self.max_position_embeddings - L0
-        else:
-            max_new_tokens = kwargs["max_new_tokens"]
+        max_new_tokens = kwargs["max_new_tokens"] if kwargs.get("max_new_tokens") is not None else self.max_position_embeddings - L0
         max_length = min(L0 + max_new_tokens, e.max_ctx)
         utts = []
         for b in range(B):
             m = attention_mask[b].bool()
-            utts.append(_Utt(b, b, input_ids[b][m].tolist(), L0, max_length, max_length_times, S["start_id"]))
+            utts.append(_Utt(b, b, input_ids[b][m].tolist(), L0, max_length, max_length_times, S.start_id))
             utts[-1].cfg_scale = cfg_scales[b]
-            if S["seeds"] is not None:
-                utts[-1].seed = S["seeds"][b]
+            if S.seeded:
+                utts[-1].seed = S.seeds[b]
         max_steps = min(max_length - L0, int(max_length_times * L0))
-        time_prefill = os.environ.get("VVHIP_TIME_PREFILL") is not None     # debug: sync + time the two prefill phases
         if tqdm_class is not None and kwargs.get("show_progress_bar", True):
             progress = tqdm_class(range(max_steps), desc="Generating", leave=False)
         else:
@@ -1774,10 +1823,10 @@ class VibeVoiceForConditionalGenerationInference:
         with torch.cuda.stream(e.stream), _end_streamer_on_error(audio_streamer):
             for b in range(B):
                 e.codec_reset(b)
-            e.embed([S["start_id"]], self._start_emb)
+            e.embed([S.start_id], self._start_emb)
             active = list(utts)
             for step in progress:
-                S["step"] = step
+                S.step = step
                 if step_cb is not None:
                     step_cb(step)
                 if stop_check_fn is not None and stop_check_fn():
@@ -1793,98 +1842,108 @@ class VibeVoiceForConditionalGenerationInference:
                         u.reach_max = True
                     break
                 if step == 0:
-                    # ---------------- prompt prefill (:467-474, _process_speech_inputs) ----------------
-                    sp_embeds = None
-                    t_pf = [time.perf_counter()] if time_prefill else None
-                    self._t_kv_fill = 0.0
-                    self._t_lm_pass = 0.0
-                    with_voice = is_prefill and speech_tensors is not None and speech_masks is not None
-                    # masks are host data (the processor's output): positions and counts on the host (a device-side .sum() costs a
-                    # lazy kernel-module load (~20 ms) on its first use and a sync on every use), uploaded while the stream is
-                    # still idle -- behind the encoder a pageable copy would hold the host until the encoder has finished
-                    sp_pos = {}
-                    sp_host = {}
-                    if speech_input_mask is not None and (with_voice or any(p is not None for p in prefixes)):
-                        for u in utts:
-                            sm_cpu = speech_input_mask[u.idx].cpu()[attention_mask[u.idx].bool().cpu()]
-                            idx = sm_cpu.to(torch.bool).nonzero().squeeze(1)
-                            sp_host[u.idx] = idx.tolist()
-                            if with_voice and idx.numel():
-                                sp_pos[u.idx] = (int(idx.numel()), idx.to(self.device))
-                    # rows that start with a prompt prefix: r leading positions come from its snapshot (0: today's full prefill)
-                    reuse = {u.idx: self._prefix_plan(prefixes[u.idx], u.ids, sp_host.get(u.idx)) for u in utts}
-                    spk_seeds = None
-                    if with_voice and S["seeds"] is not None and prefill_noise is None:
-                        # every voice sample draws from the seed of the row it belongs to, under its index within that row
-                        need = [sp_pos[u.idx][0] if u.idx in sp_pos else 0 for u in utts]
-                        spk = _speakers_of_rows(need, [int(speech_masks[i].sum()) for i in range(speech_masks.shape[0])])
-                        if spk is None:
-                            raise ValueError("generate(seed=...): a voice sample spans two batch rows; with seeds the rows' speech "
-                                             "positions must consume whole voice samples")
-                        spk_seeds = [None] * speech_masks.shape[0]
-                        for u in utts:
-                            for k, i in enumerate(spk[u.idx]):
-                                spk_seeds[i] = (u.seed, k)
-                        for i in range(len(spk_seeds)):          # samples no row consumes: their latents are never read
-                            if spk_seeds[i] is None:
-                                spk_seeds[i] = (utts[-1].seed, i)
-                    if with_voice and any(reuse.values()):
-                        # the voice samples of a prefixed row are in the prefix: only the other rows' samples are encoded (none: no
-                        # encoder call at all).  A sample that spans two rows cannot be told apart: then every sample is encoded.
-                        need = [sp_pos[u.idx][0] if u.idx in sp_pos else 0 for u in utts]
-                        spk = _speakers_of_rows(need, [int(speech_masks[i].sum()) for i in range(speech_masks.shape[0])])
-                        if spk is not None:
-                            keep_spk = [i for u in utts if not reuse[u.idx] for i in spk[u.idx]]
-                            for u in utts:
-                                if reuse[u.idx]:
-                                    sp_pos.pop(u.idx, None)
-                            if keep_spk:
-                                sel = torch.tensor(keep_spk, dtype=torch.long)
-                                speech_tensors, speech_masks = speech_tensors.cpu()[sel], speech_masks.cpu()[sel]
-                                if prefill_noise is not None:
-                                    prefill_noise = tuple(t.cpu()[sel] for t in prefill_noise)
-                                if spk_seeds is not None:
-                                    spk_seeds = [spk_seeds[i] for i in keep_spk]
-                            else:
-                                with_voice = False
-                    if with_voice:
-                        _, sp_embeds = self._process_speech_inputs(speech_tensors, speech_masks, prefill_noise, seeds=spk_seeds)
-                    if time_prefill:
-                        e.sync(); torch.cuda.current_stream(self.device).synchronize(); t_pf.append(time.perf_counter())
-                    sp_off = 0
-                    jobs = []
-                    for u in utts:
-                        rows = pos = None
-                        if sp_embeds is not None and u.idx in sp_pos:
-                            cnt, pos = sp_pos[u.idx]
-                            rows = sp_embeds[sp_off:sp_off + cnt]
-                            sp_off += cnt
-                        if reuse[u.idx]:
-                            jobs.append((u, u.ids, None, None, kv_start, kv_fill_fn, prefixes[u.idx], reuse[u.idx]))
-                        else:
-                            jobs.append((u, u.ids, rows, pos, kv_start, kv_fill_fn))
-                        pf_stats["prefix_rows_reused"] += reuse[u.idx]
-                        pf_stats["prompt_rows_computed"] += len(u.ids) - reuse[u.idx]
-                    self._prefill_checked(jobs)
-                    if time_prefill:
-                        e.sync(); t_pf.append(time.perf_counter())
-                        self.last_prefill = {"voice_encode_s": round(t_pf[1] - t_pf[0], 5),
-                                             "lm_prefill_s": round(t_pf[2] - t_pf[1] - self._t_kv_fill, 5),
-                                             "lm_passes_s": round(self._t_lm_pass, 5),      # the LM launches alone (the rest of
-                                             "bench_kv_fill_s": round(self._t_kv_fill, 5)}  # lm_prefill_s: embedding + row scatter)
+                    pf_stats = self._prefill_batch(S, utts, prefixes, attention_mask, speech_input_mask,
+                                                   (speech_tensors, speech_masks) if is_prefill else (None, None), prefill_noise,
+                                                   kv_start, kv_fill_fn)
                 active = self._iterate(S, active)
                 n_steps += 1
             if audio_streamer is not None:
                 audio_streamer.end()
-            outs = [torch.cat(u.chunks, dim=-1)[None].to(self.dtype) if u.chunks else None for u in utts]
-            seq = torch.full((B, L0 + n_steps), S["eos_id"], dtype=torch.long)
-            seq[:, :L0] = input_ids
-            for u in utts:
-                if u.tokens:
-                    seq[u.idx, L0:L0 + len(u.tokens)] = torch.tensor(u.tokens, dtype=torch.long)
+            out = self._output(utts, input_ids, n_steps, S.eos_id, return_speech)
         e.sync()
         self._release_frames()
-        self.last_stats = {"frames": S["n_frames"], "steps": n_steps, **pf_stats}
+        self.last_stats = {"frames": S.n_frames, "steps": n_steps, **pf_stats}
+        return out
+
+    def _prefill_batch(self, S, utts, prefixes, attention_mask, speech_input_mask, voice, prefill_noise, kv_start, kv_fill_fn):
+        """prompt prefill (:467-474, _process_speech_inputs) of a generate() batch: the voice samples `voice` = (speech_tensors,
+        speech_masks) encoded and scattered into the rows' speech positions, the rows that start with a prompt prefix restored from it;
+        -> the call's prefix_rows_reused / prompt_rows_computed"""
+        e = self.engine
+        speech_tensors, speech_masks = voice
+        time_prefill = os.environ.get("VVHIP_TIME_PREFILL") is not None     # debug: sync + time the two prefill phases
+        sp_embeds = None
+        t_pf = [time.perf_counter()] if time_prefill else None
+        self._t_kv_fill = self._t_lm_pass = 0.0
+        with_voice = speech_tensors is not None and speech_masks is not None
+        # masks are host data (the processor's output): positions and counts on the host (a device-side .sum() costs a
+        # lazy kernel-module load (~20 ms) on its first use and a sync on every use), uploaded while the stream is
+        # still idle -- behind the encoder a pageable copy would hold the host until the encoder has finished
+        sp_pos, sp_host = {}, {}
+        if speech_input_mask is not None and (with_voice or any(p is not None for p in prefixes)):
+            for u in utts:
+                idx = _speech_positions(speech_input_mask[u.idx], attention_mask[u.idx])
+                sp_host[u.idx] = idx.tolist()
+                if with_voice and idx.numel():
+                    sp_pos[u.idx] = (int(idx.numel()), idx.to(self.device))
+        # rows that start with a prompt prefix: r leading positions come from its snapshot (0: today's full prefill)
+        reuse = {u.idx: self._prefix_plan(prefixes[u.idx], u.ids, sp_host.get(u.idx)) for u in utts}
+        seeded_voice = with_voice and S.seeded and prefill_noise is None
+        spk = spk_seeds = None
+        if seeded_voice or (with_voice and any(reuse.values())):
+            # the voice samples every row consumes (None: a sample spans two rows)
+            spk = _speakers_of_rows([sp_pos[u.idx][0] if u.idx in sp_pos else 0 for u in utts],
+                                    [int(speech_masks[i].sum()) for i in range(speech_masks.shape[0])])
+        if seeded_voice:
+            # every voice sample draws from the seed of the row it belongs to, under its index within that row
+            if spk is None:
+                raise ValueError("generate(seed=...): a voice sample spans two batch rows; with seeds the rows' speech "
+                                 "positions must consume whole voice samples")
+            spk_seeds = [None] * speech_masks.shape[0]
+            for u in utts:
+                for k, i in enumerate(spk[u.idx]):
+                    spk_seeds[i] = (u.seed, k)
+            for i in range(len(spk_seeds)):          # samples no row consumes: their latents are never read
+                if spk_seeds[i] is None:
+                    spk_seeds[i] = (utts[-1].seed, i)
+        if with_voice and any(reuse.values()) and spk is not None:
+            # the voice samples of a prefixed row are in the prefix: only the other rows' samples are encoded (none: no
+            # encoder call at all).  A sample that spans two rows cannot be told apart: then every sample is encoded.
+            keep_spk = [i for u in utts if not reuse[u.idx] for i in spk[u.idx]]
+            for u in utts:
+                if reuse[u.idx]:
+                    sp_pos.pop(u.idx, None)
+            if keep_spk:
+                sel = torch.tensor(keep_spk, dtype=torch.long)
+                speech_tensors, speech_masks = speech_tensors.cpu()[sel], speech_masks.cpu()[sel]
+                if prefill_noise is not None:
+                    prefill_noise = tuple(t.cpu()[sel] for t in prefill_noise)
+                if spk_seeds is not None:
+                    spk_seeds = [spk_seeds[i] for i in keep_spk]
+            else:
+                with_voice = False
+        if with_voice:
+            _, sp_embeds = self._process_speech_inputs(speech_tensors, speech_masks, prefill_noise, seeds=spk_seeds)
+        if time_prefill:
+            e.sync(); torch.cuda.current_stream(self.device).synchronize(); t_pf.append(time.perf_counter())
+        sp_off = 0
+        jobs = []
+        for u in utts:
+            rows = pos = None
+            if sp_embeds is not None and u.idx in sp_pos:
+                cnt, pos = sp_pos[u.idx]
+                rows = sp_embeds[sp_off:sp_off + cnt]
+                sp_off += cnt
+            jobs.append((u, u.ids, rows, pos, kv_start, kv_fill_fn, prefixes[u.idx] if reuse[u.idx] else None, reuse[u.idx]))
+        self._prefill_checked(jobs)
+        if time_prefill:
+            e.sync(); t_pf.append(time.perf_counter())
+            self.last_prefill = {"voice_encode_s": round(t_pf[1] - t_pf[0], 5),
+                                 "lm_prefill_s": round(t_pf[2] - t_pf[1] - self._t_kv_fill, 5),
+                                 "lm_passes_s": round(self._t_lm_pass, 5),      # the LM launches alone (the rest of
+                                 "bench_kv_fill_s": round(self._t_kv_fill, 5)}  # lm_prefill_s: embedding + row scatter)
+        return {"prefix_rows_reused": sum(reuse.values()), "prompt_rows_computed": sum(len(u.ids) - reuse[u.idx] for u in utts)}
+
+    def _output(self, utts, input_ids, n_new, eos_id, return_speech):
+        """utterances -> VibeVoiceGenerationOutput (:691-695): row b = input_ids[b] + utts[b]'s tokens, padded with eos to n_new new
+        columns (:499); one waveform (or None) per row"""
+        B, L0 = input_ids.shape
+        seq = torch.full((B, L0 + n_new), eos_id, dtype=torch.long)
+        seq[:, :L0] = input_ids
+        for b, u in enumerate(utts):
+            if u.tokens:
+                seq[b, L0:L0 + len(u.tokens)] = torch.tensor(u.tokens, dtype=torch.long)
+        outs = [torch.cat(u.chunks, dim=-1)[None].to(self.dtype) if u.chunks else None for u in utts]
         return VibeVoiceGenerationOutput(
             sequences=seq.to(self.device), speech_outputs=outs if return_speech else None,
             reach_max_step_sample=torch.tensor([u.reach_max for u in utts], dtype=torch.bool).to(self.device))
@@ -1898,7 +1957,7 @@ class VibeVoiceForConditionalGenerationInference:
         padded with eos after a row's end, :499; speech_outputs one entry per row; reach_max_step_sample [B]).  Rows are
         independent in the reference's loop (no cross-sample arithmetic, :393-394,549,573,594) with ONE exception this path does not
         reproduce: a row whose first frame comes later than another's costs the rows decoded with it their tokenizer conv history
-        for that frame (the cache quirk described in _iterate; impossible on processor-built prompts, where every row takes its first
+        for that frame (the cache quirk described in _tokenizer_chain; impossible on processor-built prompts, where every row takes its first
         frame at step 0) -- and one consequence of the queue itself: the batch-level early exit with an audio_streamer (the loop ends when
         ANY stream has finished, :443-447) can fire while rows are still waiting for a slot; those rows return as their prompt without
         audio (the lock-step batch would have advanced them to that step) and a RuntimeWarning says so.
@@ -1915,7 +1974,6 @@ class VibeVoiceForConditionalGenerationInference:
         all_seeded = seeds is not None and all(v is not None for v in seeds)      # every draw is the row's own: nothing follows the queue
         if not _WARNED_QUEUED_RNG and not all_seeded and (noise_fn is None or self._generation_options(generation_config)[0]):
             _WARNED_QUEUED_RNG = True
-            import warnings
             warnings.warn(f"generate(): a batch of {B} rows exceeds one engine pass ({min(MAX_BATCH, self.engine.cfg.n_slots, self.engine.cfg.max_rows // 2)} "
                           "utterances) and is decoded through the continuous-admission queue: every row is what generate() gives it alone, but "
                           "random draws (diffusion noise, do_sample) are consumed in queue order, not in the lock-step batch's order -- a seeded "
@@ -1991,7 +2049,6 @@ class VibeVoiceForConditionalGenerationInference:
         with a "seed" key (generate_continuous) draw from their own counters instead: the lane generators are not used for them and the
         lane a request lands in does not matter.  Returns the outputs in request order.  The lanes are
         created on first use (each owns KV caches for its n_slots) and kept: `model.close_lanes()` releases them."""
-        import threading
         from .parallel import shard_utterances
         _request_cfg_scales(requests, kwargs.get("cfg_scale", 1.0), "generate_interleaved()")      # refused here, before any lane starts
         seeds = _request_seeds(requests, "generate_interleaved()")
@@ -2003,11 +2060,9 @@ class VibeVoiceForConditionalGenerationInference:
         seeds = _resolve_seeds(seeds)
         if seeds is not None:
             requests = [dict(r, seed=sd) for r, sd in zip(requests, seeds)]
-        pool = getattr(self, "_lanes", None) or []
-        while len(pool) < lanes - 1:
-            pool.append(self.fork())
-        self._lanes = pool
-        models = [self] + pool[:lanes - 1]
+        while len(self._lanes) < lanes - 1:
+            self._lanes.append(self.fork())
+        models = [self] + self._lanes[:lanes - 1]
         shards = shard_utterances([int(r["input_ids"].shape[-1]) for r in requests], lanes)
         outs: List[Optional[VibeVoiceGenerationOutput]] = [None] * len(requests)
         errs: List[Optional[BaseException]] = [None] * lanes
@@ -2015,13 +2070,13 @@ class VibeVoiceForConditionalGenerationInference:
         # sampling, multinomial and the sde variance noise on the device one), seeded here, on the caller's thread, from the
         # process-global CPU generator: a seeded call (torch.manual_seed) is reproducible, no lane can rewind or consume another
         # lane's draws, and the global device generator is not touched from the lane threads
-        seeds = torch.randint(0, 2 ** 62, (lanes, 2), dtype=torch.int64).tolist()
+        lane_seeds = torch.randint(0, 2 ** 62, (lanes, 2), dtype=torch.int64).tolist()
         gens = []
         for k in range(lanes):
             cg = torch.Generator()
-            cg.manual_seed(seeds[k][0])
+            cg.manual_seed(lane_seeds[k][0])
             dg = torch.Generator(device=self.device)
-            dg.manual_seed(seeds[k][1])
+            dg.manual_seed(lane_seeds[k][1])
             gens.append((cg, dg))
 
         def run(k):
@@ -2054,7 +2109,7 @@ class VibeVoiceForConditionalGenerationInference:
         return outs
 
     def close_lanes(self):
-        for m in getattr(self, "_lanes", None) or []:
+        for m in self._lanes:
             m.engine.close()
         self._lanes = []
 
@@ -2088,23 +2143,21 @@ class VibeVoiceForConditionalGenerationInference:
             # step (the correction of :590-624): defined for the lock-step batch of generate(), not for a queue of requests
             raise NotImplementedError("refresh_negative=False is a rule over the rows of one lock-step batch: use generate() with at "
                                       f"most {MAX_BATCH} rows (continuous admission / larger batches refuse it)")
+        # lockstep=False: independent requests, no cross-row tokenizer-cache coupling (_tokenizer_chain)
         S = self._session(tokenizer, generation_config, cfg_scales or _cfg_scale_values(cfg_scale, 1, "generate_continuous()"), kwargs,
-                          audio_streamer, n_req)
-        S["lockstep"] = False                   # independent requests: no cross-row tokenizer-cache coupling (see _iterate)
-        S["sample_rows"] = lambda order: [u.idx for u in order]
-        S["seeds"] = _resolve_seeds(_request_seeds(requests, "generate_continuous()"), S.get("cpu_gen"))
+                          audio_streamer, n_req, seeds=_request_seeds(requests, "generate_continuous()"),
+                          sample_rows=lambda order: [u.idx for u in order], lockstep=False)
         self._frame_w = cap
         self._first_row = {}
         queue = list(range(n_req))
-        free = list(range(cap))
         done = [None] * n_req
         active: List[_Utt] = []
         it = 0
         stats = {"iterations": 0, "admissions": [], "max_in_flight": 0, "prefix_rows_reused": 0, "prompt_rows_computed": 0}
         with torch.cuda.stream(e.stream), _end_streamer_on_error(audio_streamer):
-            e.embed([S["start_id"]], self._start_emb)
+            e.embed([S.start_id], self._start_emb)
             while queue or active:
-                S["step"] = it
+                S.step = it
                 if step_cb is not None:
                     step_cb(it)
                 if stop_check_fn is not None and stop_check_fn():
@@ -2116,71 +2169,19 @@ class VibeVoiceForConditionalGenerationInference:
                     # lock-step batch has advanced EVERY row to this step by then; a queue has not -- rows still waiting for a slot come
                     # back as their prompt with no audio.  Said once, loudly: a caller that streams a batch this large wants to know.
                     if queue:
-                        import warnings
                         warnings.warn(f"generate(): the batch-level early exit (a finished audio stream, modeling_vibevoice_inference.py:443-447) fired "
                                       f"while {len(queue)} of {n_req} rows were still queued for an engine slot: the reference's lock-step batch would "
                                       "have decoded them up to this step, here they return as their prompt without audio.  Use batches of at most "
                                       f"{cap} rows with an audio_streamer, or generate_continuous() (no batch-level exit).", RuntimeWarning, stacklevel=3)
                     break
-                # ---- retire by the loop-level conditions of a batch-1 generate(): range(max_steps) exhausted / max_length ----
-                keep, keep_rows = [], []
-                for i, u in enumerate(active):
-                    if u.step >= u.max_steps:
-                        u.finished = True
-                    elif u.seq_len0 + u.step >= u.max_length:
-                        u.finished = u.reach_max = True
-                    if not u.finished:
-                        keep.append(u)
-                        keep_rows.append(i)
-                    elif audio_streamer is not None:
-                        audio_streamer.end(torch.tensor([u.idx]))
-                if keep and len(keep) != len(active):
-                    # _iterate packed the next-step embeddings in the order of the utterances it returned (`active`) and reads
-                    # them back by position: the rows of the survivors move up to the survivors' new positions
-                    sel = torch.tensor(keep_rows, dtype=torch.long, device=self._x_in.device)
-                    self._x_in[:len(keep)] = self._x_in.index_select(0, sel)
-                active = keep
+                active = self._retire_at_loop_end(active, audio_streamer)
                 # ---- refill free slots ----
                 in_flight = {u.slot for u in active}
                 free = [s for s in range(cap) if s not in in_flight]
                 while queue and free:
-                    ri = queue.pop(0)
-                    slot = free.pop(0)
-                    r = requests[ri]
-                    ids_t = r["input_ids"].cpu()
-                    am = r.get("attention_mask")
-                    am = torch.ones_like(ids_t) if am is None else am.cpu()
-                    if ids_t.shape[0] != 1:
-                        raise ValueError("generate_continuous: every request carries exactly one utterance")
-                    L0 = ids_t.shape[1]
-                    mnt = r.get("max_new_tokens", max_new_tokens)
-                    mnt = self.max_position_embeddings - L0 if mnt is None else mnt
-                    u = _Utt(ri, slot, ids_t[0][am[0].bool()].tolist(), L0, min(L0 + mnt, e.max_ctx), max_length_times, S["start_id"])
-                    u.forced, u.noise_fn, u.req = r.get("_forced_tokens"), r.get("_noise_fn"), r
-                    u.cfg_scale = cfg_scales[ri]
-                    if S["seeds"] is not None:
-                        u.seed = S["seeds"][ri]
-                    u.t_admit = it
-                    e.codec_reset(slot)
-                    rows = pos = None
-                    reuse = 0
-                    if r.get("prompt_prefix") is not None:      # the request starts with a prompt prefix: its voice rows are in the snapshot
-                        sim = r.get("speech_input_mask")
-                        sp_host = None if sim is None else sim[0].cpu()[am[0].bool().cpu()].to(torch.bool).nonzero().squeeze(1).tolist()
-                        reuse = self._prefix_plan(r["prompt_prefix"], u.ids, sp_host)
-                    if not reuse and is_prefill and r.get("speech_tensors") is not None and r.get("speech_masks") is not None:
-                        _, sp = self._process_speech_inputs(r["speech_tensors"], r["speech_masks"], r.get("_prefill_noise"), dev_gen=S.get("dev_gen"),
-                                                            seeds=None if u.seed is None else [(u.seed, k) for k in range(r["speech_tensors"].shape[0])])
-                        sim = r.get("speech_input_mask")
-                        if sim is not None:
-                            idx = sim[0].cpu()[am[0].bool().cpu()].to(torch.bool).nonzero().squeeze(1)      # host data: no device count
-                            if idx.numel():
-                                pos = idx.to(self.device)
-                                rows = sp[:int(idx.numel())]
-                    if reuse:
-                        self._prefill_checked([(u, u.ids, None, None, 0, None, r["prompt_prefix"], reuse)])
-                    else:
-                        self._prefill_checked([(u, u.ids, rows, pos, 0, None)])
+                    ri, slot = queue.pop(0), free.pop(0)
+                    mnt = requests[ri].get("max_new_tokens", max_new_tokens)
+                    u, reuse = self._admit(S, ri, slot, requests[ri], cfg_scales[ri], mnt, max_length_times, is_prefill)
                     stats["prefix_rows_reused"] += reuse
                     stats["prompt_rows_computed"] += len(u.ids) - reuse
                     done[ri] = u
@@ -2196,19 +2197,7 @@ class VibeVoiceForConditionalGenerationInference:
                 before = active
                 active = self._iterate(S, active)
                 it += 1
-                # a finished utterance's frames leave the shared frame store at once (its own contiguous tensor); blocks no
-                # live utterance points into are dropped, so the store follows the audio IN FLIGHT, not the queue's total
-                ended = [u for u in before if u.finished]
-                for u in ended:
-                    if u.chunks:
-                        u.chunks = [torch.cat(u.chunks, dim=-1)]
-                if ended:
-                    rows0 = [self._first_row[id(u)] for u in active if id(u) in self._first_row]
-                    lo = min(rows0 + [S["frame_rows"]]) // self.frame_block
-                    for b in range(min(lo, len(self._audio_blocks))):
-                        self._audio_blocks[b] = None
-                    for u in ended:
-                        self._first_row.pop(id(u), None)
+                self._trim_frame_store(S, [u for u in before if u.finished], active)
             if audio_streamer is not None:
                 audio_streamer.end()
             outs = []
@@ -2217,14 +2206,77 @@ class VibeVoiceForConditionalGenerationInference:
                 if u is None:                       # stopped before admission
                     outs.append(VibeVoiceGenerationOutput(sequences=requests[ri]["input_ids"].to(self.device), speech_outputs=[None],
                                                           reach_max_step_sample=torch.tensor([False], device=self.device)))
-                    continue
-                ids_t = requests[ri]["input_ids"].cpu()
-                seq = torch.cat([ids_t, torch.tensor([u.tokens], dtype=torch.long)], dim=-1) if u.tokens else ids_t
-                audio = torch.cat(u.chunks, dim=-1)[None].to(self.dtype) if u.chunks else None
-                outs.append(VibeVoiceGenerationOutput(sequences=seq.to(self.device), speech_outputs=[audio] if return_speech else None,
-                                                      reach_max_step_sample=torch.tensor([u.reach_max], device=self.device)))
+                else:
+                    outs.append(self._output([u], requests[ri]["input_ids"].cpu(), len(u.tokens), S.eos_id, return_speech))
         e.sync()
         self._release_frames()
         stats["iterations"] = it
-        self.last_stats = {"frames": S["n_frames"], "steps": it, **stats}
+        self.last_stats = {"frames": S.n_frames, "steps": it, **stats}
         return outs
+
+    def _retire_at_loop_end(self, active, audio_streamer):
+        """retire by the loop-level conditions of a batch-1 generate(): range(max_steps) exhausted / max_length; -> the survivors"""
+        keep, keep_rows = [], []
+        for i, u in enumerate(active):
+            if u.step >= u.max_steps:
+                u.finished = True
+            elif u.seq_len0 + u.step >= u.max_length:
+                u.finished = u.reach_max = True
+            if not u.finished:
+                keep.append(u)
+                keep_rows.append(i)
+            elif audio_streamer is not None:
+                audio_streamer.end(torch.tensor([u.idx]))
+        if keep and len(keep) != len(active):
+            # _iterate packed the next-step embeddings in the order of the utterances it returned (`active`) and reads
+            # them back by position: the rows of the survivors move up to the survivors' new positions
+            sel = torch.tensor(keep_rows, dtype=torch.long, device=self._x_in.device)
+            self._x_in[:len(keep)] = self._x_in.index_select(0, sel)
+        return keep
+
+    def _admit(self, S, ri, slot, r, cfg_scale, max_new_tokens, max_length_times, is_prefill):
+        """request `r` (index ri of the queue) into engine slot `slot`: its _Utt, tokenizer state reset, voice samples encoded (or its
+        prompt prefix restored) and prompt prefilled; -> (the utterance, the prompt positions taken from a prefix)"""
+        e = self.engine
+        ids_t = r["input_ids"].cpu()
+        am = r.get("attention_mask")
+        am = torch.ones_like(ids_t) if am is None else am.cpu()
+        if ids_t.shape[0] != 1:
+            raise ValueError("generate_continuous: every request carries exactly one utterance")
+        L0 = ids_t.shape[1]
+        mnt = self.max_position_embeddings - L0 if max_new_tokens is None else max_new_tokens
+        u = _Utt(ri, slot, ids_t[0][am[0].bool()].tolist(), L0, min(L0 + mnt, e.max_ctx), max_length_times, S.start_id)
+        u.forced, u.noise_fn, u.req = r.get("_forced_tokens"), r.get("_noise_fn"), r
+        u.cfg_scale = cfg_scale
+        if S.seeded:
+            u.seed = S.seeds[ri]
+        u.t_admit = S.step
+        e.codec_reset(slot)
+        sim = r.get("speech_input_mask")
+        sp_idx = None if sim is None else _speech_positions(sim[0], am[0])
+        rows = pos = None
+        reuse = 0
+        if r.get("prompt_prefix") is not None:      # the request starts with a prompt prefix: its voice rows are in the snapshot
+            reuse = self._prefix_plan(r["prompt_prefix"], u.ids, None if sp_idx is None else sp_idx.tolist())
+        if not reuse and is_prefill and r.get("speech_tensors") is not None and r.get("speech_masks") is not None:
+            _, sp = self._process_speech_inputs(r["speech_tensors"], r["speech_masks"], r.get("_prefill_noise"), dev_gen=S.dev_gen,
+                                                seeds=None if u.seed is None else [(u.seed, k) for k in range(r["speech_tensors"].shape[0])])
+            if sp_idx is not None and sp_idx.numel():
+                pos = sp_idx.to(self.device)
+                rows = sp[:int(sp_idx.numel())]
+        self._prefill_checked([(u, u.ids, rows, pos, 0, None, r["prompt_prefix"] if reuse else None, reuse)])
+        return u, reuse
+
+    def _trim_frame_store(self, S, ended, active):
+        """a finished utterance's frames leave the shared frame store at once (its own contiguous tensor); blocks no live utterance
+        points into are dropped, so the store follows the audio IN FLIGHT, not the queue's total"""
+        for u in ended:
+            if u.chunks:
+                u.chunks = [torch.cat(u.chunks, dim=-1)]
+        if ended:
+            rows0 = [self._first_row[id(u)] for u in active if id(u) in self._first_row]
+            lo = min(rows0 + [S.frame_rows]) // self.frame_block
+            for b in range(min(lo, len(self._audio_blocks))):
+                self._audio_blocks[b] = None
+            for u in ended:
+                self._first_row.pop(id(u), None)
