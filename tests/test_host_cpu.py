@@ -40,13 +40,23 @@ def test_binary_carries_the_hash_of_its_sources(tmp_path):
     old_csrc, old_hdr = build.CSRC, build.HEADERS
     try:
         build.CSRC = src
-        build.HEADERS = [os.path.join(src, "vv_common.h"), old_hdr[1]]
+        build.HEADERS = [os.path.join(src, os.path.basename(h)) if os.path.dirname(h) == old_csrc else h for h in old_hdr]
         assert build.source_id() == sid
         with open(os.path.join(src, "misc.hip"), "a") as f:
             f.write("\n// edited\n")
         assert build.source_id() != sid and build.stale()
     finally:
         build.CSRC, build.HEADERS = old_csrc, old_hdr
+
+
+def test_every_source_and_header_is_in_the_build_lists():
+    """A unit or header under csrc/ that build.SOURCES / build.HEADERS does not name would be left out of the library or of the
+    build id (source_id hashes exactly those lists) without anything noticing."""
+    from vibevoice_amd import build
+    names = sorted(os.listdir(build.CSRC))
+    assert sorted(n for n in names if n.endswith(".hip")) == sorted(build.SOURCES)
+    listed = {os.path.basename(h) for h in build.HEADERS if os.path.dirname(h) == build.CSRC}
+    assert {n for n in names if n.endswith(".h")} == listed
 
 
 def test_engine_refuses_to_run_without_gpu():

@@ -1,6 +1,6 @@
 """Wall-clock timeline of the GEMV launches of one decode step, from per-workgroup entry/exit stamps.
 
-Needs a timing build:  tools/variant.sh t8 "-DVV_GEMM_TIMING"  (engine.hip must be compiled with the flag too:
+Needs a timing build:  tools/variant.sh t8 "-DVV_GEMM_TIMING"  (the engine*.hip units must be compiled with the flag too:
 VVHIP_CFLAGS=-DVV_GEMM_TIMING python -m vibevoice_amd.build --force), then
     VVHIP_TIMELINE=gpurun_out/tl.npz python bench.py --no-cpu-baseline --no-roofline --steps 20 --warmup 4
     python tools/step_timeline.py gpurun_out/tl.npz

@@ -18,6 +18,7 @@
 // workspace and a second tiny kernel merges the splits.
 #include <cstdlib>
 #include "vv_common.h"
+#include "vv_launch.h"
 
 namespace {
 

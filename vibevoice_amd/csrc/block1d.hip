@@ -13,6 +13,7 @@
 // the input without racing the neighbours' writes.  Streaming state = the last 6
 // *normed* rows, written to `nst + 6*C` and moved to the front by the net's shift kernel.
 #include "vv_common.h"
+#include "vv_launch.h"
 
 namespace {
 
@@ -260,21 +261,7 @@ static void go(const VVBlock& a, hipStream_t s) {
 }  // namespace
 
 extern "C" int vv_block1d_supported(int C) { return C == 32 || C == 64 || C == 128; }
-extern "C" int vv_block1d_slots_launch(int C, int xs, const float* xin, float* xout, float* nst, const float* norm_w,
-                                       const float* ffn_norm_w, const float* gamma, const float* ffn_gamma,
-                                       const float* dw_w, const float* dw_b, const float* b1, const float* b2,
-                                       const void* w1, const void* w2, int T, float eps, const int* ids, int n, int64_t sx,
-                                       int64_t snst, hipStream_t s);
-
-extern "C" int vv_block1d_launch(int C, int xs, const float* xin, float* xout, float* nst, const float* norm_w,
-                                 const float* ffn_norm_w, const float* gamma, const float* ffn_gamma,
-                                 const float* dw_w, const float* dw_b, const float* b1, const float* b2,
-                                 const void* w1, const void* w2, int T, float eps, hipStream_t s) {
-    return vv_block1d_slots_launch(C, xs, xin, xout, nst, norm_w, ffn_norm_w, gamma, ffn_gamma, dw_w, dw_b, b1, b2, w1, w2, T, eps,
-                                   nullptr, 0, 0, 0, s);
-}
-
-// the same block over n utterance slots (ids != null): xin / xout / nst are slot 0's buffers
+// ids == null: one slot, the buffers given; ids != null: the same block over n utterance slots, xin / xout / nst are slot 0's buffers
 extern "C" int vv_block1d_slots_launch(int C, int xs, const float* xin, float* xout, float* nst, const float* norm_w,
                                        const float* ffn_norm_w, const float* gamma, const float* ffn_gamma,
                                        const float* dw_w, const float* dw_b, const float* b1, const float* b2,
@@ -283,8 +270,7 @@ extern "C" int vv_block1d_slots_launch(int C, int xs, const float* xin, float* x
     if (n < 0 || n > 8) return -1;
     VVBlock a{xin, xout, nst, norm_w, ffn_norm_w, gamma, ffn_gamma, dw_w, dw_b, b1, b2,
               (const u32x4*)w1, (const u32x4*)w2, T, eps};
-    a.sl.n = ids ? n : 0;
-    for (int i = 0; i < 8; ++i) a.sl.id[i] = (ids && i < n) ? ids[i] : 0;
+    a.sl = vv_slot_ids(ids, n);
     a.sx = sx; a.snst = snst;
 #define VV_B(C_)                                                     \
     do {                                                             \

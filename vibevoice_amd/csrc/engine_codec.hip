@@ -1,0 +1,498 @@
+// engine_codec.hip -- host side of libvvhip.so: the streaming tokenizer (codec) nets: build, history tables, the stage walker, API.
+#include "engine_ctx.h"
+
+// the two conv shapes with a kernel of their own instead of a GEMM (misc.hip)
+static bool is_stem(const ConvG& g) { return g.K == 7 && g.ldx == 1; }       // encoder stem: mono input, k = 7 (only a net's first conv can have this shape)
+static bool is_conv1_head(const ConvG& g) { return g.N == 1 && g.K == 7 * g.ldx && (g.ldx & 3) == 0 && g.ldx <= 1024; }     // decoder head: k = 7 conv to one channel
+
+// Registers a net's weights and allocates its per-slot state.  The walloc / add_mat / add_vec calls keep their order: a shared child
+// replays the parent's allocation sequence and the parameter tables are compared index by index (create_impl).
+int build_codec(vv_ctx* ctx, CodecNet& net, const std::string& pfx, bool decoder, int vae_dim, int Fmax, int n_slots) {
+    const vv_config& c = ctx->c;
+    const int ns = c.n_stages;
+    const int nf = c.n_filters;
+    net.decoder = decoder; net.Fmax = Fmax;
+    std::vector<int> depths(ns), ratios(c.n_ratios);
+    if (decoder) { for (int i = 0; i < ns; ++i) depths[i] = c.enc_depths[ns - 1 - i]; for (int i = 0; i < c.n_ratios; ++i) ratios[i] = c.ratios[i]; }
+    else { for (int i = 0; i < ns; ++i) depths[i] = c.enc_depths[i]; for (int i = 0; i < c.n_ratios; ++i) ratios[i] = c.ratios[c.n_ratios - 1 - i]; }
+    int hop = 1; for (int i = 0; i < c.n_ratios; ++i) hop *= c.ratios[i];
+    ctx->hop = hop;
+    // per-stage geometry
+    std::vector<int> C(ns), Tpf(ns);
+    for (int i = 0; i < ns; ++i) {
+        if (decoder) { C[i] = nf << (ns - 1 - i); Tpf[i] = (i == 0) ? 1 : Tpf[i - 1] * ratios[i - 1]; }
+        else { C[i] = nf << i; Tpf[i] = (i == 0) ? hop : Tpf[i - 1] / ratios[i - 1]; }
+    }
+    net.in_dim = decoder ? vae_dim : 1;
+    net.out_dim = decoder ? 1 : vae_dim;
+    net.in_Tpf = decoder ? 1 : hop;
+    net.in_hist = 6;
+    net.maxC = 1;
+    size_t umax = 0;
+    // ---- weights (shared across slots) ----
+    struct StageW { ConvG in; std::vector<Block> blocks; };
+    std::vector<StageW> sw(ns);
+    for (int i = 0; i < ns; ++i) {
+        ConvG& g = sw[i].in;
+        char nm[256];
+        if (i == 0) {
+            const int Cin = net.in_dim;
+            g.K = 7 * Cin; g.N = C[0]; g.ldx = Cin; g.rows_per_frame = Tpf[0];
+            g.w = alloc_packed(ctx, g.N, g.K);
+            snprintf(nm, 256, "%s%s.0.0.conv.conv.", pfx.c_str(), decoder ? "upsample_layers" : "downsample_layers");
+            add_mat(ctx, std::string(nm) + "weight", g.N, g.K, g.w, 0, 1, Cin, g.N, 7, 1);
+            g.bias = add_vec(ctx, std::string(nm) + "bias", g.N);
+        } else if (decoder) {
+            const int s = ratios[i - 1], Cin = C[i - 1], Cout = C[i];
+            g.K = 2 * Cin; g.N = s * Cout; g.ldx = Cin; g.rows_per_frame = Tpf[i - 1];
+            g.w = alloc_packed(ctx, g.N, g.K);
+            snprintf(nm, 256, "%supsample_layers.%d.0.convtr.convtr.", pfx.c_str(), i);
+            add_mat(ctx, std::string(nm) + "weight", g.N, g.K, g.w, 0, 2, Cin, Cout, 2 * s, s, (int64_t)Cin * Cout * 2 * s);
+            g.bias = add_vec(ctx, std::string(nm) + "bias", Cout, nullptr, W_BIAS_REP, s);
+        } else {
+            const int s = ratios[i - 1], Cin = C[i - 1], Cout = C[i];
+            g.K = 2 * s * Cin; g.N = Cout; g.ldx = s * Cin; g.rows_per_frame = Tpf[i];
+            g.w = alloc_packed(ctx, g.N, g.K);
+            snprintf(nm, 256, "%sdownsample_layers.%d.0.conv.conv.", pfx.c_str(), i);
+            add_mat(ctx, std::string(nm) + "weight", g.N, g.K, g.w, 0, 1, Cin, Cout, 2 * s, s);
+            g.bias = add_vec(ctx, std::string(nm) + "bias", Cout);
+        }
+        if (C[i] > net.maxC) net.maxC = C[i];
+        for (int j = 0; j < depths[i]; ++j) {
+            Block b; b.C = C[i]; b.nb = nullptr;
+            snprintf(nm, 256, "%sstages.%d.%d.", pfx.c_str(), i, j);
+            std::string p(nm);
+            b.gamma = add_vec(ctx, p + "gamma", C[i]);
+            b.ffn_gamma = add_vec(ctx, p + "ffn_gamma", C[i]);
+            b.norm_w = add_vec(ctx, p + "norm.weight", C[i]);
+            b.ffn_norm_w = add_vec(ctx, p + "ffn_norm.weight", C[i]);
+            b.dw_w = add_vec(ctx, p + "mixer.conv.conv.conv.weight", (int64_t)C[i] * 7, nullptr, W_DW);
+            b.dw_b = add_vec(ctx, p + "mixer.conv.conv.conv.bias", C[i]);
+            b.w1 = alloc_packed(ctx, 4 * C[i], C[i]);
+            add_mat(ctx, p + "ffn.linear1.weight", 4 * C[i], C[i], b.w1, 0);
+            b.b1 = add_vec(ctx, p + "ffn.linear1.bias", 4 * C[i]);
+            b.w2 = alloc_packed(ctx, C[i], 4 * C[i]);
+            add_mat(ctx, p + "ffn.linear2.weight", C[i], 4 * C[i], b.w2, 0);
+            b.b2 = add_vec(ctx, p + "ffn.linear2.bias", C[i]);
+            sw[i].blocks.push_back(b);
+            size_t ub = (size_t)Tpf[i] * Fmax * 4 * C[i] * 4;
+            if (ub > umax) umax = ub;
+        }
+    }
+    {   // head conv k7
+        ConvG& g = net.head;
+        const int Cin = C[ns - 1];
+        g.K = 7 * Cin; g.N = net.out_dim; g.ldx = Cin; g.rows_per_frame = Tpf[ns - 1];
+        g.w = alloc_packed(ctx, g.N, g.K);
+        add_mat(ctx, pfx + "head.conv.conv.weight", g.N, g.K, g.w, 0, 1, Cin, g.N, 7, 1);
+        g.bias = add_vec(ctx, pfx + "head.conv.conv.bias", g.N);
+    }
+    // ---- per-slot buffers + shift tables.  Every kind of buffer is ONE allocation with a uniform slot stride (a multiple of
+    // 64 floats), so a slot-batched launch reaches utterance k's copy at base + k * stride ----
+    auto pad64 = [](size_t n) { return (n + 63) / 64 * 64; };
+    net.u.resize(n_slots);
+    net.u_stride = (int64_t)pad64(umax / 4 + 1);
+    float* u_all = (float*)dalloc(ctx, (size_t)n_slots * net.u_stride * 4, false);
+    net.in_buf.resize(n_slots); net.st.resize(n_slots);
+    net.in_stride = (int64_t)pad64((size_t)(6 + net.in_Tpf * Fmax) * net.in_dim);
+    float* in_all = (float*)dalloc(ctx, (size_t)n_slots * net.in_stride * 4);
+    if (!u_all || !in_all) return -1;
+    for (int sl = 0; sl < n_slots; ++sl) {
+        net.u[sl] = u_all + (size_t)sl * net.u_stride;
+        net.in_buf[sl] = in_all + (size_t)sl * net.in_stride;
+        net.st[sl].resize(ns);
+    }
+    for (int i = 0; i < ns; ++i) {
+        const int hist = (i == ns - 1) ? 6 : (decoder ? 1 : ratios[i]);
+        const bool fused = vv_block1d_supported(C[i]) && Tpf[i] >= 8 && !sw[i].blocks.empty();
+        // unfused stages ping-pong between xs and xs2 when a one-launch norm + depthwise-conv kernel exists for them:
+        // channel-sliced (T <= 8, C = 1024 / 2048) or row-tiled (middle stages, any T)
+        const bool pp = !fused && !sw[i].blocks.empty() && (vv_normdw_sliced_ok(Tpf[i], C[i]) || vv_normdw_rows_ok(Tpf[i], C[i]));
+        const int64_t xstride = (int64_t)pad64((size_t)(hist + (size_t)Tpf[i] * Fmax) * C[i]);
+        float* xs_all = (float*)dalloc(ctx, (size_t)n_slots * xstride * 4);
+        float* xs2_all = (fused || pp) ? (float*)dalloc(ctx, (size_t)n_slots * xstride * 4) : nullptr;
+        if (!xs_all || ((fused || pp) && !xs2_all)) return -1;
+        const int64_t nbstride = (int64_t)pad64(fused ? (size_t)12 * C[i] : (size_t)(6 + (size_t)Tpf[i] * Fmax) * C[i]);
+        std::vector<float*> nb_all(sw[i].blocks.size());
+        for (auto& p : nb_all) { p = (float*)dalloc(ctx, (size_t)n_slots * nbstride * 4); if (!p) return -1; }
+        for (int sl = 0; sl < n_slots; ++sl) {
+            Stage& s = net.st[sl][i];
+            s.C = C[i]; s.Tpf = Tpf[i]; s.in = sw[i].in; s.hist = hist; s.fused = fused; s.pp = pp; s.sl_stride = xstride;
+            s.xs = xs_all + (size_t)sl * xstride;
+            s.xs2 = xs2_all ? xs2_all + (size_t)sl * xstride : nullptr;
+            s.blocks = sw[i].blocks;
+            s.xfinal = ((s.fused || s.pp) && (s.blocks.size() & 1)) ? s.xs2 : s.xs;
+            for (size_t j = 0; j < s.blocks.size(); ++j) {
+                Block& b = s.blocks[j];
+                b.nb = nullptr; b.nst = nullptr; b.nb_stride = nbstride;
+                if (s.fused) b.nst = nb_all[j] + (size_t)sl * nbstride;
+                else b.nb = nb_all[j] + (size_t)sl * nbstride;
+            }
+        }
+    }
+    // which stages can run slot-batched (bf16 modes): the incoming conv as a slot-batched GEMV (or the stem kernel), the blocks
+    // as fused block kernels, or channel-sliced / row-tiled norm+conv + slot-batched FFN GEMVs.  VVHIP_BATCH_CODEC=heavy keeps
+    // only the weight-heavy T <= 8 stages batched (the rest per utterance on forked streams), =0 turns batching off.
+    {
+        const char* mode = getenv("VVHIP_BATCH_CODEC");
+        const bool off = (mode && !strcmp(mode, "0")) || ctx->c.xsplit > 2 || n_slots < 2 || Fmax != 1;
+        const bool heavy_only = mode && !strcmp(mode, "heavy");
+        auto gemm_ok = [&](const ConvG& cg, int64_t sx, int64_t sy) {
+            VVGemm g = mk_gemm(cg.w, net.in_buf[0], net.u[0], 2 * cg.rows_per_frame, cg.N, cg.K, cg.ldx, cg.N);
+            g.epi = VV_EPI_BIAS; g.bias = cg.bias;
+            g.sl_n = 2; g.sl_T = cg.rows_per_frame; g.sl_x = (int)sx; g.sl_y = (int)sy; g.sl_id[0] = 0; g.sl_id[1] = n_slots - 1;
+            return vv_gemv_ok(&g) != 0;
+        };
+        auto ok = [&](int i) {
+            const Stage& s = net.st[0][i];
+            if (off || s.blocks.empty() || (s.C & 31)) return false;
+            if (!is_stem(s.in) && !gemm_ok(s.in, i == 0 ? net.in_stride : net.st[0][i - 1].sl_stride, s.sl_stride)) return false;
+            if (s.pp && vv_normdw_sliced_ok(s.Tpf, s.C)) return true;
+            if (heavy_only) return false;
+            return s.fused || (s.pp && vv_normdw_rows_ok(s.Tpf, s.C));
+        };
+        net.kd = 0; net.ke = ns;
+        if (decoder) { while (net.kd < ns && ok(net.kd)) net.kd++; }
+        else { while (net.ke > 0 && ok(net.ke - 1)) net.ke--; }
+        const ConvG& h = net.head;
+        const bool conv1 = is_conv1_head(h);
+        net.head_batch = !off && !heavy_only && (conv1 || gemm_ok(h, net.st[0][ns - 1].sl_stride, 0));
+        if (!decoder && net.ke < ns && !(conv1 || gemm_ok(h, net.st[0][ns - 1].sl_stride, 0))) net.ke = ns;   // encoder tail needs its head batched
+    }
+    return 0;
+}
+
+// The slots one pass of the walker covers.  n == 0 (ids null): slot `sl` alone -- its base pointers, no VVGemm::sl_* fields, zero slot
+// strides.  n >= 1: slots ids[0..n) (ascending, one frame each) in ONE pass over the weights -- base pointers of slot 0, uniform slot
+// strides; every GEMM carries the rows of all n slots (sl_*: gathered from / scattered to the per-slot buffers), other kernels take the slot from blockIdx.y.
+struct SlotSet { const int* ids; int n; int sl; };
+static SlotSet one_slot(int sl) { return {nullptr, 0, sl}; }
+
+static void codec_table_entries(CodecNet& net, int sl, int F, std::vector<VVShiftH>& t) {
+    t.push_back({net.in_buf[sl], net.in_Tpf * F, 6, net.in_dim});
+    for (auto& s : net.st[sl]) {
+        t.push_back({s.xfinal, s.Tpf * F, s.hist, s.C});
+        for (auto& b : s.blocks) {
+            if (s.fused) t.push_back({b.nst, 6, 6, s.C});
+            else t.push_back({b.nb, s.Tpf * F, 6, s.C});
+        }
+    }
+}
+// the history-shift table of a slot set at F frames per pass (one launch moves every buffer's history), cached by (slot mask, F)
+static int codec_tables(vv_ctx* ctx, CodecNet& net, SlotSet ss, int F, void** tab_out, int* n_out) {
+    const int* ids = ss.n ? ss.ids : &ss.sl;
+    const int n = ss.n ? ss.n : 1;
+    uint64_t mask = 0;
+    for (int j = 0; j < n; ++j) {
+        if (ids[j] >= 64) return fail(ctx, "tokenizer slot %d: the history tables are keyed by a 64-bit slot mask", ids[j]);
+        mask |= 1ull << ids[j];
+    }
+    auto it = net.shift_tab.find({mask, F});
+    if (it == net.shift_tab.end()) {
+        std::vector<VVShiftH> t;
+        for (int j = 0; j < n; ++j) codec_table_entries(net, ids[j], F, t);
+        void* d = dalloc(ctx, t.size() * sizeof(VVShiftH), false);
+        if (!d) return -1;
+        HIPCHK(ctx, hipMemcpy(d, t.data(), t.size() * sizeof(VVShiftH), hipMemcpyHostToDevice));
+        it = net.shift_tab.emplace(std::make_pair(mask, F), std::make_pair(d, (int)t.size())).first;
+    }
+    *tab_out = it->second.first; *n_out = it->second.second;
+    return 0;
+}
+
+// Runs stages [i0, i1) (i1 < 0: to the end) of one codec net over F frames for a slot set; `head` / `shift`: run the head conv / the
+// history shift at the end.  The caller has already written the input rows into in_buf + 6 * in_dim of every slot.  `out`: the head
+// conv's rows, dense [n][rows][out_dim] for a set.  vv_codec_chain_batch runs part of a net for a set and the rest per utterance.
+// tail_valid >= 0 (encoder, last pass of a ragged input): only the first tail_valid rows of stage 0's output are real signal.
+// The reference's non-streaming encoder right-pads with zeros PER strided conv (SConv1d: get_extra_padding_for_conv1d), i.e. the
+// rows past the end of the signal are ZERO at the input of every strided conv -- not conv(0) + bias, which is what the rows past the
+// end hold here when the waveform is zero-padded to whole frames.  Every layer is causal, so zeroing those rows of stage i-1's
+// output right before stage i's incoming conv reproduces the reference exactly; only the last, partial frame's latent changes.
+// Only the voice-prompt encoder passes tail_valid, and only stages build_codec admits (fused, or pp with a one-launch norm + conv
+// kernel) run for a set: the fallback norm / conv forms below never see one.
+static int run_codec(vv_ctx* ctx, CodecNet& net, SlotSet ss, int F, float* out, hipStream_t st, int i0 = 0, int i1 = -1,
+                     bool head = true, bool shift = true, int tail_valid = -1) {
+    const float eps = ctx->c.codec_eps;
+    const bool batched = ss.n > 0;
+    const bool stream_w = (F == 1);      // T=1 stages stream their weights exactly once
+    const int base = batched ? 0 : ss.sl;      // the slot whose descriptors hold the base pointers
+    auto& stages = net.st[base];
+    float* u = net.u[base];                    // FFN hidden scratch; a set's is dense [n * T][4C]
+    const int ns = (int)stages.size();
+    if (i1 < 0) i1 = ns;
+    // what the set means for a launch: a kernel's slot stride (zero for a single slot) and a GEMM's sl_* fields (rows per slot; sx /
+    // sy: slot stride of its input / output side, 0 = dense scratch).  A single slot leaves the GEMM as mk_gemm made it.
+    auto stride = [&](int64_t s) { return batched ? s : (int64_t)0; };
+    auto slots = [&](VVGemm& g, int rows, int64_t sx, int64_t sy) {
+        if (!batched) return;
+        g.sl_n = ss.n; g.sl_T = rows; g.sl_x = (int)sx; g.sl_y = (int)sy; g.T = ss.n * rows;
+        for (int j = 0; j < 8; ++j) g.sl_id[j] = j < ss.n ? ss.ids[j] : 0;
+    };
+    // FIRST of the two places the walks of a set and of a single slot differ: a set's GEMMs always stream their weights non-temporally
+    auto nt = [&](int rows) { return batched ? 1 : (int)(stream_w && rows <= 16); };
+    // a block's FFN pair over the rows in xo.  dw_in (one-row stages): FFN1's prologue also runs the block's norm + depthwise conv +
+    // layer scale + residual on the block's input row dw_in (VV_PRO_NORMDW) and writes xo itself
+    auto ffn1 = [&](const Stage& s, const Block& b, float* xo, int T, const float* dw_in) {
+        VVGemm g1 = mk_gemm(b.w1, dw_in ? dw_in : xo, u, T, 4 * s.C, s.C, s.C, 4 * s.C);
+        g1.pro = VV_PRO_RMS; g1.nw = b.ffn_norm_w; g1.eps = eps; g1.epi = VV_EPI_BIAS_GELU; g1.bias = b.b1; g1.nt = nt(T);
+        if (dw_in) {
+            g1.pro = VV_PRO_NORMDW;
+            g1.dw_hist = b.nb; g1.dw_w = b.dw_w; g1.dw_b = b.dw_b; g1.dw_gamma = b.gamma; g1.dw_nw = b.norm_w;
+            g1.dw_xout = xo; g1.dw_hnew = b.nb + 6 * (size_t)s.C;
+        }
+        slots(g1, T, s.sl_stride, 0);
+        return g1;
+    };
+    auto ffn = [&](const Stage& s, const Block& b, const VVGemm& g1, float* xo, int T) -> int {
+        GEMM(g1);
+        VVGemm g2 = mk_gemm(b.w2, u, xo, T, s.C, 4 * s.C, 4 * s.C, s.C);
+        g2.epi = VV_EPI_RESID; g2.bias = b.b2; g2.nscale = b.ffn_gamma; g2.nt = nt(T);
+        slots(g2, T, 0, s.sl_stride);
+        GEMM(g2);
+        return 0;
+    };
+    for (int i = i0; i < i1; ++i) {
+        Stage& s = stages[i];
+        const int T = s.Tpf * F;
+        float* x = s.xs + (size_t)s.hist * s.C;
+        if (tail_valid >= 0 && i > 0) {
+            Stage& pv = stages[i - 1];
+            const int Tp = pv.Tpf * F;
+            if (tail_valid < Tp)
+                VVCHK(vv_zero_launch(pv.xfinal + ((size_t)pv.hist + tail_valid) * pv.C, (size_t)(Tp - tail_valid) * pv.C * 4, st));
+            const int r = pv.Tpf / s.Tpf;                       // this stage's incoming stride
+            tail_valid = (tail_valid + r - 1) / r;
+        }
+        {   // incoming conv: per-slot window rows in, per-slot stage rows out
+            const ConvG& cg = s.in;
+            const float* X = (i == 0) ? net.in_buf[base] : stages[i - 1].xfinal;
+            const int64_t sx = (i == 0) ? net.in_stride : stages[i - 1].sl_stride;
+            const int Trows = cg.rows_per_frame * F;
+            if (is_stem(cg)) {
+                ctx->launches++;
+                VVCHK(vv_stem_conv_slots_launch(X, cg.w, cg.bias, x, Trows, cg.N, ss.ids, ss.n, stride(sx), stride(s.sl_stride), st));
+            } else {
+                VVGemm g = mk_gemm(cg.w, X, x, Trows, cg.N, cg.K, cg.ldx, cg.N);
+                g.epi = VV_EPI_BIAS; g.bias = cg.bias; g.nt = nt(Trows);
+                slots(g, Trows, sx, s.sl_stride);
+                GEMM(g);
+            }
+        }
+        // fused and pp stages: each block reads one of xs / xs2 and writes the other
+        float* xo = (s.fused || s.pp) ? s.xs2 + (size_t)s.hist * s.C : x;
+        if (s.fused) {
+            for (auto& b : s.blocks) {
+                ctx->launches++;
+                VVCHK(vv_block1d_slots_launch(s.C, ctx->c.xsplit, x, xo, b.nst, b.norm_w, b.ffn_norm_w, b.gamma, b.ffn_gamma, b.dw_w, b.dw_b,
+                                              b.b1, b.b2, b.w1, b.w2, T, eps, ss.ids, ss.n, stride(s.sl_stride), stride(b.nb_stride), st));
+                std::swap(x, xo);
+            }
+            continue;
+        }
+        for (auto& b : s.blocks) {
+            const bool sliced = s.pp && vv_normdw_sliced_ok(T, s.C);
+            // SECOND place: one-row stages of a single slot (C = 2048: 8 blocks per net) run the block's norm + depthwise conv + layer
+            // scale + residual in FFN1's prologue -- one launch less per block on a chain where every launch is a latency link
+            if (sliced && T == 1 && !batched) {
+                const VVGemm g1 = ffn1(s, b, xo, T, x);
+                if (vv_gemv_ok(&g1)) {
+                    VVTRY(ffn(s, b, g1, xo, T));
+                    std::swap(x, xo);
+                    continue;
+                }
+            }
+            if (sliced) {
+                ctx->launches += 1;
+                VVCHK(vv_normdw_sliced_slots_launch(x, xo, b.nb, b.norm_w, b.dw_w, b.dw_b, b.gamma, T, s.C, eps, ss.ids, ss.n, stride(s.sl_stride),
+                                                    stride(b.nb_stride), st));
+            } else if (s.pp && vv_normdw_rows_ok(T, s.C)) {
+                ctx->launches += 1;
+                VVCHK(vv_normdw_rows_slots_launch(x, xo, b.nb, b.norm_w, b.dw_w, b.dw_b, b.gamma, T, s.C, eps, ss.ids, ss.n, stride(s.sl_stride),
+                                                  stride(b.nb_stride), st));
+            } else if (!s.pp && (size_t)T * s.C <= 8192 && (s.C & 3) == 0) {     // one workgroup is only faster for tiny row sets
+                ctx->launches += 1;
+                VVCHK(vv_normdw_launch(x, b.nb, b.norm_w, b.dw_w, b.dw_b, b.gamma, T, s.C, eps, st));
+            } else {
+                ctx->launches += 2;
+                VVCHK(vv_rmsnorm_rows_launch(x, s.C, b.nb + 6 * (size_t)s.C, s.C, b.norm_w, T, s.C, eps, st));
+                VVCHK(vv_dwconv_res_launch(b.nb, x, xo, b.dw_w, b.dw_b, b.gamma, T, s.C, st));
+            }
+            VVTRY(ffn(s, b, ffn1(s, b, xo, T, nullptr), xo, T));
+            if (s.pp) std::swap(x, xo);
+        }
+    }
+    if (head) {   // head conv
+        const ConvG& cg = net.head;
+        Stage& s = stages[ns - 1];
+        const int Trows = cg.rows_per_frame * F;
+        if (is_conv1_head(cg)) {
+            ctx->launches++;
+            VVCHK(vv_head_conv1_slots_launch(s.xfinal, cg.w, cg.bias, out, Trows, cg.ldx, ss.ids, ss.n, stride(s.sl_stride), stride(Trows), st));
+        } else {
+            VVGemm g = mk_gemm(cg.w, s.xfinal, out, Trows, cg.N, cg.K, cg.ldx, cg.N);
+            g.epi = VV_EPI_BIAS; g.bias = cg.bias;
+            slots(g, Trows, s.sl_stride, 0);
+            GEMM(g);
+        }
+    }
+    if (!shift) return 0;
+    void* tab; int n_tab;
+    if (codec_tables(ctx, net, ss, F, &tab, &n_tab)) return -1;
+    ctx->launches++;
+    VVCHK(vv_shift_rows_launch(tab, n_tab, net.maxC, st));
+    return 0;
+}
+
+static int zero_codec(vv_ctx* ctx, CodecNet& net, int sl, hipStream_t st) {
+    void* tab; int nt;
+    if (codec_tables(ctx, net, one_slot(sl), 1, &tab, &nt)) return -1;
+    ctx->launches++;
+    VVCHK(vv_zero_hist_launch(tab, nt, st));
+    return 0;
+}
+extern "C" int vv_codec_decode(vv_ctx* ctx, void* stream, int slot, int frames, const float* latent_dev, float* audio_out_dev, int apply) {
+    hipStream_t st = (hipStream_t)stream;
+    if (slot < 0 || slot >= ctx->c.n_slots) return fail(ctx, "slot %d out of range", slot);
+    if (frames != 1) return fail(ctx, "vv_codec_decode: streaming decode takes one frame per call");
+    CodecNet& net = ctx->dec;
+    ctx->launches = 0;
+    char key[128]; snprintf(key, 128, "dec:%d:%d:%p:%p:%d", slot, frames, (const void*)latent_dev, (void*)audio_out_dev, apply);
+    return graphed(ctx, key, st, [&]() {
+        const int L = ctx->c.latent_dim;
+        const float mul = apply ? 1.0f / ctx->scaling : 1.0f, add = apply ? -ctx->bias : 0.0f;
+        ctx->launches++;
+        VVCHK(vv_affine_launch(latent_dev, net.in_buf[slot] + 6 * L, mul, add, frames * L, st));
+        return run_codec(ctx, net, one_slot(slot), frames, audio_out_dev, st);
+    });
+}
+
+extern "C" int vv_semantic_encode(vv_ctx* ctx, void* stream, int slot, int frames, const float* audio_dev, float* sem_out_dev) {
+    hipStream_t st = (hipStream_t)stream;
+    if (ctx->c.sem_dim <= 0) return fail(ctx, "no semantic tokenizer configured");
+    if (slot < 0 || slot >= ctx->c.n_slots) return fail(ctx, "slot %d out of range", slot);
+    if (frames != 1) return fail(ctx, "vv_semantic_encode: streaming encode takes one frame per call");
+    CodecNet& net = ctx->senc;
+    ctx->launches = 0;
+    char key[128]; snprintf(key, 128, "senc:%d:%d:%p:%p", slot, frames, (const void*)audio_dev, (void*)sem_out_dev);
+    return graphed(ctx, key, st, [&]() {
+        VVCHK(vv_copy_launch(net.in_buf[slot] + 6, audio_dev, (size_t)frames * ctx->hop * 4, st));
+        return run_codec(ctx, net, one_slot(slot), frames, sem_out_dev, st);
+    });
+}
+
+// One frame of n utterances through the acoustic decoder and (sem_out_dev != null) the semantic encoder -- the batched
+// `acoustic_tokenizer.decode(..., sample_indices=diffusion_indices)` + `semantic_tokenizer.encode(...)` pair of the reference's
+// loop (modeling_vibevoice_inference.py:636-672).  Row j of latent / audio / sem belongs to slot slots[j].  The stages that
+// hold the weight bytes (decoder stages [0, kd), encoder stages [ke, end) + head) run slot-batched: one pass over the weights
+// for the whole batch; the many-row, few-channel stages in between run per utterance on forked streams.
+extern "C" int vv_codec_chain_batch(vv_ctx* ctx, void* stream, int n, const int* slots, const float* latent_dev,
+                                    float* audio_out_dev, float* sem_out_dev, int apply) {
+    hipStream_t st = (hipStream_t)stream;
+    if (n < 1 || n > 8) return fail(ctx, "vv_codec_chain_batch: n = %d, must be 1..8", n);
+    uint64_t mask = 0;
+    for (int j = 0; j < n; ++j) {
+        if (slots[j] < 0 || slots[j] >= ctx->c.n_slots || slots[j] >= 64) return fail(ctx, "slot %d out of range", slots[j]);
+        if (mask & (1ull << slots[j])) return fail(ctx, "vv_codec_chain_batch: slot %d listed twice", slots[j]);
+        mask |= 1ull << slots[j];
+    }
+    const bool sem = sem_out_dev != nullptr;
+    if (sem && ctx->c.sem_dim <= 0) return fail(ctx, "no semantic tokenizer configured");
+    if (!ctx->side_ready) {
+        for (int j = 0; j < 8; ++j) {
+            HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->side[j], hipStreamNonBlocking));
+            HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_join[j], hipEventDisableTiming));
+        }
+        HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
+        ctx->side_ready = true;
+    }
+    ctx->launches = 0;
+    std::string key = "chain:";
+    for (int j = 0; j < n; ++j) key += std::to_string(slots[j]) + ",";
+    char kp[128]; snprintf(kp, 128, ":%p:%p:%p:%d", (const void*)latent_dev, (void*)audio_out_dev, (void*)sem_out_dev, apply);
+    key += kp;
+    std::vector<int> ids(slots, slots + n);
+    return graphed(ctx, key, st, [&]() {
+        CodecNet& dec = ctx->dec; CodecNet& senc = ctx->senc;
+        const int L = ctx->c.latent_dim, S = ctx->c.sem_dim, hop = ctx->hop;
+        const float mul = apply ? 1.0f / ctx->scaling : 1.0f, add = apply ? -ctx->bias : 0.0f;
+        const int ns_d = (int)dec.st[0].size(), ns_e = sem ? (int)senc.st[0].size() : 0;
+        const bool bd = n > 1 && dec.kd > 0, be = sem && n > 1 && senc.ke < ns_e;
+        const bool dec_full = bd && dec.kd == ns_d && dec.head_batch;      // the whole decoder runs slot-batched
+        const bool enc_full = be && senc.ke == 0;
+        const bool fork = n > 1 && !(dec_full && (!sem || enc_full));      // some part still runs per utterance
+        const SlotSet set = {ids.data(), n, 0};
+        if (bd) {
+            ctx->launches++;
+            VVCHK(vv_affine_slots_launch(latent_dev, dec.in_buf[0] + 6 * L, mul, add, L, ids.data(), n, dec.in_stride, st));
+            if (run_codec(ctx, dec, set, 1, audio_out_dev, st, 0, dec.kd, dec_full, dec_full)) return -1;
+        }
+        if (fork || n == 1) {
+            if (fork) HIPCHK(ctx, hipEventRecord(ctx->ev_fork, st));
+            for (int j = 0; j < n; ++j) {
+                hipStream_t ss = fork ? ctx->side[j] : st;
+                const int sl = ids[j];
+                if (fork) HIPCHK(ctx, hipStreamWaitEvent(ss, ctx->ev_fork, 0));
+                float* audio = audio_out_dev + (size_t)j * hop;
+                if (!dec_full) {
+                    if (!bd) {
+                        ctx->launches++;
+                        VVCHK(vv_affine_launch(latent_dev + (size_t)j * L, dec.in_buf[sl] + 6 * L, mul, add, L, ss));
+                    }
+                    if (run_codec(ctx, dec, one_slot(sl), 1, audio, ss, bd ? dec.kd : 0, ns_d, true, true)) return -1;
+                }
+                if (sem) {
+                    VVCHK(vv_copy_launch(senc.in_buf[sl] + 6, audio, (size_t)hop * 4, ss));
+                    if (run_codec(ctx, senc, one_slot(sl), 1, sem_out_dev + (size_t)j * S, ss, 0, be ? senc.ke : ns_e, !be, !be)) return -1;
+                }
+                if (fork) HIPCHK(ctx, hipEventRecord(ctx->ev_join[j], ss));
+            }
+            if (fork) for (int j = 0; j < n; ++j) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_join[j], 0));
+        } else if (sem) {
+            ctx->launches++;       // the batch's audio rows into the encoder's per-utterance input buffers
+            VVCHK(vv_affine_slots_launch(audio_out_dev, senc.in_buf[0] + 6, 1.0f, 0.0f, hop, ids.data(), n, senc.in_stride, st));
+        }
+        if (be && run_codec(ctx, senc, set, 1, sem_out_dev, st, senc.ke, ns_e, true, true)) return -1;
+        return 0;
+    });
+}
+
+// valid_samples: samples of real signal in wav_dev [frames * hop] (the rest must be zeros); frames = ceil(valid_samples / hop).
+extern "C" int vv_acoustic_encode_ragged(vv_ctx* ctx, void* stream, int frames, long long valid_samples, const float* wav_dev, float* mean_out_dev) {
+    VV_SHARED;
+    hipStream_t st = (hipStream_t)stream;
+    if (!ctx->c.has_acoustic_encoder) return fail(ctx, "no acoustic encoder configured");
+    if (valid_samples <= (int64_t)(frames - 1) * ctx->hop || valid_samples > (int64_t)frames * ctx->hop)
+        return fail(ctx, "vv_acoustic_encode_ragged: %lld valid samples do not end in frame %d of %d", (long long)valid_samples, frames - 1, frames);
+    CodecNet& net = ctx->aenc;
+    if (zero_codec(ctx, net, 0, st)) return -1;
+    const int L = ctx->c.latent_dim;
+    const int pass = ctx->enc_pass > 0 ? std::min(ctx->enc_pass, net.Fmax) : net.Fmax;
+    for (int f0 = 0; f0 < frames; f0 += pass) {
+        const int F = std::min(pass, frames - f0);
+        VVCHK(vv_copy_launch(net.in_buf[0] + 6, wav_dev + (size_t)f0 * ctx->hop, (size_t)F * ctx->hop * 4, st));
+        const int64_t v = valid_samples - (int64_t)f0 * ctx->hop;            // real samples inside this pass
+        const int tail = (f0 + F == frames && v < (int64_t)F * ctx->hop) ? (int)v : -1;
+        if (run_codec(ctx, net, one_slot(0), F, mean_out_dev + (size_t)f0 * L, st, 0, -1, true, true, tail)) return -1;
+    }
+    return 0;
+}
+
+extern "C" int vv_acoustic_encode(vv_ctx* ctx, void* stream, int frames, const float* wav_dev, float* mean_out_dev) {
+    return vv_acoustic_encode_ragged(ctx, stream, frames, (long long)frames * ctx->hop, wav_dev, mean_out_dev);
+}
+
+extern "C" int vv_set_enc_pass_frames(vv_ctx* ctx, int frames_per_pass) {
+    if (!ctx->c.has_acoustic_encoder) return fail(ctx, "no acoustic encoder configured");
+    if (frames_per_pass < 1 || frames_per_pass > ctx->aenc.Fmax) return fail(ctx, "frames_per_pass %d out of range [1,%d]", frames_per_pass, ctx->aenc.Fmax);
+    ctx->enc_pass = frames_per_pass;
+    return 0;
+}
+
+extern "C" int vv_codec_reset(vv_ctx* ctx, void* stream, int slot) {
+    VV_SHARED;
+    hipStream_t st = (hipStream_t)stream;
+    if (slot < 0 || slot >= ctx->c.n_slots) return fail(ctx, "slot %d out of range", slot);
+    if (zero_codec(ctx, ctx->dec, slot, st)) return -1;
+    if (ctx->c.sem_dim > 0 && zero_codec(ctx, ctx->senc, slot, st)) return -1;
+    return 0;
+}

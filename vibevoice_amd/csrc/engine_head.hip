@@ -1,0 +1,313 @@
+// engine_head.hip -- host side of libvvhip.so: the diffusion head: schedule tables, one head evaluation, the sampler.
+#include "engine_ctx.h"
+
+static int set_schedule(vv_ctx* ctx, int n_steps, const float* t, const float* coef, int width, void* stream) {
+    VV_SHARED;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_steps < 1 || n_steps > 64) return fail(ctx, "n_steps must be in [1,64]");
+    const int H = ctx->H;
+    if (!ctx->temb) {
+        ctx->temb = (float*)dalloc(ctx, (size_t)64 * H * 4);
+        ctx->coef = (float*)dalloc(ctx, 64 * 6 * 4);
+        ctx->tvals = (float*)dalloc(ctx, 64 * 4);
+    }
+    float rows6[64 * 6];
+    for (int i = 0; i < n_steps; ++i)
+        for (int j = 0; j < 6; ++j) rows6[i * 6 + j] = (j < width) ? coef[i * width + j] : 0.f;
+    // by the API used, not by the values: a one-step stochastic schedule has sigma_t = 0 on its only step (all noise scales
+    // zero) and must still be sampled through vv_diffusion_sample_sde, as the reference runs it (a noise-free first-order step)
+    ctx->sde_on = (width == 6);
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    HIPCHK(ctx, hipMemcpy(ctx->coef, rows6, (size_t)n_steps * 6 * 4, hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(ctx->tvals, t, (size_t)n_steps * 4, hipMemcpyHostToDevice));
+    // t_emb[i] = W2 . silu(W1 . sinusoid(t_i))   (TimestepEmbedder, modular_vibevoice_diffusion_head.py:66-93)
+    VVCHK(vv_tfreq_launch(ctx->tvals, ctx->tmp2, n_steps, st));
+    for (int i0 = 0; i0 < n_steps; i0 += 16) {
+        const int nn = std::min(16, n_steps - i0);
+        VVGemm g = mk_gemm(ctx->h_t0, ctx->tmp2 + (size_t)i0 * 256, ctx->tmp1 + (size_t)i0 * H, nn, H, 256, 256, H);
+        GEMM(g);
+    }
+    VVCHK(vv_silu_launch(ctx->tmp1, n_steps * H, st));
+    for (int i0 = 0; i0 < n_steps; i0 += 16) {
+        const int nn = std::min(16, n_steps - i0);
+        VVGemm g = mk_gemm(ctx->h_t2, ctx->tmp1 + (size_t)i0 * H, ctx->temb + (size_t)i0 * H, nn, H, H, H, H);
+        GEMM(g);
+    }
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    ctx->n_steps = n_steps;
+    {   // room for the batched adaLN modulations of up to 8 sampled utterances (16 rows) per step
+        const size_t need = (size_t)n_steps * 16 * ctx->MODW * 4;
+        if (need > ctx->mod_all_bytes) {
+            dfree(ctx, ctx->mod_all);
+            dfree(ctx, ctx->ada_in);
+            ctx->mod_all = (float*)dalloc(ctx, need, false);
+            ctx->ada_in = (float*)dalloc(ctx, (size_t)n_steps * 16 * ctx->H * 4, false);
+            dfree(ctx, ctx->ada_p);
+            ctx->ada_p = (ctx->c.xsplit == 1 && (ctx->H & 7) == 0) ? dalloc(ctx, (size_t)vv_packed_elems(n_steps * 16, ctx->H) * 2, false) : nullptr;
+            ctx->mod_all_bytes = (ctx->mod_all && ctx->ada_in) ? need : 0;
+            dfree(ctx, ctx->p16_shift); ctx->p16_shift = nullptr;
+            if (ctx->p16_ok) {            // the adaLN shift rows of every (solver step, layer) as packed bf16 operand tiles
+                ctx->p16_shift_tile = (size_t)vv_packed_elems(16, ctx->H) * 2;
+                ctx->p16_shift = dalloc(ctx, (size_t)n_steps * (ctx->c.head_layers + 1) * ctx->p16_shift_tile);
+            }
+        }
+    }
+    for (auto it = ctx->graphs.begin(); it != ctx->graphs.end();) {
+        // every sampler key family: a captured sample_body holds the step count, the table offsets and the buffers reallocated above
+        if (it->first.rfind("samp", 0) == 0 || it->first.rfind("sde:", 0) == 0 || it->first.rfind("rows:", 0) == 0) { hipGraphExecDestroy(it->second.exec); it = ctx->graphs.erase(it); } else ++it;
+    }
+    return 0;
+}
+// coef: n_steps rows {a, s, cs, c0, c1} (the deterministic DPM-Solver++(2M) the model classes build)
+extern "C" int vv_set_schedule(vv_ctx* ctx, int n_steps, const float* t, const float* coef, void* stream) {
+    return set_schedule(ctx, n_steps, t, coef, 5, stream);
+}
+// coef: n_steps rows {a, s, cs, c0, c1, cn} -- sde-dpmsolver++ (demo/gradio_demo.py:142-146); sampling then needs the per-step
+// variance noise: vv_diffusion_sample_sde
+extern "C" int vv_set_schedule_sde(vv_ctx* ctx, int n_steps, const float* t, const float* coef6, void* stream) {
+    return set_schedule(ctx, n_steps, t, coef6, 6, stream);
+}
+
+// one head evaluation on 2n rows; mod/xh/hact/eps are ctx scratch. temb = t-embedding row for this step.
+static int head_eval(vv_ctx* ctx, hipStream_t st, int rows, const float* zrows, const float* temb_row, float* eps_out,
+                     const float* coef = nullptr, float cfg = 0.f, const float* mod_ready = nullptr, const float* sde_noise = nullptr,
+                     const unsigned char* sh_tiles = nullptr, int gen = 0, bool have_x = false, bool seam = false,
+                     const float* cfg_rows = nullptr) {
+    // cfg_rows: [rows / 2] one guidance scale per utterance on the device, read by the final layer's epilogue in place of cfg (null: cfg)
+    // gen / have_x / seam (sampler, decode rows, bf16 mode): the step's state is generation `gen` (xh / zz / x0p or their second copies);
+    // have_x: the previous step's seam launch already produced this step's in-projection; seam: end this step with the fused launch
+    // (final layer + CFG + solver update + the NEXT step's in-projection, written to the other generation) instead of the final layer
+    const vv_config& c = ctx->c;
+    const int H = ctx->H, L = c.latent_dim, HL = c.head_layers, HF = ctx->HF, MODW = ctx->MODW;
+    const float* mod = mod_ready ? mod_ready : ctx->mod;
+    float* const xh = gen ? ctx->xh2 : ctx->xh;
+    float* const zcur = gen ? ctx->zz2 : ctx->zz;
+    float* const x0cur = gen ? ctx->x0p2 : ctx->x0p;
+    if (!mod_ready) {
+        VVGemm ga = mk_gemm(ctx->h_ada, ctx->cproj, ctx->mod, rows, MODW, H, H, MODW);
+        ga.pro = VV_PRO_ADD_SILU; ga.addvec = temb_row; ga.nt = 1;
+        GEMM(ga);
+    }
+    if (!have_x) {
+        VVGemm gi = mk_gemm(ctx->h_in, zrows, xh, rows, H, L, L, H);
+        GEMM(gi);
+        nan_probe(ctx, st, "in-proj xh", xh, (size_t)rows * H);
+    }
+    int xp = 0;                                    // extra parts xh currently consists of
+    const int xps = 16 * H;
+    for (int l = 0; l < HL; ++l) {
+        const float* base = mod + (size_t)l * 3 * H;
+        if (rows > 4 && rows <= 16 && ctx->p16_ok && (HF % 32) == 0) {
+            // batch rows: normalise + modulate + pack ONCE, then both projections stream weights against packed fragments
+            ctx->launches += 3;
+            VVCHK(vv_pack16_launch(xh, H, 2, ctx->hl[l].norm, c.head_eps, base + H, base, MODW, ctx->p16_x, rows, H, st));
+            VVCHK(p16_gemv(ctx, st, ctx->hl[l].wg, ctx->hl[l].wu, ctx->p16_x, nullptr, ctx->p16_act, nullptr, nullptr, rows, HF, H, 0, 0, VV_EPI_SWIGLU));
+            if (l + 1 == HL && sh_tiles && coef) {
+                // the last layer's down projection leaves the FINAL layer's operand (x * (1 + scale), un-normalised) packed and the rows' sums of squares
+                VVGemv16p ad = p16_args(ctx->hl[l].wd, nullptr, ctx->p16_act, xh, ctx->p16_x, rows, H, HF, H);
+                ad.gate = base + 2 * H; ad.ld_gate = MODW; ad.ssq_out = ctx->ssq_a;
+                ad.pk_nw = nullptr; ad.pk_sc = mod + (size_t)HL * 3 * H + H; ad.ld_pk = MODW;
+                VVCHK(p16_go(ctx, st, ad, VV_EPI_GATED_RESID, 4));
+            } else
+            VVCHK(p16_gemv(ctx, st, ctx->hl[l].wd, nullptr, ctx->p16_act, xh, nullptr, nullptr, base + 2 * H, rows, H, HF, H, MODW, VV_EPI_GATED_RESID));
+            continue;
+        }
+        VVGemm g1 = mk_gemm(ctx->hl[l].wg, xh, ctx->hact, rows, HF, H, H, HF);
+        g1.W2 = (const u32x4*)ctx->hl[l].wu; g1.pro = VV_PRO_RMS_MOD; g1.nw = ctx->hl[l].norm; g1.eps = c.head_eps;
+        g1.mod_shift = base; g1.mod_scale = base + H; g1.ld_mod = MODW; g1.epi = VV_EPI_SWIGLU; g1.nt = 1;
+        float* cur = ctx->xh_parts + (size_t)(l & 1) * 2 * xps;          // parts written by layer l-1
+        float* nxt = ctx->xh_parts + (size_t)((l + 1) & 1) * 2 * xps;    // parts layer l writes
+        g1.xa = cur; g1.n_xa = xp; g1.part_stride = xps;
+        GEMM(g1);
+        VVGemm g2 = mk_gemm(ctx->hl[l].wd, ctx->hact, xh, rows, H, HF, HF, H);
+        g2.epi = VV_EPI_GATED_RESID; g2.gate = base + 2 * H; g2.ld_gate = MODW; g2.nt = 1;
+        g2.ya = cur; g2.n_ya = xp; g2.part_stride = xps;
+        xp = ksplit_parts(ctx, g2, nxt, xps);
+        if (ctx->probe_on) { char nm[64]; snprintf(nm, 64, "layer %d hact (parts in %d)", l, g1.n_xa); nan_probe(ctx, st, nm, ctx->hact, (size_t)rows * HF); }
+        GEMM(g2);
+        if (ctx->probe_on) {
+            char nm[64]; snprintf(nm, 64, "layer %d xh", l); nan_probe(ctx, st, nm, xh, (size_t)rows * H);
+            for (int q = 0; q < xp; ++q) { snprintf(nm, 64, "layer %d part %d", l, q); nan_probe(ctx, st, nm, nxt + (size_t)q * xps, (size_t)rows * H); }
+        }
+    }
+    const float* fb = mod + (size_t)HL * 3 * H;
+    if (rows > 4 && rows <= 16 && ctx->p16_ok && (HF % 32) == 0 && sh_tiles && coef && HL > 0) {
+        // the sampler's final layer over the packed operand the last down projection left (4 workgroups that only stream: the 16-row
+        // vv_gemv form staged 16 x H modulated rows in each of its 4 workgroups, 21 us), CFG + DPM-Solver++ update in the epilogue
+        ctx->launches += 1;
+        VVGemv16p af = p16_args(ctx->h_out, nullptr, ctx->p16_x, nullptr, nullptr, rows, L, H, L);
+        af.ssq_in = ctx->ssq_a; af.ssq_tiles = H / 16; af.eps = c.head_eps;
+        af.Xs = (const u32x4*)(sh_tiles + (size_t)HL * ctx->p16_shift_tile);
+        af.z = zcur; af.x0p = x0cur; af.coef = coef; af.cfg = cfg; af.n_cfg = rows / 2; af.sde_noise = sde_noise;
+        af.cfg_rows = cfg_rows;
+        VVCHK(p16_go(ctx, st, af, VV_EPI_CFG_DPM, 3));
+        return 0;
+    }
+    if (seam && coef && rows == 2 && ctx->head_tail) {
+        VVTail t{};
+        t.Wout = (const u32x4*)ctx->h_out; t.Win = (const u32x4*)ctx->h_in; t.bin = nullptr;
+        t.X = xh; t.xa = ctx->xh_parts + (size_t)(HL & 1) * 2 * xps; t.n_xa = xp; t.part_stride = xps;
+        t.sc = fb + H; t.sh = fb; t.ld_mod = MODW;
+        t.Xout = gen ? ctx->xh : ctx->xh2;
+        t.z_in = zcur; t.x0p_in = x0cur; t.z_out = gen ? ctx->zz : ctx->zz2; t.x0p_out = gen ? ctx->x0p : ctx->x0p2;
+        t.coef = coef; t.cfg = cfg; t.n_cfg = rows / 2; t.sde_noise = sde_noise; t.cfg_rows = cfg_rows;
+        t.T = rows; t.H = H; t.L = L; t.eps = c.head_eps;
+        if (vv_head_tail_ok(&t)) {
+            ctx->launches++;
+            ctx->seam_launches++;
+            if (ctx->prof_on) {
+                const VVTail tc = t;
+                ctx->prof_other.push_back({3, (double)vv_packed_elems(L, H) * 2.0 + (double)vv_packed_elems(H, L) * 2.0 + (double)rows * H * 8.0,
+                                           [=](hipStream_t s2) { return vv_head_tail_launch(&tc, s2); }});
+            }
+            VVCHK(vv_head_tail_launch(&t, st));
+            return 1;          // the next step's in-projection is done (generation gen ^ 1)
+        }
+    }
+    VVGemm gf = mk_gemm(ctx->h_out, xh, eps_out, rows, L, H, H, L);
+    gf.pro = VV_PRO_RMS_MOD; gf.nw = nullptr; gf.eps = c.head_eps; gf.mod_shift = fb; gf.mod_scale = fb + H; gf.ld_mod = MODW;
+    gf.xa = ctx->xh_parts + (size_t)(HL & 1) * 2 * xps; gf.n_xa = xp; gf.part_stride = xps;
+    if (coef) {   // CFG + DPM-Solver++ update fused into the epilogue: the noisy latent is rewritten in place
+        gf.epi = VV_EPI_CFG_DPM; gf.z = zcur; gf.x0p = x0cur; gf.coef = coef; gf.cfg = cfg; gf.n_cfg = rows / 2;
+        gf.sde_noise = sde_noise; gf.cfg_rows = cfg_rows;
+    }
+    GEMM(gf);
+    return 0;
+}
+
+static int sample_body(vv_ctx* ctx, hipStream_t st, int n, const float* cond, const float* noise, float cfg, float* latent_out,
+                       const float* step_noise = nullptr, const float* cfg_rows = nullptr) {
+    const vv_config& c = ctx->c;
+    const int H = ctx->H, L = c.latent_dim;
+    const int rows = 2 * n;
+    ctx->seam_launches = 0;
+    ctx->probe_names.clear();
+    nan_probe(ctx, st, "cond (input)", cond, (size_t)rows * H);
+    nan_probe(ctx, st, "noise (input)", noise, (size_t)n * L);
+    // both CFG halves see the same noisy latent (modeling_vibevoice_inference.py:703-704)
+    VVCHK(vv_sampler_init_launch(noise, ctx->zz, ctx->x0p, n * L, st));
+    VVGemm gc = mk_gemm(ctx->h_cond, cond, ctx->cproj, rows, H, H, H, H);
+    gc.nt = 1;
+    GEMM(gc);
+    // adaLN modulations depend on (cond, t) only, not on the evolving latent: evaluate them for ALL solver steps
+    // up front, <=16 rows per GEMM, so the (3*layers+2)*H x H modulation matrix is streamed ceil(2nN/16) times per
+    // frame instead of N times (the reference recomputes it inside every head call)
+    const int MODW = ctx->MODW;
+    const bool batch_ada = ctx->mod_all_bytes != 0;
+    if (batch_ada) {
+        // SiLU(cond + t) for all (step, row) pairs in one small launch: the GEMM workgroups (one per 16 output features,
+        // > 1000 of them) then stage plain rows instead of each re-evaluating 16 x H SiLUs
+        const int total = rows * ctx->n_steps;
+        // bf16 mode, three or more 16-row passes: ONE MFMA tile GEMM over all (step, row) pairs instead -- the modulation
+        // matrix (360 MB for the 7B head) is streamed once, not once per 16 rows (8 utterances x 20 steps: 20 passes)
+        if (ctx->ada_p && total > 32 && (MODW & 3) == 0) {
+            ctx->launches += 2;
+            VVCHK(vv_ada_pack_launch(ctx->cproj, ctx->temb, ctx->ada_p, rows, ctx->n_steps, H, st));
+            VVCHK(vv_gemm3_launch(ctx->h_ada, nullptr, ctx->ada_p, ctx->mod_all, nullptr, nullptr, total, MODW, H, MODW, VV_EPI_STORE, nullptr, st));
+        } else {
+        VVCHK(vv_ada_in_launch(ctx->cproj, ctx->temb, ctx->ada_in, rows, ctx->n_steps, H, st));
+        ctx->launches++;
+        for (int t0 = 0; t0 < total; t0 += 16) {
+            const int T = std::min(16, total - t0);
+            VVGemm ga = mk_gemm(ctx->h_ada, ctx->ada_in + (size_t)t0 * H, ctx->mod_all + (size_t)t0 * MODW, T, MODW, H, H, MODW);
+            GEMM(ga);
+        }
+        }
+    }
+    nan_probe(ctx, st, "cproj", ctx->cproj, (size_t)rows * H);
+    if (batch_ada) nan_probe(ctx, st, "mod_all", ctx->mod_all, (size_t)rows * ctx->n_steps * MODW);
+    const bool sh_ok = batch_ada && rows > 4 && rows <= 16 && ctx->p16_shift;
+    if (sh_ok) {
+        // the shift rows of every (solver step, layer) -- and the final layer's -- as packed bf16 tiles, one launch per frame:
+        // tile (i, l) = rows [i * rows, (i + 1) * rows) of mod_all, columns [l * 3H, l * 3H + H).  Only the final layer's tile (l == HL) is read
+        ctx->launches++;
+        VVCHK(vv_pack16_tiles_launch(ctx->mod_all, MODW, (int64_t)rows * MODW, ctx->c.head_layers + 1, (int64_t)3 * H, ctx->p16_shift,
+                                     (int64_t)ctx->p16_shift_tile, rows, H, ctx->n_steps * (ctx->c.head_layers + 1), st));
+    }
+    int gen = 0; bool have_x = false;
+    for (int i = 0; i < ctx->n_steps; ++i) {
+        const float* mod_i = batch_ada ? ctx->mod_all + (size_t)i * rows * MODW : nullptr;
+        const float* sn = step_noise ? step_noise + (size_t)i * n * L : nullptr;
+        const unsigned char* sht = sh_ok ? (const unsigned char*)ctx->p16_shift + (size_t)i * (ctx->c.head_layers + 1) * ctx->p16_shift_tile : nullptr;
+        // decode rows, bf16 mode: every step but the last ends with the fused seam (final layer + CFG + solver update + the next step's
+        // in-projection, headtail.hip), which leaves the next step's state in the other generation of (xh, zz, x0p)
+        const bool seam = (i + 1 < ctx->n_steps) && rows == 2 && ctx->head_tail;
+        const int hr = head_eval(ctx, st, rows, gen ? ctx->zz2 : ctx->zz, ctx->temb + (size_t)i * H, ctx->eps, ctx->coef + i * 6, cfg, mod_i, sn, sht,
+                                 gen, have_x, seam, cfg_rows);
+        if (hr < 0) return -1;
+        if (ctx->probe_on) {
+            char nm[64];
+            snprintf(nm, 64, "step %d z%s", i, hr == 1 ? " (seam, next gen)" : ""); nan_probe(ctx, st, nm, (gen ^ (hr == 1)) ? ctx->zz2 : ctx->zz, (size_t)rows * L);
+            snprintf(nm, 64, "step %d x0p", i); nan_probe(ctx, st, nm, (gen ^ (hr == 1)) ? ctx->x0p2 : ctx->x0p, (size_t)n * L);
+            if (hr == 1) { snprintf(nm, 64, "step %d next xh", i); nan_probe(ctx, st, nm, (gen ^ 1) ? ctx->xh2 : ctx->xh, (size_t)rows * H); }
+        }
+        have_x = (hr == 1);
+        if (have_x) gen ^= 1;
+    }
+    VVCHK(vv_copy_launch(latent_out, gen ? ctx->zz2 : ctx->zz, (size_t)n * L * 4, st));
+    return 0;
+}
+
+extern "C" int vv_diffusion_sample(vv_ctx* ctx, void* stream, int n, const float* cond_dev, const float* noise_dev, float cfg_scale, float* latent_out_dev) {
+    hipStream_t st = (hipStream_t)stream;
+    if (ctx->n_steps < 1) return fail(ctx, "vv_set_schedule has not been called");
+    if (n < 1 || n > 8) return fail(ctx, "vv_diffusion_sample: n must be in [1,8]");
+    if (ctx->sde_on) return fail(ctx, "the schedule is stochastic (vv_set_schedule_sde): sample with vv_diffusion_sample_sde and its per-step noise");
+    ctx->launches = 0;
+    char key[128]; snprintf(key, 128, "samp:%d:%p:%p:%p:%a", n, (const void*)cond_dev, (const void*)noise_dev, (void*)latent_out_dev, cfg_scale);
+    const int rc = graphed(ctx, key, st, [&]() { return sample_body(ctx, st, n, cond_dev, noise_dev, cfg_scale, latent_out_dev); });
+    nan_probe_report(ctx, st, key);
+    return rc;
+}
+
+// The stochastic solver: step_noise_dev = [n_steps][n][latent_dim] fp32, the variance noise scheduler.step() draws per solver step
+// (dpm_solver.py:994-997; the reference draws [2n][latent] and only the first n rows reach the next step, :703-704).
+extern "C" int vv_diffusion_sample_sde(vv_ctx* ctx, void* stream, int n, const float* cond_dev, const float* noise_dev,
+                                       const float* step_noise_dev, float cfg_scale, float* latent_out_dev) {
+    hipStream_t st = (hipStream_t)stream;
+    if (ctx->n_steps < 1) return fail(ctx, "vv_set_schedule_sde has not been called");
+    if (n < 1 || n > 8) return fail(ctx, "vv_diffusion_sample_sde: n must be in [1,8]");
+    if (!ctx->sde_on) return fail(ctx, "the schedule is deterministic (vv_set_schedule): sample with vv_diffusion_sample");
+    if (!step_noise_dev) return fail(ctx, "vv_diffusion_sample_sde: step_noise is null");
+    ctx->launches = 0;
+    char key[160]; snprintf(key, 160, "sde:%d:%p:%p:%p:%p:%a", n, (const void*)cond_dev, (const void*)noise_dev, (const void*)step_noise_dev,
+                            (void*)latent_out_dev, cfg_scale);
+    return graphed(ctx, key, st, [&]() { return sample_body(ctx, st, n, cond_dev, noise_dev, cfg_scale, latent_out_dev, step_noise_dev); });
+}
+
+// Either sampler with one guidance scale per utterance, cfg_rows_dev [n] fp32.  The kernels read the values at run time: the graph key
+// holds the POINTER, so rewriting the buffer between calls replays the same captured graph.
+extern "C" int vv_diffusion_sample_rows(vv_ctx* ctx, void* stream, int n, const float* cond_dev, const float* noise_dev,
+                                        const float* step_noise_dev, const float* cfg_rows_dev, float* latent_out_dev) {
+    hipStream_t st = (hipStream_t)stream;
+    if (ctx->n_steps < 1) return fail(ctx, "vv_set_schedule / vv_set_schedule_sde has not been called");
+    if (n < 1 || n > 8) return fail(ctx, "vv_diffusion_sample_rows: n must be in [1,8]");
+    if (!cfg_rows_dev) return fail(ctx, "vv_diffusion_sample_rows: cfg_rows is null");
+    if (ctx->sde_on && !step_noise_dev) return fail(ctx, "the schedule is stochastic (vv_set_schedule_sde): vv_diffusion_sample_rows needs its per-step noise");
+    if (!ctx->sde_on && step_noise_dev) return fail(ctx, "the schedule is deterministic (vv_set_schedule): vv_diffusion_sample_rows takes no step noise");
+    ctx->launches = 0;
+    char key[192]; snprintf(key, 192, "rows:%d:%p:%p:%p:%p:%p", n, (const void*)cond_dev, (const void*)noise_dev, (const void*)step_noise_dev,
+                            (const void*)cfg_rows_dev, (void*)latent_out_dev);
+    const int rc = graphed(ctx, key, st, [&]() { return sample_body(ctx, st, n, cond_dev, noise_dev, 0.f, latent_out_dev, step_noise_dev, cfg_rows_dev); });
+    nan_probe_report(ctx, st, key);
+    return rc;
+}
+
+extern "C" int vv_head_forward(vv_ctx* ctx, void* stream, int n, const float* noisy_dev, const float* t_host, const float* cond_dev, float* out_dev) {
+    VV_SHARED;
+    hipStream_t st = (hipStream_t)stream;
+    if (n < 1 || n > 16) return fail(ctx, "vv_head_forward: n must be in [1,16]");
+    const int H = ctx->H;
+    for (int i = 1; i < n; ++i) if (t_host[i] != t_host[0]) return fail(ctx, "vv_head_forward: all rows must share one timestep");
+    float* tdev = ctx->tmp2 + 63 * 256;     // scratch
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    HIPCHK(ctx, hipMemcpy(tdev + 128, t_host, 4, hipMemcpyHostToDevice));
+    VVCHK(vv_tfreq_launch(tdev + 128, ctx->tmp2, 1, st));
+    VVGemm g = mk_gemm(ctx->h_t0, ctx->tmp2, ctx->tmp1, 1, H, 256, 256, H); GEMM(g);
+    VVCHK(vv_silu_launch(ctx->tmp1, H, st));
+    VVGemm g2 = mk_gemm(ctx->h_t2, ctx->tmp1, ctx->tmp1 + H, 1, H, H, H, H); GEMM(g2);
+    VVGemm gc = mk_gemm(ctx->h_cond, cond_dev, ctx->cproj, n, H, H, H, H); GEMM(gc);
+    if (head_eval(ctx, st, n, noisy_dev, ctx->tmp1 + H, out_dev)) return -1;
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return 0;
+}

@@ -28,6 +28,7 @@
 //    in a fixed order -> deterministic, no atomics, enough waves for skinny N.
 #include <cstdlib>
 #include "vv_common.h"
+#include "vv_launch.h"
 
 #ifdef VV_GEMM_TIMING
 #define VV_STAMP(i) do { if (a.dbg && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) a.dbg[i] = __builtin_amdgcn_s_memtime(); } while (0)
@@ -479,12 +480,7 @@ static void launch_t(const VVGemm& a, dim3 grid, size_t smem, hipStream_t s) {
 
 static int pow2_floor(int v) { int p = 1; while (p * 2 <= v) p *= 2; return p; }
 
-extern "C" int vv_gemv_ok(const VVGemm* a);
-extern "C" int vv_gemv_launch(VVGemm a, int xs, hipStream_t s, int* form);
-
 // Chooses the kernel and its decomposition.  `xs` in {1,2,3}.
-extern "C" int vv_tile_ok(const VVGemm* a, int xs);
-extern "C" int vv_tile_launch(VVGemm a, int xs, hipStream_t s);
 extern "C" int vv_gemm_launch(VVGemm a, int xs, hipStream_t s) {
     if (a.sl_n > 0) {                  // slot-batched rows: the MFMA tile form for tall row sets, else the 16-row GEMV form
         if (vv_tile_ok(&a, xs)) {

@@ -17,6 +17,7 @@
 //   * sum(x^2) by DPP row reductions + readlane (no LDS permutes);
 //   * split-K partials go to a dedicated LDS region: a single barrier.
 #include "vv_common.h"
+#include "vv_launch.h"
 
 #ifdef VV_GEMM_TIMING
 #define VV_STAMP(i) do { if (a.dbg && blockIdx.x == 0 && threadIdx.x == 0) a.dbg[i] = __builtin_amdgcn_s_memtime(); } while (0)

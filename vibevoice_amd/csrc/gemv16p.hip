@@ -23,6 +23,7 @@
 // per frame for every solver step and layer: they depend on the condition and t only).
 #include <cstdlib>
 #include "vv_common.h"
+#include "vv_launch.h"
 
 namespace {
 

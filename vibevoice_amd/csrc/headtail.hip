@@ -16,6 +16,7 @@
 // reads buffer i & 1 and writes the other one), so no workgroup can observe another's update.  Same arithmetic as the two launches it
 // replaces (bf16 at the MFMA inputs, fp32 accumulation, the same K split over 8 waves and the same fixed reduction order).
 #include "vv_common.h"
+#include "vv_launch.h"
 
 namespace {
 

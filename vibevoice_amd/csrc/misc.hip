@@ -3,6 +3,7 @@
 // shifts, CFG + DPM-Solver++ update, affine/copy helpers.  All are one element (or
 // one float4) per lane, coalesced along the channel axis of time-major buffers.
 #include "vv_common.h"
+#include "vv_launch.h"
 
 namespace {
 
@@ -609,23 +610,16 @@ int vv_normdw_launch(float* x, float* nb, const float* nw, const float* w, const
     return okk();
 }
 int vv_normdw_sliced_ok(int T, int C) { return T >= 1 && T <= 8 && (C == 1024 || C == 2048); }
-int vv_normdw_sliced_launch(const float* xin, float* xout, float* nb, const float* nw, const float* w, const float* b,
-                            const float* gamma, int T, int C, float eps, hipStream_t s) {
-    if (!vv_normdw_sliced_ok(T, C) || xin == xout) return -1;
-    VVSlotIds none; none.n = 0;
-    if (C == 1024) hipLaunchKernelGGL((vv_normdw_sliced_kernel<1>), dim3(C / 256), dim3(256), 0, s, xin, xout, nb, nw, w, b, gamma, T, C, eps, none, (int64_t)0, (int64_t)0);
-    else hipLaunchKernelGGL((vv_normdw_sliced_kernel<2>), dim3(C / 256), dim3(256), 0, s, xin, xout, nb, nw, w, b, gamma, T, C, eps, none, (int64_t)0, (int64_t)0);
-    return okk();
-}
-// the same kernel over n utterance slots: xin / xout / nb are slot 0's buffers, slot k's are sx / snb floats further
+// ids == null: one slot, the buffers given; ids != null: the same kernel over n utterance slots, xin / xout / nb are slot 0's buffers,
+// slot k's are sx / snb floats further
 int vv_normdw_sliced_slots_launch(const float* xin, float* xout, float* nb, const float* nw, const float* w, const float* b,
                                   const float* gamma, int T, int C, float eps, const int* ids, int n, int64_t sx, int64_t snb,
                                   hipStream_t s) {
-    if (!vv_normdw_sliced_ok(T, C) || xin == xout || n < 1 || n > 8) return -1;
-    VVSlotIds sl; sl.n = n;
-    for (int i = 0; i < 8; ++i) sl.id[i] = i < n ? ids[i] : 0;
-    if (C == 1024) hipLaunchKernelGGL((vv_normdw_sliced_kernel<1>), dim3(C / 256, n), dim3(256), 0, s, xin, xout, nb, nw, w, b, gamma, T, C, eps, sl, sx, snb);
-    else hipLaunchKernelGGL((vv_normdw_sliced_kernel<2>), dim3(C / 256, n), dim3(256), 0, s, xin, xout, nb, nw, w, b, gamma, T, C, eps, sl, sx, snb);
+    if (!vv_normdw_sliced_ok(T, C) || xin == xout || n < 0 || n > 8) return -1;
+    const VVSlotIds sl = vv_slot_ids(ids, n);
+    const dim3 grid(C / 256, sl.n > 0 ? sl.n : 1);
+    if (C == 1024) hipLaunchKernelGGL((vv_normdw_sliced_kernel<1>), grid, dim3(256), 0, s, xin, xout, nb, nw, w, b, gamma, T, C, eps, sl, sx, snb);
+    else hipLaunchKernelGGL((vv_normdw_sliced_kernel<2>), grid, dim3(256), 0, s, xin, xout, nb, nw, w, b, gamma, T, C, eps, sl, sx, snb);
     return okk();
 }
 // y[id[j] * stride + c] = x[j * L + c] * mul + add: the batch's latents into the per-utterance decoder input buffers
@@ -636,19 +630,11 @@ static __global__ void vv_affine_slots_kernel(const float* __restrict__ x, float
 }
 int vv_affine_slots_launch(const float* x, float* y, float mul, float add, int L, const int* ids, int n, int64_t stride, hipStream_t s) {
     if (n < 1 || n > 8) return -1;
-    VVSlotIds sl; sl.n = n;
-    for (int i = 0; i < 8; ++i) sl.id[i] = i < n ? ids[i] : 0;
+    const VVSlotIds sl = vv_slot_ids(ids, n);
     hipLaunchKernelGGL(vv_affine_slots_kernel, dim3((L + 255) / 256, n), dim3(256), 0, s, x, y, mul, add, L, sl, stride);
     return okk();
 }
 int vv_normdw_rows_ok(int T, int C) { return T >= 1 && (C == 256 || C == 512 || C == 1024); }
-int vv_normdw_rows_slots_launch(const float* xin, float* xout, float* nb, const float* nw, const float* w, const float* b,
-                                const float* gamma, int T, int C, float eps, const int* ids, int n, int64_t sx, int64_t snb,
-                                hipStream_t s);
-int vv_normdw_rows_launch(const float* xin, float* xout, float* nb, const float* nw, const float* w, const float* b,
-                          const float* gamma, int T, int C, float eps, hipStream_t s) {
-    return vv_normdw_rows_slots_launch(xin, xout, nb, nw, w, b, gamma, T, C, eps, nullptr, 0, 0, 0, s);
-}
 // ids != null: the same kernel over n utterance slots (xin / xout / nb are slot 0's buffers, slot k's sx / snb floats further)
 int vv_normdw_rows_slots_launch(const float* xin, float* xout, float* nb, const float* nw, const float* w, const float* b,
                                 const float* gamma, int T, int C, float eps, const int* ids, int n, int64_t sx, int64_t snb,
@@ -656,8 +642,7 @@ int vv_normdw_rows_slots_launch(const float* xin, float* xout, float* nb, const 
     if (!vv_normdw_rows_ok(T, C) || xin == xout || n < 0 || n > 8) return -1;
     constexpr int RB = 8;
     const size_t smem = (size_t)(2 * RB + 6) * C * 4;
-    VVSlotIds sl; sl.n = ids ? n : 0;
-    for (int i = 0; i < 8; ++i) sl.id[i] = (ids && i < n) ? ids[i] : 0;
+    const VVSlotIds sl = vv_slot_ids(ids, n);
     const dim3 grid((T + RB - 1) / RB, sl.n > 0 ? sl.n : 1);
     static bool attr = false;
     if (!attr) {
@@ -672,24 +657,16 @@ int vv_normdw_rows_slots_launch(const float* xin, float* xout, float* nb, const 
 int vv_stem_conv_slots_launch(const float* in, const void* wp, const float* bias, float* out, int T, int N, const int* ids, int n,
                               int64_t s_in, int64_t s_out, hipStream_t s) {
     if (n < 0 || n > 8) return -1;
-    VVSlotIds sl; sl.n = ids ? n : 0;
-    for (int i = 0; i < 8; ++i) sl.id[i] = (ids && i < n) ? ids[i] : 0;
+    const VVSlotIds sl = vv_slot_ids(ids, n);
     hipLaunchKernelGGL(vv_stem_conv_kernel, dim3((T * N + 255) / 256, sl.n > 0 ? sl.n : 1), dim3(256), 0, s, in, (const __bf16*)wp, bias, out, T, N, sl, s_in, s_out);
     return okk();
-}
-int vv_stem_conv_launch(const float* in, const void* wp, const float* bias, float* out, int T, int N, hipStream_t s) {
-    return vv_stem_conv_slots_launch(in, wp, bias, out, T, N, nullptr, 0, 0, 0, s);
 }
 int vv_head_conv1_slots_launch(const float* x, const void* wp, const float* bias, float* out, int T, int Cin, const int* ids, int n,
                                int64_t s_in, int64_t s_out, hipStream_t s) {
     if ((Cin & 3) || (((uintptr_t)x) & 15) || 7 * Cin * 4 > 48 * 1024 || n < 0 || n > 8 || (s_in & 3)) return -1;
-    VVSlotIds sl; sl.n = ids ? n : 0;
-    for (int i = 0; i < 8; ++i) sl.id[i] = (ids && i < n) ? ids[i] : 0;
+    const VVSlotIds sl = vv_slot_ids(ids, n);
     hipLaunchKernelGGL(vv_head_conv1_kernel, dim3((T + 63) / 64, sl.n > 0 ? sl.n : 1), dim3(256), (size_t)7 * Cin * 4, s, x, (const __bf16*)wp, bias, out, T, Cin, sl, s_in, s_out);
     return okk();
-}
-int vv_head_conv1_launch(const float* x, const void* wp, const float* bias, float* out, int T, int Cin, hipStream_t s) {
-    return vv_head_conv1_slots_launch(x, wp, bias, out, T, Cin, nullptr, 0, 0, 0, s);
 }
 int vv_shift_rows_launch(const void* tab, int n_entries, int maxC, hipStream_t s) {
     int cy = (maxC + 255) / 256; if (cy < 1) cy = 1; if (cy > 16) cy = 16;

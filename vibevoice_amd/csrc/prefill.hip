@@ -26,6 +26,7 @@
 #include <cstring>
 #include <type_traits>
 #include "vv_common.h"
+#include "vv_launch.h"
 
 namespace {
 

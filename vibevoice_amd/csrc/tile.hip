@@ -13,6 +13,7 @@
 //   * RMSNorm: sum(x^2) per row is gathered while staging and applied to the accumulators in the epilogue.
 // Prologues NONE / RMS; epilogues STORE / BIAS / BIAS_GELU / SWIGLU / RESID (what the LM and the tokenizer stages issue).
 #include "vv_common.h"
+#include "vv_launch.h"
 
 namespace {
 

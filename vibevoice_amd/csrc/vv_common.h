@@ -149,6 +149,12 @@ struct VVTail {
 
 // up to 8 utterance slots of one launch (per-utterance kernels take the slot from blockIdx.y / .z)
 struct VVSlotIds { int n; int id[8]; };
+// ids == null: no slot set (n = 0: the kernel works on the base pointers alone); unused entries are 0
+static inline VVSlotIds vv_slot_ids(const int* ids, int n) {
+    VVSlotIds sl; sl.n = ids ? n : 0;
+    for (int i = 0; i < 8; ++i) sl.id[i] = (ids && i < n) ? ids[i] : 0;
+    return sl;
+}
 __device__ __forceinline__ int vv_slot_id(const int (&id)[8], int j) {     // select chain: no dynamic indexing of a by-value kernel argument
     int r = id[0];
 #pragma unroll

@@ -1,0 +1,88 @@
+// vv_launch.h -- prototypes of the extern "C" launchers and _ok predicates one .hip unit defines and another calls.
+// Every unit that defines one includes this header: a definition that drifts from its prototype is a compile error
+// ("conflicting types"), not undefined behaviour at the call.  Internal: hidden visibility, not part of include/vvhip.h.
+#pragma once
+#include "vv_common.h"
+extern "C" {
+int vv_gemm_launch(VVGemm a, int xs, hipStream_t s);
+int vv_pack_launch(const void* src, int src_is_bf16, void* dst, int N, int K, int kind, int Cin, int Cout, int ksz, int stride, hipStream_t s);
+int vv_rope_append_launch(int D, const float* qkv, const VVRow* rows, const float* inv_freq, float* q_out, void* kc, void* vc, int R, int Hq, int Hkv,
+                          int64_t cache_stride, int64_t head_stride, hipStream_t s);
+int vv_rope_table_launch(const float* inv_freq, void* tab, int n_pos, int half, hipStream_t s);
+int vv_attn_fused_launch(int D, int xs, const float* qkv, const VVRow* rows, const void* rope_tab, void* kc, void* vc, int R, int Hq, int Hkv,
+                         int64_t cache_stride, int64_t head_stride, int S, float* pm, float* pl, float* po, float* out, void* out_packed,
+                         hipStream_t s);
+int vv_attn_launch(int D, int xs, const float* q, const VVRow* rows, const void* kc, const void* vc, int R, int Hq, int Hkv, int64_t cache_stride,
+                   int64_t head_stride, int S, float* pm, float* pl, float* po, float* out, hipStream_t s);
+int vv_embed_launch(const void* table, const int* ids, float* out, int n, int H, hipStream_t s);
+int vv_logits_full_launch(const void* table, const float* hidden, float* out, int n, int V, int H, hipStream_t s);
+int vv_warp_valid_launch(const float* logits, const unsigned char* seen, float* out, int* survivors, int n, int V, const int* ids, int n_valid,
+                         float pen, float temp, int do_sample, int top_k, float top_p, float min_p, hipStream_t s);
+int vv_noise_rows_launch(float* out, int n, const uint32_t* keys, uint32_t stream0, int n_streams, int n_t, int width, hipStream_t s);
+int vv_rmsnorm_rows_launch(const float* x, int ldx, float* y, int ldy, const float* w, int T, int C, float eps, hipStream_t s);
+int vv_dwconv_res_launch(const float* nb, const float* x, float* xo, const float* w, const float* b, const float* gamma, int T, int C, hipStream_t s);
+int vv_normdw_sliced_ok(int T, int C);
+int vv_normdw_sliced_slots_launch(const float* xin, float* xout, float* nb, const float* nw, const float* w, const float* b, const float* gamma,
+                                  int T, int C, float eps, const int* ids, int n, int64_t sx, int64_t snb, hipStream_t s);
+int vv_normdw_rows_slots_launch(const float* xin, float* xout, float* nb, const float* nw, const float* w, const float* b, const float* gamma, int T,
+                                int C, float eps, const int* ids, int n, int64_t sx, int64_t snb, hipStream_t s);
+int vv_stem_conv_slots_launch(const float* in, const void* wp, const float* bias, float* out, int T, int N, const int* ids, int n, int64_t s_in,
+                              int64_t s_out, hipStream_t s);
+int vv_head_conv1_slots_launch(const float* x, const void* wp, const float* bias, float* out, int T, int Cin, const int* ids, int n, int64_t s_in,
+                               int64_t s_out, hipStream_t s);
+int vv_block1d_slots_launch(int C, int xs, const float* xin, float* xout, float* nst, const float* norm_w, const float* ffn_norm_w,
+                            const float* gamma, const float* ffn_gamma, const float* dw_w, const float* dw_b, const float* b1, const float* b2,
+                            const void* w1, const void* w2, int T, float eps, const int* ids, int n, int64_t sx, int64_t snst, hipStream_t s);
+int vv_affine_slots_launch(const float* x, float* y, float mul, float add, int L, const int* ids, int n, int64_t stride, hipStream_t s);
+int vv_normdw_launch(float* x, float* nb, const float* nw, const float* w, const float* b, const float* gamma, int T, int C, float eps,
+                     hipStream_t s);
+int vv_normdw_rows_ok(int T, int C);
+int vv_shift_rows_launch(const void* tab, int n_entries, int maxC, hipStream_t s);
+int vv_zero_hist_launch(const void* tab, int n_entries, hipStream_t s);
+int vv_affine_launch(const float* x, float* y, float mul, float add, int n, hipStream_t s);
+int vv_copy_launch(void* dst, const void* src, size_t bytes, hipStream_t s);
+int vv_zero_launch(void* dst, size_t bytes, hipStream_t s);
+int vv_sampler_init_launch(const float* noise, float* z, float* x0p, int nL, hipStream_t s);
+int vv_tfreq_launch(const float* t, float* out, int n, hipStream_t s);
+int vv_silu_launch(float* x, int n, hipStream_t s);
+int vv_ada_in_launch(const float* cproj, const float* temb, float* out, int rows, int n_steps, int H, hipStream_t s);
+int vv_add_rows_launch(const float* x, const float* v, float* y, int n, int C, hipStream_t s);
+int vv_relu_launch(float* x, int n, hipStream_t s);
+int vv_kv_import_launch(const void* k, const void* v, int src_bf16, void* kc, void* vc, int L, int Hkv, int D, int64_t head_stride, int pos0,
+                        hipStream_t s);
+int vv_kv_move_launch(void* kc, void* vc, int layers, int Hkv, int D, int64_t layer_stride, int64_t head_stride, int src, int dst, hipStream_t s);
+int vv_kv_zero_v_tail_launch(void* vc, const VVRow* rows, int R, int layers, int Hkv, int D, int64_t cache_stride, int64_t layer_stride,
+                             int64_t head_stride, int max_ctx, hipStream_t s);
+int vv_kv_span_copy_launch(void* kc, void* vc, void* ks, void* vs, int to_cache, int layers, int Hkv, int D, int64_t layer_stride,
+                           int64_t head_stride, int n_pos, hipStream_t s);
+int vv_kv_export_launch(const void* kc, const void* vc, void* k, void* v, int dst_bf16, int L, int Hkv, int D, int64_t head_stride, int pos0,
+                        hipStream_t s);
+int vv_pcm16_launch(const float* x, short* out, int n, int samples, hipStream_t s);
+int vv_cvt_launch(const void* src, void* dst, int64_t n, int to_bf16, hipStream_t s);
+int vv_dw_transpose_launch(const float* src, float* dst, int C, hipStream_t s);
+int vv_pack_rows_launch(const float* x, int ldx, const float* nw, float eps, void* xp, int T, int K, hipStream_t s);
+int vv_unpack_rows_launch(const void* xp, float* x, int T, int K, hipStream_t s);
+int vv_pack16_launch(const float* x, int ldx, int mode, const float* nw, float eps, const float* sc, const float* sh, int ld_mod, void* xp, int T,
+                     int K, hipStream_t s);
+int vv_gemv16p_launch(const void* W, const void* W2, const void* Xp, float* Y, void* Yp, const float* bias, const float* gate, int T, int N, int K,
+                      int ldy, int ld_gate, int epi, hipStream_t s);
+int vv_gemv16p_launch2(const VVGemv16p* a, int epi, int flags, hipStream_t s);
+int vv_head_tail_ok(const VVTail* a);
+int vv_head_tail_init();
+int vv_head_tail_launch(const VVTail* a, hipStream_t s);
+int vv_pack16_tiles_launch(const float* x, int ldx, int64_t stride_outer, int n_inner, int64_t stride_inner, void* xp, int64_t tile_bytes, int T,
+                           int K, int n_tiles, hipStream_t s);
+int vv_ada_pack_launch(const float* cproj, const float* temb, void* xp, int rows, int n_steps, int H, hipStream_t s);
+int vv_gemm3_launch(const void* W, const void* W2, const void* Xp, float* Y, void* Yp, const float* bias, int T, int N, int K, int ldy, int epi,
+                    const VVGemmWs* ws, hipStream_t s);
+int vv_gemm_qkv_rope_launch(const void* W, const void* Xp, const float* bias, int T, int K, int D, int Hq, int Hkv, const VVRow* rows_dev,
+                            const void* rope_tab, float* q_out, void* kc, void* vc, int64_t cache_stride, int64_t head_stride, const VVGemmWs* ws,
+                            hipStream_t s);
+int vv_attn_prefill4_launch(int D, const float* q, const VVRow* rows, const void* kc, const void* vc, int R, int Hq, int Hkv, int64_t cache_stride,
+                            int64_t head_stride, float* out, void* out_packed, hipStream_t s);
+int vv_block1d_supported(int C);
+int vv_gemv_ok(const VVGemm* a);
+int vv_gemv_launch(VVGemm a, int xs, hipStream_t s, int* form);      // form: the compiled form its launcher picked (tests)
+int vv_tile_ok(const VVGemm* a, int xs);
+int vv_tile_launch(VVGemm a, int xs, hipStream_t s);
+}

@@ -15,6 +15,7 @@
 //   final    Z and A[v] (top-p only): fp32 partials per thread, combined in fp64 in a fixed order -> bit-identical run to run
 // so a row costs 0 (no sampling), 1 (top-k and/or min-p), 2 (top-p) or 4 (top-k + top-p) passes of 4 V bytes.
 #include "vv_common.h"
+#include "vv_launch.h"
 
 namespace {
 
