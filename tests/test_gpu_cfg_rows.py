@@ -6,8 +6,7 @@ seam takes), 5 solver steps.  In xsplit 1 that reaches the seam (n = 1: headtail
 4-row decode GEMV (n = 2) and the packed 16-row final layer (n = 3: 6 rows, n = 8: all 16).  In xsplit 3 the final layer of
 n = 1 and n = 2 (2 and 4 rows) is still the decode GEMV, in its three-way-split instantiations, and only n = 3 and n = 8 (6 and 16
 rows) reach the general kernel's epilogue (gemm.hip).  The wide 16-row GEMV form is reached one launch at a time
-(Engine.gemv_case).  The standalone vv_cfg_dpm_kernel (misc.hip) takes the operand too but has no caller in the engine, so nothing
-here runs it.
+(Engine.gemv_case).
 
 Bit-for-bit claims rest on two facts: a per-row scale runs the same kernels with the same arithmetic as the scalar (one operand of
 one multiply comes from memory instead of an argument register), and the rows of a sampler pass do not interact.  Every path is

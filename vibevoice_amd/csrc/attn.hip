@@ -18,6 +18,7 @@
 // workspace and a second tiny kernel merges the splits.
 #include <cstdlib>
 #include "vv_common.h"
+#include "vv_device.h"
 #include "vv_launch.h"
 
 namespace {
@@ -30,6 +31,7 @@ __device__ __forceinline__ int attn_chunk(int len, int S, int gran = 128) {
     return chunk < 512 ? 512 : chunk;
 }
 
+// eight values per term, straight into MFMA operand vectors (vv_split_bf16 packs four per term into 8-byte LDS words)
 template <int XS>
 __device__ __forceinline__ void split8(const float (&v)[8], bf16x8 (&out)[XS]) {
 #pragma unroll
@@ -336,7 +338,7 @@ __global__ __launch_bounds__(WAVES * 64) void vv_attn_fused_kernel(
         {
             const int pt = pos >> 4, pl = pos & 15;
             const int64_t tile = (int64_t)pt * (D / 32) + (d >> 5);
-            kbase[(tile * 64 + pl + 16 * ((d & 31) >> 3)) * 8 + (d & 7)] = kb;
+            kbase[vv_packed_index(tile, pl, d)] = kb;
         }
         const __bf16 vb = (__bf16)qrow[(int64_t)(Hq + Hkv + kvh) * D + d];
         vnew[d] = vb;
@@ -485,12 +487,11 @@ __global__ __launch_bounds__(WAVES * 64) void vv_attn_fused_kernel(
             if (used == 1) {                      // short sequence: this workgroup saw everything
                 *reinterpret_cast<float4*>(orow + dt * 16) = float4{O[0] * inv, O[1] * inv, O[2] * inv, O[3] * inv};
                 if (out_packed) {
-                    typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
                     bf16x4 pk;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) pk[e] = (__bf16)(O[e] * inv);
                     const int k = (kvh * G + g) * D + dt * 16 + qg * 4;
-                    *reinterpret_cast<uint2*>(out_packed + ((((int64_t)(k >> 5) * 64 + (r & 15) + 16 * ((k & 31) >> 3)) * 8 + (k & 7)) * 2)) = __builtin_bit_cast(uint2, pk);
+                    *reinterpret_cast<uint2*>(out_packed + vv_packed_index((int64_t)(k >> 5), r & 15, k) * 2) = __builtin_bit_cast(uint2, pk);
                 }
             } else                                  // several splits: vv_attn_merge2_kernel (a separate wide launch that follows in
                                                   // the stream: no fence, no ticket) combines the partials in a fixed order
@@ -587,7 +588,7 @@ __global__ __launch_bounds__(512) void vv_attn_merge2_kernel(const float* __rest
     out[((int64_t)r * Hq + h) * D + d] = A / L;
     if (out_packed) {                                // batch decode: the o-projection's packed bf16 operand (see vv_attn_fused_kernel)
         const int k = h * D + d;
-        *reinterpret_cast<__bf16*>(out_packed + ((((int64_t)(k >> 5) * 64 + (r & 15) + 16 * ((k & 31) >> 3)) * 8 + (k & 7)) * 2)) = (__bf16)(A / L);
+        *reinterpret_cast<__bf16*>(out_packed + vv_packed_index((int64_t)(k >> 5), r & 15, k) * 2) = (__bf16)(A / L);
     }
 }
 

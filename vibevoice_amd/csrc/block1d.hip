@@ -13,16 +13,10 @@
 // the input without racing the neighbours' writes.  Streaming state = the last 6
 // *normed* rows, written to `nst + 6*C` and moved to the front by the net's shift kernel.
 #include "vv_common.h"
+#include "vv_device.h"
 #include "vv_launch.h"
 
 namespace {
-
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ float gelu_erf(float u) { return 0.5f * u * (1.0f + erff(u * 0.70710678118654752440f)); }
 
 struct VVBlock {
     const float* xin;      // live rows [T][C] of the input buffer
@@ -37,6 +31,7 @@ struct VVBlock {
     int64_t sx, snst;
 };
 
+// ONE value split and stored as XS scalar bf16 terms, part_stride bytes apart (vv_split_bf16 packs four values per term)
 template <int XS>
 __device__ __forceinline__ void split_store(unsigned char* base, size_t part_stride, int byte_off, float v) {
     __bf16 h = (__bf16)v;
@@ -146,7 +141,7 @@ __global__ __launch_bounds__(256) void vv_block1d_kernel(const VVBlock a) {
             float s = 0.f;
 #pragma unroll
             for (int q = 0; q < CL; ++q) s += xv[i][q] * xv[i][q];
-            const float r = rsqrtf(wsum(s) / (float)C + a.eps);
+            const float r = rsqrtf(vv_wave_sum(s) / (float)C + a.eps);
 #pragma unroll
             for (int q = 0; q < CL; ++q) {
                 const int c = lane + q * 64;
@@ -181,13 +176,13 @@ __global__ __launch_bounds__(256) void vv_block1d_kernel(const VVBlock a) {
         float xr[CL];
 #pragma unroll
         for (int q = 0; q < CL; ++q) { const int c = lane + q * 64; xr[q] = (c < C) ? xs[r * C + c] : 0.f; s += xr[q] * xr[q]; }
-        const float rr = rsqrtf(wsum(s) / (float)C + a.eps);
+        const float rr = rsqrtf(vv_wave_sum(s) / (float)C + a.eps);
 #pragma unroll
         for (int q = 0; q < CL; ++q) {
             const int c = lane + q * 64;
             if (c < C) {
                 const float n = xr[q] * rr * fnw_r[q];
-                const int off = (((c >> 5) * 64 + r + 16 * ((c & 31) >> 3)) * 8 + (c & 7)) * 2;
+                const int off = vv_packed_index(c >> 5, r, c) * 2;
                 split_store<XS>(f1, (size_t)KT1 * 1024, off, n);
             }
         }
@@ -212,8 +207,8 @@ __global__ __launch_bounds__(256) void vv_block1d_kernel(const VVBlock a) {
         float u[4];
         const float bb[4] = {b1_r[i1].x, b1_r[i1].y, b1_r[i1].z, b1_r[i1].w};
 #pragma unroll
-        for (int r = 0; r < 4; ++r) u[r] = gelu_erf(acc[r] + bb[r]);
-        const int off = (((n0 >> 5) * 64 + frow + 16 * ((n0 & 31) >> 3)) * 8 + (n0 & 7)) * 2;
+        for (int r = 0; r < 4; ++r) u[r] = vv_gelu_erf(acc[r] + bb[r]);
+        const int off = vv_packed_index(n0 >> 5, frow, n0) * 2;
 #pragma unroll
         for (int r = 0; r < 4; ++r) split_store<XS>(f2, (size_t)KT2 * 1024, off + r * 2, u[r]);
     }
@@ -250,11 +245,8 @@ template <int C, int XS>
 static void go(const VVBlock& a, hipStream_t s) {
     constexpr int TT = 16, HALO = 6, F = 4 * C;
     const size_t smem = (size_t)((TT + HALO) * C + TT * C + TT) * 4 + (size_t)XS * (C / 32) * 1024 + (size_t)XS * (F / 32) * 1024;
-    static bool attr = false;
-    if (!attr) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&vv_block1d_kernel<C, XS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr = true;
-    }
+    static const hipError_t lds = vv_raise_lds_limit(160 * 1024, &vv_block1d_kernel<C, XS>);
+    (void)lds;
     hipLaunchKernelGGL((vv_block1d_kernel<C, XS>), dim3((a.T + TT - 1) / TT, a.sl.n > 0 ? a.sl.n : 1), dim3(256), smem, s, a);
 }
 

@@ -28,6 +28,7 @@
 //    in a fixed order -> deterministic, no atomics, enough waves for skinny N.
 #include <cstdlib>
 #include "vv_common.h"
+#include "vv_device.h"
 #include "vv_launch.h"
 
 #ifdef VV_GEMM_TIMING
@@ -39,37 +40,6 @@
 #endif
 
 namespace {
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-__device__ __forceinline__ float silu_f(float u) { return u / (1.0f + expf(-u)); }
-__device__ __forceinline__ float gelu_erf_f(float u) { return 0.5f * u * (1.0f + erff(u * 0.70710678118654752440f)); }
-
-__device__ __forceinline__ bf16x8 as_bf16x8(u32x4 u) { return __builtin_bit_cast(bf16x8, u); }
-
-// 4 fp32 -> XS packed bf16x4 terms (8 bytes each)
-template <int XS>
-__device__ __forceinline__ void split4(const float (&v)[4], uint2 (&out)[XS]) {
-    typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-    bf16x4 h, m, l;
-    float r[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        h[j] = (__bf16)v[j];
-        if constexpr (XS > 1) {
-            r[j] = v[j] - (float)h[j];
-            m[j] = (__bf16)r[j];
-            if constexpr (XS > 2) l[j] = (__bf16)(r[j] - (float)m[j]);
-        }
-    }
-    out[0] = __builtin_bit_cast(uint2, h);
-    if constexpr (XS > 1) out[1] = __builtin_bit_cast(uint2, m);
-    if constexpr (XS > 2) out[2] = __builtin_bit_cast(uint2, l);
-}
 
 template <int NT, int XS, bool DUAL, int WPB, int MAXR, bool VEC>
 __global__ __launch_bounds__(WPB * 64) void vv_gemm_kernel(const VVGemm a) {
@@ -125,7 +95,7 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemm_kernel(const VVGemm a) {
                 } else {
                     for (int k = lane; k < a.K; k += 64) { float v = xr[k]; s += v * v; }
                 }
-                rstd_rows[r] = rsqrtf(wave_sum(s) / (float)a.K + a.eps);
+                rstd_rows[r] = rsqrtf(vv_wave_sum(s) / (float)a.K + a.eps);
             }
         }
     }
@@ -248,13 +218,13 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemm_kernel(const VVGemm a) {
                         av.z = k2 ? a.addvec[ao + 2] : 0.f;
                         av.w = k3 ? a.addvec[ao + 3] : 0.f;
                     }
-                    v[0] = kin ? silu_f(v[0] + av.x) : 0.f;
-                    v[1] = k1 ? silu_f(v[1] + av.y) : 0.f;
-                    v[2] = k2 ? silu_f(v[2] + av.z) : 0.f;
-                    v[3] = k3 ? silu_f(v[3] + av.w) : 0.f;
+                    v[0] = kin ? vv_silu(v[0] + av.x) : 0.f;
+                    v[1] = k1 ? vv_silu(v[1] + av.y) : 0.f;
+                    v[2] = k2 ? vv_silu(v[2] + av.z) : 0.f;
+                    v[3] = k3 ? vv_silu(v[3] + av.w) : 0.f;
                 }
                 uint2 parts[XS];
-                split4<XS>(v, parts);
+                vv_split_bf16<XS>(v, parts);
 #pragma unroll
                 for (int p = 0; p < XS; ++p)
                     *reinterpret_cast<uint2*>(stg + (size_t)p * U * 4 * Tpad * 16 + st_off + r * 16) = parts[p];
@@ -327,7 +297,7 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemm_kernel(const VVGemm a) {
 #pragma unroll
         for (int r = 0; r < MAXR; ++r) {
             if (r < Tt) {
-                const float s = wave_sum(ssq[r]);
+                const float s = vv_wave_sum(ssq[r]);
                 if (frow == r) my_ssq = s;
             }
         }
@@ -372,18 +342,17 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemm_kernel(const VVGemm a) {
         if (a.epi == VV_EPI_CFG_DPM) {
             // lanes frow = j (cond) and frow = j + n (uncond) hold the two guidance branches of latent row j
             const int nc = a.n_cfg;
-            const float ca = a.coef[0], cs_ = a.coef[1], csx = a.coef[2], c0 = a.coef[3], c1 = a.coef[4];
+            const VVSolverCoef c5 = vv_solver_coef(a.coef, false);           // {a, s, cs, c0, c1}: cn below
 #pragma unroll 1
             for (int r = 0; r < 4; ++r) {
                 const float vu = __shfl(o4[r], lane + nc);
                 const int n = n0 + r;
                 if (frow < nc && n < a.N) {
-                    const float v = vu + cfg * (o4[r] - vu);
                     const int64_t zi = (int64_t)frow * a.N + n;
-                    const float zo = a.z[zi];
-                    const float x0 = ca * zo - cs_ * v;
-                    float zn = csx * zo + c0 * x0 + c1 * (x0 - a.x0p[zi]);
-                    if (a.sde_noise) zn += a.coef[5] * a.sde_noise[zi];      // sde-dpmsolver++ variance noise
+                    VVSolverCoef cf = c5;
+                    if (a.sde_noise) cf.cn = a.coef[5];          // rolled loop: fetched on the sde path only, next to the noise
+                    float x0, zn;
+                    vv_cfg_dpm_update(o4[r], vu, cfg, a.z[zi], a.x0p[zi], cf, a.sde_noise != nullptr, [&] { return a.sde_noise[zi]; }, x0, zn);
                     a.x0p[zi] = x0;
                     a.z[zi] = zn;
                     a.z[zi + (int64_t)nc * a.N] = zn;
@@ -400,8 +369,8 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemm_kernel(const VVGemm a) {
             for (int r = 0; r < 4; ++r) {
                 o[r] = o4[r];
                 if (a.epi == VV_EPI_BIAS) o[r] += pb[r];
-                else if (a.epi == VV_EPI_BIAS_GELU) o[r] = gelu_erf_f(o[r] + pb[r]);
-                else if (a.epi == VV_EPI_SWIGLU) o[r] = silu_f(o[r]) * u4[r];
+                else if (a.epi == VV_EPI_BIAS_GELU) o[r] = vv_gelu_erf(o[r] + pb[r]);
+                else if (a.epi == VV_EPI_SWIGLU) o[r] = vv_silu(o[r]) * u4[r];
                 else if (a.epi == VV_EPI_RESID) o[r] = (o[r] + pb[r]) * pg[r] + py[r];
                 else if (a.epi == VV_EPI_GATED_RESID) o[r] = py[r] + pg[r] * o[r];
             }
@@ -414,8 +383,8 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemm_kernel(const VVGemm a) {
             if (n >= a.N) break;
             float o = o4[r];
             if (a.bias && (a.epi == VV_EPI_BIAS || a.epi == VV_EPI_BIAS_GELU || a.epi == VV_EPI_RESID)) o += a.bias[n];
-            if (a.epi == VV_EPI_BIAS_GELU) o = gelu_erf_f(o);
-            else if (a.epi == VV_EPI_SWIGLU) o = silu_f(o) * u4[r];
+            if (a.epi == VV_EPI_BIAS_GELU) o = vv_gelu_erf(o);
+            else if (a.epi == VV_EPI_SWIGLU) o = vv_silu(o) * u4[r];
             else if (a.epi == VV_EPI_RESID) { if (a.nscale) o *= a.nscale[n]; o += yp[r]; }
             else if (a.epi == VV_EPI_GATED_RESID) o = yp[r] + a.gate[(int64_t)row * a.ld_gate + n] * o;
             yp[r] = o;
@@ -469,12 +438,8 @@ __global__ void vv_pack_kernel(const ST* __restrict__ src, __bf16* __restrict__ 
 // ---- host launchers ------------------------------------------------------------
 template <int NT, int XS, bool DUAL, int WPB, int MAXR, bool VEC>
 static void launch_t(const VVGemm& a, dim3 grid, size_t smem, hipStream_t s) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&vv_gemm_kernel<NT, XS, DUAL, WPB, MAXR, VEC>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
+    static const hipError_t lds = vv_raise_lds_limit(160 * 1024, &vv_gemm_kernel<NT, XS, DUAL, WPB, MAXR, VEC>);
+    (void)lds;
     hipLaunchKernelGGL((vv_gemm_kernel<NT, XS, DUAL, WPB, MAXR, VEC>), grid, dim3(WPB * 64), smem, s, a);
 }
 

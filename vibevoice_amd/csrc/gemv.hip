@@ -14,9 +14,10 @@
 //   * 32-bit offsets from uniform bases (no 64-bit multiplies), k-range handled with
 //     clamped loads + one uniform branch per batch instead of a branch per load;
 //   * the epilogue wave issues its residual / bias / gate loads at kernel entry;
-//   * sum(x^2) by DPP row reductions + readlane (no LDS permutes);
+//   * sum(x^2) by DPP row reductions + readlane (no LDS permutes: vv_wave_sum_dpp);
 //   * split-K partials go to a dedicated LDS region: a single barrier.
 #include "vv_common.h"
+#include "vv_device.h"
 #include "vv_launch.h"
 
 #ifdef VV_GEMM_TIMING
@@ -29,46 +30,6 @@
 #endif
 
 namespace {
-
-__device__ __forceinline__ float silu_f(float u) { return u / (1.0f + __expf(-u)); }
-__device__ __forceinline__ float silu_acc(float u) { return u / (1.0f + expf(-u)); }
-__device__ __forceinline__ float gelu_erf_f(float u) { return 0.5f * u * (1.0f + erff(u * 0.70710678118654752440f)); }
-
-// full-wave sum, result uniform (returned from SGPRs): 4 DPP steps inside each row of 16 + 4 readlanes
-__device__ __forceinline__ float wave_sum_dpp(float v) {
-    int x = __builtin_bit_cast(int, v);
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
-    x = __builtin_bit_cast(int, v);
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, true));   // quad_perm [2,3,0,1]
-    x = __builtin_bit_cast(int, v);
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0x141, 0xF, 0xF, true));  // row_half_mirror
-    x = __builtin_bit_cast(int, v);
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0x140, 0xF, 0xF, true));  // row_mirror
-    x = __builtin_bit_cast(int, v);
-    const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(x, 0));
-    const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(x, 16));
-    const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(x, 32));
-    const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(x, 48));
-    return (r0 + r1) + (r2 + r3);
-}
-
-template <int XS>
-__device__ __forceinline__ void split4(const float (&v)[4], uint2 (&out)[XS]) {
-    typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-    bf16x4 h, m, l;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        h[j] = (__bf16)v[j];
-        if constexpr (XS > 1) {
-            const float r = v[j] - (float)h[j];
-            m[j] = (__bf16)r;
-            if constexpr (XS > 2) l[j] = (__bf16)(r - (float)m[j]);
-        }
-    }
-    out[0] = __builtin_bit_cast(uint2, h);
-    if constexpr (XS > 1) out[1] = __builtin_bit_cast(uint2, m);
-    if constexpr (XS > 2) out[2] = __builtin_bit_cast(uint2, l);
-}
 
 constexpr int U = 8;       // k-steps per batch (256 k = one float4 per lane per row)
 
@@ -222,7 +183,7 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemv_kernel(const u32x4* __restri
                 s1 += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
             }
         }
-        s1 = wave_sum_dpp(s1);
+        s1 = vv_wave_sum_dpp(s1);
         if (lane == 0) ssq1_sh[wave] = s1;
         __syncthreads();
         float tot = 0.f;
@@ -308,18 +269,18 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemv_kernel(const u32x4* __restri
                     v[2] = (v[2] * R.nwv.z) * (1.f + R.sc[r].z); v[3] = (v[3] * R.nwv.w) * (1.f + R.sc[r].w);
                     float sh4[4] = {R.sh[r].x * msk, R.sh[r].y * msk, R.sh[r].z * msk, R.sh[r].w * msk};
                     uint2 sparts[XS];
-                    split4<XS>(sh4, sparts);
+                    vv_split_bf16<XS>(sh4, sparts);
 #pragma unroll
                     for (int p = 0; p < XS; ++p) {
                         if constexpr (FOLD) *reinterpret_cast<uint2*>(stg + p * (U * 4 * GSB) + st_off + (MR + r) * 16) = sparts[p];
                         else *reinterpret_cast<uint2*>(stg + (XS + p) * (U * 4 * GSB) + st_off + r * 16) = sparts[p];
                     }
                 } else if constexpr (PRO == VV_PRO_ADD_SILU) {
-                    v[0] = silu_acc(v[0] + R.addv[r].x) * msk; v[1] = silu_acc(v[1] + R.addv[r].y) * msk;
-                    v[2] = silu_acc(v[2] + R.addv[r].z) * msk; v[3] = silu_acc(v[3] + R.addv[r].w) * msk;
+                    v[0] = vv_silu(v[0] + R.addv[r].x) * msk; v[1] = vv_silu(v[1] + R.addv[r].y) * msk;
+                    v[2] = vv_silu(v[2] + R.addv[r].z) * msk; v[3] = vv_silu(v[3] + R.addv[r].w) * msk;
                 }
                 uint2 parts[XS];
-                split4<XS>(v, parts);
+                vv_split_bf16<XS>(v, parts);
 #pragma unroll
                 for (int p = 0; p < XS; ++p)
                     *reinterpret_cast<uint2*>(stg + p * (U * 4 * GSB) + st_off + r * 16) = parts[p];
@@ -387,7 +348,7 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemv_kernel(const u32x4* __restri
     if constexpr (PRO == VV_PRO_RMS || PRO == VV_PRO_RMS_MOD || PRO == VV_PRO_NORMDW) {
 #pragma unroll
         for (int r = 0; r < MR; ++r) {
-            const float s = (r < T) ? wave_sum_dpp(ssq[r]) : 0.f;
+            const float s = (r < T) ? vv_wave_sum_dpp(ssq[r]) : 0.f;
             if (lane == 0) ssq_sh[wave][r] = s;
         }
     }
@@ -437,10 +398,10 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemv_kernel(const u32x4* __restri
         for (int r = 0; r < 4; ++r) o[r] += pb[r];
     } else if constexpr (EPI == VV_EPI_BIAS_GELU) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) o[r] = gelu_erf_f(o[r] + pb[r]);
+        for (int r = 0; r < 4; ++r) o[r] = vv_gelu_erf(o[r] + pb[r]);
     } else if constexpr (EPI == VV_EPI_SWIGLU) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) o[r] = silu_acc(o[r]) * up[r];
+        for (int r = 0; r < 4; ++r) o[r] = vv_silu(o[r]) * up[r];
     } else if constexpr (EPI == VV_EPI_RESID) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) o[r] = (ksb == 0) ? py[r] + pg[r] * (o[r] + pb[r]) : pg[r] * o[r];
@@ -450,8 +411,7 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemv_kernel(const u32x4* __restri
     }
     if constexpr (EPI == VV_EPI_CFG_DPM) {
         const int nc = a.n_cfg;
-        const float ca = a.coef[0], cs_ = a.coef[1], csx = a.coef[2], c0 = a.coef[3], c1 = a.coef[4];
-        const float cn = a.sde_noise ? a.coef[5] : 0.f;          // sde-dpmsolver++: + cn * eps_i (dpm_solver.py:680-686, 785-793)
+        const VVSolverCoef cf = vv_solver_coef(a.coef, a.sde_noise != nullptr);
         float cfg = a.cfg;
         if (a.cfg_rows && frow < nc) cfg = a.cfg_rows[frow];     // one guidance scale per utterance row
 #pragma unroll
@@ -459,12 +419,9 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemv_kernel(const u32x4* __restri
             const float vu = __shfl(o[r], lane + nc);
             const int n = n0 + r;
             if (frow < nc && n < pN) {
-                const float v = vu + cfg * (o[r] - vu);
                 const unsigned zi = (unsigned)(frow * pN + n);
-                const float zo = a.z[zi];
-                const float x0 = ca * zo - cs_ * v;
-                float zn = csx * zo + c0 * x0 + c1 * (x0 - a.x0p[zi]);
-                if (a.sde_noise) zn += cn * a.sde_noise[zi];
+                float x0, zn;
+                vv_cfg_dpm_update(o[r], vu, cfg, a.z[zi], a.x0p[zi], cf, a.sde_noise != nullptr, [&] { return a.sde_noise[zi]; }, x0, zn);
                 a.x0p[zi] = x0;
                 a.z[zi] = zn;
                 a.z[zi + (unsigned)(nc * pN)] = zn;
@@ -625,8 +582,10 @@ extern "C" int vv_gemv_launch(VVGemm a, int xs, hipStream_t s, int* form) {
          return vv_launch_rc(0); } while (0)
 #define X(P, E)                                                                                         \
     if (a.pro == P && a.epi == E) {                                                                     \
-        if (xs == 1 && n_tiles > 256 && E == VV_EPI_SWIGLU && a.T <= 2) VV_GOP2(P, E);                   \
-        if (xs == 1 && n_tiles > 256 && E == VV_EPI_SWIGLU) VV_GOP(1, P, E, 4, 1);                       \
+        if constexpr (E == VV_EPI_SWIGLU) {        /* wide outputs: only the gate/up projection has them */ \
+            if (xs == 1 && n_tiles > 256 && a.T <= 2) VV_GOP2(P, E);                                     \
+            if (xs == 1 && n_tiles > 256) VV_GOP(1, P, E, 4, 1);                                         \
+        }                                                                                               \
         if (xs == 1) VV_GOP(1, P, E, 8, 1); else if (xs == 2) VV_GOP(2, P, E, 8, 1); else VV_GOP(3, P, E, 8, 1); \
     }
         if (a.n_xa > 0) { VV_GEMV_PARTS_X(X) }

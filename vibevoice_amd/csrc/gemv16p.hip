@@ -23,17 +23,10 @@
 // per frame for every solver step and layer: they depend on the condition and t only).
 #include <cstdlib>
 #include "vv_common.h"
+#include "vv_device.h"
 #include "vv_launch.h"
 
 namespace {
-
-__device__ __forceinline__ float p16_silu(float u) { return u / (1.0f + expf(-u)); }
-
-__device__ __forceinline__ float p16_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // MODE 1: RMSNorm with weight nw;  MODE 2: adaLN-modulated RMSNorm (scale / shift rows, stride ld_mod).
 // grid = 16 * ceil(T / 16) workgroups (rows >= T are written as zeros), 256 threads; K % 32 == 0, K <= 8192.
@@ -54,7 +47,7 @@ __global__ __launch_bounds__(256) void vv_pack16_kernel(const float* __restrict_
         v[i] = (t < T && q < K4) ? *reinterpret_cast<const float4*>(x + (int64_t)t * ldx + q * 4) : float4{0.f, 0.f, 0.f, 0.f};
         ssq += v[i].x * v[i].x + v[i].y * v[i].y + v[i].z * v[i].z + v[i].w * v[i].w;
     }
-    ssq = p16_wave_sum(ssq);
+    ssq = vv_wave_sum(ssq);
     if (lane == 0) red[wave] = ssq;
     __syncthreads();
     const float rs = rsqrtf(((red[0] + red[1]) + (red[2] + red[3])) / (float)K + eps);
@@ -74,7 +67,6 @@ __global__ __launch_bounds__(256) void vv_pack16_kernel(const float* __restrict_
                 o[2] = o[2] * (1.f + s4.z) + h4.z; o[3] = o[3] * (1.f + s4.w) + h4.w;
             }
         }
-        typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
         bf16x4 b;
 #pragma unroll
         for (int j = 0; j < 4; ++j) b[j] = (__bf16)o[j];
@@ -98,7 +90,6 @@ __global__ __launch_bounds__(256) void vv_pack16_tiles_kernel(const float* __res
     for (int q = threadIdx.x; q < (K >> 2); q += 256) {
         const int k = q * 4;
         const float4 v = (t < T) ? *reinterpret_cast<const float4*>(xr + k) : float4{0.f, 0.f, 0.f, 0.f};
-        typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
         bf16x4 b;
         b[0] = (__bf16)v.x; b[1] = (__bf16)v.y; b[2] = (__bf16)v.z; b[3] = (__bf16)v.w;
         const int64_t tile = (k >> 5);
@@ -255,7 +246,6 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemv16p_kernel(const VVGemv16p a)
         const float pg[4] = {pre_g.x, pre_g.y, pre_g.z, pre_g.w};
         const float nw4[4] = {pre_nw.x, pre_nw.y, pre_nw.z, pre_nw.w}, sc4[4] = {pre_sc.x, pre_sc.y, pre_sc.z, pre_sc.w};
         float sq = 0.f;
-        typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
         bf16x4 pk;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -279,8 +269,7 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemv16p_kernel(const VVGemv16p a)
     if (!epi_lane) return;
     if constexpr (EPI == VV_EPI_CFG_DPM) {
         const int nc = a.n_cfg;
-        const float ca = a.coef[0], cs_ = a.coef[1], csx = a.coef[2], c0 = a.coef[3], c1 = a.coef[4];
-        const float cn = a.sde_noise ? a.coef[5] : 0.f;
+        const VVSolverCoef cf = vv_solver_coef(a.coef, a.sde_noise != nullptr);
         float cfg = a.cfg;
         if (a.cfg_rows && frow < nc) cfg = a.cfg_rows[frow];     // one guidance scale per utterance row
 #pragma unroll
@@ -289,12 +278,9 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemv16p_kernel(const VVGemv16p a)
             const float vu = __shfl(oc, lane + nc);
             const int n = n0 + r;
             if (frow < nc && n < a.N) {
-                const float v = vu + cfg * (oc - vu);
                 const unsigned zi = (unsigned)(frow * a.N + n);
-                const float zo = a.z[zi];
-                const float x0 = ca * zo - cs_ * v;
-                float zn = csx * zo + c0 * x0 + c1 * (x0 - a.x0p[zi]);
-                if (a.sde_noise) zn += cn * a.sde_noise[zi];
+                float x0, zn;
+                vv_cfg_dpm_update(oc, vu, cfg, a.z[zi], a.x0p[zi], cf, a.sde_noise != nullptr, [&] { return a.sde_noise[zi]; }, x0, zn);
                 a.x0p[zi] = x0;
                 a.z[zi] = zn;
                 a.z[zi + (unsigned)(nc * a.N)] = zn;
@@ -303,10 +289,9 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemv16p_kernel(const VVGemv16p a)
         return;
     }
     if constexpr (DUAL) {
-        typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
         bf16x4 o;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) o[r] = (__bf16)(p16_silu(acc[0][r]) * acc[1][r]);
+        for (int r = 0; r < 4; ++r) o[r] = (__bf16)(vv_silu(acc[0][r]) * acc[1][r]);
         // element (t = frow, n) of the packed output: tile n >> 5, lane frow + 16 * ((n & 31) >> 3), slot n & 7
         const int64_t otile = n0 >> 5;
         const int ol = frow + 16 * ((n0 & 31) >> 3);

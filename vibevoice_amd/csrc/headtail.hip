@@ -16,15 +16,10 @@
 // reads buffer i & 1 and writes the other one), so no workgroup can observe another's update.  Same arithmetic as the two launches it
 // replaces (bf16 at the MFMA inputs, fp32 accumulation, the same K split over 8 waves and the same fixed reduction order).
 #include "vv_common.h"
+#include "vv_device.h"
 #include "vv_launch.h"
 
 namespace {
-
-__device__ __forceinline__ float ht_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 constexpr int TU = 8;      // k-steps per staging pass (256 k = one float4 per lane and row)
 constexpr int WB = 4;      // k-steps per weight batch (x 4 latent tiles = 16 fragment loads), two batches in flight
@@ -91,7 +86,6 @@ __global__ __launch_bounds__(512) void vv_head_tail_kernel(const VVTail a) {
     const unsigned kk = lane * 4;
     const unsigned st_off = ((kk >> 5) * 4 + ((kk & 31) >> 3)) * GSB + (kk & 7) * 2;
     float ssq[MR] = {0.f, 0.f, 0.f, 0.f};
-    typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
     constexpr int NP = KMAX / TU;
     static_assert(TR == 2 || TR == 4, "rows");
     float4 rx[NP][TR], rsc[NP][TR], rsh[NP][TR];
@@ -171,7 +165,7 @@ __global__ __launch_bounds__(512) void vv_head_tail_kernel(const VVTail a) {
     for (int nt = 0; nt < NT; ++nt) reinterpret_cast<f32x4*>(stg)[nt * 64 + lane] = acc[nt];      // wave-private until the barrier
 #pragma unroll
     for (int r = 0; r < MR; ++r) {
-        const float s = (r < T) ? ht_wave_sum(ssq[r]) : 0.f;
+        const float s = (r < T) ? vv_wave_sum(ssq[r]) : 0.f;
         if (lane == 0) ssq_sh[wave][r] = s;
     }
     __syncthreads();
@@ -185,6 +179,8 @@ __global__ __launch_bounds__(512) void vv_head_tail_kernel(const VVTail a) {
 #pragma unroll
         for (int w = 0; w < WPB; ++w) s += ssq_sh[w][frow & 3];
         const float rs = rsqrtf(s / (float)H + a.eps);
+        // The update of vv_cfg_dpm_update (vv_device.h), written out on purpose: called through the helper, the compiler pairs the
+        // products of this loop's four elements differently and z' changes in its last bit (x0 and z' feed the next step directly).
         const float ca = cf[0], cs_ = cf[1], csx = cf[2], c0 = cf[3], c1 = cf[4];
         const float cn = a.sde_noise ? cf[5] : 0.f;
         bf16x4 zb;
@@ -255,8 +251,8 @@ constexpr size_t HT_SMEM = 8 * KMAX * 4 * 128 + 2 * 1024 + 8 * 4 * sizeof(float)
 
 // the kernel's dynamic LDS is above the 64 KiB default: 0 once it is granted, -1 if refused (the caller then keeps the two launches)
 extern "C" int vv_head_tail_init() {
-    for (const void* k : {reinterpret_cast<const void*>(&vv_head_tail_kernel<HT_TPW, 1, 2>), reinterpret_cast<const void*>(&vv_head_tail_kernel<HT_TPW, 0, 2>)})
-        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HT_SMEM) != hipSuccess) { (void)hipGetLastError(); return -1; }
+    // called once per context, not per launch: no once-flag to share between host threads
+    if (vv_raise_lds_limit((int)HT_SMEM, &vv_head_tail_kernel<HT_TPW, 1, 2>, &vv_head_tail_kernel<HT_TPW, 0, 2>) != hipSuccess) { (void)hipGetLastError(); return -1; }
     return 0;
 }
 

@@ -10,6 +10,7 @@
 // starts at 0 and ends on a 32-position boundary is ONE contiguous run per head whatever max_ctx is: the snapshot buffer is
 // [layer][kv head][ceil32(n) * D] bf16 and a restore needs no re-tiling.
 #include "vv_common.h"
+#include "vv_device.h"
 #include "vv_launch.h"
 
 namespace {

@@ -1,17 +1,12 @@
 // misc.hip -- the small HBM/L2-bound kernels around the GEMMs: embedding gather,
 // row RMSNorm, causal depthwise conv (+layer-scale residual), streaming-state row
-// shifts, CFG + DPM-Solver++ update, affine/copy helpers.  All are one element (or
+// shifts, affine/copy helpers.  All are one element (or
 // one float4) per lane, coalesced along the channel axis of time-major buffers.
 #include "vv_common.h"
+#include "vv_device.h"
 #include "vv_launch.h"
 
 namespace {
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // out[i][:] = (float) table[ids[i]][:]     grid (n), block 256
 __global__ void vv_embed_kernel(const __bf16* __restrict__ table, const int* __restrict__ ids,
@@ -47,7 +42,7 @@ __global__ __launch_bounds__(256) void vv_rmsnorm_rows_kernel(const float* __res
     } else if (live) {
         for (int c = tl; c < C; c += NTH) { const float q = xr[c]; s += q * q; }
     }
-    s = wave_sum(s);
+    s = vv_wave_sum(s);
     if (RPB == 1) {
         if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
         __syncthreads();
@@ -101,7 +96,7 @@ __global__ __launch_bounds__(1024) void vv_normdw_kernel(float* __restrict__ x, 
             const float4 v = *reinterpret_cast<const float4*>(xr + c);
             s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
         }
-        const float rs = rsqrtf(wave_sum(s) / (float)C + eps);
+        const float rs = rsqrtf(vv_wave_sum(s) / (float)C + eps);
         float* nr = nb + (int64_t)(6 + t) * C;
         for (int c = lane * 4; c < C; c += 256) {
             const float4 v = *reinterpret_cast<const float4*>(xr + c);
@@ -125,22 +120,6 @@ __global__ __launch_bounds__(1024) void vv_normdw_kernel(float* __restrict__ x, 
 // norm -> nb rows 6.., depthwise conv over [6 history rows ++ new rows], layer scale, residual.  Output goes to a
 // DIFFERENT buffer (the stage ping-pongs): other workgroups are still reading full rows of xin for their norms.
 // Every global load of a thread is issued before the first wait.
-__device__ __forceinline__ float wave_sum_dpp_m(float v) {
-    int x = __builtin_bit_cast(int, v);
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, true));
-    x = __builtin_bit_cast(int, v);
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, true));
-    x = __builtin_bit_cast(int, v);
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0x141, 0xF, 0xF, true));
-    x = __builtin_bit_cast(int, v);
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0x140, 0xF, 0xF, true));
-    x = __builtin_bit_cast(int, v);
-    const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(x, 0));
-    const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(x, 16));
-    const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(x, 32));
-    const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(x, 48));
-    return (r0 + r1) + (r2 + r3);
-}
 template <int NCH>      // NCH = C / 1024 float4 chunks per thread and row
 __global__ __launch_bounds__(256) void vv_normdw_sliced_kernel(const float* __restrict__ xin, float* __restrict__ xout,
                                                                float* __restrict__ nb, const float* __restrict__ nw,
@@ -174,7 +153,7 @@ __global__ __launch_bounds__(256) void vv_normdw_sliced_kernel(const float* __re
         float s = 0.f;
 #pragma unroll
         for (int i = 0; i < NCH; ++i) s += full[t][i].x * full[t][i].x + full[t][i].y * full[t][i].y + full[t][i].z * full[t][i].z + full[t][i].w * full[t][i].w;
-        s = wave_sum_dpp_m(s);
+        s = vv_wave_sum_dpp(s);
         if (lane == 0) red[wave][t] = s;
     }
     __syncthreads();
@@ -253,7 +232,7 @@ __global__ __launch_bounds__(256) void vv_normdw_rows_kernel(const float* __rest
             float s = 0.f;
 #pragma unroll
             for (int q = 0; q < NCH; ++q) s += v[i][q].x * v[i][q].x + v[i][q].y * v[i][q].y + v[i][q].z * v[i][q].z + v[i][q].w * v[i][q].w;
-            rs = rsqrtf(wave_sum(s) / (float)C + eps);
+            rs = rsqrtf(vv_wave_sum(s) / (float)C + eps);
         }
         const bool keep = cur && (rr >= 6) && (t >= T - 6);                 // owned row that belongs to the next frame's history
 #pragma unroll
@@ -284,7 +263,7 @@ __global__ __launch_bounds__(256) void vv_normdw_rows_kernel(const float* __rest
 
 // element W[n][k] of a packed matrix (vv_common.h) with KT k-tiles
 __device__ __forceinline__ float packed_w(const __bf16* __restrict__ wp, int KT, int n, int k) {
-    return (float)wp[(((int64_t)(n >> 4) * KT + (k >> 5)) * 64 + (n & 15) + 16 * ((k & 31) >> 3)) * 8 + (k & 7)];
+    return (float)wp[vv_packed_index((int64_t)(n >> 4) * KT + (k >> 5), n & 15, k)];
 }
 
 // Encoder stem: causal conv k = 7 over a MONO signal (Cin = 1): out[t][n] = b[n] + sum_j W[n][j] * in[t + j], `in` = the
@@ -344,29 +323,6 @@ __global__ void vv_zero_hist_kernel(const VVShift* __restrict__ tab) {
     for (int64_t i = blockIdx.y * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.y * blockDim.x) e.buf[i] = 0.f;
 }
 
-// Classifier-free guidance + one DPM-Solver++(2M) update on the n x L latent block.
-//   v  = v_u + cfg (v_c - v_u)                  (rows [0,n) cond, [n,2n) uncond of `eps`)
-//   x0 = a x - s v
-//   x' = cs x + c0 x0 + c1 (x0 - x0_prev)       (c1 = 0 on first-order steps)
-// coef = {a, s, cs, c0, c1} for this step.
-__global__ void vv_cfg_dpm_kernel(const float* __restrict__ eps, float* __restrict__ x, float* __restrict__ x0_prev,
-                                  const float* __restrict__ coef, float cfg, int n, int L, const float* __restrict__ sde_noise,
-                                  const float* __restrict__ cfg_rows) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n * L) return;
-    if (cfg_rows) cfg = cfg_rows[i / L];                       // one guidance scale per utterance row (null: cfg for every row)
-    const float a = coef[0], s = coef[1], cs = coef[2], c0 = coef[3], c1 = coef[4];
-    const float vc = eps[i], vu = eps[i + n * L];
-    const float v = vu + cfg * (vc - vu);
-    const float xi = x[i];
-    const float x0 = a * xi - s * v;
-    float xn = cs * xi + c0 * x0 + c1 * (x0 - x0_prev[i]);
-    if (sde_noise) xn += coef[5] * sde_noise[i];               // sde-dpmsolver++: coef row = {a, s, cs, c0, c1, cn}
-    x0_prev[i] = x0;
-    x[i] = xn;
-    x[i + n * L] = xn;        // both CFG halves see the same latent (modeling_vibevoice_inference.py:703-704)
-}
-
 // y = x * mul + add   (latent un-scaling, copies)
 __global__ void vv_affine_kernel(const float* __restrict__ x, float* __restrict__ y, float mul, float add, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -392,12 +348,6 @@ __global__ void vv_zero_words_kernel(unsigned* __restrict__ dst, size_t n) {
 __global__ void vv_sampler_init_kernel(const float* __restrict__ noise, float* __restrict__ z, float* __restrict__ x0p, int nL) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < nL) { const float v = noise[i]; z[i] = v; z[nL + i] = v; x0p[i] = 0.f; }
-}
-
-// y[i] = a[i] + b[i]
-__global__ void vv_add_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ y, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) y[i] = a[i] + b[i];
 }
 
 // sinusoidal timestep features: out[i][0:128]=cos(t_i f_k), [128:256]=sin(t_i f_k)
@@ -448,7 +398,7 @@ __global__ void vv_kv_move_kernel(__bf16* __restrict__ kc, __bf16* __restrict__ 
     __bf16* vb = vc + (int64_t)blockIdx.x * layer_stride + (int64_t)blockIdx.y * head_stride;
     auto kidx = [&](int pos) {
         const int64_t tile = (int64_t)(pos >> 4) * (D / 32) + (d >> 5);
-        return (tile * 64 + (pos & 15) + 16 * ((d & 31) >> 3)) * 8 + (d & 7);
+        return vv_packed_index(tile, pos & 15, d);
     };
     auto vidx = [&](int pos) {
         const int p = pos & 31, half = p >> 4, pp = p & 15, q4 = pp >> 2, rr = pp & 3;
@@ -510,16 +460,16 @@ __global__ void vv_ada_in_kernel(const float* __restrict__ cproj, const float* _
     const float4 e = reinterpret_cast<const float4*>(temb)[i * H4 + k4];
     float4 o;
     float u;
-    u = c.x + e.x; o.x = u / (1.0f + expf(-u));
-    u = c.y + e.y; o.y = u / (1.0f + expf(-u));
-    u = c.z + e.z; o.z = u / (1.0f + expf(-u));
-    u = c.w + e.w; o.w = u / (1.0f + expf(-u));
+    u = c.x + e.x; o.x = vv_silu(u);
+    u = c.y + e.y; o.y = vv_silu(u);
+    u = c.z + e.z; o.z = vv_silu(u);
+    u = c.w + e.w; o.w = vv_silu(u);
     reinterpret_cast<float4*>(out)[q] = o;
 }
 
 __global__ void vv_silu_kernel(float* __restrict__ x, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) { float u = x[i]; x[i] = u / (1.f + expf(-u)); }
+    if (i < n) x[i] = vv_silu(x[i]);
 }
 
 // fp32 <-> storage conversions used when uploading parameters
@@ -644,11 +594,8 @@ int vv_normdw_rows_slots_launch(const float* xin, float* xout, float* nb, const 
     const size_t smem = (size_t)(2 * RB + 6) * C * 4;
     const VVSlotIds sl = vv_slot_ids(ids, n);
     const dim3 grid((T + RB - 1) / RB, sl.n > 0 ? sl.n : 1);
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vv_normdw_rows_kernel<RB, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr = true;
-    }
+    static const hipError_t lds = vv_raise_lds_limit(160 * 1024, &vv_normdw_rows_kernel<RB, 4>);      // C = 1024 only: 88 KiB; the others fit the default
+    (void)lds;
     if (C == 256) hipLaunchKernelGGL((vv_normdw_rows_kernel<RB, 1>), grid, dim3(256), smem, s, xin, xout, nb, nw, w, b, gamma, T, C, eps, sl, sx, snb);
     else if (C == 512) hipLaunchKernelGGL((vv_normdw_rows_kernel<RB, 2>), grid, dim3(256), smem, s, xin, xout, nb, nw, w, b, gamma, T, C, eps, sl, sx, snb);
     else hipLaunchKernelGGL((vv_normdw_rows_kernel<RB, 4>), grid, dim3(256), smem, s, xin, xout, nb, nw, w, b, gamma, T, C, eps, sl, sx, snb);
@@ -677,11 +624,6 @@ int vv_zero_hist_launch(const void* tab, int n_entries, hipStream_t s) {
     hipLaunchKernelGGL(vv_zero_hist_kernel, dim3(n_entries, 8), dim3(256), 0, s, (const VVShift*)tab);
     return okk();
 }
-int vv_cfg_dpm_launch(const float* eps, float* x, float* x0_prev, const float* coef, float cfg, int n, int L, const float* sde_noise,
-                      const float* cfg_rows, hipStream_t s) {
-    hipLaunchKernelGGL(vv_cfg_dpm_kernel, dim3((n * L + 255) / 256), dim3(256), 0, s, eps, x, x0_prev, coef, cfg, n, L, sde_noise, cfg_rows);
-    return okk();
-}
 int vv_affine_launch(const float* x, float* y, float mul, float add, int n, hipStream_t s) {
     hipLaunchKernelGGL(vv_affine_kernel, dim3((n + 255) / 256), dim3(256), 0, s, x, y, mul, add, n);
     return okk();
@@ -707,10 +649,6 @@ int vv_zero_launch(void* dst, size_t bytes, hipStream_t s) {                    
 }
 int vv_sampler_init_launch(const float* noise, float* z, float* x0p, int nL, hipStream_t s) {
     hipLaunchKernelGGL(vv_sampler_init_kernel, dim3((nL + 255) / 256), dim3(256), 0, s, noise, z, x0p, nL);
-    return okk();
-}
-int vv_add_launch(const float* a, const float* b, float* y, int n, hipStream_t s) {
-    hipLaunchKernelGGL(vv_add_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a, b, y, n);
     return okk();
 }
 int vv_tfreq_launch(const float* t, float* out, int n, hipStream_t s) {

@@ -5,6 +5,7 @@
 // (blockIdx.y / .z), the keys travel by value in the kernel arguments (16 x 16 B); the kernel reads no global memory, uses no LDS and
 // keeps no state: out[s][r][f][j] depends on (keys[r], stream0 + s, f, j) alone, whatever else the launch computes beside it.
 #include "vv_common.h"
+#include "vv_device.h"
 #include "vv_launch.h"
 
 namespace {

@@ -26,6 +26,7 @@
 #include <cstring>
 #include <type_traits>
 #include "vv_common.h"
+#include "vv_device.h"
 #include "vv_launch.h"
 
 namespace {
@@ -42,12 +43,6 @@ __device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
 __device__ __forceinline__ void stage_sync() {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-}
-
-__device__ __forceinline__ float p_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
 }
 
 // ------------------------------------------------------------------------------------------------ activation packing
@@ -85,7 +80,7 @@ __global__ __launch_bounds__(256) void vv_pack_rows_kernel(const float* __restri
                     s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
                 }
             }
-            s = p_wave_sum(s);
+            s = vv_wave_sum(s);
             if (lane == 0) rs_sh[wave * 4 + r] = rsqrtf(s / (float)K + eps);
         }
         __syncthreads();
@@ -137,7 +132,7 @@ __global__ __launch_bounds__(256) void vv_ada_pack_kernel(const float* __restric
         const float4 e0 = *reinterpret_cast<const float4*>(e), e1 = *reinterpret_cast<const float4*>(e + 4);
         const float u[8] = {c0.x + e0.x, c0.y + e0.y, c0.z + e0.z, c0.w + e0.w, c1.x + e1.x, c1.y + e1.y, c1.z + e1.z, c1.w + e1.w};
 #pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = (__bf16)(u[j] / (1.0f + expf(-u[j])));
+        for (int j = 0; j < 8; ++j) o[j] = (__bf16)vv_silu(u[j]);
     }
     xp[((int64_t)blockIdx.x * KT + kt) * 64 + lane] = __builtin_bit_cast(u32x4, o);
 }
@@ -179,8 +174,6 @@ struct VVGemm3 {
     int Hq, Hkv;
     float q_scale;
 };
-
-__device__ __forceinline__ float g3_silu(float u) { return u / (1.0f + __expf(-u)); }
 
 // TR = row tiles (16 rows each) per wave: the workgroup covers 128 features x 32*TR rows.  TR = 8 (256 rows) doubles the
 // MFMAs per staged byte and per barrier: three such workgroups per CU carry enough arithmetic to cover a stage's load latency.
@@ -303,12 +296,11 @@ __global__ __launch_bounds__(256, TR == 8 ? 2 : (DB ? 2 : 4)) void vv_gemm3_kern
             for (int j = 0; j < TR; ++j) {
                 const int tt = tt0 + wr * TR + j;
                 if (tt >= t_tiles) continue;
-                typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
                 bf16x4 o;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const bool live = (n0 + r < a.N) && (tt * 16 + frow < a.T);
-                    o[r] = (__bf16)(live ? g3_silu(acc[i][j][r]) * acc[2 + i][j][r] : 0.f);
+                    o[r] = (__bf16)(live ? vv_silu_fast(acc[i][j][r]) * acc[2 + i][j][r] : 0.f);
                 }
                 // element (t, n) of the packed output: tile (tt, n >> 5), lane (t & 15) + 16 * ((n & 31) >> 3), slot n & 7
                 const int64_t tile = (int64_t)tt * KTo + (n0 >> 5);
@@ -487,7 +479,6 @@ __device__ __forceinline__ void g4_finish(const VVGemm3& a, f32x4 (&acc)[8][4], 
         float4 bs[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) bs[i] = a.bias ? *reinterpret_cast<const float4*>(a.bias + nb0 + i * 16) : float4{0.f, 0.f, 0.f, 0.f};
-        typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int t = (tt0 + wr * 4 + j) * 16 + frow;
@@ -558,12 +549,11 @@ __device__ __forceinline__ void g4_finish(const VVGemm3& a, f32x4 (&acc)[8][4], 
             for (int j = 0; j < 4; ++j) {
                 const int tt = tt0 + wr * 4 + j;
                 if (tt >= t_tiles) continue;
-                typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
                 bf16x4 o;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const bool live = (n0 + r < a.N) && (tt * 16 + frow < a.T);
-                    o[r] = (__bf16)(live ? g3_silu(acc[i][j][r]) * acc[4 + i][j][r] : 0.f);
+                    o[r] = (__bf16)(live ? vv_silu_fast(acc[i][j][r]) * acc[4 + i][j][r] : 0.f);
                 }
                 const int64_t tile = (int64_t)tt * KTo + (n0 >> 5);
                 const int ol = frow + 16 * ((n0 & 31) >> 3);
@@ -1022,7 +1012,6 @@ __global__ __launch_bounds__(512) void vv_attn_prefill4_kernel(
                     // straight into the o-projection's B operand (vv_pack_rows_kernel's layout, K = Hq * D): element (t, k) lives in
                     // tile (t >> 4, k >> 5), lane (t & 15) + 16 * ((k & 31) >> 3), slot k & 7; this lane holds 4 consecutive k
                     const int KTo = (Hq * D) >> 5;
-                    typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 #pragma unroll
                     for (int dt = 0; dt < DT; ++dt) {
                         const int k0 = h * D + dt * 16 + qg * 4;
@@ -1117,13 +1106,8 @@ int vv_gemm3_launch(const void* W, const void* W2, const void* Xp, float* Y, voi
         unsigned n_wgs = (unsigned)(a.n_blocks * a.t_blocks);
         g4_split_plan(a, ws, K, n_wgs);
         const dim3 grid4(n_wgs);
-        static bool attr4 = false;
-        if (!attr4) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vv_gemm4_kernel<VV_EPI_SWIGLU>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vv_gemm4_kernel<VV_EPI_RESID>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vv_gemm4_kernel<VV_EPI_BIAS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr4 = true;
-        }
+        static const hipError_t lds4 = vv_raise_lds_limit(160 * 1024, &vv_gemm4_kernel<VV_EPI_SWIGLU>, &vv_gemm4_kernel<VV_EPI_RESID>, &vv_gemm4_kernel<VV_EPI_BIAS>);
+        (void)lds4;
         const size_t smem4 = 4 * 32 * 1024;
         if (epi == VV_EPI_SWIGLU) hipLaunchKernelGGL((vv_gemm4_kernel<VV_EPI_SWIGLU>), grid4, dim3(512), smem4, s, a);
         else if (epi == VV_EPI_RESID) hipLaunchKernelGGL((vv_gemm4_kernel<VV_EPI_RESID>), grid4, dim3(512), smem4, s, a);
@@ -1194,11 +1178,8 @@ int vv_gemm_qkv_rope_launch(const void* W, const void* Xp, const float* bias, in
     a.cache_stride = cache_stride; a.head_stride = head_stride; a.Hq = Hq; a.Hkv = Hkv; a.q_scale = 1.0f / sqrtf((float)D);
     unsigned n_wgs = (unsigned)(n_blocks * t_blocks);
     g4_split_plan(a, ws, K, n_wgs);
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vv_gemm4_kernel<VV_EPI_QKV_ROPE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr = true;
-    }
+    static const hipError_t lds = vv_raise_lds_limit(160 * 1024, &vv_gemm4_kernel<VV_EPI_QKV_ROPE>);
+    (void)lds;
     hipLaunchKernelGGL((vv_gemm4_kernel<VV_EPI_QKV_ROPE>), dim3(n_wgs), dim3(512), (size_t)4 * 32 * 1024, s, a);
     return vv_launch_rc(1);
 }
@@ -1210,12 +1191,8 @@ int vv_attn_prefill4_launch(int D, const float* q, const VVRow* rows, const void
     if (out_packed && ((Hq * D) & 31)) return -1;
     const int G = Hq / Hkv;
     const dim3 grid((unsigned)((((int64_t)(R + 63) / 64) * G + 3) / 4), Hkv, 1);     // four (row tile, query head) units per workgroup
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vv_attn_prefill4_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vv_attn_prefill4_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr = true;
-    }
+    static const hipError_t lds = vv_raise_lds_limit(160 * 1024, &vv_attn_prefill4_kernel<128>, &vv_attn_prefill4_kernel<64>);
+    (void)lds;
     const int sm = 4 * 2 * (2 * (D / 32) + D / 16) * 1024;          // 4 stages of K + V fragments
     if (D == 128) hipLaunchKernelGGL((vv_attn_prefill4_kernel<128>), grid, dim3(512), sm, s, q, rows, (const __bf16*)kc, (const __bf16*)vc, R, Hq, Hkv, cache_stride, head_stride, out, (u32x4*)out_packed);
     else hipLaunchKernelGGL((vv_attn_prefill4_kernel<64>), grid, dim3(512), sm, s, q, rows, (const __bf16*)kc, (const __bf16*)vc, R, Hq, Hkv, cache_stride, head_stride, out, (u32x4*)out_packed);

@@ -13,41 +13,10 @@
 //   * RMSNorm: sum(x^2) per row is gathered while staging and applied to the accumulators in the epilogue.
 // Prologues NONE / RMS; epilogues STORE / BIAS / BIAS_GELU / SWIGLU / RESID (what the LM and the tokenizer stages issue).
 #include "vv_common.h"
+#include "vv_device.h"
 #include "vv_launch.h"
 
 namespace {
-
-__device__ __forceinline__ float t_silu(float u) { return u / (1.0f + expf(-u)); }
-__device__ __forceinline__ float t_gelu(float u) { return 0.5f * u * (1.0f + erff(u * 0.70710678118654752440f)); }
-__device__ __forceinline__ float t_wave_sum(float v) {
-    int x = __builtin_bit_cast(int, v);
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, true));
-    x = __builtin_bit_cast(int, v);
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, true));
-    x = __builtin_bit_cast(int, v);
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0x141, 0xF, 0xF, true));
-    x = __builtin_bit_cast(int, v);
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0x140, 0xF, 0xF, true));
-    x = __builtin_bit_cast(int, v);
-    const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(x, 0));
-    const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(x, 16));
-    const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(x, 32));
-    const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(x, 48));
-    return (r0 + r1) + (r2 + r3);
-}
-
-template <int XS>
-__device__ __forceinline__ void t_split4(const float (&v)[4], uint2 (&out)[XS]) {
-    typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-    bf16x4 h, m;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        h[j] = (__bf16)v[j];
-        if constexpr (XS > 1) m[j] = (__bf16)(v[j] - (float)h[j]);
-    }
-    out[0] = __builtin_bit_cast(uint2, h);
-    if constexpr (XS > 1) out[1] = __builtin_bit_cast(uint2, m);
-}
 
 constexpr int BM = 64;          // rows per workgroup (4 row tiles, one staged by each wave)
 constexpr int KC = 256;         // k per staged chunk = 8 k-steps = one float4 per lane and row
@@ -117,7 +86,7 @@ __global__ __launch_bounds__(256) void vv_gemm_tile_kernel(const u32x4* __restri
                 v[0] *= nwv.x; v[1] *= nwv.y; v[2] *= nwv.z; v[3] *= nwv.w;
             }
             uint2 parts[XS];
-            t_split4<XS>(v, parts);
+            vv_split_bf16<XS>(v, parts);
 #pragma unroll
             for (int p = 0; p < XS; ++p)
                 *reinterpret_cast<uint2*>(buf + p * (UU * 4 * GS) + st_off + (wave * 16 + r) * 16) = parts[p];
@@ -184,7 +153,7 @@ __global__ __launch_bounds__(256) void vv_gemm_tile_kernel(const u32x4* __restri
     if constexpr (PRO == VV_PRO_RMS) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const float s = t_wave_sum(ssq[r]);
+            const float s = vv_wave_sum_dpp(ssq[r]);
             if (lane == 0) rs_sh[wave * 16 + r] = rsqrtf(s / (float)pK + a.eps);
         }
         __syncthreads();
@@ -219,10 +188,10 @@ __global__ __launch_bounds__(256) void vv_gemm_tile_kernel(const u32x4* __restri
             if constexpr (EPI == VV_EPI_BIAS) {
                 o[0] += pb.x; o[1] += pb.y; o[2] += pb.z; o[3] += pb.w;
             } else if constexpr (EPI == VV_EPI_BIAS_GELU) {
-                o[0] = t_gelu(o[0] + pb.x); o[1] = t_gelu(o[1] + pb.y); o[2] = t_gelu(o[2] + pb.z); o[3] = t_gelu(o[3] + pb.w);
+                o[0] = vv_gelu_erf(o[0] + pb.x); o[1] = vv_gelu_erf(o[1] + pb.y); o[2] = vv_gelu_erf(o[2] + pb.z); o[3] = vv_gelu_erf(o[3] + pb.w);
             } else if constexpr (EPI == VV_EPI_SWIGLU) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) o[j] = t_silu(o[j]) * (acc[1][rt][j] * rs);
+                for (int j = 0; j < 4; ++j) o[j] = vv_silu(o[j]) * (acc[1][rt][j] * rs);
             } else if constexpr (EPI == VV_EPI_RESID) {
                 const float4 py = *reinterpret_cast<const float4*>(yp);
                 o[0] = py.x + pg.x * (o[0] + pb.x); o[1] = py.y + pg.y * (o[1] + pb.y);
@@ -274,11 +243,8 @@ static int tile_go(const VVGemm& a, hipStream_t s) {
     const int per_wg = 4 * (DUAL ? 1 : 2);
     dim3 grid((n_tiles + per_wg - 1) / per_wg, (a.T + BM - 1) / BM);
     const size_t smem = (size_t)2 * XS * UU * 4 * (BM * 16 + 16) + BM * 4;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vv_gemm_tile_kernel<XS, PRO, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr = true;
-    }
+    static const hipError_t lds = vv_raise_lds_limit(160 * 1024, &vv_gemm_tile_kernel<XS, PRO, EPI>);
+    (void)lds;
     hipLaunchKernelGGL((vv_gemm_tile_kernel<XS, PRO, EPI>), grid, dim3(256), smem, s, a.W, a.W2, a.X, a.Y, a.nw, a.T, a.N, a.K, a.ldx, a.ldy, a);
     return vv_launch_rc(0);
 }

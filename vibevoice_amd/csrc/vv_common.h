@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
@@ -17,6 +18,7 @@ typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 // A (or B) operand of v_mfma_f32_16x16x32_bf16:
 //   lane l holds W[n0 + (l & 15)][k0 + (l >> 4) * 8 + 0..7]
 // tiles are ordered [n_tile][k_tile]; rows >= N and columns >= K are zero.
+// (the element index inside a tile, for device code: vv_packed_index in vv_device.h)
 static inline __host__ __device__ int64_t vv_packed_elems(int N, int K) {
     return (int64_t)((N + 15) / 16) * ((K + 31) / 32) * 512;
 }
@@ -160,6 +162,19 @@ __device__ __forceinline__ int vv_slot_id(const int (&id)[8], int j) {     // se
 #pragma unroll
     for (int i = 1; i < 8; ++i) r = (j == i) ? id[i] : r;
     return r;
+}
+
+// Raise the dynamic-LDS limit of one or more kernels above the 64 KiB default; returns the first error.  A launcher calls it as
+// the initialiser of a function-local `static const hipError_t`: C++11 runs that initialiser once per process and makes
+// concurrent first calls wait for it (generate_interleaved and fork() drive two contexts from two host threads).
+template <class... K>
+static inline hipError_t vv_raise_lds_limit(int bytes, K*... kernels) {
+    hipError_t rc = hipSuccess;
+    for (const void* k : {reinterpret_cast<const void*>(kernels)...}) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (rc == hipSuccess) rc = e;
+    }
+    return rc;
 }
 
 // Launch status of the calling host thread: hipGetLastError() after a launch (it clears the thread's error state, so the code is

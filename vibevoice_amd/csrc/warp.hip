@@ -15,6 +15,7 @@
 //   final    Z and A[v] (top-p only): fp32 partials per thread, combined in fp64 in a fixed order -> bit-identical run to run
 // so a row costs 0 (no sampling), 1 (top-k and/or min-p), 2 (top-p) or 4 (top-k + top-p) passes of 4 V bytes.
 #include "vv_common.h"
+#include "vv_device.h"
 #include "vv_launch.h"
 
 namespace {
@@ -92,13 +93,6 @@ __device__ __forceinline__ void wv_for_row(const WvRow& r, int tid, F&& f) {
     }
     const int t0 = head + 4 * nvec;
     if (tid < V - t0) f(r.at(t0 + tid));
-}
-
-template <class T>
-__device__ __forceinline__ T wv_wave_sum(T x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    return x;
 }
 
 // The digit that holds the k-th largest element: tot[0 .. nb) are the digit counts (LDS), k >= 1 and sum(tot) >= k.  Wave 0 only.
@@ -213,7 +207,7 @@ __global__ __launch_bounds__(WV_THREADS) void vv_warp_valid_kernel(const float* 
         if (need_cnt) {
 #pragma unroll
             for (int v = 0; v < 16; ++v) {
-                const unsigned c = wv_wave_sum(cnt[v]);
+                const unsigned c = vv_wave_sum(cnt[v]);
                 if (lane == 0) red_u[wave][v] = c;
             }
         }
@@ -289,12 +283,12 @@ __global__ __launch_bounds__(WV_THREADS) void vv_warp_valid_kernel(const float* 
         });
         // fp64 from here on, one fixed tree per wave and the waves in order
         {
-            const double t = wv_wave_sum((double)z);
+            const double t = vv_wave_sum((double)z);
             if (lane == 0) red_d[wave][16] = t;
         }
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
-            const double t = wv_wave_sum((double)am[v]);
+            const double t = vv_wave_sum((double)am[v]);
             if (lane == 0) red_d[wave][v] = t;
         }
         __syncthreads();
@@ -343,12 +337,8 @@ extern "C" int vv_warp_valid_launch(const float* logits, const unsigned char* se
     a.top_k = top_k;
     const int kk = top_k > 0 ? (top_k < V ? top_k : V) : 0;
     const bool sel = do_sample && kk > 0 && kk < V && top_p < 1.f;
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&vv_warp_valid_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)WV_HIST_BYTES) != hipSuccess) { (void)hipGetLastError(); return -1; }
-        attr = true;
-    }
+    static const hipError_t lds = vv_raise_lds_limit((int)WV_HIST_BYTES, &vv_warp_valid_kernel);
+    if (lds != hipSuccess) { (void)hipGetLastError(); return -1; }
     hipLaunchKernelGGL(vv_warp_valid_kernel, dim3(n), dim3(WV_THREADS), sel ? WV_HIST_BYTES : 0, s, logits, seen, out, survivors, V, vi, a);
     return vv_launch_rc(0);
 }

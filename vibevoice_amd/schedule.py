@@ -4,8 +4,8 @@ The reference recomputes these scalars on the CPU for every generated frame
 (`noise_scheduler.set_timesteps(N)` + ~30 0-dim tensor ops per solver step,
 vibevoice/schedule/dpm_solver.py:321-423, 669-677, 738-764).  They depend only
 on N, so they are computed once here -- in fp32 with the same formulas and
-operation order -- and handed to `vv_set_schedule`; the device kernel
-(vv_cfg_dpm_kernel) then applies
+operation order -- and handed to `vv_set_schedule`; the device side
+(vv_cfg_dpm_update, csrc/vv_device.h) then applies
 
     x0  = a_i * x - s_i * v                       (v-prediction, :581-584)
     x'  = cs_i * x + c0_i * x0 + c1_i * (x0 - x0_prev)
