@@ -88,6 +88,27 @@ int vv_num_weights(vv_ctx* ctx);
 int vv_weight_info(vv_ctx* ctx, int idx, char* name, int name_cap, int64_t* nelem, int* loaded);
 /* src may be a host or a device pointer; src_dtype 0 = fp32, 1 = bf16. Synchronous. */
 int vv_upload(vv_ctx* ctx, const char* name, const void* src, int src_dtype, int64_t nelem);
+/* ---- device-resident LoRA adapters.  What the reference does by wrapping live modules in peft (lora_loading.py:140-176) and
+ * merging on the host, done on the packed weights in place: the A / B factors stay on the device and a switch is one streaming pass
+ * per target matrix.  Parent contexts only, under vv_upload's guards (refused on a shared child and while shared children exist).
+ * All three are eager launches on `stream`, never captured; no pointer changes, so cached hipGraphs stay valid, and the KV caches
+ * are not touched (K/V computed under other weights is the caller's to discard).  Refusals -- unknown name, a parameter that is not
+ * a plain linear matrix (tables, vectors, the tokenizers' convolutions), r outside [1, 256], a non-finite scale, null or misaligned
+ * (16-byte) operands -- return < 0 before anything is launched.
+ * vv_weight_read: the parameter as it is now, row-major fp32 [N][K] (exact: the storage is bf16).
+ * vv_lora_merge: active = bf16(base + scale * B.A) with the arithmetic of vv_lora_merge_raw.  The FIRST merge of a parameter copies
+ * its packed region into a base snapshot (engine allocator; vv_stat 7 counts the bytes); every merge reads that snapshot, so a merge
+ * is never cumulative: merging adapter Y after adapter X leaves no trace of X.  Parameters that share one packed region (q / k / v,
+ * the adaLN matrices) keep to their own tiles.
+ * vv_lora_reset: the snapshot copied back over the active region; name == NULL: every merged parameter.  A parameter that was
+ * never merged is left alone.  vv_upload to a parameter that has a snapshot makes the uploaded tensor the new base. */
+int vv_weight_read(vv_ctx* ctx, void* stream, const char* name, float* out_dev);
+/* [N][K] of a plain linear matrix parameter, for callers that size a_dev / b_dev / out_dev (Engine.lora_merge and weight_read check
+ * their tensors against it before the call); < 0 for an unknown name or any other kind of parameter.  No device work. */
+int vv_weight_shape(vv_ctx* ctx, const char* name, int* N, int* K);
+int vv_lora_merge(vv_ctx* ctx, void* stream, const char* name, const float* a_dev, const float* b_dev, int r, float scale,
+                  int delta_bf16);
+int vv_lora_reset(vv_ctx* ctx, void* stream, const char* name);
 /* scalar buffers speech_scaling_factor / speech_bias_factor (modeling_vibevoice.py:131-132) */
 int vv_set_speech_factors(vv_ctx* ctx, float scaling, float bias);
 /* ids the constrained sampler may emit (VibeVoiceTokenConstraintProcessor, modeling_vibevoice_inference.py:53-66,405-419) */
@@ -254,6 +275,17 @@ int vv_connect(vv_ctx* ctx, void* stream, int n, const float* latent_dev, const 
 /* pack a row-major fp32 [N][K] matrix into fragment tiles; dst needs vv_packed_bytes(N,K) */
 int64_t vv_packed_bytes(int N, int K);
 int vv_pack_matrix(void* stream, const float* src_dev, void* dst_dev, int N, int K);
+/* The inverse of vv_pack_matrix for a linear matrix: packed bf16 tiles -> row-major fp32 dst_dev [N][K] (exact); padding is skipped.
+ * packed_dev and dst_dev 16-byte aligned.  New surface (tests, vv_weight_read); the reference reads module.weight. */
+int vv_unpack_matrix(void* stream, const void* packed_dev, float* dst_dev, int N, int K);
+/* One launch of the LoRA merge kernel (lora.hip) on raw buffers: dst_packed = bf16(base_packed + scale * B.A) in the packed tile
+ * layout, a_dev [r][K] and b_dev [N][r] fp32, 1 <= r <= 256, scale finite.  delta_bf16 = 0: peft's fp32 merge, delta = scale * (B.A)
+ * in fp32 (rank index ascending, fused multiply-adds), one rounding of the product by scale and one of the sum with the base;
+ * delta_bf16 = 1: a and b rounded to bf16 as they are read and the delta rounded to bf16 before the add (lora.merge_lora's two
+ * merge_dtype paths).  Padding of edge tiles is copied from the base; dst_packed_dev == base_packed_dev is allowed.  A refusal
+ * (bad sizes, null or misaligned pointers) returns < 0 before anything is launched; vv_last_error(NULL) has the text. */
+int vv_lora_merge_raw(void* stream, const void* base_packed_dev, void* dst_packed_dev, int N, int K,
+                      const float* a_dev, const float* b_dev, int r, float scale, int delta_bf16);
 /* Y[T][N] = X[T][K] . W^T with the given prologue/epilogue ids (vv_common.h) */
 int vv_gemm_raw(void* stream, const void* w_packed_dev, const void* w2_packed_dev, const float* x_dev,
                 float* y_dev, int T, int N, int K, int ldx, int ldy, int pro, int epi,
@@ -316,7 +348,8 @@ int vv_profile_replay_family(vv_ctx* ctx, void* stream, int family, int reps, in
  * kernels of the library, because a memset node of a replayed graph was seen to fill with stale words;
  * 6: head-tail seam launches (headtail.hip: final layer + CFG + solver update + the next step's in-projection in one launch) that
  * the last recorded sampler body issued -- n_steps - 1 for one utterance in bf16 mode, 0 where the two-launch form ran; a graph
- * replay keeps the count of its capture */
+ * replay keeps the count of its capture;
+ * 7: bytes of device memory held by the base snapshots of LoRA-merged parameters (vv_lora_merge) */
 int64_t vv_stat(vv_ctx* ctx, int what);
 
 #pragma GCC visibility pop

@@ -6,5 +6,5 @@
 from .engine import Engine, EngineConfig, EngineError  # noqa: F401
 from .modeling import PromptPrefix, VibeVoiceForConditionalGenerationInference, VibeVoiceGenerationOutput  # noqa: F401
 from .modeling_streaming import VibeVoiceStreamingForConditionalGenerationInference  # noqa: F401
-from .lora import load_lora_assets  # noqa: F401
+from .lora import load_lora_assets, read_adapter  # noqa: F401
 from .streamer import AsyncAudioStreamer, AudioStreamer  # noqa: F401

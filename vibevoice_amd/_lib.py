@@ -94,6 +94,12 @@ _SIGS = {
     "vv_connect": (C.c_int, [_P, _P, C.c_int, _P, _P, _P]),
     "vv_packed_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "vv_pack_matrix": (C.c_int, [_P, _P, _P, C.c_int, C.c_int]),
+    "vv_unpack_matrix": (C.c_int, [_P, _P, _P, C.c_int, C.c_int]),
+    "vv_lora_merge_raw": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_float, C.c_int]),
+    "vv_weight_read": (C.c_int, [_P, _P, C.c_char_p, _P]),
+    "vv_weight_shape": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "vv_lora_merge": (C.c_int, [_P, _P, C.c_char_p, _P, _P, C.c_int, C.c_float, C.c_int]),
+    "vv_lora_reset": (C.c_int, [_P, _P, C.c_char_p]),
     "vv_gemm_raw": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                               _P, C.c_float, _P, _P, C.c_int, C.c_int, C.c_int]),
     "vv_gemv_case": (C.c_int, [_P, C.POINTER(VVGemvCase), C.c_int, C.POINTER(C.c_int)]),

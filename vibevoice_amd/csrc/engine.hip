@@ -1,5 +1,6 @@
 // engine.hip -- host side of libvvhip.so: context create / destroy, allocators, parameter registry and upload, hipGraph
-// capture / replay cache, connectors.  The op orchestration lives in engine_lm / engine_head / engine_codec / engine_prof.hip.
+// capture / replay cache, connectors.  The op orchestration lives in engine_lm / engine_head / engine_codec / engine_prof.hip,
+// the device-resident LoRA adapters (base snapshots, merge, reset, read-back) in engine_lora.hip.
 #include "engine_ctx.h"
 
 // declared (and explained) in engine_ctx.h; defined here and nowhere else
@@ -472,6 +473,7 @@ extern "C" int vv_upload(vv_ctx* ctx, const char* name, const void* src, int src
         else VVCHK(vv_cvt_launch(dsrc, w.dev, nelem, 1, st));
     } else if (w.kind == W_MAT) {
         VVCHK(vv_pack_launch(dsrc, src_dtype, w.dev, w.N, w.K, w.pk, w.Cin, w.Cout, w.ksz, w.stride, st));
+        VVTRY(lora_rebase(ctx, it->second, st));      // a parameter with a LoRA base snapshot: the upload is the new base
     } else {
         // fp32 vectors
         const float* f32 = (const float*)dsrc;
@@ -572,6 +574,7 @@ extern "C" int64_t vv_stat(vv_ctx* ctx, int what) {
         case 5: return ctx->foreign_nodes;        // nodes of the captured graphs that are not kernel launches (expected: 0)
         case 4: return ctx->capture_fallbacks;    // stream captures that did not close and ran eagerly instead (multi-threaded lanes)
         case 6: return ctx->seam_launches;        // head-tail seam launches of the last recorded sampler body
+        case 7: return ctx->lora_base_bytes;      // bytes held by the base snapshots of LoRA-merged parameters
         default: return (int64_t)ctx->graphs.size();
     }
 }

@@ -164,6 +164,11 @@ struct vv_ctx {
     int64_t foreign_nodes = 0;        // nodes of captured graphs that are not kernel launches (memset / memcpy nodes: none must exist, see misc.hip's copy kernels)
     int64_t capture_fallbacks = 0; char last_capture_issue[256] = "";     // stream captures that fell back to an eager run (graphed())
     std::vector<std::pair<void*, size_t>> wallocs; size_t wshare_i = 0;
+    // device-resident LoRA adapters (engine_lora.hip): parameter index -> a copy of its packed region taken at its first merge.  Every
+    // merge writes active = f(snapshot, a, b); vv_lora_reset copies the snapshot back; vv_upload refreshes it (the upload is the new base)
+    struct LoraBase { void* snap; size_t bytes; bool merged; };
+    std::map<int, LoraBase> lora_base;
+    int64_t lora_base_bytes = 0;      // vv_stat 7
     int64_t launches = 0;
     int64_t seam_launches = 0;        // head-tail seam launches the last recorded sampler body issued (vv_stat 6; a replay keeps its capture's count)
     // optional per-GEMM-launch hipEvent timing (vv_profile_begin/end)
@@ -226,6 +231,7 @@ VVGemv16p p16_args(const void* W, const void* W2, const void* Xp, float* Y, void
 void nan_probe(vv_ctx* ctx, hipStream_t st, const char* name, const void* p, size_t n);                                      // engine_prof.hip
 void nan_probe_report(vv_ctx* ctx, hipStream_t st, const char* what);
 int gemm_prof(vv_ctx* ctx, const VVGemm& g, hipStream_t st);
+int lora_rebase(vv_ctx* ctx, int widx, hipStream_t st);                                                                       // engine_lora.hip
 
 // One GEMM launch of an op body (`ctx` and `st` in scope).  ctx->launches counts these and what the bodies add by hand; some launches
 // (vv_copy_launch, vv_sampler_init_launch, ...) are not counted, and bench.py reports the figure as it is: do not "fix" it in passing.

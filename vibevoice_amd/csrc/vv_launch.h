@@ -85,4 +85,7 @@ int vv_gemv_ok(const VVGemm* a);
 int vv_gemv_launch(VVGemm a, int xs, hipStream_t s, int* form);      // form: the compiled form its launcher picked (tests)
 int vv_tile_ok(const VVGemm* a, int xs);
 int vv_tile_launch(VVGemm a, int xs, hipStream_t s);
+int vv_lora_merge_launch(const void* base, void* dst, int N, int K, const float* a, const float* b, int r, float scale, int delta_bf16,
+                         hipStream_t s);
+int vv_unpack_launch(const void* packed, float* dst, int N, int K, hipStream_t s);
 }

@@ -553,6 +553,125 @@ class Engine:
         self.sync()
         return out
 
+    # ------------------------------------------------------------------ device-resident LoRA adapters
+    MERGE_DTYPES = ("float32", "bfloat16")
+
+    def _dev_tensor(self, what, name, t, numel, dtype=torch.float32, unaligned_ok=False):
+        """an operand is checked BEFORE the call: a wrong argument must fail here, not as an out-of-bounds access on the GPU"""
+        if not isinstance(t, torch.Tensor) or t.device != self.device:
+            raise ValueError(f"{what}: {name} is not a tensor on {self.device}")
+        if t.dtype != dtype:
+            raise ValueError(f"{what}: {name} is {t.dtype}, expected {dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: {name} is not contiguous")
+        if t.data_ptr() % 16 and not unaligned_ok:
+            raise ValueError(f"{what}: {name} is not 16-byte aligned")
+        if t.numel() < numel:
+            raise ValueError(f"{what}: {name} holds {t.numel()} elements, the launch addresses {numel}")
+
+    @staticmethod
+    def _shape_ints(what, **ints):
+        for k, v in ints.items():
+            if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v < 1 or v >= (1 << 30):
+                raise ValueError(f"{what}: {k} = {v!r} is not an int in [1, 2^30)")
+
+    def _delta_flag(self, what, merge_dtype):
+        if merge_dtype not in self.MERGE_DTYPES:
+            raise ValueError(f"{what}: merge_dtype must be one of {self.MERGE_DTYPES}, got {merge_dtype!r}")
+        return 1 if merge_dtype == "bfloat16" else 0
+
+    def _raw_err(self):
+        s = self.lib.vv_last_error(None)
+        return s.decode() if s else "?"
+
+    def _mat_shape(self, name):
+        """(N, K) of a plain linear matrix parameter as the engine packs it, or None (unknown name, another kind: the library
+        refuses those with its own text)"""
+        tab = self.__dict__.setdefault("_mat_shapes", {})
+        if name not in tab:
+            n, k = C.c_int(), C.c_int()
+            tab[name] = (n.value, k.value) if self.lib.vv_weight_shape(self._ctx, name.encode(), C.byref(n), C.byref(k)) == 0 else None
+        return tab[name]
+
+    def _after_producer(self):
+        """operands made on the caller's current torch stream (fills, copies, .to(device)) are complete before the engine stream reads
+        or overwrites them: an event wait on the device, no host synchronisation"""
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+
+    def unpack_matrix(self, packed: torch.Tensor, N: int, K: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The inverse of pack_matrix: packed bf16 tiles of a linear [N, K] matrix -> row-major fp32 (exact).  out: an [N, K] fp32
+        tensor to write into (every element is written); default: a new one.  Asynchronous on the engine stream."""
+        self._shape_ints("unpack_matrix", N=N, K=K)
+        self._dev_tensor("unpack_matrix", "packed", packed, int(self.lib.vv_packed_bytes(N, K)), torch.uint8)
+        if out is None:
+            with torch.cuda.stream(self.stream):
+                out = torch.empty(N, K, dtype=torch.float32, device=self.device)
+        self._dev_tensor("unpack_matrix", "out", out, N * K)
+        self._after_producer()
+        if self.lib.vv_unpack_matrix(self._s, self._p(packed), self._p(out), int(N), int(K)) != 0:
+            raise EngineError("vv_unpack_matrix failed: " + self._raw_err())
+        return out
+
+    def lora_merge_raw(self, base_packed: torch.Tensor, dst_packed: torch.Tensor, N: int, K: int, a: torch.Tensor, b: torch.Tensor,
+                       scale: float, merge_dtype: str = "float32", unaligned_ok=()):
+        """One launch of the LoRA merge kernel on raw buffers: dst_packed = bf16(base_packed + scale * b @ a) in the packed layout
+        (a [r, K], b [N, r] fp32; dst_packed may be base_packed).  merge_dtype as lora.merge_lora.  Every tensor is checked before
+        the call (unaligned_ok names operands whose alignment check is left to the library).  Asynchronous: the caller syncs."""
+        what = "lora_merge_raw"
+        self._shape_ints(what, N=N, K=K)
+        flag = self._delta_flag(what, merge_dtype)
+        if not isinstance(a, torch.Tensor) or not isinstance(b, torch.Tensor) or a.dim() != 2 or b.dim() != 2:
+            raise ValueError(f"{what}: a and b are 2-D tensors")
+        r = int(a.shape[0])
+        if tuple(a.shape) != (r, K) or tuple(b.shape) != (N, r):
+            raise ValueError(f"{what}: a {tuple(a.shape)} / b {tuple(b.shape)} do not factor an [{N}, {K}] matrix")
+        nb = int(self.lib.vv_packed_bytes(N, K))
+        self._dev_tensor(what, "base_packed", base_packed, nb, torch.uint8, "base_packed" in unaligned_ok)
+        self._dev_tensor(what, "dst_packed", dst_packed, nb, torch.uint8, "dst_packed" in unaligned_ok)
+        self._dev_tensor(what, "a", a, r * K, unaligned_ok="a" in unaligned_ok)
+        self._dev_tensor(what, "b", b, N * r, unaligned_ok="b" in unaligned_ok)
+        self._after_producer()
+        if self.lib.vv_lora_merge_raw(self._s, self._p(base_packed), self._p(dst_packed), int(N), int(K), self._p(a), self._p(b), r,
+                                      float(scale), flag) != 0:
+            raise EngineError("vv_lora_merge_raw failed: " + self._raw_err())
+
+    def weight_read(self, name: str, shape: Sequence[int]) -> torch.Tensor:
+        """A plain linear parameter as it is NOW (base, or base + the merged adapter): row-major fp32 `shape` = [N, K], exact (the
+        storage is bf16).  The caller states the shape (the reference checkpoint's); it is checked against the engine's (vv_weight_shape)."""
+        nk = self._mat_shape(name)
+        if nk is not None and tuple(int(v) for v in shape) != nk:
+            raise ValueError(f"weight_read({name}): shape {tuple(shape)}, the parameter is {nk}")
+        with torch.cuda.stream(self.stream):
+            out = torch.empty(*[int(v) for v in shape], dtype=torch.float32, device=self.device)
+        self._chk(self.lib.vv_weight_read(self._ctx, self._s, name.encode(), self._p(out)), f"vv_weight_read({name})")
+        return out
+
+    def lora_merge(self, name: str, a: torch.Tensor, b: torch.Tensor, scale: float, merge_dtype: str = "float32", unaligned_ok=()):
+        """active(name) = bf16(base + scale * b @ a), in place in the packed weights (a [r, K], b [N, r] fp32 on the engine device).
+        The first merge of a parameter snapshots its base; a merge is never cumulative.  Eager on the engine stream; the caller
+        syncs and keeps a and b alive until then.  Cached hipGraphs stay valid (no pointer changes)."""
+        what = f"lora_merge({name})"
+        flag = self._delta_flag(what, merge_dtype)
+        if not isinstance(a, torch.Tensor) or not isinstance(b, torch.Tensor) or a.dim() != 2 or b.dim() != 2 or a.shape[0] != b.shape[1]:
+            raise ValueError(f"{what}: a [r, K] and b [N, r] are 2-D tensors with one r")
+        r, K, N = int(a.shape[0]), int(a.shape[1]), int(b.shape[0])
+        nk = self._mat_shape(name)
+        if nk is not None and (N, K) != nk:          # the library takes N and K from its registry: a and b must cover them
+            raise ValueError(f"{what}: b @ a is [{N}, {K}], the parameter is {list(nk)}")
+        self._dev_tensor(what, "a", a, r * K, unaligned_ok="a" in unaligned_ok)
+        self._dev_tensor(what, "b", b, N * r, unaligned_ok="b" in unaligned_ok)
+        self._after_producer()
+        self._chk(self.lib.vv_lora_merge(self._ctx, self._s, name.encode(), self._p(a), self._p(b), r, float(scale), flag),
+                  f"vv_lora_merge({name})")
+        if name.startswith("head."):
+            self._n_steps = None             # as upload(): the timestep-embedding table is derived from head.t_embedder
+
+    def lora_reset(self, name: Optional[str] = None):
+        """The base snapshot copied back over the parameter (None: every merged parameter); a parameter never merged is left alone."""
+        self._chk(self.lib.vv_lora_reset(self._ctx, self._s, name.encode() if name is not None else None), f"vv_lora_reset({name})")
+        if name is None or name.startswith("head."):
+            self._n_steps = None
+
     def gemm3_raw(self, wp, x, y, N, K, epi=0, w2p=None, nw=None, eps=1e-6, bias=None, ksplit=True):
         """the prefill GEMM (prefill.hip) on fp32 rows x [T, K] -> y [T, N]; ksplit=False computes every tile whole"""
         T = x.shape[0]

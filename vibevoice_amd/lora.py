@@ -132,6 +132,65 @@ def resolve_adapter_root(checkpoint_dir: str) -> str:
     return os.path.join(p, "lora") if os.path.isdir(os.path.join(p, "lora")) else p
 
 
+AdapterAssets = Dict[str, Tuple[torch.Tensor, torch.Tensor, float]]
+
+
+def _full_tensor_files(adapter_root: str):
+    return [p for p in (os.path.join(adapter_root, "diffusion_head", "diffusion_head_full.bin"), os.path.join(adapter_root, "diffusion_head_full.bin"),
+                        os.path.join(adapter_root, "acoustic_connector", "pytorch_model.bin"),
+                        os.path.join(adapter_root, "semantic_connector", "pytorch_model.bin")) if os.path.exists(p)]
+
+
+def read_adapter(checkpoint_dir: str, expected: Optional[Dict[str, int]] = None) -> AdapterAssets:
+    """The LoRA factors under checkpoint_dir as {engine parameter name: (A fp32 [r, in], B fp32 [out, r], scale)}, for the language
+    model adapter and the diffusion-head adapter -- what model.load_adapter() keeps on the device.  No base checkpoint is involved:
+    the merge W' = W + scale * B @ A happens on the packed weights (Engine.lora_merge).  expected: {engine parameter name: element
+    count} (Engine.expected_weights()); given, every pair is checked against its parameter.
+
+    Raises ValueError, naming the file or key, for what only the host path can do -- use load_lora_assets for those: full-tensor
+    assets (diffusion_head_full.bin, the connectors' pytorch_model.bin), fan_in_fan_out adapters, a pair that does not fit its
+    parameter, non-finite factors."""
+    from .engine import map_param_name
+    root = resolve_adapter_root(checkpoint_dir)
+    if not os.path.isdir(root):
+        raise FileNotFoundError(f"Adapter directory not found: {root}")
+    out: AdapterAssets = {}
+    found = False
+    for sub, prefix, strip in (("", LM_PREFIX, ""), ("diffusion_head", HEAD_PREFIX, "base.")):
+        d = os.path.join(root, sub) if sub else root
+        ad = _adapter(d)
+        if ad is None:
+            continue
+        found = True
+        cfg, sd = ad
+        cfg_p = os.path.join(d, "adapter_config.json")
+        if cfg.get("fan_in_fan_out"):
+            raise ValueError(f"{cfg_p}: fan_in_fan_out adapters are not merged on the device; use load_lora_assets")
+        scale = lora_scale(cfg)
+        for k, (a, b) in sorted(lora_pairs(sd, prefix, strip=strip).items()):
+            name = map_param_name(k)
+            a, b = a.detach().to(torch.float32).contiguous(), b.detach().to(torch.float32).contiguous()
+            if a.dim() != 2 or b.dim() != 2 or a.shape[0] != b.shape[1]:
+                raise ValueError(f"{d}: LoRA pair of {k}: A {tuple(a.shape)} and B {tuple(b.shape)} do not share a rank; use load_lora_assets")
+            if name is None:
+                raise ValueError(f"{d}: LoRA pair of {k}: not an engine parameter; use load_lora_assets")
+            if expected is not None:
+                if name not in expected:
+                    raise ValueError(f"{d}: LoRA pair of {k}: the engine has no such parameter; use load_lora_assets")
+                if int(b.shape[0]) * int(a.shape[1]) != int(expected[name]):
+                    raise ValueError(f"{d}: LoRA pair of {k}: B @ A is [{b.shape[0]}, {a.shape[1]}], the engine's parameter {name} holds "
+                                     f"{expected[name]} elements; use load_lora_assets")
+            if not (bool(torch.isfinite(a).all()) and bool(torch.isfinite(b).all())):
+                raise ValueError(f"{d}: LoRA pair of {k}: non-finite factors; use load_lora_assets")
+            out[name] = (a, b, scale)
+    full = _full_tensor_files(root)
+    if full:
+        raise ValueError(f"{full[0]}: a full-tensor asset cannot stay resident as LoRA factors; use load_lora_assets for this checkpoint")
+    if not found:
+        raise FileNotFoundError(f"no adapter_config.json + adapter_model.* under {root}")
+    return out
+
+
 def planned_updates(adapter_root: str, base: Callable[[str], torch.Tensor], merge_dtype: str = "float32") -> Iterator[Tuple[str, torch.Tensor, str]]:
     """Yields (reference key, tensor to upload, kind) for everything found under adapter_root.
     base(key) returns the base checkpoint tensor for a LoRA target; merge_dtype: see merge_lora."""

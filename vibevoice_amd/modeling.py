@@ -639,6 +639,9 @@ class VibeVoiceForConditionalGenerationInference:
         # weights epoch: [count of parameter updates since construction]; one box per weight copy (forks share their parent's).  A
         # PromptPrefix remembers the value it was computed under
         self._epoch_box = [0]
+        # device-resident LoRA adapters: {name: (merge_dtype, {engine parameter: (A, B, scale)})} with A / B on the engine device
+        self._adapters = {}
+        self._active_adapter = None
 
     # ------------------------------------------------------------------ construction
     @classmethod
@@ -780,6 +783,73 @@ class VibeVoiceForConditionalGenerationInference:
         """One parameter by its ENGINE name ("lm.layers.0.self_attn.q_proj.weight", include/vvhip.h); K/V computed before it is stale."""
         self.engine.upload(name, tensor)
         self._bump_weights_epoch()
+
+    # ------------------------------------------------------------------ device-resident LoRA adapters
+    def load_adapter(self, name: str, checkpoint_dir: str, merge_dtype: str = "float32"):
+        """Reads the LoRA adapter(s) under checkpoint_dir (lora.read_adapter: language model and diffusion head) and keeps their A / B
+        factors on the device under `name`; nothing is merged until set_adapter(name).  merge_dtype: where the delta is rounded, as
+        lora.merge_lora.  Memory: the factors, plus -- from the first set_adapter on -- one bf16 base snapshot of every matrix an
+        adapter has touched (engine.stat(7) bytes).  Needs no checkpoint on disk for the base model."""
+        from . import lora as _lora
+        if not isinstance(name, str) or not name:
+            raise ValueError("load_adapter: name is a non-empty string")
+        if merge_dtype not in _lora.MERGE_DTYPES:
+            raise ValueError(f"merge_dtype must be one of {_lora.MERGE_DTYPES}, got {merge_dtype!r}")
+        if name == self._active_adapter:
+            raise ValueError(f"adapter {name!r} is active: set_adapter(None) or switch before loading another one under its name")
+        expected = self.engine.expected_weights() if hasattr(self.engine, "expected_weights") else None
+        pairs = _lora.read_adapter(checkpoint_dir, expected)
+        shape_of = getattr(self.engine, "_mat_shape", None)
+        for k, (a, b, _) in pairs.items():                 # the exact [out, in] of the packed matrix, not only its element count
+            nk = shape_of(k) if shape_of is not None else None
+            if nk is not None and (int(b.shape[0]), int(a.shape[1])) != nk:
+                raise ValueError(f"{checkpoint_dir}: LoRA pair of {k}: B @ A is [{b.shape[0]}, {a.shape[1]}], the parameter is {list(nk)}; "
+                                 "use load_lora_assets")
+        self._register_adapter(name, pairs, merge_dtype)
+        return sorted(pairs)
+
+    def _register_adapter(self, name, pairs, merge_dtype):
+        """pairs: {engine parameter name: (A fp32 [r, in], B fp32 [out, r], scale)}, as lora.read_adapter returns them"""
+        dev = self.engine.device
+        self._adapters[name] = (merge_dtype, {k: (a.to(dev, torch.float32).contiguous(), b.to(dev, torch.float32).contiguous(), float(sc))
+                                              for k, (a, b, sc) in pairs.items()})
+
+    def set_adapter(self, name: Optional[str]):
+        """Switches the merged adapter in place on the device; None restores the base model.  Calls close_lanes() first (shared
+        engine contexts hold snapshots derived from the parameters; lanes are forked again on the next generate_interleaved).
+        Parameters the outgoing adapter touched and the incoming one does not are reset to their base; the incoming pairs are merged
+        from the base snapshots (never cumulative).  All launches go on the engine stream, with one sync at the end.  The packed
+        weights do not move, so captured hipGraphs stay valid; the weights epoch is bumped, so a PromptPrefix built under other
+        weights is refused.  Setting the adapter that is already active does nothing.  One batch has one adapter: call between
+        generate() calls."""
+        if name is not None and name not in self._adapters:
+            raise KeyError(name)
+        if name == self._active_adapter:
+            return
+        self.close_lanes()
+        eng = self.engine
+        old = self._adapters[self._active_adapter][1] if self._active_adapter is not None else {}
+        merge_dtype, new = self._adapters[name] if name is not None else ("float32", {})
+        for k in old:
+            if k not in new:
+                eng.lora_reset(k)
+        for k, (a, b, sc) in new.items():
+            eng.lora_merge(k, a, b, sc, merge_dtype)
+        eng.sync()
+        self._active_adapter = name
+        self._bump_weights_epoch()
+
+    def unload_adapter(self, name: str):
+        """Drops a resident adapter's factors (the active one must be switched away from first).  Base snapshots stay."""
+        if name not in self._adapters:
+            raise KeyError(name)
+        if name == self._active_adapter:
+            raise ValueError(f"adapter {name!r} is active: set_adapter(None) or switch first")
+        del self._adapters[name]
+
+    @property
+    def active_adapter(self) -> Optional[str]:
+        return self._active_adapter
 
     def load_state_dict(self, state_dict, strict: bool = True):
         """A (partial) state dict keyed like the reference checkpoint, uploaded into the live engine (which re-packs); returns
