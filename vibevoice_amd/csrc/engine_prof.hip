@@ -64,7 +64,7 @@ int gemm_prof(vv_ctx* ctx, const VVGemm& g, hipStream_t st) {
     ctx->prof_n++;
     ctx->prof_bytes += gemm_bytes(g);
     // which kernel vv_gemm_launch picks (gemm.hip): MFMA tile GEMM, decode GEMV, or the general kernel
-    const bool is_gemv = !vv_tile_ok(&g, ctx->c.xsplit) && g.ksplit <= 0 && vv_gemv_ok(&g) && (g.T <= 4 || ctx->c.xsplit <= 2);
+    const bool is_gemv = vv_gemm_route(&g, ctx->c.xsplit) == VV_ROUTE_GEMV;
     ctx->prof_rec.push_back({g.T, g.N, g.K, g.pro, g.epi, g.W2 ? 1 : 0, gemm_bytes(g), is_gemv});
     if (is_gemv) { ctx->prof_gemv.push_back(g); ctx->prof_gemv_bytes += gemm_bytes(g); }
     return r;
@@ -76,7 +76,7 @@ int gemm_tl(vv_ctx* ctx, VVGemm g, hipStream_t st) {
         if (hipMalloc(&ctx->tl_base, (size_t)TL_MAX * TL_STRIDE * 8) != hipSuccess) return -9;
         hipMemset(ctx->tl_base, 0, (size_t)TL_MAX * TL_STRIDE * 8);
     }
-    const bool gv = vv_gemv_ok(&g) && (g.T <= 4 || ctx->c.xsplit <= 2);
+    const bool gv = vv_gemm_route(&g, ctx->c.xsplit) == VV_ROUTE_GEMV;
     const bool want = gv ? ((g.T <= 4 || g.T != 16 || g.N > 16384) && (g.N + 15) / 16 <= 3200) : (g.T > 16);
     if (ctx->tl_base && ctx->tl_idx < TL_MAX && want) {
         g.dbg = ctx->tl_base + (size_t)ctx->tl_idx * TL_STRIDE;
@@ -125,7 +125,7 @@ extern "C" int vv_gemv_case(void* stream, const vv_gemv_case_args* c, int xsplit
     if (!vv_gemv_ok(&g)) return VV_GEMV_REFUSED;
     int form[5] = {0, 0, 0, 0, 0};
     const int r = vv_gemv_launch(g, xsplit, (hipStream_t)stream, form);
-    if (r == -3) return VV_GEMV_REFUSED;
+    if (r == VV_RC_NO_FORM) return VV_GEMV_REFUSED;
     if (r == 0 && form_out) for (int j = 0; j < 5; ++j) form_out[j] = form[j];
     return r;
 }

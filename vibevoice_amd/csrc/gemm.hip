@@ -447,24 +447,12 @@ static int pow2_floor(int v) { int p = 1; while (p * 2 <= v) p *= 2; return p; }
 
 // Chooses the kernel and its decomposition.  `xs` in {1,2,3}.
 extern "C" int vv_gemm_launch(VVGemm a, int xs, hipStream_t s) {
-    if (a.sl_n > 0) {                  // slot-batched rows: the MFMA tile form for tall row sets, else the 16-row GEMV form
-        if (vv_tile_ok(&a, xs)) {
-            const int r = vv_tile_launch(a, xs, s);
-            if (r != -3) return r;
-        }
-        if (xs > 2 || !vv_gemv_ok(&a)) return -4;
-        const int r = vv_gemv_launch(a, xs, s, nullptr);
-        return r == -3 ? -4 : r;
+    switch (vv_gemm_route(&a, xs)) {
+    case VV_ROUTE_TILE: return vv_tile_launch(a, xs, s);
+    case VV_ROUTE_GEMV: return vv_gemv_launch(a, xs, s, nullptr);
+    case VV_ROUTE_NONE: return VV_RC_NO_KERNEL;
+    default: break;                    // VV_ROUTE_GENERAL: the kernel of this file
     }
-    if (vv_tile_ok(&a, xs)) {      // tall activations: MFMA tile GEMM (tile.hip)
-        const int r = vv_tile_launch(a, xs, s);
-        if (r != -3) return r;
-    }
-    if (a.ksplit <= 0 && vv_gemv_ok(&a) && (a.T <= 4 || xs <= 2)) {
-        const int r = vv_gemv_launch(a, xs, s, nullptr);
-        if (r != -3) return r;                 // -3: no instantiation for this (pair, rows, split mode): general kernel
-    }
-    if (a.kgrid > 1 || a.n_xa > 0 || a.n_ya > 0) return -4;      // part tensors exist only on the decode GEMV path
     const int n_tiles = (a.N + 15) / 16;
     const int k_tiles = (a.K + 31) / 32;
     const int t_tiles = (a.T + 15) / 16;
@@ -508,7 +496,7 @@ extern "C" int vv_gemm_launch(VVGemm a, int xs, hipStream_t s) {
         else launch_t<NT_, 3, DUAL_, WPB_, MAXR_, VEC_>(a, grid, smem, s);        \
     } while (0)
     if (!vec) {
-        if (dual) return -3;                       // SwiGLU operands are always aligned on this path
+        if (dual) return VV_RC_NO_FORM;            // SwiGLU operands are always aligned on this path
         VV_XS(1, false, 4, 16, false);             // generic (odd K / unaligned rows): encoder stem, tiny test shapes
     } else if (wpb == 8) {
         if (dual) VV_XS(1, true, 8, 4, true);

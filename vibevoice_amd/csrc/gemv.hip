@@ -16,6 +16,8 @@
 //   * the epilogue wave issues its residual / bias / gate loads at kernel entry;
 //   * sum(x^2) by DPP row reductions + readlane (no LDS permutes: vv_wave_sum_dpp);
 //   * split-K partials go to a dedicated LDS region: a single barrier.
+#include <array>
+#include <utility>
 #include "vv_common.h"
 #include "vv_device.h"
 #include "vv_launch.h"
@@ -437,195 +439,40 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemv_kernel(const u32x4* __restri
 
 }  // namespace
 
-static bool gemv_combo_ok(int pro, int epi, bool wide);
-// pairs with a slot-batched form: strided conv / transposed conv (bias), FFN1 (RMSNorm + bias + GELU), FFN2 (layer scale + residual)
-#define VV_GEMV_SL(X) X(VV_PRO_NONE, VV_EPI_BIAS) X(VV_PRO_NONE, VV_EPI_RESID) X(VV_PRO_RMS, VV_EPI_BIAS_GELU)
-static bool gemv_parts_ok(int pro, int epi, bool xside);
-// Eligibility: decode rows, aligned operands, 32-bit offsets, a specialised (prologue, epilogue) pair.
-extern "C" int vv_gemv_ok(const VVGemm* a) {
-    if (a->T < 1) return 0;
-    if (!gemv_combo_ok(a->pro, a->epi, a->T > 4 || a->sl_n > 0)) return 0;
-    if (a->sl_n > 0) {      // slot-batched rows: the three tokenizer pairs, plain operands, 32-bit offsets inside every slot buffer
-        if (a->sl_n > 8 || a->sl_T < 1 || a->T != a->sl_n * a->sl_T || a->sl_x < 0 || a->sl_y < 0 || (a->sl_x & 3) || (a->sl_y & 3)) return 0;
-        if (a->kgrid > 1 || a->n_xa || a->n_ya || a->x_row_mod > 0 || a->add_rows_per_vec > 0) return 0;
-        bool pair = false;
-#define X(P, E) if (a->pro == P && a->epi == E) pair = true;
-        VV_GEMV_SL(X)
-#undef X
-        if (!pair) return 0;
-        for (int j = 0; j < a->sl_n; ++j)
-            if (a->sl_id[j] < 0 || (int64_t)a->sl_id[j] * a->sl_x + (int64_t)a->sl_T * a->ldx >= (1LL << 30) ||
-                (int64_t)a->sl_id[j] * a->sl_y + (int64_t)a->sl_T * a->ldy >= (1LL << 30)) return 0;
+extern "C" int vv_gemv_ok(const VVGemm* a) { return vv_gemv_eligible(a); }
+
+// One kernel per (family, pair of the family, xs <= the family's xs_max) of gemv_plan.h -- the whole set of instantiations.
+using GemvKernel = void (*)(const u32x4*, const u32x4*, const float*, float*, const float*, int, int, int, int, int, const VVGemm);
+template <int F, int I, int XS>
+static constexpr GemvKernel gemv_kernel_at() {
+    constexpr const VVGemvFamily& f = vv_gemv_families[F];
+    if constexpr (I < f.n && XS <= f.xs_max) return vv_gemv_kernel<XS, f.pair[I].pro, f.pair[I].epi, f.mr, f.wpb, f.parts, f.sl>;
+    else return nullptr;
+}
+template <size_t... J>      // J = (family * VV_GEMV_MAX_PAIRS + pair) * VV_GEMV_MAX_XS + xs - 1
+static constexpr std::array<GemvKernel, sizeof...(J)> gemv_kernel_table(std::index_sequence<J...>) {
+    return {gemv_kernel_at<J / (VV_GEMV_MAX_PAIRS * VV_GEMV_MAX_XS), J / VV_GEMV_MAX_XS % VV_GEMV_MAX_PAIRS, J % VV_GEMV_MAX_XS + 1>()...};
+}
+static const auto gemv_kernels = gemv_kernel_table(std::make_index_sequence<VV_GF_COUNT * VV_GEMV_MAX_PAIRS * VV_GEMV_MAX_XS>{});
+
+static GemvKernel gemv_kernel(const VVGemvForm& form, int pro, int epi) {
+    for (int f = 0; f < VV_GF_COUNT; ++f) {
+        const VVGemvFamily& fam = vv_gemv_families[f];
+        if (fam.mr != form.mr || fam.wpb != form.wpb || fam.parts != form.parts || fam.sl != form.sl || form.xs > fam.xs_max) continue;
+        for (int i = 0; i < fam.n; ++i)
+            if (fam.pair[i].pro == pro && fam.pair[i].epi == epi) return gemv_kernels[(f * VV_GEMV_MAX_PAIRS + i) * VV_GEMV_MAX_XS + form.xs - 1];
     }
-    if ((a->x_row_mod > 0 || a->add_rows_per_vec > 0) && a->pro != VV_PRO_ADD_SILU) return 0;
-    // CFG + solver epilogue: row r (cond) meets row r + n_cfg (uncond) by a lane shuffle inside ONE 16-row tile, and z / x0p are
-    // indexed by the tile-local row -- so the launch is exactly the 2 * n_cfg rows of one tile (decode forms: n_cfg <= 2)
-    if (a->epi == VV_EPI_CFG_DPM && (a->n_cfg < 1 || a->T != 2 * a->n_cfg || a->T > 16 || !a->z || !a->x0p || !a->coef)) return 0;
-    if (a->pro == VV_PRO_NORMDW) {     // one row, whole K inside every workgroup, every operand present and 16-B aligned
-        if (a->T != 1 || a->sl_n > 0 || a->kgrid > 1 || a->n_xa || a->n_ya || !a->dw_hist || !a->dw_w || !a->dw_b || !a->dw_gamma ||
-            !a->dw_nw || !a->dw_xout || !a->dw_hnew || a->dw_xout == a->X) return 0;
-        if ((((uintptr_t)a->dw_hist) | ((uintptr_t)a->dw_w) | ((uintptr_t)a->dw_b) | ((uintptr_t)a->dw_gamma) | ((uintptr_t)a->dw_nw) |
-             ((uintptr_t)a->dw_xout) | ((uintptr_t)a->dw_hnew)) & 15) return 0;
-        if ((int64_t)7 * a->K >= (1LL << 30)) return 0;
-    }
-    if ((a->K & 3) || (a->ldx & 3) || (((uintptr_t)a->X) & 15)) return 0;
-    if (a->pro == VV_PRO_RMS_MOD && (a->ld_mod & 3)) return 0;
-    if (a->nw && (((uintptr_t)a->nw) & 15)) return 0;
-    if (a->K < 32) return 0;
-    if ((int64_t)a->T * a->ldy >= (1LL << 30) || (int64_t)a->T * a->ldx >= (1LL << 30)) return 0;
-    if ((a->N & 3) || (a->ldy & 3)) return 0;
-    if ((((uintptr_t)a->Y) & 15) || (a->bias && (((uintptr_t)a->bias) & 15))) return 0;
-    if (a->nscale && (((uintptr_t)a->nscale) & 15)) return 0;
-    if (a->epi == VV_EPI_GATED_RESID && ((a->ld_gate & 3) || (((uintptr_t)a->gate) & 15))) return 0;
-    if (a->pro == VV_PRO_RMS_MOD && ((((uintptr_t)a->mod_scale) & 15) || (((uintptr_t)a->mod_shift) & 15))) return 0;
-    if (a->pro == VV_PRO_ADD_SILU && (((uintptr_t)a->addvec) & 15)) return 0;
-    if (a->kgrid > 1 && (a->T > 4 || a->kgrid != 3 || a->pro != VV_PRO_NONE || !a->yparts || (a->part_stride & 3) ||
-                         (a->epi != VV_EPI_RESID && a->epi != VV_EPI_GATED_RESID) || (((uintptr_t)a->yparts) & 15))) return 0;
-    if ((a->n_xa > 0 && (!a->xa || (((uintptr_t)a->xa) & 15))) || (a->n_ya > 0 && (!a->ya || (((uintptr_t)a->ya) & 15)))) return 0;
-    if ((a->n_xa != 0 && a->n_xa != 2) || (a->n_ya != 0 && a->n_ya != 2) || (a->n_xa && a->n_ya)) return 0;
-    if ((a->n_xa || a->n_ya) && ((a->part_stride & 3) || a->T > 4 || !gemv_parts_ok(a->pro, a->epi, a->n_xa > 0))) return 0;
-    return 1;
+    return nullptr;
 }
 
-// The (prologue, epilogue) pairs the engine actually issues; anything else runs on the general kernel.
-#define VV_GEMV_COMBOS(X)                                                                      \
-    X(VV_PRO_NONE, VV_EPI_STORE) X(VV_PRO_NONE, VV_EPI_BIAS) X(VV_PRO_NONE, VV_EPI_RESID)      \
-    X(VV_PRO_NONE, VV_EPI_GATED_RESID) X(VV_PRO_RMS, VV_EPI_BIAS) X(VV_PRO_RMS, VV_EPI_BIAS_GELU) \
-    X(VV_PRO_RMS, VV_EPI_SWIGLU) X(VV_PRO_RMS, VV_EPI_RESID) X(VV_PRO_RMS, VV_EPI_STORE)       \
-    X(VV_PRO_RMS_MOD, VV_EPI_SWIGLU) X(VV_PRO_RMS_MOD, VV_EPI_CFG_DPM) X(VV_PRO_RMS_MOD, VV_EPI_STORE) \
-    X(VV_PRO_ADD_SILU, VV_EPI_STORE) X(VV_PRO_NORMDW, VV_EPI_BIAS_GELU)
-// pairs that also exist in the 16-row form (prefill chunks, batched adaLN, T = 8 codec stage, connectors)
-#define VV_GEMV_WIDE(X)                                                                        \
-    X(VV_PRO_NONE, VV_EPI_STORE) X(VV_PRO_NONE, VV_EPI_BIAS) X(VV_PRO_NONE, VV_EPI_RESID)      \
-    X(VV_PRO_RMS, VV_EPI_BIAS) X(VV_PRO_RMS, VV_EPI_BIAS_GELU) X(VV_PRO_RMS, VV_EPI_SWIGLU)    \
-    X(VV_PRO_ADD_SILU, VV_EPI_STORE) X(VV_PRO_NONE, VV_EPI_GATED_RESID)
-// 16-row diffusion-head pairs (8 utterances x {cond, uncond} rows): two B operands -> 4-wave workgroups only (LDS)
-#define VV_GEMV_WIDE_MOD(X)                                                                    \
-    X(VV_PRO_RMS_MOD, VV_EPI_SWIGLU) X(VV_PRO_RMS_MOD, VV_EPI_CFG_DPM) X(VV_PRO_RMS_MOD, VV_EPI_STORE)
-
-static bool gemv_combo_ok(int pro, int epi, bool wide) {
-#define X(P, E) if (pro == P && epi == E) return true;
-    if (wide) { VV_GEMV_WIDE(X) VV_GEMV_WIDE_MOD(X) } else { VV_GEMV_COMBOS(X) }
-#undef X
-    return false;
-}
-
-// 16-row pairs that also have a 4-wave form (tall tokenizer stages, batched adaLN)
-#define VV_GEMV_WIDE4(X)                                                                       \
-    X(VV_PRO_NONE, VV_EPI_STORE) X(VV_PRO_NONE, VV_EPI_BIAS) X(VV_PRO_NONE, VV_EPI_RESID) X(VV_PRO_RMS, VV_EPI_BIAS_GELU)
-// pairs with a 4-wave form (wide outputs) and a 16-wave form (few tiles, long K); bench mode (xs == 1) only
-#define VV_GEMV_W4(X)                                                                          \
-    X(VV_PRO_RMS, VV_EPI_SWIGLU) X(VV_PRO_RMS_MOD, VV_EPI_SWIGLU) X(VV_PRO_RMS, VV_EPI_BIAS_GELU) \
-    X(VV_PRO_RMS, VV_EPI_BIAS) X(VV_PRO_NONE, VV_EPI_STORE) X(VV_PRO_NONE, VV_EPI_BIAS) X(VV_PRO_ADD_SILU, VV_EPI_STORE) \
-    X(VV_PRO_NORMDW, VV_EPI_BIAS_GELU)
-#define VV_GEMV_W16(X)                                                                         \
-    X(VV_PRO_NONE, VV_EPI_RESID) X(VV_PRO_NONE, VV_EPI_GATED_RESID) X(VV_PRO_NONE, VV_EPI_BIAS) X(VV_PRO_NONE, VV_EPI_STORE)
-
-// pairs that can consume a K-split tensor: on the activation side (x) or on the residual side (y)
-#define VV_GEMV_PARTS_X(X) X(VV_PRO_RMS, VV_EPI_BIAS) X(VV_PRO_RMS_MOD, VV_EPI_SWIGLU) X(VV_PRO_RMS_MOD, VV_EPI_CFG_DPM) X(VV_PRO_RMS_MOD, VV_EPI_STORE)
-#define VV_GEMV_PARTS_Y(X) X(VV_PRO_NONE, VV_EPI_RESID) X(VV_PRO_NONE, VV_EPI_GATED_RESID)
-#define VV_GEMV_PARTS(X) VV_GEMV_PARTS_X(X) VV_GEMV_PARTS_Y(X)
-static bool gemv_parts_ok(int pro, int epi, bool xside) {
-#define X(P, E) if (pro == P && epi == E) return true;
-    if (xside) { VV_GEMV_PARTS_X(X) } else { VV_GEMV_PARTS_Y(X) }
-#undef X
-    return false;
-}
-
-// form (optional, tests): receives {XS, MR, WPB, PARTS, SL} of the instantiation this call launches -- written by the launch
-// macros themselves, so it IS the dispatch decision, not a restatement of it.  The engine passes nullptr.
-#define VV_FORM(XS_, MR_, WP_, PT_, SL_) do { if (form) { form[0] = XS_; form[1] = MR_; form[2] = WP_; form[3] = PT_; form[4] = SL_; } } while (0)
+// form (optional, tests): receives {XS, MR, WPB, PARTS, SL} of the plan this call launches -- the kernel is looked up from
+// these very numbers, so it IS the dispatch decision, not a restatement of it.  The engine passes nullptr.
 extern "C" int vv_gemv_launch(VVGemm a, int xs, hipStream_t s, int* form) {
-    const int n_tiles = (a.N + 15) / 16, k_tiles = (a.K + 31) / 32;
     if (a.epi == VV_EPI_SWIGLU && !a.W2) return -1;
-    dim3 grid(n_tiles);
-#define VV_GO(XS_, P, E, MR_, WP_)                                                                      \
-    do { VV_FORM(XS_, MR_, WP_, 0, 0); hipLaunchKernelGGL((vv_gemv_kernel<XS_, P, E, MR_, WP_>), grid, dim3(WP_ * 64), 0, s, a.W, a.W2, a.X, a.Y, a.nw, a.T, a.N, a.K, a.ldx, a.ldy, a);       \
-         return vv_launch_rc(0); } while (0)
-    if (a.T > 4 || a.sl_n > 0) {
-        if (xs > 2) return -3;       // 16-row staging tiles of the exact mode exceed the LDS: general kernel
-        grid.y = (a.T + 15) / 16;
-        constexpr int wide4_wgs = 128;
-        // The 16-row tiles are used by the codec (T = 5..16 rows): above ~half a workgroup per CU the 4-wave form
-        // (2x the resident workgroups per CU) wins; measured 3.117 -> 3.053 ms/frame on the 1.5B config for
-        // thresholds 64..128 vs 512 (DESIGN.md section 8 lists the sweep).
-        if (a.sl_n > 0) {
-#define VV_GOSL(XS_, P, E, WP_)                                                                         \
-    do { VV_FORM(XS_, 16, WP_, 0, 1); hipLaunchKernelGGL((vv_gemv_kernel<XS_, P, E, 16, WP_, 0, 1>), grid, dim3(WP_ * 64), 0, s, a.W, a.W2, a.X, a.Y, a.nw, a.T, a.N, a.K, a.ldx, a.ldy, a);   \
-         return vv_launch_rc(0); } while (0)
-#define X(P, E) if (a.pro == P && a.epi == E) { if (xs == 2) VV_GOSL(2, P, E, 8); else if ((int64_t)n_tiles * grid.y > wide4_wgs) VV_GOSL(1, P, E, 4); else VV_GOSL(1, P, E, 8); }
-            VV_GEMV_SL(X)
-#undef X
-#undef VV_GOSL
-            return -3;
-        }
-        if (xs == 1 && (int64_t)n_tiles * grid.y > wide4_wgs) {
-#define X(P, E) if (a.pro == P && a.epi == E) VV_GO(1, P, E, 16, 4);
-            VV_GEMV_WIDE4(X)
-#undef X
-        }
-#define X(P, E) if (a.pro == P && a.epi == E) { if (xs == 1) VV_GO(1, P, E, 16, 8); else VV_GO(2, P, E, 16, 8); }
-        VV_GEMV_WIDE(X)
-#undef X
-#define X(P, E) if (a.pro == P && a.epi == E) { if (xs == 1) VV_GO(1, P, E, 16, 4); else return -3; }
-        VV_GEMV_WIDE_MOD(X)
-#undef X
-        return -3;
-    }
-    if (a.n_xa > 0 || a.n_ya > 0) {           // consumers of a K-split tensor (decode rows only)
-        if (a.kgrid > 1) grid.y = a.kgrid;
-#define VV_GOP(XS_, P, E, WP_, S_)                                                                      \
-    do { VV_FORM(XS_, 4, WP_, S_, 0); hipLaunchKernelGGL((vv_gemv_kernel<XS_, P, E, 4, WP_, S_>), grid, dim3(WP_ * 64), 0, s, a.W, a.W2, a.X, a.Y, a.nw, a.T, a.N, a.K, a.ldx, a.ldy, a);     \
-         return vv_launch_rc(0); } while (0)
-#define VV_GOP2(P, E)   /* two rows, wide output: the 2-row form of the K-split consumer (7B-width A/B of the column split, round 6) */ \
-    do { VV_FORM(1, 2, 4, 1, 0); hipLaunchKernelGGL((vv_gemv_kernel<1, P, E, 2, 4, 1>), grid, dim3(256), 0, s, a.W, a.W2, a.X, a.Y, a.nw, a.T, a.N, a.K, a.ldx, a.ldy, a);     \
-         return vv_launch_rc(0); } while (0)
-#define X(P, E)                                                                                         \
-    if (a.pro == P && a.epi == E) {                                                                     \
-        if constexpr (E == VV_EPI_SWIGLU) {        /* wide outputs: only the gate/up projection has them */ \
-            if (xs == 1 && n_tiles > 256 && a.T <= 2) VV_GOP2(P, E);                                     \
-            if (xs == 1 && n_tiles > 256) VV_GOP(1, P, E, 4, 1);                                         \
-        }                                                                                               \
-        if (xs == 1) VV_GOP(1, P, E, 8, 1); else if (xs == 2) VV_GOP(2, P, E, 8, 1); else VV_GOP(3, P, E, 8, 1); \
-    }
-        if (a.n_xa > 0) { VV_GEMV_PARTS_X(X) }
-#undef X
-#define X(P, E)                                                                                         \
-    if (a.pro == P && a.epi == E) {                                                                     \
-        if (xs == 1) VV_GOP(1, P, E, 8, 2); else if (xs == 2) VV_GOP(2, P, E, 8, 2); else VV_GOP(3, P, E, 8, 2); \
-    }
-        if (a.n_ya > 0) { VV_GEMV_PARTS_Y(X) }
-#undef X
-#undef VV_GOP
-#undef VV_GOP2
-        return -3;
-    }
-    if (a.kgrid > 1) grid.y = a.kgrid;
-    if (xs == 1 && a.kgrid <= 1) {
-        if (n_tiles > 256) {
-            // one utterance = two rows (cond + uncond): the 2-row form halves the activation registers and the staging tile, so
-            // one more workgroup fits per SIMD (RMS_MOD + SwiGLU: 160 -> <= 128 VGPRs) and a 672-tile launch is resident at once
-            if (a.T <= 2) {
-#define X(P, E) if (a.pro == P && a.epi == E) VV_GO(1, P, E, 2, 4);
-                VV_GEMV_W4(X)
-#undef X
-            }
-#define X(P, E) if (a.pro == P && a.epi == E) VV_GO(1, P, E, 4, 4);
-            VV_GEMV_W4(X)
-#undef X
-        } else if (n_tiles <= 128 && k_tiles >= 96) {
-#define X(P, E) if (a.pro == P && a.epi == E) VV_GO(1, P, E, 4, 16);
-            VV_GEMV_W16(X)
-#undef X
-        }
-    }
-#define X(P, E)                                                                                         \
-    if (a.pro == P && a.epi == E) {                                                                     \
-        if (xs == 1) VV_GO(1, P, E, 4, 8); else if (xs == 2) VV_GO(2, P, E, 4, 8); else VV_GO(3, P, E, 4, 8); \
-    }
-    VV_GEMV_COMBOS(X)
-#undef X
-#undef VV_GO
-#undef VV_FORM
-    return -3;
+    VVGemvPlan p;
+    if (!vv_gemv_plan(&a, xs, &p)) return VV_RC_NO_FORM;
+    const GemvKernel k = gemv_kernel(p.form, a.pro, a.epi);      // never null: the plan and the table read the same declaration
+    if (form) { form[0] = p.form.xs; form[1] = p.form.mr; form[2] = p.form.wpb; form[3] = p.form.parts; form[4] = p.form.sl; }
+    hipLaunchKernelGGL(k, p.grid, dim3(p.form.wpb * 64), 0, s, a.W, a.W2, a.X, a.Y, a.nw, a.T, a.N, a.K, a.ldx, a.ldy, a);
+    return vv_launch_rc(0);
 }

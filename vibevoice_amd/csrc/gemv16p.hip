@@ -335,44 +335,44 @@ int vv_pack16_tiles_launch(const float* x, int ldx, int64_t stride_outer, int n_
 }
 
 // Y / Yp (op)= W . Xp for one packed 16-row activation tile.  flags: 1 = RS (operand un-normalised, row scale from ssq_in), 2 = SH (second
-// operand Xs), 4 = PK (residual epilogue also packs the new rows for the next projection).  Returns -3 when the combination has no instantiation.
+// operand Xs), 4 = PK (residual epilogue also packs the new rows for the next projection).  Returns VV_RC_NO_FORM when the combination has no instantiation.
 int vv_gemv16p_launch2(const VVGemv16p* ap, int epi, int flags, hipStream_t s) {
     const VVGemv16p& a = *ap;
-    if (a.T < 1 || a.T > 16 || (a.N & 3) || a.K < 32 || (a.K & 31)) return -3;
+    if (a.T < 1 || a.T > 16 || (a.N & 3) || a.K < 32 || (a.K & 31)) return VV_RC_NO_FORM;
     const int n_tiles = (a.N + 15) / 16;
-    if ((flags & 1) && (!a.ssq_in || a.ssq_tiles < 1 || (((uintptr_t)a.ssq_in) & 15))) return -3;
-    if ((flags & 2) && !a.Xs) return -3;
-    if ((flags & 4) && (!a.Yp || !a.ssq_out || !a.Y || (a.N & 15) || (a.ldy & 3) || (a.pk_sc && (a.ld_pk & 3)))) return -3;
+    if ((flags & 1) && (!a.ssq_in || a.ssq_tiles < 1 || (((uintptr_t)a.ssq_in) & 15))) return VV_RC_NO_FORM;
+    if ((flags & 2) && !a.Xs) return VV_RC_NO_FORM;
+    if ((flags & 4) && (!a.Yp || !a.ssq_out || !a.Y || (a.N & 15) || (a.ldy & 3) || (a.pk_sc && (a.ld_pk & 3)))) return VV_RC_NO_FORM;
     // waves per workgroup as in vv_gemv_launch: 4 once there are more tiles than CUs (every workgroup resident at once), else 8
     constexpr int wide_tiles = 256;
     const bool w4 = n_tiles > wide_tiles;
 #define VV_P(E_, RS_, SH_, PK_) do { if (w4) hipLaunchKernelGGL((vv_gemv16p_kernel<E_, 4, RS_, SH_, PK_>), dim3(n_tiles), dim3(256), 0, s, a); \
                                    else hipLaunchKernelGGL((vv_gemv16p_kernel<E_, 8, RS_, SH_, PK_>), dim3(n_tiles), dim3(512), 0, s, a); return vv_launch_rc(0); } while (0)
     if (epi == VV_EPI_SWIGLU) {
-        if (!a.W2 || !a.Yp || (a.N & 7)) return -3;
+        if (!a.W2 || !a.Yp || (a.N & 7)) return VV_RC_NO_FORM;
         if (flags == 0) VV_P(VV_EPI_SWIGLU, 0, 0, 0);
         if (flags == 1) VV_P(VV_EPI_SWIGLU, 1, 0, 0);
         if (flags == 3) VV_P(VV_EPI_SWIGLU, 1, 1, 0);
     } else if (epi == VV_EPI_BIAS || epi == VV_EPI_STORE) {
-        if (!a.Y || (a.ldy & 3)) return -3;
+        if (!a.Y || (a.ldy & 3)) return VV_RC_NO_FORM;
         if (flags == 0) VV_P(VV_EPI_BIAS, 0, 0, 0);
         if (flags == 1) VV_P(VV_EPI_BIAS, 1, 0, 0);
         if (flags == 3) VV_P(VV_EPI_BIAS, 1, 1, 0);
     } else if (epi == VV_EPI_RESID) {
-        if (!a.Y || (a.ldy & 3)) return -3;
+        if (!a.Y || (a.ldy & 3)) return VV_RC_NO_FORM;
         if (flags == 0) VV_P(VV_EPI_RESID, 0, 0, 0);
         if (flags == 4) VV_P(VV_EPI_RESID, 0, 0, 1);
     } else if (epi == VV_EPI_GATED_RESID) {
-        if (!a.Y || !a.gate || (a.ldy & 3) || (a.ld_gate & 3)) return -3;
+        if (!a.Y || !a.gate || (a.ldy & 3) || (a.ld_gate & 3)) return VV_RC_NO_FORM;
         if (flags == 0) VV_P(VV_EPI_GATED_RESID, 0, 0, 0);
         if (flags == 4) VV_P(VV_EPI_GATED_RESID, 0, 0, 1);
     } else if (epi == VV_EPI_CFG_DPM) {
-        if (!a.z || !a.x0p || !a.coef || a.n_cfg < 1 || 2 * a.n_cfg != a.T) return -3;
+        if (!a.z || !a.x0p || !a.coef || a.n_cfg < 1 || 2 * a.n_cfg != a.T) return VV_RC_NO_FORM;
         if (flags == 0) VV_P(VV_EPI_CFG_DPM, 0, 0, 0);
         if (flags == 3) VV_P(VV_EPI_CFG_DPM, 1, 1, 0);
     }
 #undef VV_P
-    return -3;
+    return VV_RC_NO_FORM;
 }
 
 int vv_gemv16p_launch(const void* W, const void* W2, const void* Xp, float* Y, void* Yp, const float* bias, const float* gate,

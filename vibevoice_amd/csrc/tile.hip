@@ -18,7 +18,7 @@
 
 namespace {
 
-constexpr int BM = 64;          // rows per workgroup (4 row tiles, one staged by each wave)
+constexpr int BM = VV_TILE_BM;         // rows per workgroup (4 row tiles, one staged by each wave)
 constexpr int KC = 256;         // k per staged chunk = 8 k-steps = one float4 per lane and row
 constexpr int UU = KC / 32;
 
@@ -204,37 +204,7 @@ __global__ __launch_bounds__(256) void vv_gemm_tile_kernel(const u32x4* __restri
 
 }  // namespace
 
-#define VV_TILE_COMBOS(X)                                                                      \
-    X(VV_PRO_NONE, VV_EPI_STORE) X(VV_PRO_NONE, VV_EPI_BIAS) X(VV_PRO_NONE, VV_EPI_RESID)      \
-    X(VV_PRO_RMS, VV_EPI_BIAS) X(VV_PRO_RMS, VV_EPI_BIAS_GELU) X(VV_PRO_RMS, VV_EPI_SWIGLU)    \
-    X(VV_PRO_RMS, VV_EPI_STORE)
-
-// Eligibility: tall, aligned, enough workgroups (>= 48), one of the pairs above, bench / two-term activation modes, no row re-mapping or part tensors.
-extern "C" int vv_tile_ok(const VVGemm* a, int xs) {
-    if (a->T < 32 || xs > 2) return 0;
-    {   // enough workgroups to occupy the chip; smaller problems (tokenizer stages at decode) stay on the row-tiled GEMV
-        const int per_wg = 4 * (a->epi == VV_EPI_SWIGLU ? 1 : 2);
-        const int64_t wgs = (int64_t)(((a->N + 15) / 16 + per_wg - 1) / per_wg) * ((a->T + BM - 1) / BM);
-        // slot-batched tokenizer stages (several utterances' frames in one launch): the 16-row GEMV form re-normalises and
-        // re-stages its 16 rows in every one of its (feature tiles x row tiles) workgroups -- 87 us for the C = 256 FFN1 of eight
-        // utterances (1600 rows x 1024 features x 256: 0.8 GFLOP) -- so the tile form takes over much earlier there
-        const int min_wgs = a->sl_n > 0 ? 40 : 48;
-        if (wgs < min_wgs) return 0;
-    }
-    if (a->sl_n > 0) {
-        if (a->sl_n > 8 || a->sl_T < 1 || a->T != a->sl_n * a->sl_T || a->sl_x < 0 || a->sl_y < 0 || (a->sl_x & 3) || (a->sl_y & 3)) return 0;
-    }
-    if ((a->K & 3) || (a->ldx & 3) || (a->N & 3) || (a->ldy & 3)) return 0;
-    if ((((uintptr_t)a->X) | ((uintptr_t)a->Y)) & 15) return 0;
-    if ((a->nw && (((uintptr_t)a->nw) & 15)) || (a->bias && (((uintptr_t)a->bias) & 15)) || (a->nscale && (((uintptr_t)a->nscale) & 15))) return 0;
-    if (a->x_row_mod > 0 || a->add_rows_per_vec > 0 || a->kgrid > 1 || a->n_xa > 0 || a->n_ya > 0 || a->ksplit > 0) return 0;
-    if (a->K < 32) return 0;
-    if (a->epi == VV_EPI_SWIGLU && !a->W2) return 0;
-#define X(P, E) if (a->pro == P && a->epi == E) return 1;
-    VV_TILE_COMBOS(X)
-#undef X
-    return 0;
-}
+extern "C" int vv_tile_ok(const VVGemm* a, int xs) { return vv_tile_eligible(a, xs); }
 
 template <int XS, int PRO, int EPI>
 static int tile_go(const VVGemm& a, hipStream_t s) {
@@ -253,5 +223,5 @@ extern "C" int vv_tile_launch(VVGemm a, int xs, hipStream_t s) {
 #define X(P, E) if (a.pro == P && a.epi == E) return xs == 1 ? tile_go<1, P, E>(a, s) : tile_go<2, P, E>(a, s);
     VV_TILE_COMBOS(X)
 #undef X
-    return -3;
+    return VV_RC_NO_FORM;
 }

@@ -3,6 +3,10 @@
 // ("conflicting types"), not undefined behaviour at the call.  Internal: hidden visibility, not part of include/vvhip.h.
 #pragma once
 #include "vv_common.h"
+#include "gemv_plan.h"       // VV_ROUTE_* and vv_gemm_route(a, xs): which kernel vv_gemm_launch runs a call on
+// what a launcher answers when it launched nothing: no compiled form of ITS kernel for this call (the caller may route the call to
+// another kernel), or no kernel at all can run it
+enum { VV_RC_NO_FORM = -3, VV_RC_NO_KERNEL = -4 };
 extern "C" {
 int vv_gemm_launch(VVGemm a, int xs, hipStream_t s);
 int vv_pack_launch(const void* src, int src_is_bf16, void* dst, int N, int K, int kind, int Cin, int Cout, int ksz, int stride, hipStream_t s);
@@ -82,7 +86,8 @@ int vv_attn_prefill4_launch(int D, const float* q, const VVRow* rows, const void
                             int64_t head_stride, float* out, void* out_packed, hipStream_t s);
 int vv_block1d_supported(int C);
 int vv_gemv_ok(const VVGemm* a);
-int vv_gemv_launch(VVGemm a, int xs, hipStream_t s, int* form);      // form: the compiled form its launcher picked (tests)
+// vv_gemv_plan (gemv_plan.h) -> the kernel of that form -> launch; VV_RC_NO_FORM where the plan finds none.  form (tests): the plan's form.
+int vv_gemv_launch(VVGemm a, int xs, hipStream_t s, int* form);
 int vv_tile_ok(const VVGemm* a, int xs);
 int vv_tile_launch(VVGemm a, int xs, hipStream_t s);
 int vv_lora_merge_launch(const void* base, void* dst, int N, int K, const float* a, const float* b, int r, float scale, int delta_bf16,
