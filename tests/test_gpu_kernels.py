@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import prefill_shapes
 import synth
 from gpu_util import build_small, max_err, rel_err
 from oracle import codec, connector, dpm, head
@@ -104,9 +105,8 @@ def test_gemm_tile_prefill_shapes(sm, pro, epi, xs, tol):
     assert rel_err(y, ref) <= tol, rel_err(y, ref)
 
 
-@pytest.mark.parametrize("epi", [0, 1, 4, 3])
-@pytest.mark.parametrize("T,N,K", [(333, 4112, 416), (128, 128, 64), (2048, 1024, 1536), (70, 200, 96), (500, 36, 3584),
-                                   (4100, 4112, 416), (4100, 4100, 2080)])
+@pytest.mark.parametrize("epi", prefill_shapes.PREFILL_GEMM3_EPIS)
+@pytest.mark.parametrize("T,N,K", prefill_shapes.PREFILL_GEMM3)
 def test_prefill_gemm3(sm, epi, T, N, K):
     """prefill.hip: activations packed to bf16 MFMA fragments (+ RMSNorm in the packing kernel for the BIAS case), 128 x 128
     LDS-staged MFMA GEMM with the store / bias / residual / SwiGLU epilogues; ragged T (not a multiple of 128 / 16), N not a

@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 import torch
 
+import prefill_shapes
 import synth
 from gpu_util import build_small, rel_err
 from oracle import codec, dpm, head
@@ -344,16 +345,20 @@ def test_two_pass_prefill_with_the_fused_qkv_epilogue_at_a_position_offset():
 
 
 # ---------------------------------------------------------------------------------------------- (c2) the GEMM's K-split partial round
-@pytest.mark.parametrize("epi", [0, 1, 4, 3])
-@pytest.mark.parametrize("T,N,K", [(4100, 4112, 2080), (4352, 4096, 2048), (1100, 8200, 1024)])
+@pytest.mark.parametrize("epi", prefill_shapes.K_SPLIT_ROUND_EPIS)
+@pytest.mark.parametrize("T,N,K", prefill_shapes.K_SPLIT_ROUND)
 def test_prefill_gemm4_k_split_round(epi, T, N, K):
     """vv_gemm4_kernel with the tiles past its last whole round of 256 workgroups split along K (prefill.hip): the contributors'
     partial accumulators travel through the workspace (write-through + arrival word), the last part adds them in part order
-    and runs the epilogue.  Shapes: 289 tiles with ragged T / N and an odd k-tile count (XCD 0 has one more remainder tile than the
-    others: the early-exit path), 272 tiles (2 remainder tiles per XCD, split 4), 5 x 65 (SwiGLU: 5 x 129) tiles.  Against the
+    and runs the epilogue.  Shapes (tests/prefill_shapes.py; test_prefill_plan_cpu.py asserts that the plan splits every one of them
+    under every epilogue): 17 x 17 = 289 tiles (SwiGLU: 33 x 17 = 561) with ragged T / N and an odd k-tile count, XCD 0 with one
+    more remainder tile than the others (the early-exit path), split 4; 16 x 17 = 272 tiles (SwiGLU 544), 2 (4) remainder tiles
+    on every XCD, split 4; 29 x 9 = 261 tiles (SwiGLU: 58 x 9 = 522), ragged T / N, 49 k-tiles: one remainder tile on XCDs 0-4
+    and none on 5-7 (SwiGLU: two on XCDs 0-1, one on the others), split 3 = 25 steps / 8.  Against the
     bf16-rounded-activation reference at the bounds of test_prefill_gemm3, against the unsplit kernel (summation order only),
     and launched twice (the arrival words are reset by the consumer)."""
-    s = build_fast(GEOM["0.5b"], xsplit=1, max_ctx=128, max_rows=1024, head_layers=1)
+    geom, max_rows = prefill_shapes.K_SPLIT_ROUND_ENGINE
+    s = build_fast(GEOM[geom], xsplit=1, max_ctx=128, max_rows=max_rows, head_layers=1)
     eng = s.eng
     try:
         g = _FastGen(7700 + T + N + K + epi)
@@ -389,8 +394,8 @@ def test_prefill_gemm4_k_split_round(epi, T, N, K):
         eng.close()
 
 
-@pytest.mark.parametrize("epi", [0, 1, 4])
-@pytest.mark.parametrize("T,N,K", [(330, 1536, 8960), (330, 2048, 1536), (333, 1540, 1056), (75, 896, 4864), (500, 36, 3584)])
+@pytest.mark.parametrize("epi", prefill_shapes.SHORT_PROMPT_EPIS)
+@pytest.mark.parametrize("T,N,K", prefill_shapes.SHORT_PROMPT)
 def test_short_prompt_gemm3_k_split_and_reduce(epi, T, N, K):
     """Short prompts (round 4): vv_gemm3_kernel launches a few dozen 128 x 128 tiles for such shapes (36 for the 1.5B down projection
     of a 330-token prompt), so K is split over grid.y into dense fp32 partial tensors and vv_g3_reduce_kernel adds them in part order
@@ -398,7 +403,8 @@ def test_short_prompt_gemm3_k_split_and_reduce(epi, T, N, K):
     Shapes: the 1.5B down / QKV projections at 330 rows, ragged T / N with an odd k-tile count (33), a 75-row voice prompt at 0.5B
     widths, a one-block problem.  Against the bf16-rounded-activation reference at test_prefill_gemm3's bounds, against the unsplit
     kernel (no workspace: summation order only), twice (bit-identical repeats)."""
-    s = build_fast(GEOM["0.5b"], xsplit=1, max_ctx=128, max_rows=512, head_layers=1)
+    geom, max_rows = prefill_shapes.SHORT_PROMPT_ENGINE
+    s = build_fast(GEOM[geom], xsplit=1, max_ctx=128, max_rows=max_rows, head_layers=1)
     eng = s.eng
     try:
         g = _FastGen(8800 + T + N + K + epi)

@@ -443,7 +443,16 @@ static void launch_t(const VVGemm& a, dim3 grid, size_t smem, hipStream_t s) {
     hipLaunchKernelGGL((vv_gemm_kernel<NT, XS, DUAL, WPB, MAXR, VEC>), grid, dim3(WPB * 64), smem, s, a);
 }
 
-static int pow2_floor(int v) { int p = 1; while (p * 2 <= v) p *= 2; return p; }
+// One launcher per form (NT, DUAL, WPB, MAXR, VEC) of vv_gemm_general_plan (gemv_plan.h) and xs = 1..3 -- the whole set of instantiations.
+using GeneralLaunch = void (*)(const VVGemm&, dim3, size_t, hipStream_t);
+struct GeneralForm { int nt; bool dual; int wpb, maxr; bool vec; GeneralLaunch launch[3]; };
+#define VV_FORM(NT_, DUAL_, WPB_, MAXR_, VEC_) \
+    {NT_, DUAL_, WPB_, MAXR_, VEC_, {launch_t<NT_, 1, DUAL_, WPB_, MAXR_, VEC_>, launch_t<NT_, 2, DUAL_, WPB_, MAXR_, VEC_>, launch_t<NT_, 3, DUAL_, WPB_, MAXR_, VEC_>}}
+static const GeneralForm general_forms[] = {
+    VV_FORM(1, false, 4, 16, false),            // generic (odd K / unaligned rows): encoder stem, tiny test shapes
+    VV_FORM(1, true, 8, 4, true), VV_FORM(2, false, 8, 4, true), VV_FORM(1, false, 8, 4, true),
+    VV_FORM(1, true, 4, 16, true), VV_FORM(2, false, 4, 16, true), VV_FORM(1, false, 4, 16, true)};
+#undef VV_FORM
 
 // Chooses the kernel and its decomposition.  `xs` in {1,2,3}.
 extern "C" int vv_gemm_launch(VVGemm a, int xs, hipStream_t s) {
@@ -453,62 +462,17 @@ extern "C" int vv_gemm_launch(VVGemm a, int xs, hipStream_t s) {
     case VV_ROUTE_NONE: return VV_RC_NO_KERNEL;
     default: break;                    // VV_ROUTE_GENERAL: the kernel of this file
     }
-    const int n_tiles = (a.N + 15) / 16;
-    const int k_tiles = (a.K + 31) / 32;
-    const int t_tiles = (a.T + 15) / 16;
-    const bool dual = a.epi == VV_EPI_SWIGLU;
-    if (dual && !a.W2) return -1;
-    const int Tt = a.T < 16 ? a.T : 16;
-    const bool vec = ((a.K & 3) == 0) && ((a.ldx & 3) == 0) && ((((uintptr_t)a.X) & 15) == 0) &&
-                     (a.pro != VV_PRO_RMS_MOD || (a.ld_mod & 3) == 0);
-    // LDS row stride of the staging tile: odd multiples avoid bank conflicts on the 8-byte writes
-    a.t_pad = Tt;
-    // waves per block: 8 for decode-sized row counts (small staging tiles, deep K split), 4 otherwise
-    const int wpb = (Tt <= 4 && vec) ? 8 : 4;
-    // two tiles per wave once there are plenty of tiles (halves staging work per weight byte)
-    int nt = 1;
-    if (!dual && vec && (long)n_tiles * t_tiles >= 4096) nt = 2;
-    const long work = ((long)n_tiles + nt - 1) / nt * t_tiles;     // waves if K is not split
-    int ks = 1;
-    if (a.ksplit > 0) ks = a.ksplit;
-    else {
-        // enough waves to cover 256 CUs x ~8, at least 8 k-steps (one batch) per wave
-        const int want = (int)((2048 + work - 1) / work);
-        ks = pow2_floor(want < 1 ? 1 : want);
-        const int kmax = pow2_floor(k_tiles / 8 < 1 ? 1 : k_tiles / 8);
-        if (ks > kmax) ks = kmax;
-    }
-    if (ks > wpb) ks = wpb;
-    // few tiles: give every tile its own workgroup (more CUs pulling on HBM) rather than packing tiles into one
-    if (a.ksplit <= 0 && wpb == 8 && work < 512) { while (ks < wpb && (k_tiles / (ks * 2)) >= 2) ks *= 2; }
-    a.ksplit = ks;
-    const int ng = wpb / ks;
-    const int per_block = ng * nt;
-    dim3 grid((n_tiles + per_block - 1) / per_block, t_tiles);
-    const int nm = dual ? 2 : nt;
-    size_t stage_b = (size_t)wpb * xs * 8 * 4 * a.t_pad * 16;
-    size_t red_b = (size_t)wpb * nm * 64 * 16 + (size_t)wpb * 64 * 4;
-    size_t smem = stage_b > red_b ? stage_b : red_b;
-#define VV_XS(NT_, DUAL_, WPB_, MAXR_, VEC_)                                      \
-    do {                                                                          \
-        if (xs == 1) launch_t<NT_, 1, DUAL_, WPB_, MAXR_, VEC_>(a, grid, smem, s); \
-        else if (xs == 2) launch_t<NT_, 2, DUAL_, WPB_, MAXR_, VEC_>(a, grid, smem, s); \
-        else launch_t<NT_, 3, DUAL_, WPB_, MAXR_, VEC_>(a, grid, smem, s);        \
-    } while (0)
-    if (!vec) {
-        if (dual) return VV_RC_NO_FORM;            // SwiGLU operands are always aligned on this path
-        VV_XS(1, false, 4, 16, false);             // generic (odd K / unaligned rows): encoder stem, tiny test shapes
-    } else if (wpb == 8) {
-        if (dual) VV_XS(1, true, 8, 4, true);
-        else if (nt == 2) VV_XS(2, false, 8, 4, true);
-        else VV_XS(1, false, 8, 4, true);
-    } else {
-        if (dual) VV_XS(1, true, 4, 16, true);
-        else if (nt == 2) VV_XS(2, false, 4, 16, true);
-        else VV_XS(1, false, 4, 16, true);
-    }
-#undef VV_XS
-    return vv_launch_rc(0);
+    VVGemmGeneralPlan p;
+    const int rc = vv_gemm_general_plan(&a, xs, &p);
+    if (rc != 0) return rc;
+    a.t_pad = p.t_pad;
+    a.ksplit = p.ks;
+    for (const GeneralForm& f : general_forms)      // never misses: the plan's forms are the rows of the table
+        if (f.nt == p.nt && f.dual == p.dual && f.wpb == p.wpb && f.maxr == p.maxr && f.vec == p.vec) {
+            f.launch[xs == 1 ? 0 : xs == 2 ? 1 : 2](a, p.grid, p.lds, s);
+            return vv_launch_rc(0);
+        }
+    return VV_RC_NO_FORM;
 }
 
 extern "C" int vv_pack_launch(const void* src, int src_is_bf16, void* dst, int N, int K, int kind,

@@ -1,5 +1,6 @@
 // gemv_plan.h -- which compiled form of vv_gemv_kernel (gemv.hip) a launch takes, decided on the host before anything is launched;
-// at the end, the question one level up: which of the three GEMM kernels vv_gemm_launch runs a call on (vv_gemm_route).
+// at the end, the question one level up: which of the three GEMM kernels vv_gemm_launch runs a call on (vv_gemm_route), and the
+// form and decomposition of the general kernel of gemm.hip where the route ends there (vv_gemm_general_plan).
 // Plain host C++: no kernel, no HIP call, no operand pointer is dereferenced (a test drives it on a machine without a GPU).
 #pragma once
 #include "vv_common.h"
@@ -194,4 +195,50 @@ inline int vv_gemm_route(const VVGemm* a, int xs) {
     if (a->ksplit <= 0 && vv_gemv_plan(a, xs, &p)) return VV_ROUTE_GEMV;
     if (a->kgrid > 1 || a->n_xa > 0 || a->n_ya > 0) return VV_ROUTE_NONE;      // part tensors exist only on the decode GEMV path
     return VV_ROUTE_GENERAL;
+}
+
+// ---- the general kernel (gemm.hip): the form vv_gemm_kernel<NT, XS, DUAL, WPB, MAXR, VEC> and the decomposition of a call ----
+struct VVGemmGeneralPlan {
+    bool vec, dual;             // aligned operands (float4 staging); two matrices (SwiGLU)
+    int wpb, maxr, nt;          // waves per block, the staging tile's row capacity, tiles per wave
+    int ks, t_pad;              // waves of a block that split K; LDS row stride of the staging tile (both go into the VVGemm argument)
+    dim3 grid;
+    size_t lds;                 // dynamic LDS bytes
+};
+constexpr int VV_GG_NT2_TILE_PAIRS = 4096;       // two tiles per wave once there are plenty of tiles (halves staging work per weight byte)
+constexpr int VV_GG_WAVES = 2048, VV_GG_MIN_KSTEPS = 8;      // enough waves to cover 256 CUs x ~8, at least 8 k-steps (one batch) per wave
+constexpr int VV_GG_FEW_TILES = 512;             // few tiles: give every tile its own workgroup (more CUs pulling on HBM) rather than packing tiles into one
+inline int vv_pow2_floor(int v) { int p = 1; while (p * 2 <= v) p *= 2; return p; }
+
+// -1: SwiGLU without its second matrix;  VV_RC_NO_FORM: unaligned SwiGLU;  0: *p is the launch.  `xs` in {1,2,3}.
+inline int vv_gemm_general_plan(const VVGemm* a, int xs, VVGemmGeneralPlan* p) {
+    const int n_tiles = (a->N + 15) / 16, k_tiles = (a->K + 31) / 32, t_tiles = (a->T + 15) / 16;
+    p->dual = a->epi == VV_EPI_SWIGLU;
+    if (p->dual && !a->W2) return -1;
+    p->vec = ((a->K & 3) == 0) && ((a->ldx & 3) == 0) && ((((uintptr_t)a->X) & 15) == 0) && (a->pro != VV_PRO_RMS_MOD || (a->ld_mod & 3) == 0);
+    if (!p->vec && p->dual) return VV_RC_NO_FORM;                  // SwiGLU operands are always aligned on this path
+    p->t_pad = a->T < 16 ? a->T : 16;       // odd multiples avoid bank conflicts on the 8-byte writes
+    // waves per block: 8 for decode-sized row counts (small staging tiles, deep K split), 4 otherwise -- and for the generic
+    // form (odd K / unaligned rows): encoder stem, tiny test shapes
+    p->wpb = (p->t_pad <= 4 && p->vec) ? 8 : 4;
+    p->maxr = p->wpb == 8 ? 4 : 16;
+    p->nt = (!p->dual && p->vec && (long)n_tiles * t_tiles >= VV_GG_NT2_TILE_PAIRS) ? 2 : 1;
+    const long work = ((long)n_tiles + p->nt - 1) / p->nt * t_tiles;     // waves if K is not split
+    int ks = 1;
+    if (a->ksplit > 0) ks = a->ksplit;
+    else {
+        const int want = (int)((VV_GG_WAVES + work - 1) / work);
+        ks = vv_pow2_floor(want < 1 ? 1 : want);
+        const int kmax = vv_pow2_floor(k_tiles / VV_GG_MIN_KSTEPS < 1 ? 1 : k_tiles / VV_GG_MIN_KSTEPS);
+        if (ks > kmax) ks = kmax;
+    }
+    if (ks > p->wpb) ks = p->wpb;
+    if (a->ksplit <= 0 && p->wpb == 8 && work < VV_GG_FEW_TILES) { while (ks < p->wpb && (k_tiles / (ks * 2)) >= 2) ks *= 2; }
+    p->ks = ks;
+    const int per_block = p->wpb / ks * p->nt;
+    p->grid = dim3((n_tiles + per_block - 1) / per_block, t_tiles);
+    const size_t stage_b = (size_t)p->wpb * xs * 8 * 4 * p->t_pad * 16;
+    const size_t red_b = (size_t)p->wpb * (p->dual ? 2 : p->nt) * 64 * 16 + (size_t)p->wpb * 64 * 4;
+    p->lds = stage_b > red_b ? stage_b : red_b;
+    return 0;
 }

@@ -23,11 +23,13 @@
 //                           ring; 8 waves = 4 units x 2 row halves in anti-phase (matrix segment / softmax segment), one
 //                           lazy-rescaled softmax step per stage, row sums through the matrix pipe; the result leaves as the
 //                           o-projection's packed operand.
-#include <cstring>
+// Which GEMM kernel a call runs on, its grid and its K-splits are decided in prefill_plan.h (plain host code, tested without a
+// GPU); the launchers at the end of this file are plan -> kernel arguments -> the kernel of (form, epilogue) -> launch.
 #include <type_traits>
 #include "vv_common.h"
 #include "vv_device.h"
 #include "vv_launch.h"
+#include "prefill_plan.h"
 
 namespace {
 
@@ -175,19 +177,19 @@ struct VVGemm3 {
     float q_scale;
 };
 
-// TR = row tiles (16 rows each) per wave: the workgroup covers 128 features x 32*TR rows.  TR = 8 (256 rows) doubles the
-// MFMAs per staged byte and per barrier: three such workgroups per CU carry enough arithmetic to cover a stage's load latency.
-// DB = 1: two stage buffers (TR = 4 only), the next stage's copies issued before the current stage's MFMAs, one barrier per stage.
+// TR = row tiles (16 rows each) per wave: the workgroup covers 128 features x 32*TR = 128 rows.  (A 256-row form, TR = 8, was
+// removed: no launch could reach it past the 256 x 256 kernel, and it had measured no better -- docs/negative_results.md.)
+// DB = 1: two stage buffers, the next stage's copies issued before the current stage's MFMAs, one barrier per stage.
 // Launches of at most ~2 workgroups per CU (short prompts: a few hundred tiles) have no neighbour workgroup to hide a stage's
 // load latency behind; with four resident workgroups per CU the single-buffer form overlaps through occupancy and keeps its LDS.
-template <int EPI, int TR, int DB = 0>
-__global__ __launch_bounds__(256, TR == 8 ? 2 : (DB ? 2 : 4)) void vv_gemm3_kernel(const VVGemm3 a) {
+template <int EPI, int DB = 0>
+__global__ __launch_bounds__(256, DB ? 2 : 4) void vv_gemm3_kernel(const VVGemm3 a) {
     constexpr bool DUAL = (EPI == VV_EPI_SWIGLU);
+    constexpr int TR = 4;
     constexpr int FT = DUAL ? 4 : 8;              // feature tiles (per matrix) per workgroup
     // LDS stage: 16 A fragments then 4*TR B fragments of one 64-wide K step (2 k-tiles): [frag][64 lanes][16 B]
     constexpr int NFR = 16 + 4 * TR;               // fragments per stage
     constexpr int FPW = NFR / 4;                   // copied by each wave
-    static_assert(DB == 0 || TR == 4, "two stage buffers: 64 KiB of static LDS, TR = 4 only");
     __shared__ __attribute__((aligned(16))) unsigned char stage_all[NFR * 1024 * (DB + 1)];
     unsigned char* stage = stage_all;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1037,21 +1039,29 @@ __global__ __launch_bounds__(512) void vv_attn_prefill4_kernel(
 
 }  // namespace
 
-// the K-split of the partial last round (see vv_gemm3_launch): fills a.full_idx / a.split / workspace pointers, updates the grid size
-static void g4_split_plan(VVGemm3& a, const VVGemmWs* ws, int K, unsigned& n_wgs) {
-    if (!(ws && ws->partials && ws->flags && ws->err)) return;
-    const int total = a.n_blocks * a.t_blocks, q = total >> 3, r = total & 7;
-    const int full_idx = (total / 256) * 32;
-    const int max_rem = q + (r ? 1 : 0) - full_idx;           // 0..32 tiles per XCD in the partial round
-    const int n_steps = ((K + 31) / 32 + 1) / 2;
-    int split = max_rem > 0 ? 32 / max_rem : 1;
-    if (split > 8) split = 8;
-    if (split > n_steps / 8) split = n_steps / 8;             // a part keeps >= 8 of the 64-wide steps
-    if (split == 2 && n_steps < 256) split = 1;               // halves of a short K do not pay (see vv_gemm3_launch)
-    if (split > 1) {
-        a.full_idx = full_idx; a.split = split; a.ws = ws->partials; a.flags = ws->flags; a.err = ws->err;
-        n_wgs = (unsigned)(8 * full_idx + 8 * max_rem * split);
-    }
+// One kernel per (form, compiled epilogue) of prefill_plan.h -- the whole set of GEMM instantiations of this file.
+using Gemm3Kernel = void (*)(const VVGemm3);
+static Gemm3Kernel gemm3_kernel(int form, int epi) {
+    static const int epis[4] = {VV_EPI_BIAS, VV_EPI_RESID, VV_EPI_SWIGLU, VV_EPI_QKV_ROPE};
+    static const Gemm3Kernel table[VV_PF_FORMS][4] = {      // in the order of the enum; the RoPE epilogue exists in the 256 x 256 kernel only
+        {vv_gemm4_kernel<VV_EPI_BIAS>, vv_gemm4_kernel<VV_EPI_RESID>, vv_gemm4_kernel<VV_EPI_SWIGLU>, vv_gemm4_kernel<VV_EPI_QKV_ROPE>},
+        {vv_gemm3_kernel<VV_EPI_BIAS, 0>, vv_gemm3_kernel<VV_EPI_RESID, 0>, vv_gemm3_kernel<VV_EPI_SWIGLU, 0>, nullptr},
+        {vv_gemm3_kernel<VV_EPI_BIAS, 1>, vv_gemm3_kernel<VV_EPI_RESID, 1>, vv_gemm3_kernel<VV_EPI_SWIGLU, 1>, nullptr}};
+    for (int i = 0; i < 4; ++i)
+        if (epis[i] == epi) return table[form][i];
+    return nullptr;
+}
+
+// the plan's decomposition and the workspace of its K-split (if any) into the kernel's arguments, then the launch
+static void gemm3_run(const VVGemm3Plan& p, VVGemm3 a, const VVGemmWs* ws, hipStream_t s) {
+    a.n_blocks = p.n_blocks; a.t_blocks = p.t_blocks; a.sfw = 4;
+    a.full_idx = p.full_idx; a.split = p.split;
+    if (p.split > 1) { a.ws = ws->partials; a.flags = ws->flags; a.err = ws->err; }
+    if (p.ks > 1) { a.ws = ws->g3_partials; a.split = p.ks; }
+    static const hipError_t lds4 = vv_raise_lds_limit(160 * 1024, &vv_gemm4_kernel<VV_EPI_BIAS>, &vv_gemm4_kernel<VV_EPI_RESID>,
+                                                      &vv_gemm4_kernel<VV_EPI_SWIGLU>, &vv_gemm4_kernel<VV_EPI_QKV_ROPE>);
+    (void)lds4;
+    hipLaunchKernelGGL(gemm3_kernel(p.form, p.epi), p.grid, dim3(p.block), p.lds, s, a);
 }
 
 extern "C" {
@@ -1068,7 +1078,6 @@ int vv_unpack_rows_launch(const void* xp, float* x, int T, int K, hipStream_t s)
     return vv_launch_rc(0);
 }
 
-// Y (op)= Xp . W^T.  epi: VV_EPI_STORE / BIAS / RESID -> fp32 Y[T][ldy];  VV_EPI_SWIGLU -> packed bf16 Yp [T][N] (W = gate, W2 = up)
 int vv_ada_pack_launch(const float* cproj, const float* temb, void* xp, int rows, int n_steps, int H, hipStream_t s) {
     if ((H & 7) || rows < 1 || n_steps < 1) return -1;
     const int T = rows * n_steps, KT = (H + 31) >> 5;
@@ -1076,114 +1085,43 @@ int vv_ada_pack_launch(const float* cproj, const float* temb, void* xp, int rows
     return vv_launch_rc(0);
 }
 
+// Y (op)= Xp . W^T.  epi: VV_EPI_STORE / BIAS / RESID -> fp32 Y[T][ldy];  VV_EPI_SWIGLU -> packed bf16 Yp [T][N] (W = gate, W2 = up)
+// vv_gemm3_plan (prefill_plan.h) -> the kernel of its (form, epilogue) -> launch (-> the reduce of a short prompt's K parts)
 int vv_gemm3_launch(const void* W, const void* W2, const void* Xp, float* Y, void* Yp, const float* bias, int T, int N, int K,
                     int ldy, int epi, const VVGemmWs* ws, hipStream_t s) {
-    if (T < 1 || N < 1 || K < 32 || (N & 3)) return -1;
-    VVGemm3 a;
+    VVGemm3Plan p;
+    const int rc = vv_gemm3_plan(T, N, K, ldy, epi, W2 != nullptr, Y != nullptr, Yp != nullptr, vv_prefill_ws(ws), &p);
+    if (rc != 0) return rc;
+    VVGemm3 a = {};
     a.W = (const u32x4*)W; a.W2 = (const u32x4*)W2; a.Xp = (const u32x4*)Xp; a.Y = Y; a.Yp = (u32x4*)Yp; a.bias = bias;
     a.T = T; a.N = N; a.K = K; a.ldy = ldy;
-    a.full_idx = 0; a.split = 1; a.ws = nullptr; a.flags = nullptr; a.err = nullptr; a.sfw = 4;
-    const int n_tiles = (N + 15) / 16;
-    // long prompts: the 256 x 256 kernel whenever its grid fills the chip at least once; smaller problems keep the 128-feature
-    // kernel, whose tiles quantise better.  Per launch at T = 10,922 (7B layer), 128-feature kernel -> round-2 256 x 256 ->
-    // round-3 schedule + strip order + K-split: gate/up 3188 -> 2650 -> 2350 us, down 1751 -> 1470 -> 1390, qkv 518 -> 404 -> 315,
-    // o 432 -> 340 -> 271.
-    const int64_t wgs4 = (int64_t)((n_tiles + ((epi == VV_EPI_SWIGLU) ? 8 : 16) - 1) / ((epi == VV_EPI_SWIGLU) ? 8 : 16)) * ((T + 255) / 256);
-    if (wgs4 >= 256 &&
-        (epi == VV_EPI_SWIGLU || epi == VV_EPI_RESID || epi == VV_EPI_BIAS || epi == VV_EPI_STORE)) {
-        const int ft4 = (epi == VV_EPI_SWIGLU) ? 8 : 16;
-        a.n_blocks = (n_tiles + ft4 - 1) / ft4;
-        a.t_blocks = (T + 255) / 256;
-        if (epi == VV_EPI_SWIGLU && (!W2 || !Yp)) return -1;
-        if (epi != VV_EPI_SWIGLU && (!Y || (ldy & 3))) return -1;
-        // One workgroup per CU (128 KiB of LDS): the grid runs in rounds of 256 and the tiles past the last whole round (T =
-        // 10,922 at 7B widths: 602 tiles for down / o = 2.35 rounds, 774 for QKV = 3.02) cost most of a round however few they
-        // are.  Each XCD's share of that remainder (<= 32 tiles) is split along K by the largest factor that still fits one
-        // round (g4_map / g4_finish).  Measured (tools/experiments/gemm_pingpong): it pays when the remainder is a handful of
-        // tiles (QKV: split 7, -6 %) or the parts stay long (down: K = 18,944 halved, -3.5 %); halving K = 3584 tiles does not
-        // (o: +6 %; gate/up: neutral) -- a partial round is not a lost round on this chip: the package is at its power limit
-        // under these kernels and the clock rises when fewer CUs compute -- so those launches stay whole.
-        unsigned n_wgs = (unsigned)(a.n_blocks * a.t_blocks);
-        g4_split_plan(a, ws, K, n_wgs);
-        const dim3 grid4(n_wgs);
-        static const hipError_t lds4 = vv_raise_lds_limit(160 * 1024, &vv_gemm4_kernel<VV_EPI_SWIGLU>, &vv_gemm4_kernel<VV_EPI_RESID>, &vv_gemm4_kernel<VV_EPI_BIAS>);
-        (void)lds4;
-        const size_t smem4 = 4 * 32 * 1024;
-        if (epi == VV_EPI_SWIGLU) hipLaunchKernelGGL((vv_gemm4_kernel<VV_EPI_SWIGLU>), grid4, dim3(512), smem4, s, a);
-        else if (epi == VV_EPI_RESID) hipLaunchKernelGGL((vv_gemm4_kernel<VV_EPI_RESID>), grid4, dim3(512), smem4, s, a);
-        else hipLaunchKernelGGL((vv_gemm4_kernel<VV_EPI_BIAS>), grid4, dim3(512), smem4, s, a);
-        return vv_launch_rc(0);
-    }
-    const int ft = (epi == VV_EPI_SWIGLU) ? 4 : 8;
-    a.n_blocks = (n_tiles + ft - 1) / ft;
-    // 256-row workgroups once the problem is tall enough to fill the chip with them
-    const int tr = (int64_t)a.n_blocks * ((T + 255) / 256) >= 768 ? 8 : 4;
-    a.t_blocks = (T + 32 * tr - 1) / (32 * tr);
-    dim3 grid((unsigned)(a.n_blocks * a.t_blocks));
-    // Short prompts (a 330-token request: 36 tiles for the o / down projections of a 1.5B layer, 48 for QKV): a few dozen workgroups
-    // stream the whole matrix -- 170 us for the 27.5 MB down projection.  K is split over grid.y (each part >= 4 of the 64-wide
-    // steps) until ~192 workgroups pull on HBM; the parts go to dense fp32 tensors and vv_g3_reduce_kernel sums them in part order
-    // with the bias / residual: deterministic, no hand-off inside a launch.
-    int ks = 1;
-    if (epi != VV_EPI_SWIGLU && ws && ws->g3_partials && grid.x < 128 && (N & 3) == 0 && Y) {
-        const int n_steps = (((K + 31) >> 5) + 1) >> 1;
-        ks = (int)((192 + grid.x - 1) / grid.x);
-        if (ks > 8) ks = 8;
-        if (ks > n_steps / 4) ks = n_steps / 4;
-        if (ks < 2 || (size_t)ks * T * N * 4 > ws->g3_bytes) ks = 1;
-    }
-    const float* bias_r = bias; const int resid_r = (epi == VV_EPI_RESID) ? 1 : 0;
-    if (ks > 1) { grid.y = (unsigned)ks; a.ws = ws->g3_partials; a.split = ks; }
-    const bool db = tr == 4 && (int64_t)grid.x * (ks > 1 ? ks : 1) <= 512;      // at most ~2 workgroups per CU: nothing else hides a stage's latency
-#define VV_G3(E_) do { if (tr == 8) hipLaunchKernelGGL((vv_gemm3_kernel<E_, 8>), grid, dim3(256), 0, s, a); \
-                       else if (db) hipLaunchKernelGGL((vv_gemm3_kernel<E_, 4, 1>), grid, dim3(256), 0, s, a); \
-                       else hipLaunchKernelGGL((vv_gemm3_kernel<E_, 4>), grid, dim3(256), 0, s, a); } while (0)
-    if (epi == VV_EPI_SWIGLU) {
-        if (!W2 || !Yp) return -1;
-        VV_G3(VV_EPI_SWIGLU);
-    } else if (epi == VV_EPI_RESID) {
-        if (!Y || (ldy & 3)) return -1;
-        VV_G3(VV_EPI_RESID);
-    } else if (epi == VV_EPI_BIAS || epi == VV_EPI_STORE) {
-        if (!Y || (ldy & 3)) return -1;
-        VV_G3(VV_EPI_BIAS);                        // bias == null: plain store
-    } else {
-        return -3;
-    }
-#undef VV_G3
-    if (ks > 1) {
+    gemm3_run(p, a, ws, s);
+    if (p.ks > 1) {
         const int64_t n4 = ((int64_t)T * N + 3) / 4;
-        hipLaunchKernelGGL(vv_g3_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, ws->g3_partials, ks, T, N, bias_r, Y, ldy, resid_r);
+        hipLaunchKernelGGL(vv_g3_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, ws->g3_partials, p.ks, T, N, bias, Y, ldy,
+                           epi == VV_EPI_RESID ? 1 : 0);
     }
     return vv_launch_rc(0);
 }
 
-// causal prefill attention of R consecutive rows of one cache (64 query rows x the GQA group of one kv head per workgroup)
-// The QKV projection of a prompt pass with RoPE + KV-cache append in the epilogue (head_dim 128, vv_gemm4 shapes only).
+// The QKV projection of a prompt pass with RoPE + KV-cache append in the epilogue (head_dim 128, vv_gemm4 shapes only: vv_qkv_rope_plan).
 // Returns 1 when the fused kernel was launched, 0 when the shape does not qualify (the caller runs the plain GEMM + vv_rope_append),
 // < 0 on error.  rows_dev[0] = (cache, first position): read on the device, so a captured graph replays at other positions.
 int vv_gemm_qkv_rope_launch(const void* W, const void* Xp, const float* bias, int T, int K, int D, int Hq, int Hkv, const VVRow* rows_dev,
                             const void* rope_tab, float* q_out, void* kc, void* vc, int64_t cache_stride, int64_t head_stride,
                             const VVGemmWs* ws, hipStream_t s) {
-    const int N = (Hq + 2 * Hkv) * D;
-    if (D != 128 || T < 1 || K < 32 || !rows_dev || !rope_tab || !q_out || !kc || !vc) return 0;
-    const int n_blocks = N / 256, t_blocks = (T + 255) / 256;
-    if ((N & 255) || (int64_t)n_blocks * t_blocks < 256) return 0;
-    VVGemm3 a;
-    memset(&a, 0, sizeof(a));
+    VVGemm3Plan p;
+    if (!vv_qkv_rope_plan(T, K, D, Hq, Hkv, rows_dev && rope_tab && q_out && kc && vc, vv_prefill_ws(ws).round, &p)) return 0;
+    VVGemm3 a = {};
     a.W = (const u32x4*)W; a.Xp = (const u32x4*)Xp; a.bias = bias;
-    a.T = T; a.N = N; a.K = K; a.ldy = N;
-    a.n_blocks = n_blocks; a.t_blocks = t_blocks; a.sfw = 4; a.split = 1;
+    a.T = T; a.N = (Hq + 2 * Hkv) * D; a.K = K; a.ldy = a.N;
     a.rows = rows_dev; a.rope_tab = (const float2*)rope_tab; a.q_out = q_out; a.kc = (__bf16*)kc; a.vc = (__bf16*)vc;
     a.cache_stride = cache_stride; a.head_stride = head_stride; a.Hq = Hq; a.Hkv = Hkv; a.q_scale = 1.0f / sqrtf((float)D);
-    unsigned n_wgs = (unsigned)(n_blocks * t_blocks);
-    g4_split_plan(a, ws, K, n_wgs);
-    static const hipError_t lds = vv_raise_lds_limit(160 * 1024, &vv_gemm4_kernel<VV_EPI_QKV_ROPE>);
-    (void)lds;
-    hipLaunchKernelGGL((vv_gemm4_kernel<VV_EPI_QKV_ROPE>), dim3(n_wgs), dim3(512), (size_t)4 * 32 * 1024, s, a);
+    gemm3_run(p, a, ws, s);
     return vv_launch_rc(1);
 }
 
+// causal prefill attention of R consecutive rows of one cache (64 query rows x the GQA group of one kv head per workgroup)
 // out_packed != null: the result goes out as packed bf16 B fragments [R][Hq * D] (the o-projection GEMM's operand) instead of fp32 rows
 int vv_attn_prefill4_launch(int D, const float* q, const VVRow* rows, const void* kc, const void* vc, int R, int Hq, int Hkv,
                             int64_t cache_stride, int64_t head_stride, float* out, void* out_packed, hipStream_t s) {

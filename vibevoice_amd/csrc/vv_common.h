@@ -177,6 +177,10 @@ static inline hipError_t vv_raise_lds_limit(int bytes, K*... kernels) {
     return rc;
 }
 
+// what a launcher (or its plan) answers when nothing is launched: no compiled form of ITS kernel for this call (the caller may route
+// the call to another kernel), or no kernel at all can run it
+enum { VV_RC_NO_FORM = -3, VV_RC_NO_KERNEL = -4 };
+
 // Launch status of the calling host thread: hipGetLastError() after a launch (it clears the thread's error state, so the code is
 // kept here for the message the API layer prints).  rc_ok is what the launcher returns on success.
 inline thread_local int g_vv_launch_err = 0;

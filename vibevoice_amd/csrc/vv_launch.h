@@ -4,9 +4,6 @@
 #pragma once
 #include "vv_common.h"
 #include "gemv_plan.h"       // VV_ROUTE_* and vv_gemm_route(a, xs): which kernel vv_gemm_launch runs a call on
-// what a launcher answers when it launched nothing: no compiled form of ITS kernel for this call (the caller may route the call to
-// another kernel), or no kernel at all can run it
-enum { VV_RC_NO_FORM = -3, VV_RC_NO_KERNEL = -4 };
 extern "C" {
 int vv_gemm_launch(VVGemm a, int xs, hipStream_t s);
 int vv_pack_launch(const void* src, int src_is_bf16, void* dst, int N, int K, int kind, int Cin, int Cout, int ksz, int stride, hipStream_t s);
