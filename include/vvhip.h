@@ -265,6 +265,30 @@ int vv_set_enc_pass_frames(vv_ctx* ctx, int frames_per_pass);
  * of convert_to_16_bit_wav (demo/gradio_demo.py:1058-1073, applied per streamed chunk at :404-418): peak = max|x| of the
  * chunk; x /= peak when peak > 1; int16(trunc(x * 32767)).  audio_dev [n][samples] fp32 -> pcm_out_dev [n][samples] int16. */
 int vv_audio_to_pcm16(vv_ctx* ctx, void* stream, int n, int samples, const float* audio_dev, int16_t* pcm_out_dev);
+/* ---- audio at another sample rate: a streaming rational resampler L / M (vibevoice_amd/resample.py defines it and designs the
+ * filter).  Output m is the input at time m * M / L, the input taken as zero outside itself: with k = m * M + (L * T - 2) / 2,
+ * y[m] = sum_{t < T} coef[k % L][t] * x[k / L - t], fp32 fmaf in that order.  What a stream emits does not depend on how its input
+ * was cut into pushes: a push emits every output whose last input sample has arrived (the last T / 2 samples wait for the next
+ * push), the flush emits the rest against zeros, ceil(total * L / M) outputs in all.
+ * vv_resampler_set: configuration rs (0..3) of this context: coef_host [L][T] fp32 in HOST memory, T even, n_streams history rows,
+ * all zero.  Replaces what rs held.  Synchronous.  Refused with a message: a table that does not fit the kernel's 64 KiB of LDS. */
+int vv_resampler_set(vv_ctx* ctx, int rs, int L, int M, int T, const float* coef_host, int n_streams, void* stream);
+/* Back to the state after vv_resampler_set for n streams (stream_ids_host == NULL: all of them): history zeroed by a kernel on
+ * `stream`, input total 0, flush mark cleared. */
+int vv_resampler_reset(vv_ctx* ctx, void* stream, int rs, int n, const int* stream_ids_host);
+/* One push of n <= 16 rows, ONE launch on `stream`: row i = n_in samples at audio_dev + i * ld_in for stream rows_host[i].stream
+ * (distinct), flush != 0: the stream's last push.  Its outputs go to out_dev + i * ld_out (elements): out_fmt 0 = fp32, 1 = int16
+ * with the arithmetic of vv_audio_to_pcm16 over the row's resampled chunk.  n_out_host [n]: what each row emitted, computed on the
+ * host from the streams' input totals (no sync).  Rows may stand at different totals.  Refused with a message, nothing written, no
+ * state changed: n outside [1,16], a stream id out of range or named twice, n_in < 0 or above ld_in, a row that emits more than
+ * ld_out or more than 8192 samples, a chunk too long for the kernel's LDS, a push to a flushed stream before its reset. */
+typedef struct vv_resample_row { int stream; int n_in; int flush; } vv_resample_row;
+int vv_resample_rows(vv_ctx* ctx, void* stream, int rs, int n, const vv_resample_row* rows_host, const float* audio_dev, int ld_in,
+                     void* out_dev, int ld_out, int out_fmt, int* n_out_host);
+/* Stateless: n whole signals of n_in samples (audio_dev + i * ld_in) -> ceil(n_in * L / M) fp32 samples each (out_dev + i * ld_out),
+ * coef_dev [L][T] on the device.  Bit-identical to the same signal pushed and flushed through vv_resample_rows. */
+int vv_resample_once(vv_ctx* ctx, void* stream, int L, int M, int T, const float* coef_dev, int n, int n_in, const float* audio_dev,
+                     int ld_in, float* out_dev, int ld_out);
 /* acoustic_cache.set_to_zero + semantic_cache.set_to_zero for a slot (:542-546) */
 int vv_codec_reset(vv_ctx* ctx, void* stream, int slot);
 /* acoustic_connector(latent) [+ semantic_connector(sem)] (:667-669, :161); sem_dev may be NULL */

@@ -50,6 +50,11 @@ class VVNoiseKey(C.Structure):
     _fields_ = [("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("t0", C.c_uint32), ("aux", C.c_uint32)]
 
 
+class VVResampleRow(C.Structure):
+    """vv_resample_row (include/vvhip.h): the stream, the input samples and the flush mark of one row of vv_resample_rows"""
+    _fields_ = [("stream", C.c_int), ("n_in", C.c_int), ("flush", C.c_int)]
+
+
 GEMV_REFUSED = 1     # VV_GEMV_REFUSED
 _SIGS = {
     "vv_create": (C.c_int, [C.POINTER(VVConfig), C.POINTER(_P)]),
@@ -90,6 +95,11 @@ _SIGS = {
     "vv_kv_restore": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     "vv_set_enc_pass_frames": (C.c_int, [_P, C.c_int]),
     "vv_audio_to_pcm16": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
+    "vv_resampler_set": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "vv_resampler_reset": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "vv_resample_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(VVResampleRow), _P, C.c_int, _P, C.c_int, C.c_int,
+                                   C.POINTER(C.c_int)]),
+    "vv_resample_once": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int]),
     "vv_codec_reset": (C.c_int, [_P, _P, C.c_int]),
     "vv_connect": (C.c_int, [_P, _P, C.c_int, _P, _P, _P]),
     "vv_packed_bytes": (C.c_int64, [C.c_int, C.c_int]),

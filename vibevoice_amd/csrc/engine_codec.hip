@@ -496,3 +496,112 @@ extern "C" int vv_codec_reset(vv_ctx* ctx, void* stream, int slot) {
     if (ctx->c.sem_dim > 0 && zero_codec(ctx, ctx->senc, slot, st)) return -1;
     return 0;
 }
+
+// ------------------------------------------------------------------ audio at another sample rate (kernels: resample.hip)
+// Outputs a stream has emitted once `total` input samples have arrived: every m whose newest input sample, index
+// (m * M + D) / L with D = (L * T - 2) / 2, is below total.  vibevoice_amd/resample.py (emitted) is the same arithmetic.
+static int64_t rs_emitted(int64_t total, int L, int M, int T) {
+    const int64_t a = total * L - (L * T - 2) / 2 - 1;
+    return a < 0 ? 0 : a / M + 1;
+}
+
+extern "C" int vv_resampler_set(vv_ctx* ctx, int rs, int L, int M, int T, const float* coef_host, int n_streams, void* stream) {
+    VV_SHARED;
+    if (rs < 0 || rs >= vv_ctx::N_RESAMPLERS) return fail(ctx, "vv_resampler_set: configuration %d out of range [0,%d)", rs, vv_ctx::N_RESAMPLERS);
+    if (L < 1 || L > 4096 || M < 1 || M > 4096) return fail(ctx, "vv_resampler_set: L = %d, M = %d must be in [1,4096]", L, M);
+    if (T < 2 || (T & 1) || T > 4096) return fail(ctx, "vv_resampler_set: T = %d must be even and in [2,4096]", T);
+    if (n_streams < 1 || n_streams > 65536) return fail(ctx, "vv_resampler_set: n_streams = %d must be in [1,65536]", n_streams);
+    if (!coef_host) return fail(ctx, "vv_resampler_set: null coefficient table");
+    // the table, the history and at least the T / 2 samples a push must be able to bring must fit the kernel's LDS
+    if (vv_resample_lds_bytes(L, T, T) > 65536 - 64)
+        return fail(ctx, "vv_resampler_set: the %d x %d coefficient table (%d bytes) does not fit the resampling kernel's 64 KiB of LDS; "
+                         "this rate pair is not served", L, T, L * T * 4);
+    vv_ctx::Resampler& r = ctx->rs[rs];
+    HIPCHK(ctx, hipStreamSynchronize((hipStream_t)stream));      // pushes that still read what is replaced
+    dfree(ctx, r.coef); dfree(ctx, r.hist);
+    r = vv_ctx::Resampler();
+    float* coef = (float*)dalloc(ctx, (size_t)L * T * 4, false);
+    float* hist = (float*)dalloc(ctx, (size_t)n_streams * T * 4, true);
+    if (!coef || !hist) { dfree(ctx, coef); dfree(ctx, hist); return -1; }
+    if (hipMemcpy(coef, coef_host, (size_t)L * T * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        dfree(ctx, coef); dfree(ctx, hist);
+        return fail(ctx, "vv_resampler_set: the coefficient upload failed");
+    }
+    r.L = L; r.M = M; r.T = T; r.n_streams = n_streams; r.coef = coef; r.hist = hist;
+    r.total.assign(n_streams, 0); r.flushed.assign(n_streams, 0);
+    return 0;
+}
+
+extern "C" int vv_resampler_reset(vv_ctx* ctx, void* stream, int rs, int n, const int* stream_ids_host) {
+    VV_SHARED;
+    hipStream_t st = (hipStream_t)stream;
+    if (rs < 0 || rs >= vv_ctx::N_RESAMPLERS || !ctx->rs[rs].coef) return fail(ctx, "vv_resampler_reset: configuration %d is not set", rs);
+    vv_ctx::Resampler& r = ctx->rs[rs];
+    std::vector<int> ids;
+    if (!stream_ids_host) { for (int i = 0; i < r.n_streams; ++i) ids.push_back(i); }
+    else {
+        if (n < 1) return fail(ctx, "vv_resampler_reset: n = %d must be >= 1", n);
+        ids.assign(stream_ids_host, stream_ids_host + n);
+    }
+    for (int id : ids)
+        if (id < 0 || id >= r.n_streams) return fail(ctx, "vv_resampler_reset: stream id %d out of range [0,%d)", id, r.n_streams);
+    for (size_t i0 = 0; i0 < ids.size(); i0 += 16)
+        VVCHK(vv_resample_reset_launch(r.hist, r.T, r.n_streams, ids.data() + i0, (int)std::min<size_t>(16, ids.size() - i0), st));
+    for (int id : ids) { r.total[id] = 0; r.flushed[id] = 0; }
+    return 0;
+}
+
+extern "C" int vv_resample_rows(vv_ctx* ctx, void* stream, int rs, int n, const vv_resample_row* rows_host, const float* audio_dev, int ld_in,
+                                void* out_dev, int ld_out, int out_fmt, int* n_out_host) {
+    VV_SHARED;
+    if (rs < 0 || rs >= vv_ctx::N_RESAMPLERS || !ctx->rs[rs].coef) return fail(ctx, "vv_resample_rows: configuration %d is not set", rs);
+    vv_ctx::Resampler& r = ctx->rs[rs];
+    if (n < 1 || n > 16) return fail(ctx, "vv_resample_rows: n = %d must be in [1,16]", n);
+    if (!rows_host || !out_dev || !n_out_host) return fail(ctx, "vv_resample_rows: null rows / out / n_out pointer");
+    if (out_fmt != 0 && out_fmt != 1) return fail(ctx, "vv_resample_rows: out_fmt = %d must be 0 (fp32) or 1 (int16)", out_fmt);
+    VVRsRows kr;
+    memset(&kr, 0, sizeof(kr));
+    int max_in = 0;
+    for (int i = 0; i < n; ++i) {
+        const vv_resample_row& q = rows_host[i];
+        if (q.stream < 0 || q.stream >= r.n_streams) return fail(ctx, "vv_resample_rows: row %d: stream id %d out of range [0,%d)", i, q.stream, r.n_streams);
+        for (int j = 0; j < i; ++j)
+            if (rows_host[j].stream == q.stream) return fail(ctx, "vv_resample_rows: stream %d is named twice (rows %d and %d)", q.stream, j, i);
+        if (q.n_in < 0) return fail(ctx, "vv_resample_rows: row %d: n_in = %d must be >= 0", i, q.n_in);
+        if (q.n_in > ld_in || (q.n_in > 0 && !audio_dev)) return fail(ctx, "vv_resample_rows: row %d: n_in = %d exceeds the input rows (ld_in = %d)", i, q.n_in, ld_in);
+        if (r.flushed[q.stream]) return fail(ctx, "vv_resample_rows: stream %d has been flushed; reset it before its next push", q.stream);
+        const int64_t before = r.total[q.stream], after = before + q.n_in;
+        const int64_t m0 = rs_emitted(before, r.L, r.M, r.T);
+        const int64_t m1 = q.flush ? (after * r.L + r.M - 1) / r.M : rs_emitted(after, r.L, r.M, r.T);
+        const int64_t n_out = m1 - m0;
+        if (n_out > ld_out) return fail(ctx, "vv_resample_rows: row %d emits %lld samples, the output rows hold %d", i, (long long)n_out, ld_out);
+        if (n_out > VV_RS_MAX_OUT) return fail(ctx, "vv_resample_rows: row %d emits %lld samples, one push emits at most %d per row", i, (long long)n_out, VV_RS_MAX_OUT);
+        const int64_t k0 = m0 * r.M + (r.L * r.T - 2) / 2;
+        kr.r[i].stream = q.stream; kr.r[i].n_in = q.n_in; kr.r[i].n_out = (int)n_out;
+        kr.r[i].p0 = (int)(k0 % r.L); kr.r[i].b0 = (int)(k0 / r.L - before + r.T);
+        max_in = std::max(max_in, q.n_in);
+    }
+    if (vv_resample_lds_bytes(r.L, r.T, max_in) > 65536 - 64)
+        return fail(ctx, "vv_resample_rows: a chunk of %d samples does not fit the kernel's LDS beside the %d x %d table; push at most %d at a time",
+                    max_in, r.L, r.T, (65536 - 64) / 4 - r.L * (r.T + 1) - r.T - r.T / 2);
+    for (int i = n; i < 16; ++i) kr.r[i] = kr.r[0];
+    VVCHK(vv_resample_rows_launch(&kr, n, r.L, r.M, r.T, r.coef, r.hist, r.n_streams, audio_dev, ld_in, out_dev, ld_out, out_fmt, (hipStream_t)stream));
+    for (int i = 0; i < n; ++i) {
+        r.total[rows_host[i].stream] += rows_host[i].n_in;
+        if (rows_host[i].flush) r.flushed[rows_host[i].stream] = 1;
+        n_out_host[i] = kr.r[i].n_out;
+    }
+    return 0;
+}
+
+extern "C" int vv_resample_once(vv_ctx* ctx, void* stream, int L, int M, int T, const float* coef_dev, int n, int n_in, const float* audio_dev,
+                                int ld_in, float* out_dev, int ld_out) {
+    VV_SHARED;
+    if (L < 1 || L > 4096 || M < 1 || M > 4096 || T < 2 || (T & 1) || T > 4096) return fail(ctx, "vv_resample_once: L = %d, M = %d in [1,4096], T = %d even in [2,4096]", L, M, T);
+    if (n < 1 || n > 65535 || n_in < 1 || n_in > ld_in) return fail(ctx, "vv_resample_once: n = %d in [1,65535], n_in = %d in [1, ld_in = %d]", n, n_in, ld_in);
+    const int64_t n_out = ((int64_t)n_in * L + M - 1) / M;
+    if (n_out > ld_out || n_out >= ((int64_t)1 << 31) - 256) return fail(ctx, "vv_resample_once: %lld output samples per row, the output rows hold %d", (long long)n_out, ld_out);
+    if (!coef_dev || !audio_dev || !out_dev) return fail(ctx, "vv_resample_once: null coef / audio / out pointer");
+    VVCHK(vv_resample_once_launch(L, M, T, coef_dev, n, n_in, audio_dev, ld_in, out_dev, ld_out, (hipStream_t)stream));
+    return 0;
+}

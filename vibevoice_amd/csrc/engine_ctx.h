@@ -169,6 +169,13 @@ struct vv_ctx {
     struct LoraBase { void* snap; size_t bytes; bool merged; };
     std::map<int, LoraBase> lora_base;
     int64_t lora_base_bytes = 0;      // vv_stat 7
+    // streaming resamplers (vv_resampler_set, engine_codec.hip; kernels: resample.hip): the filter, one history row of T samples per
+    // stream on the device, and on the host each stream's input total (what the next push's outputs are counted from) and whether it
+    // has been flushed.  This context's own, a shared child's included; the buffers are dalloc()s, released by vv_destroy.
+    struct Resampler { int L = 0, M = 0, T = 0, n_streams = 0; float* coef = nullptr; float* hist = nullptr;
+                       std::vector<int64_t> total; std::vector<char> flushed; };
+    static constexpr int N_RESAMPLERS = 4;
+    Resampler rs[N_RESAMPLERS];
     int64_t launches = 0;
     int64_t seam_launches = 0;        // head-tail seam launches the last recorded sampler body issued (vv_stat 6; a replay keeps its capture's count)
     // optional per-GEMM-launch hipEvent timing (vv_profile_begin/end)

@@ -164,6 +164,15 @@ __device__ __forceinline__ int vv_slot_id(const int (&id)[8], int j) {     // se
     return r;
 }
 
+// ---- streaming resampler (resample.hip): one row of a push, passed by value in the kernel arguments ----
+// The host keeps each stream's 64-bit input total; what the kernel needs of it is the position of the row's first output:
+// with k0 = m0 * M + (L * T - 2) / 2 for that output m0, p0 = k0 % L is its phase and b0 = k0 / L - total + T the index of its newest
+// input sample in the row's staging buffer [T history | n_in chunk | T / 2 zeros].  Output j of the push then sits at
+// phase (p0 + j * M) % L, index b0 + (p0 + j * M) / L: 32-bit arithmetic whatever the stream's age.
+struct VVRsRow { int stream, n_in, n_out, p0, b0; };
+struct VVRsRows { VVRsRow r[16]; };
+constexpr int VV_RS_MAX_OUT = 8192;        // outputs one row of a push may emit (1024 threads x 8 accumulators)
+
 // Raise the dynamic-LDS limit of one or more kernels above the 64 KiB default; returns the first error.  A launcher calls it as
 // the initialiser of a function-local `static const hipError_t`: C++11 runs that initialiser once per process and makes
 // concurrent first calls wait for it (generate_interleaved and fork() drive two contexts from two host threads).

@@ -90,4 +90,10 @@ int vv_tile_launch(VVGemm a, int xs, hipStream_t s);
 int vv_lora_merge_launch(const void* base, void* dst, int N, int K, const float* a, const float* b, int r, float scale, int delta_bf16,
                          hipStream_t s);
 int vv_unpack_launch(const void* packed, float* dst, int N, int K, hipStream_t s);
+// resample.hip.  _lds_bytes: what a push of n_in samples per row needs of the 64 KiB a workgroup has (the launcher refuses more).
+int vv_resample_lds_bytes(int L, int T, int n_in);
+int vv_resample_rows_launch(const VVRsRows* rows, int n, int L, int M, int T, const float* coef, float* hist, int n_streams, const float* x,
+                            int ld_in, void* out, int ld_out, int pcm16, hipStream_t s);
+int vv_resample_once_launch(int L, int M, int T, const float* coef, int n, int n_in, const float* x, int ld_in, float* out, int ld_out, hipStream_t s);
+int vv_resample_reset_launch(float* hist, int T, int n_streams, const int* ids, int n, hipStream_t s);
 }

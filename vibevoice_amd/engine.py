@@ -516,6 +516,42 @@ class Engine:
         self._chk(self.lib.vv_audio_to_pcm16(self._ctx, self._sp(stream), n, samples, self._p(audio), self._p(pcm_out)),
                   "vv_audio_to_pcm16")
 
+    # ------------------------------------------------------------------ audio at another sample rate (resample.py, csrc/resample.hip)
+    def resampler(self, src_rate: int, dst_rate: int, n_streams: int) -> "Resampler":
+        """A streaming resampler src_rate -> dst_rate with n_streams independent streams, in one of this engine's four resampler
+        configurations (close() it to give the configuration back)."""
+        used = self.__dict__.setdefault("_rs_used", [None] * 4)
+        for k in range(len(used)):
+            if used[k] is None:
+                used[k] = r = Resampler(self, k, src_rate, dst_rate, n_streams)
+                return r
+        raise EngineError("Engine.resampler: all 4 resampler configurations of this engine are in use; close() one")
+
+    def resample(self, audio: torch.Tensor, src_rate: int, dst_rate: int, stream=None) -> torch.Tensor:
+        """Whole signals at another rate: audio [samples] or [n, samples] (any float dtype, any device) -> fp32 on the engine's device,
+        ceil(samples * dst / src) samples each, the definition of vibevoice_amd/resample.py.  Stateless; runs on `stream` (default:
+        the current torch stream of the device, the one that produced a device tensor)."""
+        from . import resample as _rs
+        L, M, T, coef = _rs.design(src_rate, dst_rate)
+        x = audio.detach().to(device=self.device, dtype=torch.float32)
+        if x.dim() not in (1, 2):
+            raise ValueError(f"Engine.resample: audio is [samples] or [n, samples], got {tuple(audio.shape)}")
+        x2 = x.reshape(-1, x.shape[-1]).contiguous()
+        n, n_in = x2.shape
+        n_out = _rs.total_out(n_in, L, M)
+        out = torch.empty((n, n_out), dtype=torch.float32, device=self.device)
+        if n and n_in:
+            cache = self.__dict__.setdefault("_rs_coef", {})
+            cd = cache.get((L, M, T))
+            if cd is None:
+                cd = cache[(L, M, T)] = torch.from_numpy(np.array(coef)).to(self.device)
+            st = stream if stream is not None else torch.cuda.current_stream(self.device)
+            for i0 in range(0, n, 65535):
+                nn = min(65535, n - i0)
+                self._chk(self.lib.vv_resample_once(self._ctx, self._sp(st), L, M, T, self._p(cd), nn, n_in, self._p(x2[i0:]), n_in,
+                                                    self._p(out[i0:]), n_out), "vv_resample_once")
+        return out.reshape(x.shape[:-1] + (n_out,))
+
     def codec_reset(self, slot: int):
         self._chk(self.lib.vv_codec_reset(self._ctx, self._s, slot), "vv_codec_reset")
 
@@ -821,3 +857,89 @@ class Engine:
         if rc != 0:
             raise EngineError(f"vv_gemv_case failed ({rc})")
         return tuple(form)
+
+
+class Resampler:
+    """One streaming resampler configuration of an engine (Engine.resampler): n_streams chunk-continuous streams src_rate -> dst_rate.
+    What a stream delivers does not depend on how its input was cut into pushes (vibevoice_amd/resample.py): the concatenation of its
+    pushes and its flush equals Engine.resample() of the concatenated input, bit for bit in float mode, ceil(n * L / M) samples.
+    taps: filter taps per output sample; delay_samples: the input samples (taps / 2) a stream holds back until its next push."""
+
+    def __init__(self, engine: Engine, slot: int, src_rate: int, dst_rate: int, n_streams: int):
+        from . import resample as _rs
+        self.engine, self.slot = engine, slot
+        self.src_rate, self.dst_rate, self.n_streams = int(src_rate), int(dst_rate), int(n_streams)
+        self.L, self.M, self.T, coef = _rs.design(src_rate, dst_rate)
+        self.taps, self.delay_samples = self.T, _rs.delay_samples(self.T)
+        self.total = [0] * self.n_streams                 # input samples each stream has taken (the C side keeps the same figures)
+        c = np.ascontiguousarray(coef)
+        engine._chk(engine.lib.vv_resampler_set(engine._ctx, slot, self.L, self.M, self.T, C.c_void_p(c.ctypes.data), self.n_streams,
+                                                engine._s), "vv_resampler_set")
+
+    def counts(self, stream_id: int, n_in: int, flush: bool = False) -> int:
+        """samples a push of n_in samples to stream_id would emit now (host integers, no device sync)"""
+        from . import resample as _rs
+        return _rs.counts(self.L, self.M, self.T, self.total[stream_id], n_in, flush)[1]
+
+    def max_out(self, n_in: int) -> int:
+        """upper bound of what any push of up to n_in samples emits, the flush included"""
+        return -((-(int(n_in) + self.delay_samples + 1) * self.L) // self.M) + 1
+
+    def push(self, audio: Optional[torch.Tensor], stream_ids: Sequence[int], flush=False, out: Optional[torch.Tensor] = None,
+             pcm16: bool = False, n_in=None, stream=None):
+        """Row i of audio [n, samples] (contiguous fp32 on the engine's device; None where no row brings samples) goes to stream
+        stream_ids[i] (distinct); n_in: samples of each row that count (default: all), flush: bool or one per row -- a stream's last
+        push, after which it takes no more until reset().  -> (out, counts): out[i, :counts[i]] is what row i emitted, fp32, or int16
+        under pcm16 (the arithmetic of Engine.audio_to_pcm16 over the row's resampled chunk, in the same launch).  out: a contiguous
+        [>= n, capacity] tensor of that dtype to write into (default: a new one of max_out(samples) columns).  One launch per 16 rows
+        on `stream` (default: the device's current torch stream); the counts are host integers, nothing waits for the device."""
+        e = self.engine
+        ids = [int(i) for i in stream_ids]
+        n = len(ids)
+        samples = 0 if audio is None else int(audio.shape[-1])
+        if audio is not None:
+            if audio.dim() != 2 or audio.dtype != torch.float32 or not audio.is_contiguous() or audio.device != e.device or audio.shape[0] < n:
+                raise ValueError(f"Resampler.push: audio is a contiguous fp32 [n >= {n}, samples] tensor on {e.device}")
+        nin = [samples] * n if n_in is None else [int(v) for v in n_in]
+        fl = [bool(flush)] * n if isinstance(flush, (bool, int)) else [bool(v) for v in flush]
+        if len(nin) != n or len(fl) != n:
+            raise ValueError("Resampler.push: n_in and flush name one value per row")
+        dt = torch.int16 if pcm16 else torch.float32
+        if out is None:
+            out = torch.empty((max(n, 1), self.max_out(max(nin, default=0))), dtype=dt, device=e.device)
+        elif out.dim() != 2 or out.dtype != dt or not out.is_contiguous() or out.device != e.device or out.shape[0] < n:
+            raise ValueError(f"Resampler.push: out is a contiguous {dt} [n >= {n}, capacity] tensor on {e.device}")
+        st = stream if stream is not None else torch.cuda.current_stream(e.device)
+        cnts = (C.c_int * max(n, 1))()
+        rows = (_lib.VVResampleRow * max(n, 1))()
+        for i in range(n):
+            rows[i].stream, rows[i].n_in, rows[i].flush = ids[i], nin[i], int(fl[i])
+        cap = int(out.shape[1])
+        for i0 in range(0, max(n, 1), 16):
+            nn = min(16, n - i0)
+            a = C.c_void_p(audio.data_ptr() + i0 * samples * 4) if audio is not None else C.c_void_p()
+            o = C.c_void_p(out.data_ptr() + i0 * cap * out.element_size())
+            e._chk(e.lib.vv_resample_rows(e._ctx, e._sp(st), self.slot, nn, C.cast(C.byref(rows, i0 * C.sizeof(_lib.VVResampleRow)), C.POINTER(_lib.VVResampleRow)),
+                                          a, samples, o, cap, int(pcm16), C.cast(C.byref(cnts, i0 * 4), C.POINTER(C.c_int))), "vv_resample_rows")
+            for i in range(i0, i0 + nn):
+                self.total[ids[i]] += nin[i]
+        return out, [int(cnts[i]) for i in range(n)]
+
+    def reset(self, ids: Optional[Sequence[int]] = None, stream=None):
+        """streams `ids` (default: all) back to their first sample: history zeroed on `stream`, totals 0, flush marks cleared"""
+        e = self.engine
+        st = stream if stream is not None else torch.cuda.current_stream(e.device)
+        if ids is None:
+            e._chk(e.lib.vv_resampler_reset(e._ctx, e._sp(st), self.slot, 0, None), "vv_resampler_reset")
+            self.total = [0] * self.n_streams
+            return
+        arr = (C.c_int * max(1, len(ids)))(*[int(i) for i in ids])
+        e._chk(e.lib.vv_resampler_reset(e._ctx, e._sp(st), self.slot, len(ids), arr), "vv_resampler_reset")
+        for i in ids:
+            self.total[int(i)] = 0
+
+    def close(self):
+        """give the engine's configuration back (its device buffers are released when the configuration is set again or the engine closes)"""
+        used = getattr(self.engine, "_rs_used", None)
+        if used is not None and used[self.slot] is self:
+            used[self.slot] = None

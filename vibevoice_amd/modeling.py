@@ -561,7 +561,17 @@ class _Utt:
         self.neg_book = [[1], 0, 0]
 
 
-class VibeVoiceForConditionalGenerationInference:
+class _AudioRates:
+    """What both model classes offer around the 24 kHz the tokenizers work at (self.engine: the class's Engine)."""
+
+    def resample_audio(self, audio: torch.Tensor, dst_rate: int, src_rate: int = 24000) -> torch.Tensor:
+        """audio [samples] or [n, samples] at src_rate -> fp32 on the engine's device at dst_rate, ceil(samples * dst / src) samples
+        (Engine.resample).  For speech_outputs after the fact -- resample_audio(out.speech_outputs[0], 48000) -- and for a voice
+        sample before the processor, which wants 24 kHz: resample_audio(wav, 24000, src_rate=44100).  generate() itself stays at 24 kHz."""
+        return self.engine.resample(audio, int(src_rate), int(dst_rate))
+
+
+class VibeVoiceForConditionalGenerationInference(_AudioRates):
     """Drop-in for the reference class on the generate() path, backed by libvvhip.so."""
 
     def __init__(self, config: dict, engine: Engine, model_dtype=torch.bfloat16, attn_implementation: Optional[str] = None):

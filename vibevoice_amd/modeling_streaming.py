@@ -18,7 +18,7 @@ import numpy as np
 
 from . import noise as _noise
 from .engine import Engine, EngineConfig
-from .modeling import VibeVoiceGenerationOutput, WeightHandle, _Ns, _SchedulerView, engine_config_from_reference
+from .modeling import VibeVoiceGenerationOutput, WeightHandle, _AudioRates, _Ns, _SchedulerView, engine_config_from_reference
 
 TTS_TEXT_WINDOW_SIZE = 5
 TTS_SPEECH_WINDOW_SIZE = 6
@@ -111,7 +111,7 @@ def _kv_layers(past):
     return list(past)
 
 
-class VibeVoiceStreamingForConditionalGenerationInference:
+class VibeVoiceStreamingForConditionalGenerationInference(_AudioRates):
     """Drop-in for the reference class on the streaming generate() path (demo/streaming_inference_from_file.py:226-355:
     from_pretrained -> eval -> set_ddpm_inference_steps -> model.model.language_model.config._attn_implementation ->
     generate(**processor_inputs, all_prefilled_outputs=preset, ...)), backed by libvvhip.so."""

@@ -9,6 +9,15 @@ reference does `.detach().cpu()` per sample = one stream sync each).
 gradio demo's convert_to_16_bit_wav, demo/gradio_demo.py:404-418,1058-1073), so the consumer receives int16 tensors and
 the D2H copy is half the size of a bf16->fp32 round trip.
 
+`sample_rate=R` (R other than 24000) delivers the audio at R Hz: put() resamples the chunk batch on the device, on the producing
+stream, before the copy -- one launch (Engine.resampler, csrc/resample.hip), the int16 conversion included under pcm16 -- and the
+delivered chunks are trimmed to what each sample emitted (a put that completes no output sample delivers nothing for that row).
+The resampler is chunk-continuous: per sample, the concatenated chunks equal Engine.resample() of the concatenated 24 kHz chunks,
+ceil(n * R / 24000) samples, bit for bit in float mode.  The price is latency: the last taps / 2 input samples of a sample wait for
+its next chunk (1.3 ms at 48 kHz, 4 ms at 8 kHz); end(indices) flushes those tails as a last chunk in front of the stop signal,
+close() does not.  Device chunks need an engine: the `pcm16=` one, or `engine=` where the chunks stay float; CPU chunks go through
+resample.HostResampler on the host.  Stream id = sample index.
+
 The drain thread exits when every sample has ended (or on close()); its pinned ring goes back to a process-wide pool.
 """
 import asyncio
@@ -61,9 +70,22 @@ def _pinned_give(bufs):
                 held += 1
 
 
+SOURCE_RATE = 24000      # what the acoustic decoder produces
+
+
 class AudioStreamer:
-    def __init__(self, batch_size: int, stop_signal=None, timeout: Optional[float] = None, ring_slots: int = 8, pcm16=None):
+    def __init__(self, batch_size: int, stop_signal=None, timeout: Optional[float] = None, ring_slots: int = 8, pcm16=None,
+                 sample_rate: Optional[int] = None, engine=None):
         self.batch_size = batch_size
+        self.sample_rate = SOURCE_RATE if sample_rate is None else int(sample_rate)
+        self._rs = None                            # Engine.resampler (device chunks), one stream per sample index
+        self._rs_host = {}                         # sample index -> resample.HostResampler (CPU chunks)
+        self._rs_stream = None                     # the producing stream of the last resampled put: the tails are flushed on it
+        self._lead = ()                            # a chunk's dimensions between the row and the samples, kept for the tail
+        if self.sample_rate != SOURCE_RATE:
+            eng = engine if engine is not None else pcm16
+            if eng is not None:                    # without one, only CPU chunks are served (resample.HostResampler); put() refuses others
+                self._rs = eng.resampler(SOURCE_RATE, self.sample_rate, batch_size)
         self.stop_signal = stop_signal
         self.timeout = timeout
         self.audio_queues = [self._make_queue() for _ in range(batch_size)]
@@ -96,14 +118,82 @@ class AudioStreamer:
             return
         if not audio_chunks.is_cuda:
             for row, idx in live:
-                self._work.put(("chunk", idx, audio_chunks[row].detach().clone(), None, None))
+                chunk = audio_chunks[row].detach().clone()
+                if self.sample_rate != SOURCE_RATE:
+                    chunk = self._host_chunk(idx, chunk)
+                    if chunk is None:
+                        continue
+                self._work.put(("chunk", idx, chunk, None, None))
             return
+        if self.sample_rate != SOURCE_RATE and self._rs is None:
+            raise ValueError(f"AudioStreamer(sample_rate={self.sample_rate}): device chunks are resampled on the device and need an engine "
+                             "(pcm16=engine for 16-bit chunks, engine=engine for float chunks)")
         slot = self._free.get()                                    # back-pressure only if the consumer is > ring_slots behind
         with self._lock:                                           # the drain thread hands the ring back to the pool under this lock
             if self._closed:
                 self._free.put(slot)
                 return
-            self._put_slot(audio_chunks, live, slot)
+            if self._rs is not None:
+                self._put_resampled(audio_chunks, live, slot)
+            else:
+                self._put_slot(audio_chunks, live, slot)
+
+    def _host_chunk(self, idx, chunk):
+        """a CPU chunk of sample idx (None: its flush) at the streamer's rate, None where it completes no output sample"""
+        from .resample import HostResampler
+        h = self._rs_host.get(idx)
+        if h is None:
+            if chunk is None:
+                return None
+            h = self._rs_host[idx] = HostResampler(SOURCE_RATE, self.sample_rate)
+        if chunk is not None:
+            self._lead = tuple(chunk.shape[:-1])
+        y = h.flush() if chunk is None else h.push(chunk.reshape(-1))
+        return y.reshape(self._lead + (y.shape[0],)) if y.shape[0] else None
+
+    def _put_resampled(self, audio_chunks, live, slot, flush=False):
+        """One Resampler.push for the live rows (audio_chunks None: their flush), then the ring copy of _put_slot; the work item carries
+        each row's sample count."""
+        rs, pcm = self._rs, self._pcm_engine is not None
+        dev = rs.engine.device
+        ids = [idx for _, idx in live]
+        n = len(live)
+        if audio_chunks is not None:
+            src = audio_chunks.detach()
+            self._lead = tuple(src.shape[1:-1])
+            flat = src.reshape(src.shape[0], -1).to(torch.float32)
+            if [row for row, _ in live] != list(range(n)):
+                flat = flat[[row for row, _ in live]]
+            flat = flat.contiguous()
+            samples = flat.shape[1]
+            self._rs_stream = torch.cuda.current_stream(dev)
+        else:
+            flat, samples = None, 0
+        prod = self._rs_stream if self._rs_stream is not None else torch.cuda.current_stream(dev)
+        cap, dt = rs.max_out(samples), torch.int16 if pcm else torch.float32
+        pd = self._pcm_dev[slot]
+        if pd is None or pd.shape[0] < n or pd.shape[1] < cap or pd.dtype != dt:
+            pd = torch.empty((max(n, self.batch_size), cap), dtype=dt, device=dev)
+            self._pcm_dev[slot] = pd
+        with torch.cuda.stream(prod):
+            _, cnts = rs.push(flat, ids, flush=flush, out=pd, pcm16=pcm, n_in=None if flat is not None else [0] * n, stream=prod)
+        buf = self._ring[slot]
+        if buf is None or buf.dim() != 2 or buf.shape[1] != pd.shape[1] or buf.shape[0] < n or buf.dtype != dt:
+            if buf is not None:
+                _pinned_give([buf])
+            buf = _pinned_take((max(n, self.batch_size), pd.shape[1]), dt)
+            self._ring[slot] = buf
+        if self._copy_stream is None:
+            self._copy_stream = _copy_stream_for(dev)
+        ready = torch.cuda.Event()
+        ready.record(prod)
+        self._copy_stream.wait_event(ready)
+        with torch.cuda.stream(self._copy_stream):
+            buf[:n].copy_(pd[:n], non_blocking=True)              # whole rows: both sides contiguous, one asynchronous copy
+        pd.record_stream(self._copy_stream)
+        ev = torch.cuda.Event()
+        ev.record(self._copy_stream)
+        self._work.put(("rslot", [(i, idx, cnts[i]) for i, idx in enumerate(ids)], slot, ev, self._lead))
 
     def _put_slot(self, audio_chunks, live, slot):
         src = audio_chunks.detach()
@@ -146,10 +236,27 @@ class AudioStreamer:
             idxs = list(range(self.batch_size))
         else:
             idxs = [int(i.item()) if torch.is_tensor(i) else int(i) for i in sample_indices]
+        idxs = [idx for idx in dict.fromkeys(idxs) if idx < self.batch_size and not self.finished_flags[idx]]
+        if self.sample_rate != SOURCE_RATE and idxs and not self._closed:
+            self._flush_tails(idxs)
         for idx in idxs:
-            if idx < self.batch_size and not self.finished_flags[idx]:
-                self.finished_flags[idx] = True
-                self._work.put(("end", idx, None, None, None))       # ordered after that sample's pending chunks
+            self.finished_flags[idx] = True
+            self._work.put(("end", idx, None, None, None))       # ordered after that sample's pending chunks
+
+    def _flush_tails(self, idxs):
+        """the samples the resampler still holds for these sample indices, as a last chunk each, in front of their stop signals"""
+        for idx in idxs:
+            tail = self._host_chunk(idx, None)
+            if tail is not None:
+                self._work.put(("chunk", idx, tail, None, None))
+        live = [(row, idx) for row, idx in enumerate(i for i in idxs if self._rs is not None and self._rs.total[i] > 0)]
+        for i0 in range(0, len(live), 16):
+            slot = self._free.get()
+            with self._lock:
+                if self._closed:
+                    self._free.put(slot)
+                    return
+                self._put_resampled(None, [(r - i0, idx) for r, idx in live[i0:i0 + 16]], slot, flush=True)
 
     def close(self):
         """Stop the drain thread and release the pinned ring (also happens by itself once every sample has ended)."""
@@ -183,6 +290,13 @@ class AudioStreamer:
                 for row, idx in a:
                     self._deliver(idx, buf[row].clone())
                 self._free.put(b)
+            elif kind == "rslot":
+                ev.synchronize()
+                buf = self._ring[b]
+                for row, idx, cnt in a:
+                    if cnt:
+                        self._deliver(idx, buf[row, :cnt].clone().reshape(n + (cnt,)))
+                self._free.put(b)
             elif kind == "chunk":
                 self._deliver(a, b)
             elif kind == "end":
@@ -200,13 +314,15 @@ class AudioStreamer:
                 item = self._work.get_nowait()
             except _q.Empty:
                 break
-            if item[0] == "slot":
+            if item[0] in ("slot", "rslot"):
                 item[3].synchronize()
                 self._free.put(item[2])                  # a producer still blocked in _free.get() wakes up, sees _closed, returns
         with self._lock:
             _pinned_give(self._ring)                     # every copy into them has completed (their events have been waited on)
             self._ring = [None] * len(self._ring)
             self._pcm_dev = [None] * len(self._pcm_dev)  # release the device staging
+            if self._rs is not None:
+                self._rs.close()                         # the engine's resampler configuration is free for the next streamer
 
     # ---- consumer side ----
     def __iter__(self):
@@ -270,9 +386,10 @@ class AsyncAudioStreamer(AudioStreamer):
     a worker thread, as in the reference's gradio path -- never touches the loop and never syncs the stream.
         async for chunk in streamer.get_stream(0): ...      async for batch in streamer: ..."""
 
-    def __init__(self, batch_size: int, stop_signal=None, timeout: Optional[float] = None, ring_slots: int = 8, pcm16=None):
+    def __init__(self, batch_size: int, stop_signal=None, timeout: Optional[float] = None, ring_slots: int = 8, pcm16=None,
+                 sample_rate: Optional[int] = None, engine=None):
         self.loop = asyncio.get_running_loop()
-        super().__init__(batch_size, stop_signal, timeout, ring_slots=ring_slots, pcm16=pcm16)
+        super().__init__(batch_size, stop_signal, timeout, ring_slots=ring_slots, pcm16=pcm16, sample_rate=sample_rate, engine=engine)
 
     def _make_queue(self):
         return asyncio.Queue()
