@@ -1,0 +1,39 @@
+"""The row sets behind the route claims of the LM pass's GPU tests, and the engine settings that decide what their context offers, as
+plain data: the GPU tests take their shapes from here, and test_pass_plan_cpu.py asks the routing (csrc/pass_plan.h), on a machine
+without a GPU, whether every row set runs the launches its test's docstring says it does.  Engines: (key of LM_CASES in
+test_gpu_kernels.py or an LMCfg, max_rows); the tests build them at the xsplit values of their parametrisation."""
+import synth
+
+
+def span(cache, pos0, n):
+    """n consecutive positions of one cache, as Engine.lm_forward_span issues them"""
+    return [(cache, pos0 + j) for j in range(n)]
+
+
+# test_gpu_prompt_prefix.py::test_suffix_over_a_restored_prefix_equals_the_chunked_pass: (prefix rows n, suffix rows m); the suffix
+# starts at position n.  A 1-row suffix is a decode row (fused attention), 2..7 rows split + merge, 8..63 vv_attn_prefill4 in the
+# bf16 mode, >= 64 the packed prefill
+SUFFIX_SPANS = ((8, 1), (37, 5), (37, 20), (100, 64), (100, 150), (128, 20), (64, 7))
+SUFFIX_ENGINE = ("gqa", 256)
+
+# test_gpu_kernels.py::test_short_prompt_spans_ignore_cache_slots_past_their_end: spans at position 0, then a chunked prompt (pos0, rows)
+SHORT_SPANS = (2, 5, 7, 8, 20, 48, 63)
+SHORT_SPANS_CHUNKED = ((0, 128), (128, 20))
+SHORT_SPANS_ENGINE = ("gqa", 256)
+
+# test_gpu_kernels.py::test_lm_prefill_one_pass_and_ragged_chunks_match_the_oracle: the prompt in one pass, then in ragged chunks
+# (below the 8 rows of a contiguous chunk: rope/append + split + merge, one launch of the pair per layer); exact mode
+RAGGED_PROMPT, RAGGED_CHUNK = 150, 7
+RAGGED_ENGINE = (synth.LMCfg(), 160)
+
+# test_gpu_kernels.py::test_decode_batches_ignore_cache_slots_past_each_row: cache lengths of the rows of one launch (row i on cache i),
+# DECODE_STEPS steps each.  6 and 16 rows: the batch-decode route in the bf16 mode; 1100: two splits, the merge kernel runs
+DECODE_LENS = {"1": [37], "6": [1, 31, 32, 33, 64, 90], "16": [1, 2, 7, 16, 31, 32, 33, 40, 63, 64, 65, 70, 95, 96, 97, 127],
+               "long": [1100]}
+DECODE_STEPS = 3
+DECODE_ENGINE = ("gqa", 16)
+
+# test_gpu_geometry.py::test_prefill_attention_over_4k_positions: the prompt in chunks of max_rows rows; bf16 mode: the packed prefill;
+# exact modes: per whole chunk, eight 64-row launches of the split + merge pair
+PREFILL_4K_PROMPT, PREFILL_4K_CHUNK = 4200, 512
+PREFILL_4K_ENGINE = (synth.LMCfg(hidden=512, layers=1, heads=4, kv_heads=2, inter=512, vocab=64, max_pos=8192), 512)

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 import torch
 
+import lm_shapes as ls
 import synth
 from gpu_util import build_small, rel_err
 from oracle import dpm, head
@@ -169,22 +170,23 @@ def test_decode_attention_over_the_full_context(tag, L, xs, tol):
 def test_prefill_attention_over_4k_positions(xs, tol):
     """A 4,200-token prompt through one layer in 512-row chunks against the oracle's full causal attention: xs = 1 runs the
     packed-activation GEMMs + vv_attn_prefill4_kernel; xs = 2, 3 the tile / general GEMMs and, per chunk, eight 64-row launches of
-    the split + merge attention pair (every row attends its own causal prefix)."""
-    c = synth.LMCfg(hidden=512, layers=1, heads=4, kv_heads=2, inter=512, vocab=64, max_pos=8192)
-    s = build_fast(c, xsplit=xs, max_ctx=4352, max_rows=512, head_layers=1)
+    the split + merge attention pair (every row attends its own causal prefix).  Shapes: tests/lm_shapes.py; test_pass_plan_cpu.py
+    asserts the routes."""
+    c, chunk = ls.PREFILL_4K_ENGINE
+    s = build_fast(c, xsplit=xs, max_ctx=4352, max_rows=chunk, head_layers=1)
     eng = s.eng
     try:
         H = c.hidden
         m = s.oracle_lm(kv_round_bf16=True)
         g = synth.Gen(4200)
-        L0 = 4200
+        L0 = ls.PREFILL_4K_PROMPT
         x = g.normal((L0, H), 1.0, mat=False)
         ref = m.forward(x, m.new_cache())
         hid = eng.new(L0, H)
         xd = dev(x, eng)
         with torch.cuda.stream(eng.stream):
-            for i0 in range(0, L0, 512):
-                n = min(512, L0 - i0)
+            for i0 in range(0, L0, chunk):
+                n = min(chunk, L0 - i0)
                 eng.lm_forward([(0, i0 + j) for j in range(n)], xd[i0:i0 + n], hid[i0:i0 + n])
         eng.sync()
         assert rel_err(hid[-64:], ref[-64:]) <= tol, rel_err(hid[-64:], ref[-64:])

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import lm_shapes as ls
 import prefill_shapes
 import synth
 from gpu_util import build_small, max_err, rel_err
@@ -23,7 +24,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def sm():
-    s = build_small(synth.LMCfg(), xsplit=3, max_rows=160)
+    s = build_small(ls.RAGGED_ENGINE[0], xsplit=3, max_rows=ls.RAGGED_ENGINE[1])
     yield s
     s.eng.close()
 
@@ -145,12 +146,13 @@ def test_prefill_gemm3(sm, epi, T, N, K):
 
 
 def test_lm_prefill_one_pass_and_ragged_chunks_match_the_oracle(sm):
-    """A 150-token prompt prefilled (a) in one launch (prefill attention kernel: 16 query rows per workgroup) and (b) in ragged
-    7-row chunks (rope/append + split + merge kernels, below 8 rows): both against the oracle's causal forward."""
+    """A 150-token prompt prefilled (a) in one launch (exact mode: rope/append, then the split + merge pair 64 rows at a time) and (b) in
+    ragged 7-row chunks (rope/append + split + merge kernels, below 8 rows): both against the oracle's causal forward.  Shapes:
+    tests/lm_shapes.py; test_pass_plan_cpu.py asserts the routes named here."""
     eng = sm.eng
     H = sm.lmcfg.hidden
     g = synth.Gen(4242)
-    n = min(150, eng.cfg.max_rows)
+    n = min(ls.RAGGED_PROMPT, eng.cfg.max_rows)
     x = g.normal((n, H), 1.0, mat=False)
     m = sm.oracle_lm(kv_round_bf16=True)
     ref = m.forward(x, m.new_cache())
@@ -159,8 +161,8 @@ def test_lm_prefill_one_pass_and_ragged_chunks_match_the_oracle(sm):
     hid_b = eng.new(n, H)
     with torch.cuda.stream(eng.stream):
         eng.lm_forward([(0, j) for j in range(n)], xd, hid_a)                # cache 0: one pass
-        for i0 in range(0, n, 7):                                            # cache 1: ragged 7-row chunks
-            k = min(7, n - i0)
+        for i0 in range(0, n, ls.RAGGED_CHUNK):                              # cache 1: ragged 7-row chunks
+            k = min(ls.RAGGED_CHUNK, n - i0)
             eng.lm_forward([(1, i0 + j) for j in range(k)], xd[i0:i0 + k], hid_b[i0:i0 + k])
     eng.sync()
     assert rel_err(hid_a, ref) <= 5e-4, rel_err(hid_a, ref)
@@ -592,15 +594,15 @@ def test_short_prompt_spans_ignore_cache_slots_past_their_end(xs):
     bf16 mode (through the per-layer GEMMs, not the packed-activation pass), whose V tail past the span must be zeroed as well;
     2..7 rows take the split + merge pair, as do all of them in the exact mode.  Then a chunked prompt: 128 rows, and a trailing
     span of 20 rows at position 128 (the last chunk of a longer prompt).  NaN / Inf in every cache slot past the prompt, every
-    layer: the hidden states must be the clean run's, bit for bit."""
-    s = build_small(LM_CASES["gqa"], xsplit=xs, max_ctx=512, max_rows=256)
+    layer: the hidden states must be the clean run's, bit for bit.  Spans: tests/lm_shapes.py; test_pass_plan_cpu.py asserts the routes."""
+    s = build_small(LM_CASES[ls.SHORT_SPANS_ENGINE[0]], xsplit=xs, max_ctx=512, max_rows=ls.SHORT_SPANS_ENGINE[1])
     eng = s.eng
     try:
         cfg = s.lmcfg
         H = cfg.hidden
         g = synth.Gen(709)
         bad = []
-        for L0 in (2, 5, 7, 8, 20, 48, 63):
+        for L0 in ls.SHORT_SPANS:
             x = dev(g.normal((L0, H), 1.0, mat=False), eng)
 
             def run(poison):
@@ -618,8 +620,8 @@ def test_short_prompt_spans_ignore_cache_slots_past_their_end(xs):
             hid = eng.new(148, H)
             with torch.cuda.stream(eng.stream):
                 _fill_past(eng, cfg, 0, 128, poison)
-                eng.lm_forward_span(0, 0, 128, x[:128], hid[:128])
-                eng.lm_forward_span(0, 128, 20, x[128:], hid[128:])
+                for p0, k in ls.SHORT_SPANS_CHUNKED:
+                    eng.lm_forward_span(0, p0, k, x[p0:p0 + k], hid[p0:p0 + k])
             eng.sync()
             return hid.clone()
         if not _clean_and_dirty(chunked):
@@ -635,14 +637,14 @@ def test_decode_batches_ignore_cache_slots_past_each_row(xs, case):
     """Decode rows over caches of different lengths in one launch: a single row, 6 and 16 rows (the bf16 mode's packed-activation
     batch forms, vv_gemv16p, with the attention writing the packed o-projection operand) and one row at position 1100 (two
     flash-decoding splits: the merge kernel runs).  Every cache holds random K/V up to its own length and NaN / Inf (or, for the
-    clean run, zeros) past it in every layer; three decode steps must give the clean run's hidden states bit for bit."""
-    s = build_small(LM_CASES["gqa"], xsplit=xs, max_ctx=1280, max_rows=16, n_slots=8)
+    clean run, zeros) past it in every layer; three decode steps must give the clean run's hidden states bit for bit.  Row sets:
+    tests/lm_shapes.py; test_pass_plan_cpu.py asserts the routes and the split count."""
+    s = build_small(LM_CASES[ls.DECODE_ENGINE[0]], xsplit=xs, max_ctx=1280, max_rows=ls.DECODE_ENGINE[1], n_slots=8)
     eng = s.eng
     try:
         cfg = s.lmcfg
         H, kvh, hd = cfg.hidden, cfg.kv_heads, cfg.head_dim
-        lens = {"1": [37], "6": [1, 31, 32, 33, 64, 90], "16": [1, 2, 7, 16, 31, 32, 33, 40, 63, 64, 65, 70, 95, 96, 97, 127],
-                "long": [1100]}[case]
+        lens = ls.DECODE_LENS[case]
         gk = torch.Generator().manual_seed(710 + len(lens))
         kv = [tuple(torch.randn(cfg.layers, kvh, n, hd, generator=gk).to(torch.bfloat16) for _ in "kv") for n in lens]
         g = synth.Gen(711)
@@ -655,7 +657,7 @@ def test_decode_batches_ignore_cache_slots_past_each_row(xs, case):
                     for layer in range(cfg.layers):
                         eng.kv_import_at(c, layer, 0, kv[c][0][layer].to(eng.device), kv[c][1][layer].to(eng.device))
                     _fill_past(eng, cfg, c, n, poison)
-                for step in range(3):
+                for step in range(ls.DECODE_STEPS):
                     hid = eng.new(len(lens), H)
                     eng.lm_forward([(c, n + step) for c, n in enumerate(lens)], x[step], hid)
                     outs.append(hid)

@@ -13,6 +13,7 @@ import types
 import pytest
 import torch
 
+import lm_shapes as ls
 import synth
 from gpu_util import build_small, rel_err
 from oracle import generate as ogen
@@ -34,7 +35,7 @@ def engs():
 
     def get(xs):
         if xs not in made:
-            made[xs] = build_small(LM_CASES["gqa"], xsplit=xs, n_slots=2, max_ctx=512, max_rows=256)
+            made[xs] = build_small(LM_CASES[ls.SUFFIX_ENGINE[0]], xsplit=xs, n_slots=2, max_ctx=512, max_rows=ls.SUFFIX_ENGINE[1])
         return made[xs]
     yield get
     for s in made.values():
@@ -204,14 +205,15 @@ def test_snapshot_is_clean_whatever_lay_behind_it(engs, xs):
 # ---------------------------------------------------------------- 4. suffix over a restored prefix == the in-place chunked pass
 @pytest.mark.parametrize("xs,tol", [(1, 3e-2), (3, 3e-4)])
 def test_suffix_over_a_restored_prefix_equals_the_chunked_pass(engs, xs, tol):
-    """suffixes of 1..7 rows (split + merge attention), 8..63 rows (vv_attn_prefill4 in the bf16 mode) and >= 64 rows (the packed
-    prefill), starting on and off the 16- / 32- / 64-position grids"""
+    """suffixes of 1 row (a decode row: fused attention), 2..7 rows (split + merge attention), 8..63 rows (vv_attn_prefill4 in the bf16
+    mode) and >= 64 rows (the packed prefill), starting on and off the 16- / 32- / 64-position grids.  The spans: tests/lm_shapes.py;
+    test_pass_plan_cpu.py asserts that each takes the route named here"""
     s = engs(xs)
     eng, cfg = s.eng, s.lmcfg
     H = cfg.hidden
     om = s.oracle_lm(kv_round_bf16=True)
     unequal, errs = [], {}
-    for n, m in ((8, 1), (37, 5), (37, 20), (100, 64), (100, 150), (128, 20), (64, 7)):
+    for n, m in ls.SUFFIX_SPANS:
         xc = synth.Gen(300 + n + m).normal((n + m, H), 1.0, mat=False)
         x = xc.to(eng.device)
         torch.cuda.synchronize()

@@ -13,7 +13,7 @@ LIB = os.path.join(HERE, "libvvhip.so")
 SOURCES = ["gemm.hip", "gemv.hip", "gemv16p.hip", "headtail.hip", "tile.hip", "prefill.hip", "attn.hip", "misc.hip", "warp.hip", "noise.hip", "kvspan.hip", "block1d.hip", "lora.hip", "resample.hip", "engine.hip",
            "engine_lm.hip", "engine_head.hip", "engine_codec.hip", "engine_prof.hip", "engine_lora.hip"]
 HEADERS = [os.path.join(CSRC, "vv_common.h"), os.path.join(CSRC, "vv_device.h"), os.path.join(CSRC, "vv_launch.h"), os.path.join(CSRC, "gemv_plan.h"),
-           os.path.join(CSRC, "prefill_plan.h"), os.path.join(CSRC, "engine_ctx.h"),
+           os.path.join(CSRC, "prefill_plan.h"), os.path.join(CSRC, "pass_plan.h"), os.path.join(CSRC, "engine_ctx.h"),
            os.path.join(os.path.dirname(HERE), "include", "vvhip.h")]
 
 

@@ -609,46 +609,41 @@ extern "C" int vv_rope_append_launch(int D, const float* qkv, const VVRow* rows,
     return vv_launch_rc(0);
 }
 
-template <int D, int XS>
-static void attn_go(const float* q, const VVRow* rows, const void* kc, const void* vc, int R, int Hq, int Hkv,
-                    int64_t cs, int64_t hs, int S, float* pm, float* pl, float* po, float* out, hipStream_t s) {
-    hipLaunchKernelGGL((vv_attn_split_kernel<D, XS>), dim3(S, Hkv, R), dim3(256), 0, s, q, rows,
-                       (const __bf16*)kc, (const __bf16*)vc, Hq, Hkv, cs, hs, pm, pl, po);
-    hipLaunchKernelGGL((vv_attn_merge_kernel<D>), dim3(R, Hq), dim3(D), 0, s, pm, pl, po, rows, out, Hq, Hkv, S);
-}
-
 extern "C" int vv_rope_table_launch(const float* inv_freq, void* tab, int n_pos, int half, hipStream_t s) {
     const int64_t n = (int64_t)n_pos * half;
     hipLaunchKernelGGL(vv_rope_table_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, inv_freq, (float2*)tab, n_pos, half);
     return vv_launch_rc(0);
 }
 
+// ---- one table per kernel family, indexed by (D in {64, 128}, xs in {1, 2, 3}); any other xs runs the xs = 3 form, as it always did.
+// The merge kernels do not depend on xs ----
+constexpr int ATTN_W = 4;                // waves per workgroup of the fused kernel
+static int attn_d(int D) { return D == 64 ? 0 : D == 128 ? 1 : -1; }
+static int attn_x(int xs) { return xs == 1 ? 0 : xs == 2 ? 1 : 2; }
+static const decltype(&vv_attn_fused_kernel<64, 1, ATTN_W>) attn_fused_kernels[2][3] = {
+    {vv_attn_fused_kernel<64, 1, ATTN_W>, vv_attn_fused_kernel<64, 2, ATTN_W>, vv_attn_fused_kernel<64, 3, ATTN_W>},
+    {vv_attn_fused_kernel<128, 1, ATTN_W>, vv_attn_fused_kernel<128, 2, ATTN_W>, vv_attn_fused_kernel<128, 3, ATTN_W>}};
+static const decltype(&vv_attn_split_kernel<64, 1>) attn_split_kernels[2][3] = {
+    {vv_attn_split_kernel<64, 1>, vv_attn_split_kernel<64, 2>, vv_attn_split_kernel<64, 3>},
+    {vv_attn_split_kernel<128, 1>, vv_attn_split_kernel<128, 2>, vv_attn_split_kernel<128, 3>}};
+static const decltype(&vv_attn_merge_kernel<64>) attn_merge_kernels[2] = {vv_attn_merge_kernel<64>, vv_attn_merge_kernel<128>};
+static const decltype(&vv_attn_merge2_kernel<64>) attn_merge2_kernels[2] = {vv_attn_merge2_kernel<64>, vv_attn_merge2_kernel<128>};
+
 // Decode-step attention in one launch; requires every row to own a different cache (the new token of row r must not
 // be visible to -- or needed by -- another row of the same launch).
-template <int D, int XS>
-static void attn_fused_go(dim3 grid, hipStream_t s, const float* qkv, const VVRow* rows, const void* rope_tab, void* kc, void* vc,
-                          int Hq, int Hkv, int64_t cache_stride, int64_t head_stride, float scale, float* pm, float* pl, float* po, float* out, void* out_packed) {
-    constexpr int W = 4;                 // waves per workgroup
-    constexpr size_t smem = (size_t)W * (D / 16) * 64 * 16 + (size_t)2 * W * 16 * 4 + (size_t)2 * D * 2;      // <= 33 KiB
-    hipLaunchKernelGGL((vv_attn_fused_kernel<D, XS, W>), grid, dim3(W * 64), smem, s, qkv, rows, (const float2*)rope_tab, (__bf16*)kc, (__bf16*)vc,
-                       Hq, Hkv, cache_stride, head_stride, scale, pm, pl, po, out, (unsigned char*)out_packed);
-}
 extern "C" int vv_attn_fused_launch(int D, int xs, const float* qkv, const VVRow* rows, const void* rope_tab, void* kc, void* vc,
                                     int R, int Hq, int Hkv, int64_t cache_stride, int64_t head_stride, int S,
                                     float* pm, float* pl, float* po, float* out, void* out_packed, hipStream_t s) {
     if (Hq % Hkv != 0 || Hq / Hkv > 16) return -1;
     if (out_packed && (R > 16 || ((Hq * D) & 31))) return -1;
+    const int d = attn_d(D);
+    if (d < 0) return -1;
     const float scale = 1.0f / sqrtf((float)D);
-    const dim3 grid(S, Hkv, R);
-#define VV_F(D_, XS_) attn_fused_go<D_, XS_>(grid, s, qkv, rows, rope_tab, kc, vc, Hq, Hkv, cache_stride, head_stride, scale, pm, pl, po, out, out_packed)
-    if (D == 128) { if (xs == 1) VV_F(128, 1); else if (xs == 2) VV_F(128, 2); else VV_F(128, 3); }
-    else if (D == 64) { if (xs == 1) VV_F(64, 1); else if (xs == 2) VV_F(64, 2); else VV_F(64, 3); }
-    else return -1;
-#undef VV_F
-    if (S > 1) {      // rows that needed one split were finished by the attention kernel; the merge kernel skips them
-        if (D == 128) hipLaunchKernelGGL((vv_attn_merge2_kernel<128>), dim3(R, Hq), dim3(512), 0, s, pm, pl, po, rows, out, Hq, Hkv, S, (unsigned char*)out_packed);
-        else hipLaunchKernelGGL((vv_attn_merge2_kernel<64>), dim3(R, Hq), dim3(512), 0, s, pm, pl, po, rows, out, Hq, Hkv, S, (unsigned char*)out_packed);
-    }
+    const size_t smem = (size_t)ATTN_W * (D / 16) * 64 * 16 + (size_t)2 * ATTN_W * 16 * 4 + (size_t)2 * D * 2;      // <= 33 KiB
+    hipLaunchKernelGGL(attn_fused_kernels[d][attn_x(xs)], dim3(S, Hkv, R), dim3(ATTN_W * 64), smem, s, qkv, rows, (const float2*)rope_tab, (__bf16*)kc, (__bf16*)vc,
+                       Hq, Hkv, cache_stride, head_stride, scale, pm, pl, po, out, (unsigned char*)out_packed);
+    if (S > 1)        // rows that needed one split were finished by the attention kernel; the merge kernel skips them
+        hipLaunchKernelGGL(attn_merge2_kernels[d], dim3(R, Hq), dim3(512), 0, s, pm, pl, po, rows, out, Hq, Hkv, S, (unsigned char*)out_packed);
     return vv_launch_rc(0);
 }
 
@@ -656,15 +651,10 @@ extern "C" int vv_attn_launch(int D, int xs, const float* q, const VVRow* rows, 
                               int R, int Hq, int Hkv, int64_t cache_stride, int64_t head_stride, int S,
                               float* pm, float* pl, float* po, float* out, hipStream_t s) {
     if (Hq % Hkv != 0 || Hq / Hkv > 16) return -1;
-#define VV_A(D_)                                                                                              \
-    do {                                                                                                      \
-        if (xs == 1) attn_go<D_, 1>(q, rows, kc, vc, R, Hq, Hkv, cache_stride, head_stride, S, pm, pl, po, out, s); \
-        else if (xs == 2) attn_go<D_, 2>(q, rows, kc, vc, R, Hq, Hkv, cache_stride, head_stride, S, pm, pl, po, out, s); \
-        else attn_go<D_, 3>(q, rows, kc, vc, R, Hq, Hkv, cache_stride, head_stride, S, pm, pl, po, out, s);   \
-    } while (0)
-    if (D == 128) VV_A(128);
-    else if (D == 64) VV_A(64);
-    else return -1;
-#undef VV_A
+    const int d = attn_d(D);
+    if (d < 0) return -1;
+    hipLaunchKernelGGL(attn_split_kernels[d][attn_x(xs)], dim3(S, Hkv, R), dim3(256), 0, s, q, rows,
+                       (const __bf16*)kc, (const __bf16*)vc, Hq, Hkv, cache_stride, head_stride, pm, pl, po);
+    hipLaunchKernelGGL(attn_merge_kernels[d], dim3(R, Hq), dim3(D), 0, s, pm, pl, po, rows, out, Hq, Hkv, S);
     return vv_launch_rc(0);
 }

@@ -1,5 +1,6 @@
 // engine_head.hip -- host side of libvvhip.so: the diffusion head: schedule tables, one head evaluation, the sampler.
 #include "engine_ctx.h"
+#include "pass_plan.h"
 
 static int set_schedule(vv_ctx* ctx, int n_steps, const float* t, const float* coef, int width, void* stream) {
     VV_SHARED;
@@ -68,16 +69,21 @@ extern "C" int vv_set_schedule_sde(vv_ctx* ctx, int n_steps, const float* t, con
     return set_schedule(ctx, n_steps, t, coef6, 6, stream);
 }
 
-// one head evaluation on 2n rows; mod/xh/hact/eps are ctx scratch. temb = t-embedding row for this step.
-static int head_eval(vv_ctx* ctx, hipStream_t st, int rows, const float* zrows, const float* temb_row, float* eps_out,
+static VVHeadPlan head_plan(const vv_ctx* ctx, int rows, int n_steps, bool has_coef) {
+    return vv_head_plan(rows, n_steps, ctx->HF, ctx->c.head_layers, ctx->MODW,
+                        {ctx->p16_ok, ctx->p16_shift != nullptr, ctx->ada_p != nullptr, ctx->mod_all_bytes != 0, ctx->head_tail}, has_coef);
+}
+
+// one head evaluation on 2n rows, solver step `step` of the plan; mod/xh/hact/eps are ctx scratch. temb = t-embedding row for this step.
+static int head_eval(vv_ctx* ctx, hipStream_t st, const VVHeadPlan& p, int step, const float* zrows, const float* temb_row, float* eps_out,
                      const float* coef = nullptr, float cfg = 0.f, const float* mod_ready = nullptr, const float* sde_noise = nullptr,
-                     const unsigned char* sh_tiles = nullptr, int gen = 0, bool have_x = false, bool seam = false,
-                     const float* cfg_rows = nullptr) {
+                     const unsigned char* sh_tiles = nullptr, int gen = 0, bool have_x = false, const float* cfg_rows = nullptr) {
     // cfg_rows: [rows / 2] one guidance scale per utterance on the device, read by the final layer's epilogue in place of cfg (null: cfg)
-    // gen / have_x / seam (sampler, decode rows, bf16 mode): the step's state is generation `gen` (xh / zz / x0p or their second copies);
-    // have_x: the previous step's seam launch already produced this step's in-projection; seam: end this step with the fused launch
-    // (final layer + CFG + solver update + the NEXT step's in-projection, written to the other generation) instead of the final layer
+    // gen / have_x (sampler, decode rows, bf16 mode): the step's state is generation `gen` (xh / zz / x0p or their second copies);
+    // have_x: the previous step's seam launch already produced this step's in-projection; a step whose final stage is the seam ends with
+    // the fused launch (final layer + CFG + solver update + the NEXT step's in-projection, written to the other generation)
     const vv_config& c = ctx->c;
+    const int rows = p.rows, final_stage = vv_head_final(p, step);
     const int H = ctx->H, L = c.latent_dim, HL = c.head_layers, HF = ctx->HF, MODW = ctx->MODW;
     const float* mod = mod_ready ? mod_ready : ctx->mod;
     float* const xh = gen ? ctx->xh2 : ctx->xh;
@@ -97,12 +103,12 @@ static int head_eval(vv_ctx* ctx, hipStream_t st, int rows, const float* zrows, 
     const int xps = 16 * H;
     for (int l = 0; l < HL; ++l) {
         const float* base = mod + (size_t)l * 3 * H;
-        if (rows > 4 && rows <= 16 && ctx->p16_ok && (HF % 32) == 0) {
+        if (p.layers == VV_HEAD_P16) {
             // batch rows: normalise + modulate + pack ONCE, then both projections stream weights against packed fragments
             ctx->launches += 3;
             VVCHK(vv_pack16_launch(xh, H, 2, ctx->hl[l].norm, c.head_eps, base + H, base, MODW, ctx->p16_x, rows, H, st));
             VVCHK(p16_gemv(ctx, st, ctx->hl[l].wg, ctx->hl[l].wu, ctx->p16_x, nullptr, ctx->p16_act, nullptr, nullptr, rows, HF, H, 0, 0, VV_EPI_SWIGLU));
-            if (l + 1 == HL && sh_tiles && coef) {
+            if (l + 1 == HL && final_stage == VV_FINAL_P16_CFG) {
                 // the last layer's down projection leaves the FINAL layer's operand (x * (1 + scale), un-normalised) packed and the rows' sums of squares
                 VVGemv16p ad = p16_args(ctx->hl[l].wd, nullptr, ctx->p16_act, xh, ctx->p16_x, rows, H, HF, H);
                 ad.gate = base + 2 * H; ad.ld_gate = MODW; ad.ssq_out = ctx->ssq_a;
@@ -131,7 +137,7 @@ static int head_eval(vv_ctx* ctx, hipStream_t st, int rows, const float* zrows, 
         }
     }
     const float* fb = mod + (size_t)HL * 3 * H;
-    if (rows > 4 && rows <= 16 && ctx->p16_ok && (HF % 32) == 0 && sh_tiles && coef && HL > 0) {
+    if (final_stage == VV_FINAL_P16_CFG) {
         // the sampler's final layer over the packed operand the last down projection left (4 workgroups that only stream: the 16-row
         // vv_gemv form staged 16 x H modulated rows in each of its 4 workgroups, 21 us), CFG + DPM-Solver++ update in the epilogue
         ctx->launches += 1;
@@ -143,7 +149,7 @@ static int head_eval(vv_ctx* ctx, hipStream_t st, int rows, const float* zrows, 
         VVCHK(p16_go(ctx, st, af, VV_EPI_CFG_DPM, 3));
         return 0;
     }
-    if (seam && coef && rows == 2 && ctx->head_tail) {
+    if (final_stage == VV_FINAL_SEAM) {
         VVTail t{};
         t.Wout = (const u32x4*)ctx->h_out; t.Win = (const u32x4*)ctx->h_in; t.bin = nullptr;
         t.X = xh; t.xa = ctx->xh_parts + (size_t)(HL & 1) * 2 * xps; t.n_xa = xp; t.part_stride = xps;
@@ -167,7 +173,7 @@ static int head_eval(vv_ctx* ctx, hipStream_t st, int rows, const float* zrows, 
     VVGemm gf = mk_gemm(ctx->h_out, xh, eps_out, rows, L, H, H, L);
     gf.pro = VV_PRO_RMS_MOD; gf.nw = nullptr; gf.eps = c.head_eps; gf.mod_shift = fb; gf.mod_scale = fb + H; gf.ld_mod = MODW;
     gf.xa = ctx->xh_parts + (size_t)(HL & 1) * 2 * xps; gf.n_xa = xp; gf.part_stride = xps;
-    if (coef) {   // CFG + DPM-Solver++ update fused into the epilogue: the noisy latent is rewritten in place
+    if (final_stage != VV_FINAL_GEMM) {   // CFG + DPM-Solver++ update fused into the epilogue: the noisy latent is rewritten in place
         gf.epi = VV_EPI_CFG_DPM; gf.z = zcur; gf.x0p = x0cur; gf.coef = coef; gf.cfg = cfg; gf.n_cfg = rows / 2;
         gf.sde_noise = sde_noise; gf.cfg_rows = cfg_rows;
     }
@@ -193,14 +199,13 @@ static int sample_body(vv_ctx* ctx, hipStream_t st, int n, const float* cond, co
     // up front, <=16 rows per GEMM, so the (3*layers+2)*H x H modulation matrix is streamed ceil(2nN/16) times per
     // frame instead of N times (the reference recomputes it inside every head call)
     const int MODW = ctx->MODW;
-    const bool batch_ada = ctx->mod_all_bytes != 0;
+    const VVHeadPlan p = head_plan(ctx, rows, ctx->n_steps, true);
+    const bool batch_ada = p.ada != VV_ADA_PER_STEP;
     if (batch_ada) {
         // SiLU(cond + t) for all (step, row) pairs in one small launch: the GEMM workgroups (one per 16 output features,
         // > 1000 of them) then stage plain rows instead of each re-evaluating 16 x H SiLUs
         const int total = rows * ctx->n_steps;
-        // bf16 mode, three or more 16-row passes: ONE MFMA tile GEMM over all (step, row) pairs instead -- the modulation
-        // matrix (360 MB for the 7B head) is streamed once, not once per 16 rows (8 utterances x 20 steps: 20 passes)
-        if (ctx->ada_p && total > 32 && (MODW & 3) == 0) {
+        if (p.ada == VV_ADA_TILE) {      // ONE MFMA tile GEMM over all (step, row) pairs instead
             ctx->launches += 2;
             VVCHK(vv_ada_pack_launch(ctx->cproj, ctx->temb, ctx->ada_p, rows, ctx->n_steps, H, st));
             VVCHK(vv_gemm3_launch(ctx->h_ada, nullptr, ctx->ada_p, ctx->mod_all, nullptr, nullptr, total, MODW, H, MODW, VV_EPI_STORE, nullptr, st));
@@ -216,8 +221,7 @@ static int sample_body(vv_ctx* ctx, hipStream_t st, int n, const float* cond, co
     }
     nan_probe(ctx, st, "cproj", ctx->cproj, (size_t)rows * H);
     if (batch_ada) nan_probe(ctx, st, "mod_all", ctx->mod_all, (size_t)rows * ctx->n_steps * MODW);
-    const bool sh_ok = batch_ada && rows > 4 && rows <= 16 && ctx->p16_shift;
-    if (sh_ok) {
+    if (p.sh_tiles) {
         // the shift rows of every (solver step, layer) -- and the final layer's -- as packed bf16 tiles, one launch per frame:
         // tile (i, l) = rows [i * rows, (i + 1) * rows) of mod_all, columns [l * 3H, l * 3H + H).  Only the final layer's tile (l == HL) is read
         ctx->launches++;
@@ -228,12 +232,11 @@ static int sample_body(vv_ctx* ctx, hipStream_t st, int n, const float* cond, co
     for (int i = 0; i < ctx->n_steps; ++i) {
         const float* mod_i = batch_ada ? ctx->mod_all + (size_t)i * rows * MODW : nullptr;
         const float* sn = step_noise ? step_noise + (size_t)i * n * L : nullptr;
-        const unsigned char* sht = sh_ok ? (const unsigned char*)ctx->p16_shift + (size_t)i * (ctx->c.head_layers + 1) * ctx->p16_shift_tile : nullptr;
+        const unsigned char* sht = p.sh_tiles ? (const unsigned char*)ctx->p16_shift + (size_t)i * (ctx->c.head_layers + 1) * ctx->p16_shift_tile : nullptr;
         // decode rows, bf16 mode: every step but the last ends with the fused seam (final layer + CFG + solver update + the next step's
         // in-projection, headtail.hip), which leaves the next step's state in the other generation of (xh, zz, x0p)
-        const bool seam = (i + 1 < ctx->n_steps) && rows == 2 && ctx->head_tail;
-        const int hr = head_eval(ctx, st, rows, gen ? ctx->zz2 : ctx->zz, ctx->temb + (size_t)i * H, ctx->eps, ctx->coef + i * 6, cfg, mod_i, sn, sht,
-                                 gen, have_x, seam, cfg_rows);
+        const int hr = head_eval(ctx, st, p, i, gen ? ctx->zz2 : ctx->zz, ctx->temb + (size_t)i * H, ctx->eps, ctx->coef + i * 6, cfg, mod_i, sn, sht,
+                                 gen, have_x, cfg_rows);
         if (hr < 0) return -1;
         if (ctx->probe_on) {
             char nm[64];
@@ -307,7 +310,7 @@ extern "C" int vv_head_forward(vv_ctx* ctx, void* stream, int n, const float* no
     VVCHK(vv_silu_launch(ctx->tmp1, H, st));
     VVGemm g2 = mk_gemm(ctx->h_t2, ctx->tmp1, ctx->tmp1 + H, 1, H, H, H, H); GEMM(g2);
     VVGemm gc = mk_gemm(ctx->h_cond, cond_dev, ctx->cproj, n, H, H, H, H); GEMM(gc);
-    if (head_eval(ctx, st, n, noisy_dev, ctx->tmp1 + H, out_dev)) return -1;
+    if (head_eval(ctx, st, head_plan(ctx, n, 1, false), 0, noisy_dev, ctx->tmp1 + H, out_dev)) return -1;
     HIPCHK(ctx, hipStreamSynchronize(st));
     return 0;
 }

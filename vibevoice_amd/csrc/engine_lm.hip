@@ -1,5 +1,6 @@
 // engine_lm.hip -- host side of libvvhip.so: the LM forward (prefill / batch decode / GEMV layers), KV cache entries, logits.
 #include "engine_ctx.h"
+#include "pass_plan.h"
 
 // batch-decode projection (gemv16p.hip); inside a profile window the launch is also recorded for the family replay
 int p16_gemv(vv_ctx* ctx, hipStream_t st, const void* W, const void* W2, const void* Xp, float* Y, void* Yp, const float* bias,
@@ -30,7 +31,7 @@ VVGemv16p p16_args(const void* W, const void* W2, const void* Xp, float* Y, void
     return a;
 }
 
-// ---- the three layer paths of one LM pass.  lm_body picks one; the launch sequence of each is what it was when they were interleaved ----
+// ---- the three layer paths of one LM pass.  The plan (pass_plan.h) names one and its attention; the launch sequence of each is what it was when they were interleaved ----
 static char* lm_kc(vv_ctx* ctx, int l) { return (char*)ctx->kc + (size_t)l * ctx->layer_stride * 2; }
 static char* lm_vc(vv_ctx* ctx, int l) { return (char*)ctx->vc + (size_t)l * ctx->layer_stride * 2; }
 // cache slots past a prompt chunk inside its last 64-position stage: V zeroed once for every layer of this pass (0 x NaN, see misc.hip)
@@ -51,7 +52,6 @@ static int lm_finish(vv_ctx* ctx, hipStream_t st, int R, float* hidden_out, int 
 static int lm_prefill_layers(vv_ctx* ctx, hipStream_t st, int R, float* hidden_out, int l0, int l1, int final_norm) {
     const vv_config& c = ctx->c;
     const int H = ctx->H, D = ctx->D, Hq = ctx->Hq, Hkv = ctx->Hkv, I = ctx->I, QKV = ctx->QKV;
-    VVTRY(lm_zero_v_tail(ctx, st, R, l0, l1));
     for (int l = l0; l < l1; ++l) {
         auto& L = ctx->layers[l];
         char *kl = lm_kc(ctx, l), *vl = lm_vc(ctx, l);
@@ -81,14 +81,15 @@ static int lm_prefill_layers(vv_ctx* ctx, hipStream_t st, int R, float* hidden_o
 
 // decode rows (one cache each): RoPE + KV append + split attention in ONE launch (+ the merge launch when split).  out_packed (batch
 // decode): the attention (or its merge) writes the o-projection's packed bf16 operand itself
-static int lm_decode_attn(vv_ctx* ctx, hipStream_t st, int R, int l, int attn_S, int64_t kv_positions, void* out_packed) {
+static int lm_decode_attn(vv_ctx* ctx, hipStream_t st, int R, int l, const VVLmPlan& p, void* out_packed) {
     const vv_config& c = ctx->c;
     const int D = ctx->D, Hq = ctx->Hq, Hkv = ctx->Hkv;
     char *kl = lm_kc(ctx, l), *vl = lm_vc(ctx, l);
+    const int attn_S = p.attn_S;
     ctx->launches += (attn_S > 1) ? 2 : 1;
     if (ctx->prof_on) {
         // algorithmic bytes: every cached position of every row once, K and V (bf16) + the row's q / new k, v / output
-        const double by = (double)kv_positions * Hkv * D * 2.0 * 2.0 + (double)R * (ctx->QKV + Hq * D) * 4.0;
+        const double by = (double)p.kv_positions * Hkv * D * 2.0 * 2.0 + (double)R * (ctx->QKV + Hq * D) * 4.0;
         const int xs = c.xsplit; vv_ctx* cx = ctx;
         ctx->prof_other.push_back({2, by, [=](hipStream_t s) {
             return vv_attn_fused_launch(D, xs, cx->qkv, cx->rows_dev, cx->rope_tab, kl, vl, R, Hq, Hkv, cx->cache_stride,
@@ -100,7 +101,7 @@ static int lm_decode_attn(vv_ctx* ctx, hipStream_t st, int R, int l, int attn_S,
 }
 
 // batch decode (5..16 rows, one cache each): packed-activation projections (gemv16p.hip)
-static int lm_p16_layer(vv_ctx* ctx, hipStream_t st, int R, int l, int l0, int l1, int attn_S, int64_t kv_positions) {
+static int lm_p16_layer(vv_ctx* ctx, hipStream_t st, int R, int l, int l0, int l1, const VVLmPlan& p) {
     const vv_config& c = ctx->c;
     const int H = ctx->H, Hq = ctx->Hq, D = ctx->D, I = ctx->I, QKV = ctx->QKV;
     auto& L = ctx->layers[l];
@@ -115,7 +116,7 @@ static int lm_p16_layer(vv_ctx* ctx, hipStream_t st, int R, int l, int l0, int l
         VVCHK(vv_pack16_launch(ctx->h, H, 1, L.ln1, c.lm_eps, nullptr, nullptr, 0, ctx->p16_x, R, H, st));
         VVCHK(p16_gemv(ctx, st, L.wqkv, nullptr, ctx->p16_x, ctx->qkv, nullptr, L.bqkv, nullptr, R, QKV, H, QKV, 0, VV_EPI_BIAS));
     }
-    VVTRY(lm_decode_attn(ctx, st, R, l, attn_S, kv_positions, ctx->p16_y));
+    VVTRY(lm_decode_attn(ctx, st, R, l, p, ctx->p16_y));
     ctx->launches += 3;
     // o-projection: h += Wo . attn; its epilogue packs h * ln2 (-> p16_x) and the rows' partial sums of squares (-> ssq_a)
     VVGemv16p ao = p16_args(L.wo, nullptr, ctx->p16_y, ctx->h, ctx->p16_x, R, H, Hq * D, H);
@@ -135,8 +136,7 @@ static int lm_p16_layer(vv_ctx* ctx, hipStream_t st, int R, int l, int l0, int l
 
 // every other row set: the GEMM dispatcher's kernels (decode GEMV for <= 4 rows).  hp: extra K-split parts the residual stream h
 // consists of on entry and on return (the down projection may split, the next layer's consumers add the parts back)
-static int lm_gemv_layer(vv_ctx* ctx, hipStream_t st, int R, int l, int l1, bool fused_attn, bool contiguous, int attn_S, int64_t kv_positions,
-                         int& hp) {
+static int lm_gemv_layer(vv_ctx* ctx, hipStream_t st, int R, int l, int l1, const VVLmPlan& p, int& hp) {
     const vv_config& c = ctx->c;
     const int H = ctx->H, D = ctx->D, Hq = ctx->Hq, Hkv = ctx->Hkv, I = ctx->I, QKV = ctx->QKV;
     const int hps = ctx->c.max_rows * H;
@@ -145,24 +145,24 @@ static int lm_gemv_layer(vv_ctx* ctx, hipStream_t st, int R, int l, int l1, bool
     g.pro = VV_PRO_RMS; g.nw = L.ln1; g.eps = c.lm_eps; g.epi = VV_EPI_BIAS; g.bias = L.bqkv; g.nt = 1;
     g.xa = ctx->h_parts; g.n_xa = hp; g.part_stride = hps;
     GEMM(g);
-    if (fused_attn) {
-        VVTRY(lm_decode_attn(ctx, st, R, l, attn_S, kv_positions, nullptr));
+    if (p.attn == VV_ATTN_FUSED) {
+        VVTRY(lm_decode_attn(ctx, st, R, l, p, nullptr));
     } else {
         // rows of one launch share caches (prefill chunks): every append must land before any row attends
         char *kl = lm_kc(ctx, l), *vl = lm_vc(ctx, l);
         ctx->launches += 3;
         VVCHK(vv_rope_append_launch(D, ctx->qkv, ctx->rows_dev, ctx->inv_freq, ctx->qrot, kl, vl,
                                     R, Hq, Hkv, ctx->cache_stride, ctx->head_stride, st));
-        if (contiguous && ctx->attn2_ok)      // prompt chunk, bf16 mode: 64 query rows x all heads of the group share every K/V block
+        if (p.attn == VV_ATTN_PREFILL4)       // prompt chunk, bf16 mode: 64 query rows x all heads of the group share every K/V block
             VVCHK(vv_attn_prefill4_launch(D, ctx->qrot, ctx->rows_dev, kl, vl, R, Hq, Hkv, ctx->cache_stride, ctx->head_stride, ctx->attn, nullptr, st));
         else {
             // ragged row sets (the streaming model's text windows) and the prompt chunks of the exact modes (xsplit 2, 3): the
             // split + merge pair, at most ws_rows rows per launch (its partial buffers); every row attends its own causal prefix
-            for (int g0 = 0; g0 < R; g0 += ctx->ws_rows) {
-                const int ng = std::min(ctx->ws_rows, R - g0);
+            for (int k = 0; k < p.attn_groups; ++k) {
+                const int g0 = k * ctx->ws_rows, ng = std::min(ctx->ws_rows, R - g0);
                 if (g0) ctx->launches += 2;
                 VVCHK(vv_attn_launch(D, c.xsplit, ctx->qrot + (size_t)g0 * Hq * D, ctx->rows_dev + g0, kl, vl, ng, Hq, Hkv, ctx->cache_stride,
-                                     ctx->head_stride, attn_S, ctx->pm, ctx->pl, ctx->po, ctx->attn + (size_t)g0 * Hq * D, st));
+                                     ctx->head_stride, p.attn_S, ctx->pm, ctx->pl, ctx->po, ctx->attn + (size_t)g0 * Hq * D, st));
             }
         }
     }
@@ -181,16 +181,13 @@ static int lm_gemv_layer(vv_ctx* ctx, hipStream_t st, int R, int l, int l1, bool
     return 0;
 }
 
-static int lm_body(vv_ctx* ctx, hipStream_t st, int R, const float* x_in, float* hidden_out, int l0, int l1, int final_norm, bool fused_attn, bool contiguous,
-                   int attn_S, int64_t kv_positions = 0) {
+static int lm_body(vv_ctx* ctx, hipStream_t st, int R, const float* x_in, float* hidden_out, int l0, int l1, int final_norm, const VVLmPlan& p) {
     VVCHK(vv_copy_launch(ctx->h, x_in, (size_t)R * ctx->H * 4, st));   // copies / fills inside captured sequences are kernels, never memcpy / memset nodes (misc.hip)
-    if (contiguous && ctx->tile3_ok && R >= 64) return lm_prefill_layers(ctx, st, R, hidden_out, l0, l1, final_norm);
-    const bool p16 = R > 4 && R <= 16 && ctx->p16_ok && fused_attn;      // batch decode rows: packed-activation projections
-    // short prompt chunks reach vv_attn_prefill4 as well: the same V tail past the chunk
-    if (contiguous && ctx->attn2_ok) VVTRY(lm_zero_v_tail(ctx, st, R, l0, l1));
+    if (p.zero_v_tail) VVTRY(lm_zero_v_tail(ctx, st, R, l0, l1));      // every pass that reaches vv_attn_prefill4, on either route
+    if (p.route == VV_LM_PREFILL) return lm_prefill_layers(ctx, st, R, hidden_out, l0, l1, final_norm);
     int hp = 0;                                    // extra parts the residual stream h currently consists of
     for (int l = l0; l < l1; ++l)
-        VVTRY(p16 ? lm_p16_layer(ctx, st, R, l, l0, l1, attn_S, kv_positions) : lm_gemv_layer(ctx, st, R, l, l1, fused_attn, contiguous, attn_S, kv_positions, hp));
+        VVTRY(p.route == VV_LM_P16 ? lm_p16_layer(ctx, st, R, l, l0, l1, p) : lm_gemv_layer(ctx, st, R, l, l1, p, hp));
     return lm_finish(ctx, st, R, hidden_out, final_norm);
 }
 
@@ -233,37 +230,16 @@ extern "C" int vv_lm_forward_range(vv_ctx* ctx, void* stream, int n_rows, const 
     HIPCHK(ctx, hipMemcpyAsync(ctx->rows_dev, pin, sizeof(VVRow) * n_rows, hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipEventRecord(ctx->ring_ev[slot], st));
     ctx->launches = 0;
-    bool fused = true;
-    for (int i = 0; i < n_rows && fused; ++i)
-        for (int j = 0; j < i; ++j) if (rows[i].cache == rows[j].cache) { fused = false; break; }
     if (!ctx->rope_ready) {                   // (cos, sin) table of every position, once the inv_freq parameter is in place
         VVCHK(vv_rope_table_launch(ctx->inv_freq, ctx->rope_tab, ctx->c.max_ctx, ctx->D / 2, st));
         ctx->rope_ready = true;
     }
-    bool contiguous = !fused && n_rows >= 8;      // one cache, consecutive positions
-    for (int i = 1; i < n_rows && contiguous; ++i)
-        if (rows[i].cache != rows[0].cache || rows[i].pos != rows[0].pos + i) contiguous = false;
-    if (!contiguous && n_rows > ctx->ws_rows)
+    VVLmPlan plan;
+    if (vv_lm_pass_plan(pin, n_rows, {ctx->ws_rows, ctx->c.attn_splits, ctx->Hkv, ctx->tile3_ok, ctx->attn2_ok, ctx->p16_ok}, &plan))
         return fail(ctx, "a launch of %d rows must be consecutive positions of one cache (decode / ragged launches take <= %d rows)", n_rows, ctx->ws_rows);
-    // decode attention geometry: one split (workgroup column) per 1024 positions of the longest row, at most attn_splits.  A grid
-    // choice, so it is part of the graph key: a growing context re-captures the step graph when the split count changes.
-    int max_len = 1;
-    for (int i = 0; i < n_rows; ++i) max_len = std::max(max_len, rows[i].pos + 1);
-    // ... and no more splits than it takes to put ~256 workgroups on the chip: with eight 32K-context utterances in flight the
-    // rows themselves are the parallelism (8 splits of 4096 positions: 122 us per layer against 162 us with 32 splits).
-    // Measured and left alone: 512 / 256 positions per split (no gain once the merge is its own launch), 8-wave workgroups (three
-    // times, slower than 4 waves: round 4, 8.90 vs 8.28 us per unit at 400 positions, 1.5B; 5.84 vs 5.78 at 250, 0.5B).
-    constexpr int split_pos = 1024;
-    constexpr int target_wgs = 256;        // workgroups a launch of long rows aims for
-    int n_long = 0;
-    for (int i = 0; i < n_rows; ++i) if (rows[i].pos + 1 > split_pos) ++n_long;
-    const int by_wgs = std::max(1, (target_wgs + std::max(1, n_long) * ctx->Hkv - 1) / (std::max(1, n_long) * ctx->Hkv));
-    const int attn_S = std::min(std::min(ctx->c.attn_splits, by_wgs), std::max(1, (max_len + split_pos - 1) / split_pos));
     char key[160]; snprintf(key, 160, "lm:%d:%p:%p:%d:%d:%d:%d:%d", n_rows, (const void*)x_in_dev, (void*)hidden_out_dev, l0, l1, final_norm,
-                            fused ? 1 : (contiguous ? 2 : 0), (contiguous && ctx->attn2_ok) ? 0 : attn_S);
-    int64_t kv_positions = 0;
-    for (int i = 0; i < n_rows; ++i) kv_positions += rows[i].pos + 1;
-    return graphed(ctx, key, st, [&]() { return lm_body(ctx, st, n_rows, x_in_dev, hidden_out_dev, l0, l1, final_norm, fused, contiguous, attn_S, kv_positions); });
+                            plan.key_mode, plan.key_split);
+    return graphed(ctx, key, st, [&]() { return lm_body(ctx, st, n_rows, x_in_dev, hidden_out_dev, l0, l1, final_norm, plan); });
 }
 
 extern "C" int vv_kv_import_at(vv_ctx* ctx, void* stream, int cache, int layer, int pos0, int n_pos, const void* k_dev, const void* v_dev, int src_dtype) {

@@ -45,7 +45,8 @@ class EngineConfig:
     max_ctx: int = 4096
     max_rows: int = 16
     xsplit: int = 2
-    attn_splits: int = 128      # upper bound on flash-decoding splits; a launch uses one per 512 positions of its longest row
+    attn_splits: int = 128      # upper bound on flash-decoding splits; a launch uses one per 1024 positions of its longest row,
+                                 # capped so that a launch of long rows aims at about 256 workgroups (csrc/pass_plan.h)
     enc_frames: int = 75         # voice-prompt frames per acoustic-encoder pass: one pass per 10-s speaker prompt (any pass size gives the
                                  # same result, tests/test_gpu_shipped.py; 0.042 s at 5 frames per pass -> 0.027 s at 75 for two speakers)
     use_graph: bool = True
