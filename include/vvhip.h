@@ -109,7 +109,9 @@ int vv_weight_shape(vv_ctx* ctx, const char* name, int* N, int* K);
 int vv_lora_merge(vv_ctx* ctx, void* stream, const char* name, const float* a_dev, const float* b_dev, int r, float scale,
                   int delta_bf16);
 int vv_lora_reset(vv_ctx* ctx, void* stream, const char* name);
-/* scalar buffers speech_scaling_factor / speech_bias_factor (modeling_vibevoice.py:131-132) */
+/* scalar buffers speech_scaling_factor / speech_bias_factor (modeling_vibevoice.py:131-132).  May be called at any time: graphs
+ * captured by vv_codec_decode / vv_codec_chain_batch with apply = 1 hold the old factors and are dropped (after a device-wide wait
+ * when there are any), so the next frame applies the new ones. */
 int vv_set_speech_factors(vv_ctx* ctx, float scaling, float bias);
 /* ids the constrained sampler may emit (VibeVoiceTokenConstraintProcessor, modeling_vibevoice_inference.py:53-66,405-419) */
 int vv_set_valid_tokens(vv_ctx* ctx, const int* ids, int n);

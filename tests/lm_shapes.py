@@ -37,3 +37,27 @@ DECODE_ENGINE = ("gqa", 16)
 # exact modes: per whole chunk, eight 64-row launches of the split + merge pair
 PREFILL_4K_PROMPT, PREFILL_4K_CHUNK = 4200, 512
 PREFILL_4K_ENGINE = (synth.LMCfg(hidden=512, layers=1, heads=4, kv_heads=2, inter=512, vocab=64, max_pos=8192), 512)
+
+
+def decode_steps(starts, n):
+    """n decode steps of the rows starting at (cache, position) `starts`: one row set per step"""
+    return [[(c, p + s) for c, p in starts] for s in range(n)]
+
+
+# test_gpu_graph_replay.py::test_lm_replays_follow_the_row_table: decode row sets a use_graph engine replays with ONE x / hidden
+# buffer per row count, so the row table (device memory) and the split count (a key field) are all that tells two steps apart.
+# Per case: the row set of every step, and the split count each step's key carries (key_split; the merge kernel joins the launches at 2).
+#   one         cache 0 over the 1024-position boundary, then cache 1 from position 0: back to the one-split graph
+#   short+long  a row at 5 beside a row crossing 1024: the short row rides in a two-split launch, the merge kernel skips it (the first
+#               four steps reach the boundary; three more let the two-split key come back and be replayed)
+#   block-edge  two rows crossing position 32 / 64: the 32-position block edge of the V layout and of the owner split
+#   6, 16       DECODE_LENS as starting lengths: the packed batch route in the bf16 mode
+REPLAY_ROWS = {"one": decode_steps([(0, 1021)], 7) + decode_steps([(1, 0)], 3),
+               "short+long": decode_steps([(0, 1021), (1, 5)], 7),
+               "block-edge": decode_steps([(0, 30), (1, 62)], 5),
+               "6": decode_steps(list(enumerate(DECODE_LENS["6"])), 4),
+               "16": decode_steps(list(enumerate(DECODE_LENS["16"])), 4)}
+REPLAY_SPLITS = {"one": [1, 1, 1, 2, 2, 2, 2, 1, 1, 1], "short+long": [1, 1, 1, 2, 2, 2, 2], "block-edge": [1] * 5, "6": [1] * 4, "16": [1] * 4}
+REPLAY_ENGINE = ("gqa", 16)
+# test_gpu_graph_replay.py::test_replays_after_an_upload: a 3-row span of one cache (rope/append reads inv_freq itself, then split + merge)
+REPLAY_SPAN = 3

@@ -230,6 +230,30 @@ def test_the_gpu_tests_run_the_launches_they_name(probe):
             check_lm(probe, [(lm([(c, n + step) for c, n in enumerate(lens)], **caps), want) for step in range(ls.DECODE_STEPS)])
     assert (len(ls.DECODE_LENS["6"]), len(ls.DECODE_LENS["16"]), ls.DECODE_LENS["long"]) == (6, 16, [1100])
 
+    for xs in (1, 3):                               # test_gpu_graph_replay.py::test_lm_replays_follow_the_row_table
+        caps = engine_caps(ls.REPLAY_ENGINE, xs)
+        assert set(ls.REPLAY_ROWS) == set(ls.REPLAY_SPLITS) == {"one", "short+long", "block-edge", "6", "16"}
+        for case, steps in ls.REPLAY_ROWS.items():
+            splits = ls.REPLAY_SPLITS[case]
+            assert len(splits) == len(steps)
+            packed = xs == 1 and case in ("6", "16")
+            check_lm(probe, [(lm(rows, **caps), dict(fused=1, attn=FUSED, key_mode=1, route=P16 if packed else GEMV, attn_S=S, key_split=S))
+                             for rows, S in zip(steps, splits)])
+        # the claims of the docstring: the boundary sits between positions 1023 and 1024, both split counts come back often enough
+        # to be replayed (three sights), and the one-row case ends on the one-split key it began with
+        one = [(rows[0], S) for rows, S in zip(ls.REPLAY_ROWS["one"], ls.REPLAY_SPLITS["one"])]
+        assert ((0, 1023), 1) in one and ((0, 1024), 2) in one and one[-3:] == [((1, 0), 1), ((1, 1), 1), ((1, 2), 1)]
+        for case in ("one", "short+long"):
+            assert ls.REPLAY_SPLITS[case].count(1) >= 3 and ls.REPLAY_SPLITS[case].count(2) >= 3
+        assert [rows[1] for rows in ls.REPLAY_ROWS["short+long"][:4]] == [(1, 5), (1, 6), (1, 7), (1, 8)]
+        assert ls.REPLAY_SPLITS["short+long"][:4] == [1, 1, 1, 2]
+        edge = ls.REPLAY_ROWS["block-edge"]
+        assert edge[0] == [(0, 30), (1, 62)] and edge[-1] == [(0, 34), (1, 66)]
+        assert [len(ls.REPLAY_ROWS[c][0]) for c in ("6", "16")] == [6, 16]
+        # test_replays_after_an_upload: the 3-row span of one cache is the rope/append + split + merge route in both modes
+        check_lm(probe, [(lm(ls.span(2, p0, ls.REPLAY_SPAN), **caps), dict(fused=0, contiguous=0, route=GEMV, attn=SPLIT_MERGE, key_mode=0, key_split=1))
+                         for p0 in range(0, 6 * ls.REPLAY_SPAN, ls.REPLAY_SPAN)])
+
     for xs in (1, 2, 3):                            # test_prefill_attention_over_4k_positions
         caps = engine_caps(ls.PREFILL_4K_ENGINE, xs)
         chunks = [(i0, min(ls.PREFILL_4K_CHUNK, ls.PREFILL_4K_PROMPT - i0)) for i0 in range(0, ls.PREFILL_4K_PROMPT, ls.PREFILL_4K_CHUNK)]

@@ -174,6 +174,26 @@ int graphed_run(vv_ctx* ctx, const std::string& key, hipStream_t st, const std::
     return 0;
 }
 
+// A setter that changes a host-side value captured launches hold (engine_ctx.h: the table above graphed()) drops the key families
+// that hold it.  Waits first, as the eviction above does and for its reason: a victim's replay may still be running, on the caller's
+// stream, a side stream or another stream the caller chose -- the setters have no stream of their own to wait on.  Device-wide is safe
+// here because the caller holds g_dev_mu shared: no capture of the process is open.  Nothing matches (the usual case: factors and
+// schedule are set before the first frame): no wait.
+int drop_graphs(vv_ctx* ctx, std::initializer_list<const char*> prefixes) {
+    auto hit = [&](const std::string& key) {
+        for (const char* p : prefixes) if (key.rfind(p, 0) == 0) return true;
+        return false;
+    };
+    bool any = false;
+    for (auto& g : ctx->graphs) if (hit(g.first)) { any = true; break; }
+    if (!any) return 0;
+    HIPCHK(ctx, hipDeviceSynchronize());
+    for (auto it = ctx->graphs.begin(); it != ctx->graphs.end();) {
+        if (hit(it->first)) { hipGraphExecDestroy(it->second.exec); it = ctx->graphs.erase(it); } else ++it;
+    }
+    return 0;
+}
+
 // ------------------------------------------------------------------ API
 extern "C" const char* vv_last_error(vv_ctx* ctx) { return ctx ? ctx->err : g_err; }
 
@@ -504,10 +524,8 @@ extern "C" int vv_upload(vv_ctx* ctx, const char* name, const void* src, int src
 extern "C" int vv_set_speech_factors(vv_ctx* ctx, float scaling, float bias) {
     VV_SHARED;
     ctx->scaling = scaling; ctx->bias = bias;
-    for (auto it = ctx->graphs.begin(); it != ctx->graphs.end();) {
-        if (it->first.rfind("dec", 0) == 0) { hipGraphExecDestroy(it->second.exec); it = ctx->graphs.erase(it); } else ++it;
-    }
-    return 0;
+    // 1 / scaling and -bias are arguments of the affine launch in front of the decoder: every graph captured with apply = 1
+    return drop_graphs(ctx, {"dec:1:", "chain:1:"});
 }
 
 extern "C" int vv_set_valid_tokens(vv_ctx* ctx, const int* ids, int n) {

@@ -356,7 +356,8 @@ extern "C" int vv_codec_decode(vv_ctx* ctx, void* stream, int slot, int frames, 
     if (frames != 1) return fail(ctx, "vv_codec_decode: streaming decode takes one frame per call");
     CodecNet& net = ctx->dec;
     ctx->launches = 0;
-    char key[128]; snprintf(key, 128, "dec:%d:%d:%p:%p:%d", slot, frames, (const void*)latent_dev, (void*)audio_out_dev, apply);
+    // apply leads the key: vv_set_speech_factors drops the graphs that hold the factors by the prefix "dec:1:"
+    char key[128]; snprintf(key, 128, "dec:%d:%d:%d:%p:%p", apply ? 1 : 0, slot, frames, (const void*)latent_dev, (void*)audio_out_dev);
     return graphed(ctx, key, st, [&]() {
         const int L = ctx->c.latent_dim;
         const float mul = apply ? 1.0f / ctx->scaling : 1.0f, add = apply ? -ctx->bias : 0.0f;
@@ -406,9 +407,9 @@ extern "C" int vv_codec_chain_batch(vv_ctx* ctx, void* stream, int n, const int*
         ctx->side_ready = true;
     }
     ctx->launches = 0;
-    std::string key = "chain:";
+    std::string key = apply ? "chain:1:" : "chain:0:";      // vv_set_speech_factors drops "chain:1:", the graphs that hold the factors
     for (int j = 0; j < n; ++j) key += std::to_string(slots[j]) + ",";
-    char kp[128]; snprintf(kp, 128, ":%p:%p:%p:%d", (const void*)latent_dev, (void*)audio_out_dev, (void*)sem_out_dev, apply);
+    char kp[128]; snprintf(kp, 128, ":%p:%p:%p", (const void*)latent_dev, (void*)audio_out_dev, (void*)sem_out_dev);
     key += kp;
     std::vector<int> ids(slots, slots + n);
     return graphed(ctx, key, st, [&]() {

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <set>
@@ -251,6 +252,34 @@ int gemm_tl(vv_ctx* ctx, VVGemm g, hipStream_t st);
 
 // Runs `body` (the launches of one op) eagerly at the first sight of `key`, captured into a hipGraph at the second, replayed after.
 // The cache policy is graphed_run (engine.hip); the template only erases the body's type, by reference.
+//
+// A replay repeats every scalar argument and every pointer of the captured launches: whatever can change between two calls is READ
+// FROM DEVICE MEMORY, is a FIELD OF THE KEY, or is changed only by a call that DROPS the family (drop_graphs).  Never moving, for
+// every family: weight storage (vv_upload and the LoRA merges write in place), the buffers vv_create allocates, the route
+// (pass_plan.h: a function of the row count, the key fields and what the context offers).  Per family (DESIGN.md section 3 has the
+// same table; the tests are those of tests/test_gpu_graph_replay.py unless another file is named):
+//   lm:     key: rows, x / hidden pointers, layer range, final norm, row-set mode, SPLIT COUNT of the attention (from 2 on the merge
+//           kernel is in the graph).  device: the row table (cache, position), x, the KV caches, the (cos, sin) table (rebuilt in
+//           place in front of the graph after an upload), inv_freq.  by value: nothing else.
+//           test_lm_replays_follow_the_row_table, test_replays_after_an_upload
+//   samp: sde:  key: n, cond / noise / step-noise / output pointers, CFG_SCALE.  device: conditions, noise, the schedule's rows.
+//           by value: STEP COUNT, TABLE OFFSETS, THE PER-STEP MODULATION BUFFERS (a longer schedule reallocates them), sde_on --
+//           dropped by vv_set_schedule / vv_set_schedule_sde.  test_sampler_graphs_follow_the_schedule, test_replays_after_an_upload
+//   rows:   as samp: / sde:, with the POINTER of the per-row scales in the key and the scales on the device.
+//           test_gpu_cfg_rows.py: test_graph_replay_follows_the_buffer, test_a_new_schedule_drops_the_cached_rows_graph
+//   dec:    key: APPLY, slot, frames, latent / audio pointers.  device: latent, the slot's conv history.  by value: 1 / SCALING, -BIAS
+//           (apply = 1) -- dropped by vv_set_speech_factors ("dec:1:").  test_speech_factors_reach_the_tokenizer_replays[dec-*]
+//   senc:   key: slot, frames, audio / output pointers.  device: audio, the slot's conv history.  by value: nothing; no setter drops it.
+//           test_speech_factors_reach_the_tokenizer_replays[dec-*]
+//   chain:  key: APPLY, THE SLOT LIST IN ORDER, latent / audio / semantic pointers.  device: latents, both nets' conv history.
+//           by value: 1 / SCALING, -BIAS (apply = 1) -- dropped by vv_set_speech_factors ("chain:1:"); the fork / join of the
+//           per-utterance branches (VVHIP_BATCH_CODEC, read by vv_create).  test_speech_factors_reach_the_tokenizer_replays[chain-*],
+//           test_chain_graphs_are_keyed_by_slot_order, test_warmup_before_the_speech_factors_leaves_no_stale_graph
+// A new host-side value inside a body goes into the key or into a drop_graphs call, and into this table with the test that pins it.
 int graphed_run(vv_ctx* ctx, const std::string& key, hipStream_t st, const std::function<int()>& body);
+// Destroys the cached graphs whose key starts with one of `prefixes`, after waiting for the device (a victim's replay may still be
+// running).  The caller holds g_dev_mu shared (VV_SHARED), so no capture of the process is open.  Which families a setter drops is said in
+// its call of this function and nowhere else.
+int drop_graphs(vv_ctx* ctx, std::initializer_list<const char*> prefixes);
 template <class F>
 static int graphed(vv_ctx* ctx, const std::string& key, hipStream_t st, F&& body) { return graphed_run(ctx, key, st, std::ref(body)); }

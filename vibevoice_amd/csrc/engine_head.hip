@@ -53,11 +53,8 @@ static int set_schedule(vv_ctx* ctx, int n_steps, const float* t, const float* c
             }
         }
     }
-    for (auto it = ctx->graphs.begin(); it != ctx->graphs.end();) {
-        // every sampler key family: a captured sample_body holds the step count, the table offsets and the buffers reallocated above
-        if (it->first.rfind("samp", 0) == 0 || it->first.rfind("sde:", 0) == 0 || it->first.rfind("rows:", 0) == 0) { hipGraphExecDestroy(it->second.exec); it = ctx->graphs.erase(it); } else ++it;
-    }
-    return 0;
+    // every sampler key family: a captured sample_body holds the step count, the table offsets and the buffers reallocated above
+    return drop_graphs(ctx, {"samp:", "sde:", "rows:"});
 }
 // coef: n_steps rows {a, s, cs, c0, c1} (the deterministic DPM-Solver++(2M) the model classes build)
 extern "C" int vv_set_schedule(vv_ctx* ctx, int n_steps, const float* t, const float* coef, void* stream) {
