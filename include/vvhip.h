@@ -229,6 +229,21 @@ int vv_diffusion_sample_sde(vv_ctx* ctx, void* stream, int n, const float* cond_
  * scalar entry points).  New surface: the reference's sample_speech_tokens takes one cfg_scale for the whole batch. */
 int vv_diffusion_sample_rows(vv_ctx*, void* stream, int n, const float* cond_dev, const float* noise_dev,
                              const float* step_noise_dev, const float* cfg_rows_dev, float* latent_out_dev);
+/* The reference scheduler's other sampling-time settings (DPMSolverMultistepScheduler: solver_order 1..3, solver_type midpoint /
+ * heun, lower_order_final, euler_at_final, final_sigmas_type, timestep_spacing, steps_offset, lambda_min_clipped; both
+ * dpmsolver++ and sde-dpmsolver++) as one table row per solver step, coef8 = n_steps rows {a, s, cs, c0, c1, c2, cn, 0}:
+ *   x0 = a z - s v;   z' = cs z + c0 x0 + c1 (x0 - m1) + c2 (m1 - m2) + cn noise      (m1, m2: the two previous x0)
+ * (schedule/dpm_solver.py:669-686, 738-800, 861-893 with the model-output differences factored out; the host side is
+ * vibevoice_amd/schedule.py: make_general_table).  stochastic != 0: the table carries variance-noise scales and sampling needs the
+ * per-step noise.  Replaces whatever table was installed; the two shipped configurations keep vv_set_schedule / _sde and their
+ * samplers, and each sampler refuses the other kind of table. */
+int vv_set_schedule_general(vv_ctx* ctx, int n_steps, const float* t, const float* coef8, int stochastic, void* stream);
+/* sample_speech_tokens under a general table, 1 <= n <= 8.  step_noise_dev [n_steps][n][latent] for a stochastic table, NULL for
+ * a deterministic one (the other way round is refused); cfg_rows_dev [n] per-utterance guidance scales read at run time (the
+ * graph key holds the pointer, never the values), or NULL: cfg_scale for every row.  A step is the head's layers, the final
+ * layer's plain GEMM and one launch of solver.hip (update + the next step's in-projection where its rule allows). */
+int vv_diffusion_sample_general(vv_ctx* ctx, void* stream, int n, const float* cond_dev, const float* noise_dev,
+                                const float* step_noise_dev, float cfg_scale, const float* cfg_rows_dev, float* latent_out_dev);
 /* one prediction_head forward (modular_vibevoice_diffusion_head.py:254-280) for tests:
  * noisy [n][latent], t[n] (host), cond [n][H] -> out [n][latent].  Synchronous. */
 int vv_head_forward(vv_ctx* ctx, void* stream, int n, const float* noisy_dev, const float* t_host,
@@ -375,7 +390,9 @@ int vv_profile_replay_family(vv_ctx* ctx, void* stream, int family, int reps, in
  * 6: head-tail seam launches (headtail.hip: final layer + CFG + solver update + the next step's in-projection in one launch) that
  * the last recorded sampler body issued -- n_steps - 1 for one utterance in bf16 mode, 0 where the two-launch form ran; a graph
  * replay keeps the count of its capture;
- * 7: bytes of device memory held by the base snapshots of LoRA-merged parameters (vv_lora_merge) */
+ * 7: bytes of device memory held by the base snapshots of LoRA-merged parameters (vv_lora_merge);
+ * 8: step ends of the general sampler (vv_diffusion_sample_general) that carried the next step's in-projection in the same launch,
+ * in the last recorded sampler body -- n_steps - 1 where solver.hip's rule holds, 0 where the update ran alone */
 int64_t vv_stat(vv_ctx* ctx, int what);
 
 #pragma GCC visibility pop

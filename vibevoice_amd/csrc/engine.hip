@@ -347,6 +347,7 @@ static int create_impl(const vv_config* cfg, vv_ctx* parent, vv_ctx** out) {
     ctx->xh2 = (float*)dalloc(ctx, (size_t)R2 * H * 4);
     // decode rows of the bf16 mode: final layer + solver update + next in-projection as one launch (headtail.hip)
     ctx->head_tail = c.xsplit == 1 && L == 64 && (H % 32) == 0 && vv_head_tail_init() == 0;
+    if (const char* e = getenv("VVHIP_SOLVER_FUSE"); e && e[0] == '0') ctx->solver_fuse = false;      // A/B: update kernel + the in-projection GEMM
     if (const char* e = getenv("VVHIP_NAN_PROBE"); e && e[0] == '1') {
         ctx->probe_rec = (unsigned*)dalloc(ctx, PROBE_MAX * 16);
         ctx->probe_on = ctx->probe_rec != nullptr;
@@ -592,6 +593,7 @@ extern "C" int64_t vv_stat(vv_ctx* ctx, int what) {
         case 5: return ctx->foreign_nodes;        // nodes of the captured graphs that are not kernel launches (expected: 0)
         case 4: return ctx->capture_fallbacks;    // stream captures that did not close and ran eagerly instead (multi-threaded lanes)
         case 6: return ctx->seam_launches;        // head-tail seam launches of the last recorded sampler body
+        case 8: return ctx->solver_fused;         // general-path step ends that carried the next in-projection (last recorded sampler body)
         case 7: return ctx->lora_base_bytes;      // bytes held by the base snapshots of LoRA-merged parameters
         default: return (int64_t)ctx->graphs.size();
     }

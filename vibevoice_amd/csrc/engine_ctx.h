@@ -138,6 +138,11 @@ struct vv_ctx {
     // second generation of the sampler's state (headtail.hip: a solver step reads one generation and writes the other)
     float *zz2 = nullptr, *x0p2 = nullptr, *xh2 = nullptr;
     bool head_tail = false;         // the fused seam (headtail.hip); off in the exact modes or when its LDS size is refused
+    // the general solver table (vv_set_schedule_general; solver.hip): 8-float rows, the second-previous x0 in two generations.
+    // Allocated by the first general schedule; general_on says which of `coef` / `coef8` the installed table is
+    float *coef8 = nullptr, *m2a = nullptr, *m2b = nullptr;
+    bool general_on = false;
+    bool solver_fuse = true;        // the step end carries the next in-projection where solver.hip's rule allows (VVHIP_SOLVER_FUSE=0: never)
     float *tmp1 = nullptr, *tmp2 = nullptr;
     // connectors
     struct Conn { void *fc1, *fc2; float *b1, *b2, *norm; } ac_conn, sem_conn;
@@ -178,6 +183,7 @@ struct vv_ctx {
     static constexpr int N_RESAMPLERS = 4;
     Resampler rs[N_RESAMPLERS];
     int64_t launches = 0;
+    int64_t solver_fused = 0;         // general-path step ends that carried the next in-projection, last recorded body (vv_stat 8)
     int64_t seam_launches = 0;        // head-tail seam launches the last recorded sampler body issued (vv_stat 6; a replay keeps its capture's count)
     // optional per-GEMM-launch hipEvent timing (vv_profile_begin/end)
     bool prof_on = false;
@@ -267,6 +273,10 @@ int gemm_tl(vv_ctx* ctx, VVGemm g, hipStream_t st);
 //           dropped by vv_set_schedule / vv_set_schedule_sde.  test_sampler_graphs_follow_the_schedule, test_replays_after_an_upload
 //   rows:   as samp: / sde:, with the POINTER of the per-row scales in the key and the scales on the device.
 //           test_gpu_cfg_rows.py: test_graph_replay_follows_the_buffer, test_a_new_schedule_drops_the_cached_rows_graph
+//   gen:    the general solver table (vv_diffusion_sample_general).  key: n, cond / noise / step-noise / PER-ROW-SCALE / output
+//           pointers, CFG_SCALE.  device: conditions, noise, the table's rows, the per-row scales.  by value: as samp: -- dropped by
+//           all three vv_set_schedule* calls.  test_gpu_solver_family.py: test_cfg_rows_match_scalar_runs_and_replay,
+//           test_switching_to_a_shipped_table_and_back
 //   dec:    key: APPLY, slot, frames, latent / audio pointers.  device: latent, the slot's conv history.  by value: 1 / SCALING, -BIAS
 //           (apply = 1) -- dropped by vv_set_speech_factors ("dec:1:").  test_speech_factors_reach_the_tokenizer_replays[dec-*]
 //   senc:   key: slot, frames, audio / output pointers.  device: audio, the slot's conv history.  by value: nothing; no setter drops it.

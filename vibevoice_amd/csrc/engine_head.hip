@@ -2,7 +2,8 @@
 #include "engine_ctx.h"
 #include "pass_plan.h"
 
-static int set_schedule(vv_ctx* ctx, int n_steps, const float* t, const float* coef, int width, void* stream) {
+// width 5 / 6: the shipped tables (rows of ctx->coef);  8: a general table (rows of ctx->coef8), stochastic as the caller says
+static int set_schedule(vv_ctx* ctx, int n_steps, const float* t, const float* coef, int width, void* stream, bool stochastic = false) {
     VV_SHARED;
     hipStream_t st = (hipStream_t)stream;
     if (n_steps < 1 || n_steps > 64) return fail(ctx, "n_steps must be in [1,64]");
@@ -12,13 +13,23 @@ static int set_schedule(vv_ctx* ctx, int n_steps, const float* t, const float* c
         ctx->coef = (float*)dalloc(ctx, 64 * 6 * 4);
         ctx->tvals = (float*)dalloc(ctx, 64 * 4);
     }
+    const bool general = width == 8;
+    if (general && !ctx->coef8) {
+        ctx->coef8 = (float*)dalloc(ctx, 64 * 8 * 4);
+        ctx->m2a = (float*)dalloc(ctx, (size_t)8 * ctx->c.latent_dim * 4);
+        ctx->m2b = (float*)dalloc(ctx, (size_t)8 * ctx->c.latent_dim * 4);
+        if (!ctx->coef8 || !ctx->m2a || !ctx->m2b) return fail(ctx, "vv_set_schedule_general: out of device memory");
+    }
     float rows6[64 * 6];
     for (int i = 0; i < n_steps; ++i)
         for (int j = 0; j < 6; ++j) rows6[i * 6 + j] = (j < width) ? coef[i * width + j] : 0.f;
     // by the API used, not by the values: a one-step stochastic schedule has sigma_t = 0 on its only step (all noise scales
     // zero) and must still be sampled through vv_diffusion_sample_sde, as the reference runs it (a noise-free first-order step)
-    ctx->sde_on = (width == 6);
+    ctx->sde_on = general ? stochastic : (width == 6);
+    ctx->general_on = general;
     HIPCHK(ctx, hipStreamSynchronize(st));
+    if (general) HIPCHK(ctx, hipMemcpy(ctx->coef8, coef, (size_t)n_steps * 8 * 4, hipMemcpyHostToDevice));
+    else
     HIPCHK(ctx, hipMemcpy(ctx->coef, rows6, (size_t)n_steps * 6 * 4, hipMemcpyHostToDevice));
     HIPCHK(ctx, hipMemcpy(ctx->tvals, t, (size_t)n_steps * 4, hipMemcpyHostToDevice));
     // t_emb[i] = W2 . silu(W1 . sinusoid(t_i))   (TimestepEmbedder, modular_vibevoice_diffusion_head.py:66-93)
@@ -54,7 +65,7 @@ static int set_schedule(vv_ctx* ctx, int n_steps, const float* t, const float* c
         }
     }
     // every sampler key family: a captured sample_body holds the step count, the table offsets and the buffers reallocated above
-    return drop_graphs(ctx, {"samp:", "sde:", "rows:"});
+    return drop_graphs(ctx, {"samp:", "sde:", "rows:", "gen:"});
 }
 // coef: n_steps rows {a, s, cs, c0, c1} (the deterministic DPM-Solver++(2M) the model classes build)
 extern "C" int vv_set_schedule(vv_ctx* ctx, int n_steps, const float* t, const float* coef, void* stream) {
@@ -66,9 +77,14 @@ extern "C" int vv_set_schedule_sde(vv_ctx* ctx, int n_steps, const float* t, con
     return set_schedule(ctx, n_steps, t, coef6, 6, stream);
 }
 
-static VVHeadPlan head_plan(const vv_ctx* ctx, int rows, int n_steps, bool has_coef) {
+// coef8: n_steps rows {a, s, cs, c0, c1, c2, cn, 0} (vibevoice_amd/schedule.py: make_general_table); sampled by vv_diffusion_sample_general
+extern "C" int vv_set_schedule_general(vv_ctx* ctx, int n_steps, const float* t, const float* coef8, int stochastic, void* stream) {
+    return set_schedule(ctx, n_steps, t, coef8, 8, stream, stochastic != 0);
+}
+
+static VVHeadPlan head_plan(const vv_ctx* ctx, int rows, int n_steps, bool has_coef, bool general = false) {
     return vv_head_plan(rows, n_steps, ctx->HF, ctx->c.head_layers, ctx->MODW,
-                        {ctx->p16_ok, ctx->p16_shift != nullptr, ctx->ada_p != nullptr, ctx->mod_all_bytes != 0, ctx->head_tail}, has_coef);
+                        {ctx->p16_ok, ctx->p16_shift != nullptr, ctx->ada_p != nullptr, ctx->mod_all_bytes != 0, ctx->head_tail}, has_coef, general);
 }
 
 // one head evaluation on 2n rows, solver step `step` of the plan; mod/xh/hact/eps are ctx scratch. temb = t-embedding row for this step.
@@ -178,12 +194,14 @@ static int head_eval(vv_ctx* ctx, hipStream_t st, const VVHeadPlan& p, int step,
     return 0;
 }
 
+// general: the installed table is a general one (rows of ctx->coef8): a step is the head with a plain final layer, then solver.hip's launch
 static int sample_body(vv_ctx* ctx, hipStream_t st, int n, const float* cond, const float* noise, float cfg, float* latent_out,
-                       const float* step_noise = nullptr, const float* cfg_rows = nullptr) {
+                       const float* step_noise = nullptr, const float* cfg_rows = nullptr, bool general = false) {
     const vv_config& c = ctx->c;
     const int H = ctx->H, L = c.latent_dim;
     const int rows = 2 * n;
     ctx->seam_launches = 0;
+    ctx->solver_fused = 0;
     ctx->probe_names.clear();
     nan_probe(ctx, st, "cond (input)", cond, (size_t)rows * H);
     nan_probe(ctx, st, "noise (input)", noise, (size_t)n * L);
@@ -196,7 +214,7 @@ static int sample_body(vv_ctx* ctx, hipStream_t st, int n, const float* cond, co
     // up front, <=16 rows per GEMM, so the (3*layers+2)*H x H modulation matrix is streamed ceil(2nN/16) times per
     // frame instead of N times (the reference recomputes it inside every head call)
     const int MODW = ctx->MODW;
-    const VVHeadPlan p = head_plan(ctx, rows, ctx->n_steps, true);
+    const VVHeadPlan p = head_plan(ctx, rows, ctx->n_steps, true, general);
     const bool batch_ada = p.ada != VV_ADA_PER_STEP;
     if (batch_ada) {
         // SiLU(cond + t) for all (step, row) pairs in one small launch: the GEMM workgroups (one per 16 output features,
@@ -230,6 +248,26 @@ static int sample_body(vv_ctx* ctx, hipStream_t st, int n, const float* cond, co
         const float* mod_i = batch_ada ? ctx->mod_all + (size_t)i * rows * MODW : nullptr;
         const float* sn = step_noise ? step_noise + (size_t)i * n * L : nullptr;
         const unsigned char* sht = p.sh_tiles ? (const unsigned char*)ctx->p16_shift + (size_t)i * (ctx->c.head_layers + 1) * ctx->p16_shift_tile : nullptr;
+        if (general) {
+            // head (plain final layer -> eps), then ONE launch: CFG + table-driven update of generation gen into gen ^ 1 and, on every
+            // step but the last, the next step's in-projection where solver.hip's rule holds (else the next head_eval does its own)
+            if (head_eval(ctx, st, p, i, gen ? ctx->zz2 : ctx->zz, ctx->temb + (size_t)i * H, ctx->eps, nullptr, 0.f, mod_i, nullptr, nullptr,
+                          gen, have_x) < 0) return -1;
+            VVSolverStep s{};
+            s.eps = ctx->eps; s.coef = ctx->coef8 + i * 8; s.cfg = cfg; s.cfg_rows = cfg_rows; s.noise = sn; s.n = n; s.L = L;
+            s.z_in = gen ? ctx->zz2 : ctx->zz; s.m1_in = gen ? ctx->x0p2 : ctx->x0p; s.m2_in = gen ? ctx->m2b : ctx->m2a;
+            s.z_out = gen ? ctx->zz : ctx->zz2; s.m1_out = gen ? ctx->x0p : ctx->x0p2; s.m2_out = gen ? ctx->m2a : ctx->m2b;
+            if (i + 1 < ctx->n_steps && ctx->solver_fuse) { s.Win = (const u32x4*)ctx->h_in; s.Xout = gen ? ctx->xh : ctx->xh2; s.H = H; s.xs = c.xsplit; }
+            ctx->launches++;
+            const int sr = vv_solver_step_launch(&s, st);
+            if (sr == VV_RC_NO_FORM) return fail(ctx, "vv_diffusion_sample_general: solver.hip has no form for n = %d, latent_dim = %d", n, L);
+            if (sr < 0) return fail(ctx, "%s:%d launch failed (%d): hip error %d (%s)", __FILE__, __LINE__, sr, g_vv_launch_err, hipGetErrorString((hipError_t)g_vv_launch_err));
+            have_x = (sr == 1);
+            if (have_x) ctx->solver_fused++;
+            gen ^= 1;
+            if (ctx->probe_on) { char nm[64]; snprintf(nm, 64, "step %d z (general)", i); nan_probe(ctx, st, nm, gen ? ctx->zz2 : ctx->zz, (size_t)rows * L); }
+            continue;
+        }
         // decode rows, bf16 mode: every step but the last ends with the fused seam (final layer + CFG + solver update + the next step's
         // in-projection, headtail.hip), which leaves the next step's state in the other generation of (xh, zz, x0p)
         const int hr = head_eval(ctx, st, p, i, gen ? ctx->zz2 : ctx->zz, ctx->temb + (size_t)i * H, ctx->eps, ctx->coef + i * 6, cfg, mod_i, sn, sht,
@@ -252,6 +290,7 @@ extern "C" int vv_diffusion_sample(vv_ctx* ctx, void* stream, int n, const float
     hipStream_t st = (hipStream_t)stream;
     if (ctx->n_steps < 1) return fail(ctx, "vv_set_schedule has not been called");
     if (n < 1 || n > 8) return fail(ctx, "vv_diffusion_sample: n must be in [1,8]");
+    if (ctx->general_on) return fail(ctx, "the installed table is a general one (vv_set_schedule_general): sample with vv_diffusion_sample_general");
     if (ctx->sde_on) return fail(ctx, "the schedule is stochastic (vv_set_schedule_sde): sample with vv_diffusion_sample_sde and its per-step noise");
     ctx->launches = 0;
     char key[128]; snprintf(key, 128, "samp:%d:%p:%p:%p:%a", n, (const void*)cond_dev, (const void*)noise_dev, (void*)latent_out_dev, cfg_scale);
@@ -267,6 +306,7 @@ extern "C" int vv_diffusion_sample_sde(vv_ctx* ctx, void* stream, int n, const f
     hipStream_t st = (hipStream_t)stream;
     if (ctx->n_steps < 1) return fail(ctx, "vv_set_schedule_sde has not been called");
     if (n < 1 || n > 8) return fail(ctx, "vv_diffusion_sample_sde: n must be in [1,8]");
+    if (ctx->general_on) return fail(ctx, "the installed table is a general one (vv_set_schedule_general): sample with vv_diffusion_sample_general");
     if (!ctx->sde_on) return fail(ctx, "the schedule is deterministic (vv_set_schedule): sample with vv_diffusion_sample");
     if (!step_noise_dev) return fail(ctx, "vv_diffusion_sample_sde: step_noise is null");
     ctx->launches = 0;
@@ -282,6 +322,7 @@ extern "C" int vv_diffusion_sample_rows(vv_ctx* ctx, void* stream, int n, const 
     hipStream_t st = (hipStream_t)stream;
     if (ctx->n_steps < 1) return fail(ctx, "vv_set_schedule / vv_set_schedule_sde has not been called");
     if (n < 1 || n > 8) return fail(ctx, "vv_diffusion_sample_rows: n must be in [1,8]");
+    if (ctx->general_on) return fail(ctx, "the installed table is a general one (vv_set_schedule_general): sample with vv_diffusion_sample_general");
     if (!cfg_rows_dev) return fail(ctx, "vv_diffusion_sample_rows: cfg_rows is null");
     if (ctx->sde_on && !step_noise_dev) return fail(ctx, "the schedule is stochastic (vv_set_schedule_sde): vv_diffusion_sample_rows needs its per-step noise");
     if (!ctx->sde_on && step_noise_dev) return fail(ctx, "the schedule is deterministic (vv_set_schedule): vv_diffusion_sample_rows takes no step noise");
@@ -289,6 +330,24 @@ extern "C" int vv_diffusion_sample_rows(vv_ctx* ctx, void* stream, int n, const 
     char key[192]; snprintf(key, 192, "rows:%d:%p:%p:%p:%p:%p", n, (const void*)cond_dev, (const void*)noise_dev, (const void*)step_noise_dev,
                             (const void*)cfg_rows_dev, (void*)latent_out_dev);
     const int rc = graphed(ctx, key, st, [&]() { return sample_body(ctx, st, n, cond_dev, noise_dev, 0.f, latent_out_dev, step_noise_dev, cfg_rows_dev); });
+    nan_probe_report(ctx, st, key);
+    return rc;
+}
+
+// The sampler under a general table (vv_set_schedule_general): one guidance scale, or cfg_rows_dev [n] read at run time (the key
+// holds the POINTER); step_noise_dev as the table's kind demands.  Its own graph family, dropped by every vv_set_schedule* call.
+extern "C" int vv_diffusion_sample_general(vv_ctx* ctx, void* stream, int n, const float* cond_dev, const float* noise_dev,
+                                           const float* step_noise_dev, float cfg_scale, const float* cfg_rows_dev, float* latent_out_dev) {
+    hipStream_t st = (hipStream_t)stream;
+    if (ctx->n_steps < 1) return fail(ctx, "vv_set_schedule_general has not been called");
+    if (n < 1 || n > 8) return fail(ctx, "vv_diffusion_sample_general: n must be in [1,8]");
+    if (!ctx->general_on) return fail(ctx, "the installed table is a shipped one (vv_set_schedule / vv_set_schedule_sde): sample with vv_diffusion_sample, _sde or _rows");
+    if (ctx->sde_on && !step_noise_dev) return fail(ctx, "the general table is stochastic: vv_diffusion_sample_general needs its per-step noise");
+    if (!ctx->sde_on && step_noise_dev) return fail(ctx, "the general table is deterministic: vv_diffusion_sample_general takes no step noise");
+    ctx->launches = 0;
+    char key[224]; snprintf(key, 224, "gen:%d:%p:%p:%p:%p:%p:%a", n, (const void*)cond_dev, (const void*)noise_dev, (const void*)step_noise_dev,
+                            (const void*)cfg_rows_dev, (void*)latent_out_dev, cfg_rows_dev ? 0.f : cfg_scale);
+    const int rc = graphed(ctx, key, st, [&]() { return sample_body(ctx, st, n, cond_dev, noise_dev, cfg_scale, latent_out_dev, step_noise_dev, cfg_rows_dev, true); });
     nan_probe_report(ctx, st, key);
     return rc;
 }

@@ -4,6 +4,20 @@
 #pragma once
 #include "vv_common.h"
 #include "gemv_plan.h"       // VV_ROUTE_* and vv_gemm_route(a, xs): which kernel vv_gemm_launch runs a call on
+
+// ---- the end of a solver step on the general path (solver.hip): CFG + table-driven DPM-Solver++ update (+ the next in-projection) ----
+struct VVSolverStep {
+    const float* eps;      // [2n][L] the final layer's plain output: conditional rows, then the negative ones
+    const float* z_in; const float* m1_in; const float* m2_in;      // this step's state: z [2n][L] (rows < n read), previous two x0 [n][L]
+    float* z_out; float* m1_out; float* m2_out;                     // the next step's state (DIFFERENT buffers)
+    const float* coef;     // {a, s, cs, c0, c1, c2, cn, 0}: one 8-float row of the general table
+    float cfg; const float* cfg_rows;      // one guidance scale, or [n] of them on the device (then read in place of cfg)
+    const float* noise;    // [n][L] this step's variance noise (stochastic solver) or null
+    int n, L;
+    const u32x4* Win;      // packed [H][L] noisy_images_proj, or null: the update alone
+    float* Xout;           // [2n][H] the next step's in-projection
+    int H, xs;             // xs: bf16 terms per operand element (the engine's xsplit)
+};
 extern "C" {
 int vv_gemm_launch(VVGemm a, int xs, hipStream_t s);
 int vv_pack_launch(const void* src, int src_is_bf16, void* dst, int N, int K, int kind, int Cin, int Cout, int ksz, int stride, hipStream_t s);
@@ -71,6 +85,9 @@ int vv_gemv16p_launch2(const VVGemv16p* a, int epi, int flags, hipStream_t s);
 int vv_head_tail_ok(const VVTail* a);
 int vv_head_tail_init();
 int vv_head_tail_launch(const VVTail* a, hipStream_t s);
+int vv_solver_step_ok(const VVSolverStep* a);
+int vv_solver_step_fused_ok(const VVSolverStep* a);
+int vv_solver_step_launch(const VVSolverStep* a, hipStream_t s);
 int vv_pack16_tiles_launch(const float* x, int ldx, int64_t stride_outer, int n_inner, int64_t stride_inner, void* xp, int64_t tile_bytes, int T,
                            int K, int n_tiles, hipStream_t s);
 int vv_ada_pack_launch(const float* cproj, const float* temb, void* xp, int rows, int n_steps, int H, hipStream_t s);

@@ -279,20 +279,38 @@ class Engine:
         self.n_valid = len(ids)
         self._valid_ids = [int(i) for i in ids]
 
-    def set_num_steps(self, n_steps: int, t_cast_bf16: bool = False, algorithm_type: str = "dpmsolver++"):
+    def set_num_steps(self, n_steps: int, t_cast_bf16: bool = False, algorithm_type: str = "dpmsolver++", solver: Optional[dict] = None):
         """Solver table for N steps.  algorithm_type: "dpmsolver++" (the model classes' scheduler) or "sde-dpmsolver++" (what
-        demo/gradio_demo.py:142-146 installs); the stochastic one is sampled with diffusion_sample(..., step_noise=...)."""
-        key = (int(n_steps), bool(t_cast_bf16), str(algorithm_type))
+        demo/gradio_demo.py:142-146 installs); the stochastic one is sampled with diffusion_sample(..., step_noise=...).
+        solver: the non-default sampling-time settings of the reference scheduler (schedule.SAMPLING_KEYS: solver_order,
+        solver_type, lower_order_final, euler_at_final, final_sigmas_type, timestep_spacing, steps_offset, lambda_min_clipped) as a
+        dict.  Settings equal to a shipped configuration -- None, an empty dict, defaults spelled out -- keep the shipped table and
+        sampler; anything else installs the general table (schedule.make_general_table) and diffusion_sample routes to the general
+        sampler.  n_solver_steps is then what the reference's set_timesteps(n_steps) yields."""
+        cfg = dict(solver or {}, algorithm_type=str(algorithm_type))
+        unknown = sorted(set(cfg) - set(_schedule.SAMPLING_KEYS))
+        if unknown:
+            raise ValueError(f"set_num_steps: {unknown} are not sampling-time settings {_schedule.SAMPLING_KEYS}")
+        general = not _schedule.is_shipped(cfg)
+        key = (int(n_steps), bool(t_cast_bf16), str(algorithm_type)) + ((tuple(sorted(_schedule.solver_settings(cfg).items())),) if general else ())
         if self._n_steps == key:
             return
-        tv, coef = _schedule.make_table(n_steps, t_cast_bf16, algorithm_type)
-        fn, name = ((self.lib.vv_set_schedule_sde, "vv_set_schedule_sde") if coef.shape[1] == 6
-                    else (self.lib.vv_set_schedule, "vv_set_schedule"))
-        self._chk(fn(self._ctx, n_steps, tv.ctypes.data_as(C.POINTER(C.c_float)),
-                     np.ascontiguousarray(coef).ctypes.data_as(C.POINTER(C.c_float)), self._s), name)
+        if general:
+            tv, coef = _schedule.make_general_table(cfg, n_steps, t_cast_bf16)
+            stochastic = algorithm_type == "sde-dpmsolver++"
+            self._chk(self.lib.vv_set_schedule_general(self._ctx, len(tv), tv.ctypes.data_as(C.POINTER(C.c_float)),
+                                                       np.ascontiguousarray(coef).ctypes.data_as(C.POINTER(C.c_float)), int(stochastic),
+                                                       self._s), "vv_set_schedule_general")
+        else:
+            tv, coef = _schedule.make_table(n_steps, t_cast_bf16, algorithm_type)
+            stochastic = coef.shape[1] == 6
+            fn, name = ((self.lib.vv_set_schedule_sde, "vv_set_schedule_sde") if stochastic else (self.lib.vv_set_schedule, "vv_set_schedule"))
+            self._chk(fn(self._ctx, n_steps, tv.ctypes.data_as(C.POINTER(C.c_float)),
+                         np.ascontiguousarray(coef).ctypes.data_as(C.POINTER(C.c_float)), self._s), name)
         self._n_steps = key
-        self.n_solver_steps = int(n_steps)
-        self.stochastic = coef.shape[1] == 6
+        self.n_solver_steps = len(tv)
+        self.stochastic = stochastic
+        self.general_solver = general
 
     # ------------------------------------------------------------------ ops
     @staticmethod
@@ -450,6 +468,18 @@ class Engine:
         """step_noise [n_steps, n, latent] fp32 (contiguous, on the device): the per-step variance noise of the stochastic solver.
         cfg_scale: one float for every row, or a 1-D fp32 device tensor of n guidance scales, one per utterance row.  The kernels read
         the tensor at run time and the graph is keyed by its address: rewrite the same buffer between calls and nothing is re-captured."""
+        rows = isinstance(cfg_scale, torch.Tensor)
+        if getattr(self, "general_solver", False):          # routed by the installed table (set_num_steps(..., solver=...))
+            if rows and (cfg_scale.dim() != 1 or cfg_scale.shape[0] != n or cfg_scale.dtype != torch.float32 or cfg_scale.device != self.device
+                         or not cfg_scale.is_contiguous()):
+                raise ValueError(f"diffusion_sample: a per-row cfg_scale is a contiguous 1-D fp32 tensor of n = {n} entries on {self.device}")
+            if step_noise is not None:
+                assert step_noise.dtype == torch.float32 and step_noise.is_contiguous() and step_noise.shape[1] == n
+                assert step_noise.shape[0] >= self.n_solver_steps
+            self._chk(self.lib.vv_diffusion_sample_general(self._ctx, self._s, n, self._p(cond), self._p(noise), self._p(step_noise),
+                                                           0.0 if rows else float(cfg_scale), self._p(cfg_scale) if rows else C.c_void_p(),
+                                                           self._p(latent_out)), "vv_diffusion_sample_general")
+            return
         if isinstance(cfg_scale, torch.Tensor):
             if (cfg_scale.dim() != 1 or cfg_scale.shape[0] != n or cfg_scale.dtype != torch.float32 or cfg_scale.device != self.device
                     or not cfg_scale.is_contiguous()):

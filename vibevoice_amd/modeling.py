@@ -45,6 +45,7 @@ import numpy as np
 import torch
 
 from . import noise as _noise
+from . import schedule as _schedule
 from .engine import Engine, EngineConfig, map_param_name
 
 _WARNED_QUEUED_RNG = False
@@ -236,24 +237,39 @@ class _SchedulerView:
     @property
     def timesteps(self):
         from . import schedule as _schedule
-        tv, _ = _schedule.make_table(self.num_inference_steps or 20, False)
+        n = self.num_inference_steps or 20
+        if _schedule.is_shipped(self.config):
+            tv, _ = _schedule.make_table(n, False)
+        else:                       # the configuration's own spacing, offset and lambda cut, as the reference's set_timesteps(n) lists them
+            tv, _ = _schedule.general_timesteps_and_sigmas(self.config, n)
         return torch.from_numpy(np.asarray(tv)).long()
 
+    TRAINING = "a property of how the checkpoint was trained, not of how it is sampled"
+    REFERENCE_FAILS = "the reference itself fails on this model's [2n, 64] latents"
+
     def check_supported(self):
-        """the configurations the HIP sampler implements; anything else must fail loudly, not run a different solver"""
+        """The configurations the HIP sampler implements: every combination of the reference's sampling-time settings
+        (schedule.SAMPLING_KEYS) -- the two shipped configurations on the shipped sampler, the rest through the general table.
+        Anything else fails loudly, naming the key and why it stays refused, rather than running a different solver."""
         from . import schedule as _schedule
         c = self.config
-        want = dict(num_train_timesteps=1000, trained_betas=None, solver_order=2, prediction_type="v_prediction", thresholding=False,
-                    solver_type="midpoint", lower_order_final=True, euler_at_final=False, use_karras_sigmas=False,
-                    use_lu_lambdas=False, final_sigmas_type="zero", timestep_spacing="linspace", steps_offset=0,
-                    rescale_betas_zero_snr=False)
-        bad = {k: c[k] for k, v in want.items() if c[k] != v}
+        bad = {}
+        for k, v in dict(num_train_timesteps=1000, trained_betas=None, prediction_type="v_prediction", rescale_betas_zero_snr=False,
+                         variance_type=None).items():
+            if c[k] != v:
+                bad[k] = (c[k], self.TRAINING)
         if c["beta_schedule"] not in ("cosine", "squaredcos_cap_v2"):          # the same Glide cosine betas (dpm_solver.py:240-242)
-            bad["beta_schedule"] = c["beta_schedule"]
-        if c["algorithm_type"] not in _schedule.ALGORITHMS:
-            bad["algorithm_type"] = c["algorithm_type"]
+            bad["beta_schedule"] = (c["beta_schedule"], self.TRAINING)
+        for k, exc in (("use_karras_sigmas", "KeyError: 'sigma_min'"), ("thresholding", "TypeError in reshape"),
+                       ("use_lu_lambdas", "IndexError at 20 steps")):
+            if c[k]:
+                bad[k] = (c[k], f"{self.REFERENCE_FAILS} ({exc})")
+        bad.update(_schedule.check_solver(c))
         if bad:
-            raise NotImplementedError(f"noise scheduler configuration not implemented by the HIP sampler: {bad}")
+            raise NotImplementedError("noise scheduler configuration not implemented by the HIP sampler: "
+                                      + "; ".join(f"{k}={v!r}: {why}" for k, (v, why) in bad.items()))
+        if not _schedule.is_shipped(c) and self.num_inference_steps:
+            _schedule.general_timesteps_and_sigmas(c, self.num_inference_steps)      # a steps_offset that leaves [0, 1000): ValueError
 
 
 def _engine_name_to_reference(name: str):
@@ -494,6 +510,7 @@ class _Session:
     """What one generate() / generate_continuous() call holds beside its utterances (_session builds it; every field has a default, so
     a caller of one stage -- a test, a tool -- names only what that stage reads)."""
     sde: bool = False                              # the stochastic solver ('sde-dpmsolver++')
+    solver_steps: int = 0                          # general solver table: the steps the reference's set_timesteps yields (0: ddpm_inference_steps)
     sde_noise_fn: Optional[Callable] = None        # test hook: the recorded variance draws
     nv: int = 0                                    # number of valid ids
     valid_t: Optional[torch.Tensor] = None         # the valid ids in the engine's order (host, int64)
@@ -1797,7 +1814,7 @@ class VibeVoiceForConditionalGenerationInference(_AudioRates):
         global generator (dpm_solver.py:994-997; generate() passes no generator); only the first n rows survive the next step's
         `speech[:n]` (modeling_vibevoice_inference.py:703-704).  Same calls, same order -> same stream for a seeded run."""
         e = self.engine
-        N, L = self.ddpm_inference_steps, e.cfg.latent_dim
+        N, L = S.solver_steps or self.ddpm_inference_steps, e.cfg.latent_dim
         if self._sde_flat is None:
             self._sde_flat = e.new(64 * MAX_BATCH * L)
         buf = self._sde_flat[:N * n * L].view(N, n, L)
@@ -1830,10 +1847,15 @@ class VibeVoiceForConditionalGenerationInference(_AudioRates):
             e.set_valid_tokens(valid)
             self._valid_key = tuple(valid)
         algo = self._sched_cfg["algorithm_type"]
+        # a shipped configuration is installed as before (engines and stand-ins that predate the general table take no solver=);
+        # any other one passes its non-default sampling-time settings, and the engine routes diffusion_sample by the installed table
+        general = not _schedule.is_shipped(self._sched_cfg)
+        solver = {k: self._sched_cfg[k] for k, v in _schedule.SHIPPED.items() if self._sched_cfg[k] != v} if general else None
         e.set_num_steps(self.ddpm_inference_steps, t_cast_bf16=(self.dtype == torch.bfloat16 and kwargs.get("_t_cast", True)),
-                        **({} if algo == "dpmsolver++" else {"algorithm_type": algo}))
+                        **({} if algo == "dpmsolver++" else {"algorithm_type": algo}), **({"solver": solver} if general else {}))
+        solver_steps = len(_schedule.general_timesteps_and_sigmas(self._sched_cfg, self.ddpm_inference_steps)[0]) if general else 0
         cpu_gen, dev_gen = kwargs.pop("_generators", None) or (None, None)
-        return _Session(sde=(algo == "sde-dpmsolver++"), sde_noise_fn=kwargs.pop("_sde_noise_fn", None), nv=len(valid),
+        return _Session(sde=(algo == "sde-dpmsolver++"), solver_steps=solver_steps, sde_noise_fn=kwargs.pop("_sde_noise_fn", None), nv=len(valid),
                         valid_t=torch.tensor(valid, dtype=torch.long), start_id=start_id, end_id=end_id, diff_id=diff_id, eos_id=eos_id,
                         pad_id=getattr(tokenizer, "pad_token_id", None), cfg_scale=cfg_scales[0] if cfg_scales else 1.0,
                         cfg_rows=len(set(cfg_scales)) > 1, do_sample=do_sample, temperature=temperature, warp=warp,
