@@ -39,14 +39,16 @@ class Small:
             max_position_embeddings=self.lmcfg.max_pos, head_eps=self.hc.eps, codec_eps=self.cc.eps)
 
 
-def build_small(lmcfg=None, xsplit=3, use_graph=False, n_slots=2, max_ctx=512, tied=False, max_rows=16, head_layers=2, head_ffn_ratio=3.0):
+def build_small(lmcfg=None, xsplit=3, use_graph=False, n_slots=2, max_ctx=512, tied=False, max_rows=16, head_layers=2, head_ffn_ratio=3.0,
+                lm_w=None):
+    """lm_w: the LM's weights (oracle keys) instead of synth.lm_weights(lmcfg) -- e.g. the readout layer of tests/attn_cases.py"""
     from vibevoice_amd.engine import Engine, EngineConfig
     lmcfg = lmcfg or synth.LMCfg()
     H = lmcfg.hidden
     hc = synth.HeadCfg(hidden=H, layers=head_layers, ffn_ratio=head_ffn_ratio)
     cc = synth.CodecCfg()
     sc = synth.CodecCfg(vae_dim=128)
-    lm_w = synth.lm_weights(lmcfg)
+    lm_w = synth.lm_weights(lmcfg) if lm_w is None else lm_w
     lm_head = lm_w["embed_tokens.weight"] if tied else synth.lm_head_weight(lmcfg)
     head_w = synth.head_weights(hc)
     ac_w = {**synth.encoder_weights(cc, 2), **synth.decoder_weights(cc, 3)}

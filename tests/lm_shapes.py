@@ -61,3 +61,31 @@ REPLAY_SPLITS = {"one": [1, 1, 1, 2, 2, 2, 2, 1, 1, 1], "short+long": [1, 1, 1, 
 REPLAY_ENGINE = ("gqa", 16)
 # test_gpu_graph_replay.py::test_replays_after_an_upload: a 3-row span of one cache (rope/append reads inv_freq itself, then split + merge)
 REPLAY_SPAN = 3
+
+# ---- test_gpu_attn_paths.py: one attention launch at a time through the readout layer (tests/attn_cases.py) ----
+# geometries: A head_dim 64, 4 query / 2 kv heads; B head_dim 128, 7 query heads on 1 kv head (the 7B group: a vv_attn_prefill4
+# workgroup of four units straddles two 64-row tiles).  heads * head_dim == hidden: the identity o-projection reads attention out
+ATTN_GEO = {"A": synth.LMCfg(hidden=256, layers=1, heads=4, kv_heads=2, inter=256, vocab=64),
+            "B": synth.LMCfg(hidden=896, layers=1, heads=7, kv_heads=1, inter=256, vocab=64)}
+ATTN_MAX_CTX, ATTN_SLOTS, ATTN_MAX_ROWS = 2304, 8, 160
+# test_fused_decode: cache lengths before the first step (row i on cache i), ATTN_DECODE_STEPS steps each.  Between them the sets hold
+# every length of 0, 1, 15, 16, 31, 32, 33, 63, 64, 127, 128, 129, 1022, 1023, 1024, 2047, 2048, 2100; "6", "16" and "mix" take the
+# batch-decode route in the bf16 mode; "mix": rows of one block (used = 1) and of two (used < S) beside a row of three splits
+ATTN_DECODE_LENS = {"1": [1023], "2": [1055, 31], "6": [2048, 2100, 2030, 33, 1022, 129],
+                    "16": [0, 1, 15, 16, 31, 32, 33, 63, 64, 127, 128, 129, 1022, 1023, 1024, 2047],
+                    "mix": [2100, 1, 32, 33, 40, 96, 97]}
+ATTN_DECODE_STEPS = 3
+# the split count of every step of a case (one per 1024 positions of the longest row), and with attn_splits = 2 capping it
+ATTN_DECODE_SPLITS = {"1": [1, 2, 2], "2": [2, 2, 2], "6": [3, 3, 3], "16": [2, 3, 3], "mix": [3, 3, 3]}
+ATTN_DECODE_CAPPED = [2100, 40]
+# test_split_merge: (rows, pos0) spans of one cache; a 5-row span at 6 beside a row at 1500 of another cache (a short row in a
+# two-split launch whose positions per split sit at the 512 floor); exact modes: a 70-row chunk (two launches of the pair)
+ATTN_SPANS = tuple((n, p0) for n in (2, 5, 7) for p0 in (0, 30, 510, 1020, 2046))
+ATTN_SHORT_LONG = span(0, 6, 5) + [(1, 1500)]
+ATTN_EXACT_CHUNK = (70, 1000)
+# test_prefill4 (bf16 mode): (rows, pos0) chunks; below 64 rows through the per-layer GEMMs, from 64 the packed prefill
+ATTN_CHUNKS = tuple((n, p0) for n in (8, 20, 63, 64, 100, 150) for p0 in (0, 37, 64, 100, 1000))
+# test_append_exact: one decode step per position class, a 5-row span and two chunks at each pos0
+ATTN_APPEND_DECODE = [0, 15, 16, 31, 32, 2040]
+ATTN_APPEND_POS0 = (0, 37, 2040)
+ATTN_APPEND_SPAN, ATTN_APPEND_CHUNKS = 5, (64, 150)

@@ -262,3 +262,50 @@ def test_the_gpu_tests_run_the_launches_they_name(probe):
         if xs != 1:                                 # "eight 64-row launches" per whole chunk
             whole = lm_plans(probe, [lm(ls.span(0, i0, k), **caps) for i0, k in chunks if k == 512])
             assert all(p["attn_groups"] == 8 for _, p in whole), whole
+
+
+def test_the_attention_path_tests_run_the_launches_they_name(probe):
+    """test_gpu_attn_paths.py: the kernel family, the split count and the projection route of every row set of lm_shapes.ATTN_*"""
+    for geo, cfg in ls.ATTN_GEO.items():
+        eng = (cfg, ls.ATTN_MAX_ROWS)
+        for xs in (1, 2, 3):
+            caps = engine_caps(eng, xs)
+            assert caps["ws"] == 64 and caps["hkv"] == cfg.kv_heads and caps["tile3"] == caps["p16"] == caps["attn2"] == (xs == 1)
+            # test_fused_decode: fused attention, the split count of every step, the packed batch route for 5..16 rows in the bf16 mode
+            assert set(ls.ATTN_DECODE_LENS) == set(ls.ATTN_DECODE_SPLITS)
+            for case, lens in ls.ATTN_DECODE_LENS.items():
+                steps = ls.decode_steps(list(enumerate(lens)), ls.ATTN_DECODE_STEPS)
+                route = P16 if xs == 1 and 5 <= len(lens) <= 16 else GEMV
+                check_lm(probe, [(lm(rows, **caps), dict(fused=1, attn=FUSED, route=route, attn_S=S))
+                                 for rows, S in zip(steps, ls.ATTN_DECODE_SPLITS[case])])
+            capped = engine_caps(eng, xs, attn_splits=2)
+            check_lm(probe, [(lm(rows, **capped), dict(fused=1, attn=FUSED, route=GEMV, attn_S=2))
+                             for rows in ls.decode_steps(list(enumerate(ls.ATTN_DECODE_CAPPED)), ls.ATTN_DECODE_STEPS)])
+            check_lm(probe, [(lm(ls.decode_steps(list(enumerate(ls.ATTN_DECODE_CAPPED)), 1)[0], **caps), dict(attn_S=3))])
+            # test_split_merge: rope/append + the split + merge pair in every mode
+            ragged = dict(fused=0, contiguous=0, route=GEMV, attn=SPLIT_MERGE, attn_groups=1, zero_v_tail=0)
+            check_lm(probe, [(lm(ls.span(0, p0, n), **caps), dict(ragged, attn_S=(p0 + n - 1) // 1024 + 1)) for n, p0 in ls.ATTN_SPANS])
+            check_lm(probe, [(lm(ls.ATTN_SHORT_LONG, **caps), dict(ragged, attn_S=2))])
+            n, p0 = ls.ATTN_EXACT_CHUNK
+            if xs != 1:
+                check_lm(probe, [(lm(ls.span(0, p0, n), **caps), dict(contiguous=1, route=GEMV, attn=SPLIT_MERGE, attn_groups=2, attn_S=2))])
+            # test_prefill4 and the chunks of test_append_exact
+            chunks = list(ls.ATTN_CHUNKS) + [(n, p0) for n in ls.ATTN_APPEND_CHUNKS for p0 in ls.ATTN_APPEND_POS0]
+            check_lm(probe, [(lm(ls.span(0, p0, n), **caps), span_claim(n, xs)) for n, p0 in chunks])
+            # test_append_exact: one decode step of six rows, the 5-row spans
+            check_lm(probe, [(lm(list(enumerate(ls.ATTN_APPEND_DECODE)), **caps), dict(fused=1, attn=FUSED, route=P16 if xs == 1 else GEMV))] +
+                            [(lm([(0, p)], **caps), dict(fused=1, attn=FUSED, route=GEMV)) for p in ls.ATTN_APPEND_DECODE] +
+                            [(lm(ls.span(0, p0, ls.ATTN_APPEND_SPAN), **caps), ragged) for p0 in ls.ATTN_APPEND_POS0])
+    # what the docstrings of the GPU file say about the row sets
+    lens = sorted({n for v in ls.ATTN_DECODE_LENS.values() for n in v})
+    assert set(lens) >= {0, 1, 15, 16, 31, 32, 33, 63, 64, 127, 128, 129, 1022, 1023, 1024, 2047, 2048, 2100}
+    assert [len(ls.ATTN_DECODE_LENS[c]) for c in ("1", "2", "6", "16")] == [1, 2, 6, 16]
+    assert set(ls.ATTN_DECODE_LENS["mix"][1:]) == {1, 32, 33, 40, 96, 97} and ls.ATTN_DECODE_LENS["mix"][0] == 2100
+    # the owner split (pos >> 5) % S takes every residue for S = 2 and S = 3
+    owners = {2: set(), 3: set()}
+    for case, lens in ls.ATTN_DECODE_LENS.items():
+        for step, S in enumerate(ls.ATTN_DECODE_SPLITS[case]):
+            if S in owners:
+                owners[S] |= {((n + step) >> 5) % S for n in lens}
+    assert owners == {2: {0, 1}, 3: {0, 1, 2}}, owners
+    assert any(n < 64 for n, _ in ls.ATTN_CHUNKS) and any(n >= 64 for n, _ in ls.ATTN_CHUNKS)

@@ -753,8 +753,9 @@ __device__ __forceinline__ float a3_xrow_max(float v) {
     return fmaxf(__uint_as_float(t0), __uint_as_float(t1));
 }
 
-// rows = consecutive positions of ONE cache (rows[0] first); q = the rotated queries (vv_rope_append_kernel), fp32 [R][Hq][D]; the
-// softmax scale is applied here.  A workgroup = 4 units (64 query rows x one query head) of one kv head, 8 waves = unit x row half (two
+// rows = consecutive positions of ONE cache (rows[0] first); q = the rotated queries, fp32 [R][Hq][D], ALREADY scaled by 1 / sqrt(D)
+// (vv_rope_append_kernel or the QKV GEMM's RoPE epilogue); only log2(e) is folded in here, before the bf16 rounding: the softmax
+// runs in the log2 domain.  A workgroup = 4 units (64 query rows x one query head) of one kv head, 8 waves = unit x row half (two
 // 16-row tiles per wave), the causal prefix streamed ONCE, 64 positions per stage through a 4-slot LDS ring (LDS-DMA).
 // Round 2's form of this kernel (all waves in step: S^T MFMAs -> softmax -> P.V MFMAs between two barriers per stage) ran the
 // matrix pipe 31-33 % busy: both waves of a SIMD contended for it, then both for the VALU.  Here the two waves of a SIMD (w and
