@@ -306,6 +306,33 @@ int vv_resample_rows(vv_ctx* ctx, void* stream, int rs, int n, const vv_resample
  * coef_dev [L][T] on the device.  Bit-identical to the same signal pushed and flushed through vv_resample_rows. */
 int vv_resample_once(vv_ctx* ctx, void* stream, int L, int M, int T, const float* coef_dev, int n, int n_in, const float* audio_dev,
                      int ld_in, float* out_dev, int ld_out);
+/* ---- speaking rate: a streaming, pitch-preserving tempo change P / Q in [1/2, 2], Q <= 100, at 24 kHz (vibevoice_amd/tempo.py
+ * defines it: WSOLA, hop 240, window 480, search radius 160, an exact integer similarity search -- the device chooses the offsets the
+ * definition chooses).  A signal of n samples yields ceil(n * Q / P), in blocks of 240.  What a stream emits does not depend on how
+ * its input was cut into pushes: a push emits every block all of whose input has arrived (at most 640 samples wait for the next
+ * push), the flush emits the rest against zeros.
+ * vv_tempo_set: configuration tp (0..3) of this context: window_host [480] fp32 in HOST memory (the periodic Hann table of the
+ * definition), n_streams streams at their first sample.  Replaces what tp held.  Synchronous. */
+int vv_tempo_set(vv_ctx* ctx, int tp, const float* window_host, int n_streams, void* stream);
+/* Back to the state after vv_tempo_set for n streams (stream_ids_host == NULL: all of them): history and last offset zeroed by a
+ * kernel on `stream`, input total 0, speed and flush mark cleared. */
+int vv_tempo_reset(vv_ctx* ctx, void* stream, int tp, int n, const int* stream_ids_host);
+/* One push of n <= 16 rows, ONE launch on `stream`: row i = n_in samples at audio_dev + i * ld_in for stream rows_host[i].stream
+ * (distinct) at speed P / Q (a stream keeps the speed of its first push until its reset), flush != 0: the stream's last push.  Its
+ * outputs go to out_dev + i * ld_out (elements): out_fmt 0 = fp32, 1 = int16 with the arithmetic of vv_audio_to_pcm16 over the row's
+ * stretched chunk.  n_out_host [n]: what each row emitted, computed on the host from the streams' input totals (no sync).
+ * offsets_dev (may be NULL): the offset chosen for each block the row walked, row i at offsets_dev + i * ld_off, n_out / 240 rounded
+ * up of them.  Refused with a message, nothing written, no state changed: as vv_resample_rows, and a stream whose speed changes; with
+ * the return value VV_TEMPO_OVER_CAPACITY a row of more than 7680 input samples, more than 96 blocks or more than ld_out outputs:
+ * the caller splits that push. */
+#define VV_TEMPO_OVER_CAPACITY 3
+typedef struct vv_tempo_row { int stream; int n_in; int flush; int P; int Q; } vv_tempo_row;
+int vv_tempo_rows(vv_ctx* ctx, void* stream, int tp, int n, const vv_tempo_row* rows_host, const float* audio_dev, int ld_in,
+                  void* out_dev, int ld_out, int out_fmt, int* n_out_host, int* offsets_dev, int ld_off);
+/* Stateless: n whole signals of n_in samples (audio_dev + i * ld_in) -> ceil(n_in * Q / P) fp32 samples each (out_dev + i * ld_out),
+ * window_dev [480] on the device; offsets_dev as above.  Bit-identical to the same signal pushed and flushed through vv_tempo_rows. */
+int vv_tempo_once(vv_ctx* ctx, void* stream, const float* window_dev, int P, int Q, int n, int n_in, const float* audio_dev, int ld_in,
+                  float* out_dev, int ld_out, int* offsets_dev, int ld_off);
 /* acoustic_cache.set_to_zero + semantic_cache.set_to_zero for a slot (:542-546) */
 int vv_codec_reset(vv_ctx* ctx, void* stream, int slot);
 /* acoustic_connector(latent) [+ semantic_connector(sem)] (:667-669, :161); sem_dev may be NULL */

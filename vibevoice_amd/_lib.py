@@ -55,7 +55,13 @@ class VVResampleRow(C.Structure):
     _fields_ = [("stream", C.c_int), ("n_in", C.c_int), ("flush", C.c_int)]
 
 
+class VVTempoRow(C.Structure):
+    """vv_tempo_row (include/vvhip.h): the stream, the input samples, the flush mark and the speed P / Q of one row of vv_tempo_rows"""
+    _fields_ = [("stream", C.c_int), ("n_in", C.c_int), ("flush", C.c_int), ("P", C.c_int), ("Q", C.c_int)]
+
+
 GEMV_REFUSED = 1     # VV_GEMV_REFUSED
+TEMPO_OVER_CAPACITY = 3     # VV_TEMPO_OVER_CAPACITY
 _SIGS = {
     "vv_create": (C.c_int, [C.POINTER(VVConfig), C.POINTER(_P)]),
     "vv_create_shared": (C.c_int, [C.POINTER(VVConfig), _P, C.POINTER(_P)]),
@@ -102,6 +108,11 @@ _SIGS = {
     "vv_resample_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(VVResampleRow), _P, C.c_int, _P, C.c_int, C.c_int,
                                    C.POINTER(C.c_int)]),
     "vv_resample_once": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int]),
+    "vv_tempo_set": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),
+    "vv_tempo_reset": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "vv_tempo_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(VVTempoRow), _P, C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_int), _P,
+                                C.c_int]),
+    "vv_tempo_once": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, _P, C.c_int]),
     "vv_codec_reset": (C.c_int, [_P, _P, C.c_int]),
     "vv_connect": (C.c_int, [_P, _P, C.c_int, _P, _P, _P]),
     "vv_packed_bytes": (C.c_int64, [C.c_int, C.c_int]),

@@ -606,3 +606,123 @@ extern "C" int vv_resample_once(vv_ctx* ctx, void* stream, int L, int M, int T, 
     VVCHK(vv_resample_once_launch(L, M, T, coef_dev, n, n_in, audio_dev, ld_in, out_dev, ld_out, (hipStream_t)stream));
     return 0;
 }
+
+// ------------------------------------------------------------------ speaking rate (kernels: tempo.hip; vibevoice_amd/tempo.py defines it)
+static int64_t tp_a(int64_t k, int P, int Q) { return k < 0 ? -(int64_t)VV_TP_HS : (k * VV_TP_HS * P) / Q; }
+
+// Blocks a stream has emitted before its flush once `total` input samples have arrived: every k with
+// max(a_k, a_{k-1} + HS) + DELTA + N <= total.  vibevoice_amd/tempo.py (emitted_blocks) is the same arithmetic.
+static int64_t tp_emitted(int64_t total, int P, int Q) {
+    const int64_t room = total - VV_TP_DELTA - VV_TP_N;
+    if (room < 0) return 0;
+    int64_t k = ((room + 1) * Q) / ((int64_t)VV_TP_HS * P) + 1;
+    while (k > 0 && std::max(tp_a(k - 1, P, Q), tp_a(k - 2, P, Q) + VV_TP_HS) > room) --k;
+    return k;
+}
+
+static bool tp_speed_ok(int P, int Q) { return P >= 1 && Q >= 1 && Q <= 100 && P <= 2 * Q && Q <= 2 * P; }
+
+extern "C" int vv_tempo_set(vv_ctx* ctx, int tp, const float* window_host, int n_streams, void* stream) {
+    VV_SHARED;
+    if (tp < 0 || tp >= vv_ctx::N_TEMPOS) return fail(ctx, "vv_tempo_set: configuration %d out of range [0,%d)", tp, vv_ctx::N_TEMPOS);
+    if (n_streams < 1 || n_streams > 65536) return fail(ctx, "vv_tempo_set: n_streams = %d must be in [1,65536]", n_streams);
+    if (!window_host) return fail(ctx, "vv_tempo_set: null window table");
+    vv_ctx::Tempo& t = ctx->tp[tp];
+    HIPCHK(ctx, hipStreamSynchronize((hipStream_t)stream));      // pushes that still read what is replaced
+    dfree(ctx, t.window); dfree(ctx, t.hist); dfree(ctx, t.dstate);
+    t = vv_ctx::Tempo();
+    float* window = (float*)dalloc(ctx, (size_t)VV_TP_N * 4, false);
+    float* hist = (float*)dalloc(ctx, (size_t)n_streams * VV_TP_HIST * 4, true);
+    int* dstate = (int*)dalloc(ctx, (size_t)n_streams * 4, true);
+    if (!window || !hist || !dstate || hipMemcpy(window, window_host, (size_t)VV_TP_N * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        dfree(ctx, window); dfree(ctx, hist); dfree(ctx, dstate);
+        return fail(ctx, "vv_tempo_set: allocating the state or uploading the window failed");
+    }
+    t.n_streams = n_streams; t.window = window; t.hist = hist; t.dstate = dstate;
+    t.total.assign(n_streams, 0); t.P.assign(n_streams, 0); t.Q.assign(n_streams, 0); t.flushed.assign(n_streams, 0);
+    return 0;
+}
+
+extern "C" int vv_tempo_reset(vv_ctx* ctx, void* stream, int tp, int n, const int* stream_ids_host) {
+    VV_SHARED;
+    hipStream_t st = (hipStream_t)stream;
+    if (tp < 0 || tp >= vv_ctx::N_TEMPOS || !ctx->tp[tp].hist) return fail(ctx, "vv_tempo_reset: configuration %d is not set", tp);
+    vv_ctx::Tempo& t = ctx->tp[tp];
+    std::vector<int> ids;
+    if (!stream_ids_host) { for (int i = 0; i < t.n_streams; ++i) ids.push_back(i); }
+    else {
+        if (n < 1) return fail(ctx, "vv_tempo_reset: n = %d must be >= 1", n);
+        ids.assign(stream_ids_host, stream_ids_host + n);
+    }
+    for (int id : ids)
+        if (id < 0 || id >= t.n_streams) return fail(ctx, "vv_tempo_reset: stream id %d out of range [0,%d)", id, t.n_streams);
+    for (size_t i0 = 0; i0 < ids.size(); i0 += 16)
+        VVCHK(vv_tempo_reset_launch(t.hist, t.dstate, t.n_streams, ids.data() + i0, (int)std::min<size_t>(16, ids.size() - i0), st));
+    for (int id : ids) { t.total[id] = 0; t.P[id] = 0; t.Q[id] = 0; t.flushed[id] = 0; }
+    return 0;
+}
+
+extern "C" int vv_tempo_rows(vv_ctx* ctx, void* stream, int tp, int n, const vv_tempo_row* rows_host, const float* audio_dev, int ld_in,
+                             void* out_dev, int ld_out, int out_fmt, int* n_out_host, int* offsets_dev, int ld_off) {
+    VV_SHARED;
+    if (tp < 0 || tp >= vv_ctx::N_TEMPOS || !ctx->tp[tp].hist) return fail(ctx, "vv_tempo_rows: configuration %d is not set", tp);
+    vv_ctx::Tempo& t = ctx->tp[tp];
+    if (n < 1 || n > 16) return fail(ctx, "vv_tempo_rows: n = %d must be in [1,16]", n);
+    if (!rows_host || !out_dev || !n_out_host) return fail(ctx, "vv_tempo_rows: null rows / out / n_out pointer");
+    if (out_fmt != 0 && out_fmt != 1) return fail(ctx, "vv_tempo_rows: out_fmt = %d must be 0 (fp32) or 1 (int16)", out_fmt);
+    VVTpRows kr;
+    memset(&kr, 0, sizeof(kr));
+    for (int i = 0; i < n; ++i) {
+        const vv_tempo_row& q = rows_host[i];
+        if (q.stream < 0 || q.stream >= t.n_streams) return fail(ctx, "vv_tempo_rows: row %d: stream id %d out of range [0,%d)", i, q.stream, t.n_streams);
+        for (int j = 0; j < i; ++j)
+            if (rows_host[j].stream == q.stream) return fail(ctx, "vv_tempo_rows: stream %d is named twice (rows %d and %d)", q.stream, j, i);
+        if (q.n_in < 0) return fail(ctx, "vv_tempo_rows: row %d: n_in = %d must be >= 0", i, q.n_in);
+        if (q.n_in > VV_TP_MAX_IN) {
+            fail(ctx, "vv_tempo_rows: row %d brings %d samples, one push takes at most %d per row; split it", i, q.n_in, VV_TP_MAX_IN);
+            return VV_TEMPO_OVER_CAPACITY;
+        }
+        if (q.n_in > ld_in || (q.n_in > 0 && !audio_dev)) return fail(ctx, "vv_tempo_rows: row %d: n_in = %d exceeds the input rows (ld_in = %d)", i, q.n_in, ld_in);
+        if (!tp_speed_ok(q.P, q.Q)) return fail(ctx, "vv_tempo_rows: row %d: speed %d / %d must lie in [1/2, 2] with a denominator of at most 100", i, q.P, q.Q);
+        if (t.P[q.stream] && (t.P[q.stream] != q.P || t.Q[q.stream] != q.Q))
+            return fail(ctx, "vv_tempo_rows: stream %d runs at speed %d / %d since its first push; reset it before it changes to %d / %d", q.stream,
+                        t.P[q.stream], t.Q[q.stream], q.P, q.Q);
+        if (t.flushed[q.stream]) return fail(ctx, "vv_tempo_rows: stream %d has been flushed; reset it before its next push", q.stream);
+        const int64_t before = t.total[q.stream], after = before + q.n_in;
+        const int64_t k0 = tp_emitted(before, q.P, q.Q), total = (after * q.Q + q.P - 1) / q.P;
+        const int64_t k1 = q.flush ? (total + VV_TP_HS - 1) / VV_TP_HS : tp_emitted(after, q.P, q.Q);
+        const int64_t n_out = q.flush ? total - k0 * VV_TP_HS : (k1 - k0) * VV_TP_HS;
+        if (n_out > ld_out || k1 - k0 > VV_TP_MAX_BLOCKS) {
+            fail(ctx, "vv_tempo_rows: row %d emits %lld samples in %lld blocks, the output rows hold %d and one push walks at most %d blocks; split it", i,
+                 (long long)n_out, (long long)(k1 - k0), ld_out, VV_TP_MAX_BLOCKS);
+            return VV_TEMPO_OVER_CAPACITY;
+        }
+        if (offsets_dev && k1 - k0 > ld_off) return fail(ctx, "vv_tempo_rows: row %d walks %lld blocks, the offset rows hold %d", i, (long long)(k1 - k0), ld_off);
+        kr.r[i].k0 = k0; kr.r[i].base = before - VV_TP_HIST; kr.r[i].stream = q.stream; kr.r[i].n_in = q.n_in;
+        kr.r[i].nblk = (int)(k1 - k0); kr.r[i].n_out = (int)n_out; kr.r[i].P = q.P; kr.r[i].Q = q.Q;
+    }
+    for (int i = n; i < 16; ++i) kr.r[i] = kr.r[0];
+    VVCHK(vv_tempo_rows_launch(&kr, n, t.window, t.hist, t.dstate, t.n_streams, audio_dev, ld_in, out_dev, ld_out, out_fmt, offsets_dev, ld_off,
+                               (hipStream_t)stream));
+    for (int i = 0; i < n; ++i) {
+        const int id = rows_host[i].stream;
+        t.total[id] += rows_host[i].n_in; t.P[id] = rows_host[i].P; t.Q[id] = rows_host[i].Q;
+        if (rows_host[i].flush) t.flushed[id] = 1;
+        n_out_host[i] = kr.r[i].n_out;
+    }
+    return 0;
+}
+
+extern "C" int vv_tempo_once(vv_ctx* ctx, void* stream, const float* window_dev, int P, int Q, int n, int n_in, const float* audio_dev, int ld_in,
+                             float* out_dev, int ld_out, int* offsets_dev, int ld_off) {
+    VV_SHARED;
+    if (!tp_speed_ok(P, Q)) return fail(ctx, "vv_tempo_once: speed %d / %d must lie in [1/2, 2] with a denominator of at most 100", P, Q);
+    if (n < 1 || n > 65535 || n_in < 1 || n_in > ld_in) return fail(ctx, "vv_tempo_once: n = %d in [1,65535], n_in = %d in [1, ld_in = %d]", n, n_in, ld_in);
+    const int64_t total = ((int64_t)n_in * Q + P - 1) / P;
+    if (total > ld_out) return fail(ctx, "vv_tempo_once: %lld output samples per row, the output rows hold %d", (long long)total, ld_out);
+    if (offsets_dev && (total + VV_TP_HS - 1) / VV_TP_HS > ld_off)
+        return fail(ctx, "vv_tempo_once: %lld blocks per row, the offset rows hold %d", (long long)((total + VV_TP_HS - 1) / VV_TP_HS), ld_off);
+    if (!window_dev || !audio_dev || !out_dev) return fail(ctx, "vv_tempo_once: null window / audio / out pointer");
+    VVCHK(vv_tempo_once_launch(window_dev, P, Q, n, n_in, audio_dev, ld_in, out_dev, ld_out, offsets_dev, ld_off, (hipStream_t)stream));
+    return 0;
+}

@@ -182,6 +182,13 @@ struct vv_ctx {
                        std::vector<int64_t> total; std::vector<char> flushed; };
     static constexpr int N_RESAMPLERS = 4;
     Resampler rs[N_RESAMPLERS];
+    // streaming tempo changes (vv_tempo_set, engine_codec.hip; kernels: tempo.hip): the window table, per stream VV_TP_HIST history samples
+    // and its last block's offset on the device, and on the host its input total, its speed P / Q (fixed by its first push, 0 before) and
+    // whether it has been flushed.  Kept like the resamplers.
+    struct Tempo { int n_streams = 0; float* window = nullptr; float* hist = nullptr; int* dstate = nullptr;
+                   std::vector<int64_t> total; std::vector<int> P, Q; std::vector<char> flushed; };
+    static constexpr int N_TEMPOS = 4;
+    Tempo tp[N_TEMPOS];
     int64_t launches = 0;
     int64_t solver_fused = 0;         // general-path step ends that carried the next in-projection, last recorded body (vv_stat 8)
     int64_t seam_launches = 0;        // head-tail seam launches the last recorded sampler body issued (vv_stat 6; a replay keeps its capture's count)

@@ -173,6 +173,20 @@ struct VVRsRow { int stream, n_in, n_out, p0, b0; };
 struct VVRsRows { VVRsRow r[16]; };
 constexpr int VV_RS_MAX_OUT = 8192;        // outputs one row of a push may emit (1024 threads x 8 accumulators)
 
+// ---- streaming tempo change (tempo.hip): one row of a push, passed by value in the kernel arguments ----
+// The host keeps each stream's 64-bit input total and speed P / Q; the row names the blocks the push completes, k0 .. k0 + nblk - 1,
+// and base = total - VV_TP_HIST, the signal index of the first sample in the row's staging buffer [history | n_in chunk | zeros]:
+// the kernel forms a_k = (k * 240 * P) / Q in 64 bits and indexes with a_k - base.  n_out: nblk * 240, less where a flush cuts the
+// last block.
+struct VVTpRow { long long k0, base; int stream, n_in, nblk, n_out, P, Q; };
+struct VVTpRows { VVTpRow r[16]; };
+constexpr int VV_TP_HS = 240, VV_TP_N = 480, VV_TP_DELTA = 160;
+constexpr int VV_TP_HIST = 1280;           // input samples a stream keeps between pushes: > DELTA + 480 + 639 (vibevoice_amd/tempo.py)
+constexpr int VV_TP_MAX_IN = 7680;         // input samples one row of a push may bring (the staging buffer is LDS)
+constexpr int VV_TP_PAD = 896;             // zeros behind the chunk: a flush reads up to DELTA + HS + N = 880 samples past the signal's end
+constexpr int VV_TP_BUF = VV_TP_HIST + VV_TP_MAX_IN + VV_TP_PAD;
+constexpr int VV_TP_MAX_BLOCKS = 96;       // blocks per staged buffer: a block advances >= 120 input samples, (MAX_IN + PAD) / 120 < 96
+
 // Raise the dynamic-LDS limit of one or more kernels above the 64 KiB default; returns the first error.  A launcher calls it as
 // the initialiser of a function-local `static const hipError_t`: C++11 runs that initialiser once per process and makes
 // concurrent first calls wait for it (generate_interleaved and fork() drive two contexts from two host threads).

@@ -113,4 +113,11 @@ int vv_resample_rows_launch(const VVRsRows* rows, int n, int L, int M, int T, co
                             int ld_in, void* out, int ld_out, int pcm16, hipStream_t s);
 int vv_resample_once_launch(int L, int M, int T, const float* coef, int n, int n_in, const float* x, int ld_in, float* out, int ld_out, hipStream_t s);
 int vv_resample_reset_launch(float* hist, int T, int n_streams, const int* ids, int n, hipStream_t s);
+// tempo.hip.  hist [n_streams][VV_TP_HIST], dstate [n_streams] (each stream's last offset), window [VV_TP_N]; offsets (may be null):
+// the chosen offset of every block, row i at offsets + i * ld_off.
+int vv_tempo_rows_launch(const VVTpRows* rows, int n, const float* window, float* hist, int* dstate, int n_streams, const float* x, int ld_in,
+                         void* out, int ld_out, int pcm16, int* offsets, int ld_off, hipStream_t s);
+int vv_tempo_once_launch(const float* window, int P, int Q, int n, int n_in, const float* x, int ld_in, float* out, int ld_out, int* offsets,
+                         int ld_off, hipStream_t s);
+int vv_tempo_reset_launch(float* hist, int* dstate, int n_streams, const int* ids, int n, hipStream_t s);
 }

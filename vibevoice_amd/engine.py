@@ -583,6 +583,50 @@ class Engine:
                                                     self._p(out[i0:]), n_out), "vv_resample_once")
         return out.reshape(x.shape[:-1] + (n_out,))
 
+    # ------------------------------------------------------------------ speaking rate (tempo.py, csrc/tempo.hip)
+    def tempo(self, n_streams: int) -> "Tempo":
+        """A streaming tempo change with n_streams independent streams, each at its own speed, in one of this engine's four tempo
+        configurations (close() it to give the configuration back)."""
+        used = self.__dict__.setdefault("_tp_used", [None] * 4)
+        for k in range(len(used)):
+            if used[k] is None:
+                used[k] = t = Tempo(self, k, n_streams)
+                return t
+        raise EngineError("Engine.tempo: all 4 tempo configurations of this engine are in use; close() one")
+
+    def _tempo_window(self):
+        from . import tempo as _tp
+        w = self.__dict__.get("_tp_window")
+        if w is None:
+            w = self.__dict__["_tp_window"] = torch.from_numpy(np.array(_tp.window())).to(self.device)
+        return w
+
+    def time_stretch(self, audio: torch.Tensor, speed: float, stream=None, return_offsets: bool = False):
+        """Whole signals at another speaking rate, the pitch kept: audio [samples] or [n, samples] (24 kHz, any float dtype, any
+        device) -> fp32 on the engine's device, ceil(samples * Q / P) samples each for speed = P / Q in [0.5, 2.0], the definition of
+        vibevoice_amd/tempo.py.  Stateless; runs on `stream` (default: the current torch stream of the device).  return_offsets:
+        -> (out, offsets), offsets int32 [..., blocks]: the offset the search chose for each block of 240 output samples."""
+        from . import tempo as _tp
+        P, Q = _tp.ratio(speed)
+        x = audio.detach().to(device=self.device, dtype=torch.float32)
+        if x.dim() not in (1, 2):
+            raise ValueError(f"Engine.time_stretch: audio is [samples] or [n, samples], got {tuple(audio.shape)}")
+        x2 = x.reshape(-1, x.shape[-1]).contiguous()
+        n, n_in = x2.shape
+        n_out = _tp.total_out(n_in, P, Q)
+        nblk = -(-n_out // _tp.HS)
+        out = torch.empty((n, n_out), dtype=torch.float32, device=self.device)
+        offs = torch.zeros((n, max(nblk, 1)), dtype=torch.int32, device=self.device) if return_offsets else None
+        if n and n_in:
+            w = self._tempo_window()
+            st = stream if stream is not None else torch.cuda.current_stream(self.device)
+            for i0 in range(0, n, 65535):
+                nn = min(65535, n - i0)
+                self._chk(self.lib.vv_tempo_once(self._ctx, self._sp(st), self._p(w), P, Q, nn, n_in, self._p(x2[i0:]), n_in, self._p(out[i0:]),
+                                                 n_out, self._p(offs[i0:]) if offs is not None else None, max(nblk, 1)), "vv_tempo_once")
+        out = out.reshape(x.shape[:-1] + (n_out,))
+        return (out, offs[:, :nblk].reshape(x.shape[:-1] + (nblk,))) if return_offsets else out
+
     def codec_reset(self, slot: int):
         self._chk(self.lib.vv_codec_reset(self._ctx, self._s, slot), "vv_codec_reset")
 
@@ -888,6 +932,112 @@ class Engine:
         if rc != 0:
             raise EngineError(f"vv_gemv_case failed ({rc})")
         return tuple(form)
+
+
+class TempoCapacityError(EngineError):
+    """A Tempo.push row that brings more input, or emits more output, than one launch takes per row; nothing ran, no state changed:
+    push it in pieces."""
+
+
+class Tempo:
+    """One streaming tempo configuration of an engine (Engine.tempo): n_streams chunk-continuous streams at 24 kHz, each at the speed
+    of its first push until its reset.  What a stream delivers does not depend on how its input was cut into pushes
+    (vibevoice_amd/tempo.py): the concatenation of its pushes and its flush equals Engine.time_stretch() of the concatenated input, bit
+    for bit in float mode, ceil(n * Q / P) samples.  delay_samples: the input samples (640, 26.7 ms) a stream holds back at most until
+    its next push; max_in: the input samples one row of a push may bring."""
+
+    def __init__(self, engine: Engine, slot: int, n_streams: int):
+        from . import tempo as _tp
+        self.engine, self.slot, self.n_streams = engine, slot, int(n_streams)
+        self.delay_samples, self.max_in = _tp.delay_samples(), 7680
+        self.total = [0] * self.n_streams                 # input samples each stream has taken (the C side keeps the same figures)
+        self.ratio = [None] * self.n_streams              # (P, Q) of each stream, None before its first push
+        w = np.ascontiguousarray(_tp.window())
+        engine._chk(engine.lib.vv_tempo_set(engine._ctx, slot, C.c_void_p(w.ctypes.data), self.n_streams, engine._s), "vv_tempo_set")
+
+    def counts(self, stream_id: int, n_in: int, speed=None, flush: bool = False) -> int:
+        """samples a push of n_in samples to stream_id would emit now (host integers, no device sync); speed: for its first push"""
+        from . import tempo as _tp
+        P, Q = self.ratio[stream_id] or _tp.ratio(speed)
+        return _tp.counts(P, Q, self.total[stream_id], n_in, flush)[1]
+
+    def max_out(self, n_in: int) -> int:
+        """upper bound of what any push of up to n_in samples emits at any speed, the flush included: a stream has emitted every
+        block that starts 880 input samples or more before its total, and a signal of n samples yields at most 2 n"""
+        return 2 * (int(n_in) + 880) + 1
+
+    def push(self, audio: Optional[torch.Tensor], stream_ids: Sequence[int], speeds, flush=False, out: Optional[torch.Tensor] = None,
+             n_in=None, stream=None, pcm16: bool = False, return_offsets: bool = False):
+        """Row i of audio [n, samples] (contiguous fp32 on the engine's device; None where no row brings samples) goes to stream
+        stream_ids[i] (distinct) at speeds[i] (or one speed for all rows; a stream keeps the speed of its first push); n_in: samples
+        of each row that count (default: all), flush: bool or one per row -- a stream's last push, after which it takes no more until
+        reset().  -> (out, counts): out[i, :counts[i]] is what row i emitted, fp32, or int16 under pcm16 (the arithmetic of
+        Engine.audio_to_pcm16 over the row's stretched chunk, in the same launch).  out: a contiguous [>= n, capacity] tensor of that
+        dtype to write into (default: a new one of max_out(samples) columns).  return_offsets: -> (out, counts, offsets), offsets
+        int32 [n, blocks]: the offset chosen for each block of 240 samples a row emitted.  One launch per 16 rows on `stream`
+        (default: the device's current torch stream); the counts are host integers, nothing waits for the device.  A row beyond the
+        launch's capacity raises TempoCapacityError before anything ran."""
+        from . import tempo as _tp
+        e = self.engine
+        ids = [int(i) for i in stream_ids]
+        n = len(ids)
+        samples = 0 if audio is None else int(audio.shape[-1])
+        if audio is not None:
+            if audio.dim() != 2 or audio.dtype != torch.float32 or not audio.is_contiguous() or audio.device != e.device or audio.shape[0] < n:
+                raise ValueError(f"Tempo.push: audio is a contiguous fp32 [n >= {n}, samples] tensor on {e.device}")
+        nin = [samples] * n if n_in is None else [int(v) for v in n_in]
+        fl = [bool(flush)] * n if isinstance(flush, (bool, int)) else [bool(v) for v in flush]
+        sp = [speeds] * n if not hasattr(speeds, "__len__") else list(speeds)
+        if len(nin) != n or len(fl) != n or len(sp) != n:
+            raise ValueError("Tempo.push: n_in, flush and speeds name one value per row")
+        pq = [_tp.ratio(v) for v in sp]
+        dt = torch.int16 if pcm16 else torch.float32
+        if out is None:
+            out = torch.empty((max(n, 1), self.max_out(max(nin, default=0))), dtype=dt, device=e.device)
+        elif out.dim() != 2 or out.dtype != dt or not out.is_contiguous() or out.device != e.device or out.shape[0] < n:
+            raise ValueError(f"Tempo.push: out is a contiguous {dt} [n >= {n}, capacity] tensor on {e.device}")
+        cap = int(out.shape[1])
+        ld_off = -(-cap // _tp.HS)
+        offs = torch.zeros((max(n, 1), ld_off), dtype=torch.int32, device=e.device) if return_offsets else None
+        st = stream if stream is not None else torch.cuda.current_stream(e.device)
+        cnts = (C.c_int * max(n, 1))()
+        rows = (_lib.VVTempoRow * max(n, 1))()
+        for i in range(n):
+            rows[i].stream, rows[i].n_in, rows[i].flush, rows[i].P, rows[i].Q = ids[i], nin[i], int(fl[i]), pq[i][0], pq[i][1]
+        for i0 in range(0, n, 16):
+            nn = min(16, n - i0)
+            a = C.c_void_p(audio.data_ptr() + i0 * samples * 4) if audio is not None else C.c_void_p()
+            o = C.c_void_p(out.data_ptr() + i0 * cap * out.element_size())
+            f = C.c_void_p(offs.data_ptr() + i0 * ld_off * 4) if offs is not None else C.c_void_p()
+            rc = e.lib.vv_tempo_rows(e._ctx, e._sp(st), self.slot, nn, C.cast(C.byref(rows, i0 * C.sizeof(_lib.VVTempoRow)), C.POINTER(_lib.VVTempoRow)),
+                                     a, samples, o, cap, int(pcm16), C.cast(C.byref(cnts, i0 * 4), C.POINTER(C.c_int)), f, ld_off)
+            if rc == _lib.TEMPO_OVER_CAPACITY:
+                raise TempoCapacityError(f"Tempo.push: {e._err()}")
+            e._chk(rc, "vv_tempo_rows")
+            for i in range(i0, i0 + nn):
+                self.total[ids[i]] += nin[i]
+                self.ratio[ids[i]] = pq[i]
+        res = [int(cnts[i]) for i in range(n)]
+        return (out, res, offs) if return_offsets else (out, res)
+
+    def reset(self, ids: Optional[Sequence[int]] = None, stream=None):
+        """streams `ids` (default: all) back to their first sample: history zeroed on `stream`, totals 0, speeds and flush marks cleared"""
+        e = self.engine
+        st = stream if stream is not None else torch.cuda.current_stream(e.device)
+        if ids is None:
+            e._chk(e.lib.vv_tempo_reset(e._ctx, e._sp(st), self.slot, 0, None), "vv_tempo_reset")
+            self.total, self.ratio = [0] * self.n_streams, [None] * self.n_streams
+            return
+        arr = (C.c_int * max(1, len(ids)))(*[int(i) for i in ids])
+        e._chk(e.lib.vv_tempo_reset(e._ctx, e._sp(st), self.slot, len(ids), arr), "vv_tempo_reset")
+        for i in ids:
+            self.total[int(i)], self.ratio[int(i)] = 0, None
+
+    def close(self):
+        """give the engine's configuration back (its device buffers are released when the configuration is set again or the engine closes)"""
+        used = getattr(self.engine, "_tp_used", None)
+        if used is not None and used[self.slot] is self:
+            used[self.slot] = None
 
 
 class Resampler:

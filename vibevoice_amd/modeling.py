@@ -587,6 +587,12 @@ class _AudioRates:
         sample before the processor, which wants 24 kHz: resample_audio(wav, 24000, src_rate=44100).  generate() itself stays at 24 kHz."""
         return self.engine.resample(audio, int(src_rate), int(dst_rate))
 
+    def time_stretch(self, audio: torch.Tensor, speed: float) -> torch.Tensor:
+        """audio [samples] or [n, samples] at 24 kHz -> fp32 on the engine's device at `speed` times the speaking rate (0.5 .. 2.0), the
+        pitch kept, ceil(samples / speed) samples (Engine.time_stretch).  For speech_outputs after the fact --
+        time_stretch(out.speech_outputs[0], 1.2); in front of resample_audio where both are wanted.  generate() itself has no rate input."""
+        return self.engine.time_stretch(audio, speed)
+
 
 class VibeVoiceForConditionalGenerationInference(_AudioRates):
     """Drop-in for the reference class on the generate() path, backed by libvvhip.so."""

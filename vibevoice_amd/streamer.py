@@ -18,6 +18,15 @@ its next chunk (1.3 ms at 48 kHz, 4 ms at 8 kHz); end(indices) flushes those tai
 close() does not.  Device chunks need an engine: the `pcm16=` one, or `engine=` where the chunks stay float; CPU chunks go through
 resample.HostResampler on the host.  Stream id = sample index.
 
+`speed=S` (a float in [0.5, 2.0], or one per sample index; anything but 1) changes the speaking rate and keeps the pitch: put() runs the
+chunk batch through the engine's tempo stage (Engine.tempo, csrc/tempo.hip: WSOLA, vibevoice_amd/tempo.py is the definition) on the
+producing stream, at 24 kHz, IN FRONT of whatever follows it today -- the resampler, else the 16-bit conversion (over each row's
+stretched chunk), else the copy; float chunks arrive as fp32.  Chunk-continuous like the resampler: per sample, the concatenated
+chunks equal Engine.time_stretch() of the concatenated input (then Engine.resample() of that, under sample_rate), ceil(n / S) samples,
+bit for bit in float mode.  A sample holds back at most 640 input samples (26.7 ms) until its next chunk; a put that completes no
+block of 240 delivers nothing for that row; end(indices) flushes the tempo tail, then the resampler's.  Device chunks need an engine
+(as above), CPU chunks go through tempo.HostTempo.  A chunk too long for one launch is pushed in pieces and arrives as several.
+
 The drain thread exits when every sample has ended (or on close()); its pinned ring goes back to a process-wide pool.
 """
 import asyncio
@@ -73,10 +82,26 @@ def _pinned_give(bufs):
 SOURCE_RATE = 24000      # what the acoustic decoder produces
 
 
+def _speeds_of(speed, batch_size):
+    """AudioStreamer's speed argument as one float per sample index; None where it asks for no change (absent, or 1 everywhere)"""
+    if speed is None:
+        return None
+    from .tempo import ratio
+    speeds = [float(speed)] * batch_size if not hasattr(speed, "__len__") else [float(v) for v in speed]
+    if len(speeds) != batch_size:
+        raise ValueError(f"AudioStreamer(speed=...): one value, or one per sample index ({batch_size}), got {len(speeds)}")
+    if all(p == q for p, q in map(ratio, speeds)):            # ratio() refuses what lies outside [0.5, 2.0]
+        return None
+    return speeds
+
+
 class AudioStreamer:
     def __init__(self, batch_size: int, stop_signal=None, timeout: Optional[float] = None, ring_slots: int = 8, pcm16=None,
-                 sample_rate: Optional[int] = None, engine=None):
+                 sample_rate: Optional[int] = None, engine=None, speed=None):
         self.batch_size = batch_size
+        self._speeds = _speeds_of(speed, batch_size)   # one per sample index, or None: no tempo stage anywhere
+        self._tp = None                            # Engine.tempo (device chunks), one stream per sample index
+        self._tp_host = {}                         # sample index -> tempo.HostTempo (CPU chunks)
         self.sample_rate = SOURCE_RATE if sample_rate is None else int(sample_rate)
         self._rs = None                            # Engine.resampler (device chunks), one stream per sample index
         self._rs_host = {}                         # sample index -> resample.HostResampler (CPU chunks)
@@ -86,6 +111,10 @@ class AudioStreamer:
             eng = engine if engine is not None else pcm16
             if eng is not None:                    # without one, only CPU chunks are served (resample.HostResampler); put() refuses others
                 self._rs = eng.resampler(SOURCE_RATE, self.sample_rate, batch_size)
+        if self._speeds is not None:
+            eng = engine if engine is not None else pcm16
+            if eng is not None:
+                self._tp = eng.tempo(batch_size)
         self.stop_signal = stop_signal
         self.timeout = timeout
         self.audio_queues = [self._make_queue() for _ in range(batch_size)]
@@ -119,7 +148,7 @@ class AudioStreamer:
         if not audio_chunks.is_cuda:
             for row, idx in live:
                 chunk = audio_chunks[row].detach().clone()
-                if self.sample_rate != SOURCE_RATE:
+                if self.sample_rate != SOURCE_RATE or self._speeds is not None:
                     chunk = self._host_chunk(idx, chunk)
                     if chunk is None:
                         continue
@@ -128,6 +157,12 @@ class AudioStreamer:
         if self.sample_rate != SOURCE_RATE and self._rs is None:
             raise ValueError(f"AudioStreamer(sample_rate={self.sample_rate}): device chunks are resampled on the device and need an engine "
                              "(pcm16=engine for 16-bit chunks, engine=engine for float chunks)")
+        if self._speeds is not None:
+            if self._tp is None:
+                raise ValueError("AudioStreamer(speed=...): device chunks are stretched on the device and need an engine "
+                                 "(pcm16=engine for 16-bit chunks, engine=engine for float chunks)")
+            self._put_tempo(audio_chunks, live)
+            return
         slot = self._free.get()                                    # back-pressure only if the consumer is > ring_slots behind
         with self._lock:                                           # the drain thread hands the ring back to the pool under this lock
             if self._closed:
@@ -139,17 +174,30 @@ class AudioStreamer:
                 self._put_slot(audio_chunks, live, slot)
 
     def _host_chunk(self, idx, chunk):
-        """a CPU chunk of sample idx (None: its flush) at the streamer's rate, None where it completes no output sample"""
-        from .resample import HostResampler
-        h = self._rs_host.get(idx)
-        if h is None:
-            if chunk is None:
-                return None
-            h = self._rs_host[idx] = HostResampler(SOURCE_RATE, self.sample_rate)
-        if chunk is not None:
+        """a CPU chunk of sample idx (None: its flush) at the streamer's speed and rate, None where it completes no output sample"""
+        flush = chunk is None
+        y = None
+        if not flush:
             self._lead = tuple(chunk.shape[:-1])
-        y = h.flush() if chunk is None else h.push(chunk.reshape(-1))
-        return y.reshape(self._lead + (y.shape[0],)) if y.shape[0] else None
+            y = chunk.reshape(-1)
+        if self._speeds is not None:
+            from .tempo import HostTempo
+            t = self._tp_host.get(idx)
+            if t is None and not flush:
+                t = self._tp_host[idx] = HostTempo(self._speeds[idx])
+            if t is not None:
+                y = t.flush() if flush else t.push(y)
+        if self.sample_rate != SOURCE_RATE:
+            from .resample import HostResampler
+            h = self._rs_host.get(idx)
+            if h is None:
+                if y is None:
+                    return None
+                h = self._rs_host[idx] = HostResampler(SOURCE_RATE, self.sample_rate)
+            y = h.push(y if y is not None else torch.zeros(0), flush=flush)
+        if y is None or not y.shape[0]:
+            return None
+        return y.reshape(self._lead + (y.shape[0],))
 
     def _put_resampled(self, audio_chunks, live, slot, flush=False):
         """One Resampler.push for the live rows (audio_chunks None: their flush), then the ring copy of _put_slot; the work item carries
@@ -171,12 +219,14 @@ class AudioStreamer:
             flat, samples = None, 0
         prod = self._rs_stream if self._rs_stream is not None else torch.cuda.current_stream(dev)
         cap, dt = rs.max_out(samples), torch.int16 if pcm else torch.float32
-        pd = self._pcm_dev[slot]
-        if pd is None or pd.shape[0] < n or pd.shape[1] < cap or pd.dtype != dt:
-            pd = torch.empty((max(n, self.batch_size), cap), dtype=dt, device=dev)
-            self._pcm_dev[slot] = pd
+        pd = self._staging(slot, n, cap, dt, dev)
         with torch.cuda.stream(prod):
             _, cnts = rs.push(flat, ids, flush=flush, out=pd, pcm16=pcm, n_in=None if flat is not None else [0] * n, stream=prod)
+        self._ring_copy(pd, ids, cnts, slot, prod)
+
+    def _ring_copy(self, pd, ids, cnts, slot, prod):
+        """rows [0, len(ids)) of the device staging pd, cnts[i] samples each, to the slot's pinned buffer behind the producing stream"""
+        n, dt, dev = len(ids), pd.dtype, pd.device
         buf = self._ring[slot]
         if buf is None or buf.dim() != 2 or buf.shape[1] != pd.shape[1] or buf.shape[0] < n or buf.dtype != dt:
             if buf is not None:
@@ -194,6 +244,93 @@ class AudioStreamer:
         ev = torch.cuda.Event()
         ev.record(self._copy_stream)
         self._work.put(("rslot", [(i, idx, cnts[i]) for i, idx in enumerate(ids)], slot, ev, self._lead))
+
+    def _with_slot(self, fn):
+        """fn(slot) with a free ring slot, under the lock the drain thread hands the ring back under; False once the streamer is closed"""
+        slot = self._free.get()
+        with self._lock:
+            if self._closed:
+                self._free.put(slot)
+                return False
+            fn(slot)
+            return True
+
+    def _staging(self, slot, n, cap, dt, dev):
+        pd = self._pcm_dev[slot]
+        if pd is None or pd.shape[0] < n or pd.shape[1] < cap or pd.dtype != dt:
+            pd = torch.empty((max(n, self.batch_size), cap), dtype=dt, device=dev)
+            self._pcm_dev[slot] = pd
+        return pd
+
+    def _rs_width(self, ids, rem, flush):
+        """how many of the rows' remaining stretched samples (rem[i] for stream ids[i]) the next Resampler.push takes: all of them where
+        that fits the kernel -- at most 8192 outputs per row, the chunk within its LDS beside the filter table (vv_resample_rows
+        refuses more) -- else a width that fits whatever the streams' state"""
+        rs = self._rs
+        lds_max = (65536 - 64) // 4 - rs.L * (rs.T + 1) - rs.T - rs.T // 2
+        if max(rem) <= lds_max and all(rs.counts(i, r, flush) <= 8192 for i, r in zip(ids, rem)):
+            return max(rem)
+        return max(1, min(8191 * rs.M // rs.L - rs.T // 2 - 1, lds_max))
+
+    def _put_tempo(self, audio_chunks, live, flush=False):
+        """Tempo.push for the live rows (audio_chunks None: their flush), then what follows today on the stretched rows with their
+        per-row counts: the resampler push, else nothing more (the tempo launch converts to 16 bits itself); one ring slot and one work
+        item per launch that delivers.  A chunk longer than one launch takes goes in pieces."""
+        tp, rs, pcm = self._tp, self._rs, self._pcm_engine is not None
+        dev = tp.engine.device
+        ids = [idx for _, idx in live]
+        n = len(live)
+        speeds = [self._speeds[idx] for idx in ids]
+        if audio_chunks is not None:
+            src = audio_chunks.detach()
+            self._lead = tuple(src.shape[1:-1])
+            flat = src.reshape(src.shape[0], -1).to(torch.float32)
+            if [row for row, _ in live] != list(range(n)):
+                flat = flat[[row for row, _ in live]]
+            flat = flat.contiguous()
+            samples = flat.shape[1]
+            self._rs_stream = torch.cuda.current_stream(dev)
+        else:
+            flat, samples = None, 0
+        prod = self._rs_stream if self._rs_stream is not None else torch.cuda.current_stream(dev)
+        dt = torch.int16 if pcm else torch.float32
+        for c0 in range(0, max(samples, 1), tp.max_in):
+            w = min(tp.max_in, samples - c0)
+            piece = flat[:, c0:c0 + w].contiguous() if flat is not None else None      # the whole chunk but for one longer than a launch takes
+            last = c0 + w >= samples
+            tcap = tp.max_out(w)
+            if rs is None:
+                def stage(slot):
+                    pd = self._staging(slot, n, tcap, dt, dev)
+                    with torch.cuda.stream(prod):
+                        _, cnts = tp.push(piece, ids, speeds, flush=flush and last, out=pd, n_in=[w] * n, stream=prod, pcm16=pcm)
+                    self._ring_copy(pd, ids, cnts, slot, prod)
+                if not self._with_slot(stage):
+                    return
+                continue
+            with torch.cuda.stream(prod):
+                td = torch.empty((n, tcap), dtype=torch.float32, device=dev)       # this stream's: the resampler push below reads it there
+                _, ct = tp.push(piece, ids, speeds, flush=flush and last, out=td, n_in=[w] * n, stream=prod)
+            if not any(ct) and not (flush and last):
+                continue                                 # no block completed: nothing for the resampler, nothing to deliver
+            at = 0
+            while True:                                # one resampler push, but for a stretched chunk longer than it takes
+                rem = [max(c - at, 0) for c in ct]
+                wr = self._rs_width(ids, rem, flush and last)
+                final = wr >= max(rem)
+                nin = [min(r, wr) for r in rem]
+
+                def stage(slot):
+                    pd = self._staging(slot, n, rs.max_out(wr), dt, dev)
+                    with torch.cuda.stream(prod):
+                        _, cnts = rs.push(td if at == 0 else td[:, at:].contiguous(), ids, flush=flush and last and final, out=pd, pcm16=pcm,
+                                          n_in=nin, stream=prod)
+                    self._ring_copy(pd, ids, cnts, slot, prod)
+                if not self._with_slot(stage):
+                    return
+                if final:
+                    break
+                at += wr
 
     def _put_slot(self, audio_chunks, live, slot):
         src = audio_chunks.detach()
@@ -237,7 +374,7 @@ class AudioStreamer:
         else:
             idxs = [int(i.item()) if torch.is_tensor(i) else int(i) for i in sample_indices]
         idxs = [idx for idx in dict.fromkeys(idxs) if idx < self.batch_size and not self.finished_flags[idx]]
-        if self.sample_rate != SOURCE_RATE and idxs and not self._closed:
+        if (self.sample_rate != SOURCE_RATE or self._speeds is not None) and idxs and not self._closed:
             self._flush_tails(idxs)
         for idx in idxs:
             self.finished_flags[idx] = True
@@ -249,6 +386,11 @@ class AudioStreamer:
             tail = self._host_chunk(idx, None)
             if tail is not None:
                 self._work.put(("chunk", idx, tail, None, None))
+        if self._tp is not None:                 # the tempo tail first, then (in the same pass) the resampler's
+            live = [(row, idx) for row, idx in enumerate(i for i in idxs if self._tp.total[i] > 0)]
+            if live:
+                self._put_tempo(None, live, flush=True)
+            return
         live = [(row, idx) for row, idx in enumerate(i for i in idxs if self._rs is not None and self._rs.total[i] > 0)]
         for i0 in range(0, len(live), 16):
             slot = self._free.get()
@@ -323,6 +465,8 @@ class AudioStreamer:
             self._pcm_dev = [None] * len(self._pcm_dev)  # release the device staging
             if self._rs is not None:
                 self._rs.close()                         # the engine's resampler configuration is free for the next streamer
+            if self._tp is not None:
+                self._tp.close()                         # ... and its tempo configuration
 
     # ---- consumer side ----
     def __iter__(self):
@@ -387,9 +531,10 @@ class AsyncAudioStreamer(AudioStreamer):
         async for chunk in streamer.get_stream(0): ...      async for batch in streamer: ..."""
 
     def __init__(self, batch_size: int, stop_signal=None, timeout: Optional[float] = None, ring_slots: int = 8, pcm16=None,
-                 sample_rate: Optional[int] = None, engine=None):
+                 sample_rate: Optional[int] = None, engine=None, speed=None):
         self.loop = asyncio.get_running_loop()
-        super().__init__(batch_size, stop_signal, timeout, ring_slots=ring_slots, pcm16=pcm16, sample_rate=sample_rate, engine=engine)
+        super().__init__(batch_size, stop_signal, timeout, ring_slots=ring_slots, pcm16=pcm16, sample_rate=sample_rate, engine=engine,
+                         speed=speed)
 
     def _make_queue(self):
         return asyncio.Queue()
