@@ -292,6 +292,32 @@ def test_streamer_at_48k_int16_end_to_end(small):
     assert eng._rs_used == [None] * 4                                     # finished streamers gave their configurations back
 
 
+def test_streamer_flushes_seventeen_samples_at_once(small):
+    """AudioStreamer(17, engine=eng, sample_rate=16000), one put of [17, 1, 480] and end(): more rows than one launch takes, in the put
+    and in the flush.  Every sample's chunks concatenate to Engine.resample of its row bit for bit and each gets its stop signal"""
+    eng = small.eng
+    x = _noise(12, 17, 1, 480).to(eng.device)
+    st = AudioStreamer(17, engine=eng, sample_rate=16000, stop_signal="stop", timeout=20)
+    with torch.cuda.stream(eng.stream):
+        st.put(x, torch.arange(17))
+        st.end()
+        want = eng.resample(x[:, 0], 24000, 16000).cpu()
+    eng.sync()
+    counts = []
+    for idx in range(17):
+        items = [st.audio_queues[idx].get(timeout=20)]
+        while not (isinstance(items[-1], str) and items[-1] == "stop"):
+            items.append(st.audio_queues[idx].get(timeout=20))
+        f = items[:-1]                                                    # the stop signal came, behind the sample's chunks
+        counts.append(len(f))
+        assert all(c.dtype == torch.float32 and c.dim() == 2 and c.shape[0] == 1 and c.shape[1] > 0 for c in f)
+        assert torch.equal(torch.cat(f, dim=-1)[0], want[idx]) and want[idx].shape[0] == 320, idx
+    print(f"[17 samples, one put and the flush] chunks per sample: {counts}")
+    assert counts == [2] * 17
+    st._thread.join(timeout=20)
+    assert st.audio_queues[0].empty() and eng._rs_used == [None] * 4
+
+
 def test_requests_through_generate_continuous_at_16k(small):
     """two requests through ONE slot of generate_continuous with a 16 kHz float streamer (stream id = request index, whatever slot
     the request decodes in): per request, the streamed audio has the length of model.resample_audio(speech_outputs[0], 16000) and

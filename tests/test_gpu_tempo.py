@@ -357,6 +357,69 @@ def test_streamer_put_that_completes_no_block_in_front_of_the_resampler(small):
     st._thread.join(timeout=20)
 
 
+def test_streamer_stretched_chunk_longer_than_one_resampler_push(small):
+    """speed 0.5 in front of 48 kHz: a put of 3200 samples stretches row 0 to about 6400 and those to about 12800 at 48 kHz, beyond the
+    8192 outputs of one resampler push, so the stretched chunk goes to the resampler in pieces and arrives as several.  Per sample the
+    float chunks concatenate to Engine.resample(Engine.time_stretch(whole)) bit for bit and the int16 chunks are the pcm16 rule of the
+    float ones chunk by chunk; both streamers give their configurations back"""
+    eng = small.eng
+    speeds = [0.5, 1.25]
+    x = torch.from_numpy(np.stack([3.0 * _voice(90, 6400), _voice(91, 6400)])[:, None, :]).to(eng.device)
+    sts = [AudioStreamer(2, pcm16=eng, sample_rate=48000, speed=speeds, timeout=20),
+           AudioStreamer(2, engine=eng, sample_rate=48000, speed=speeds, timeout=20)]
+    with torch.cuda.stream(eng.stream):
+        for st in sts:
+            st.put(x[:, :, :3200], torch.tensor([0, 1]))
+            st.put(x[:, :, 3200:], torch.tensor([0, 1]))
+            st.end()
+        want = [eng.resample(eng.time_stretch(x[i, 0], speeds[i]), 24000, 48000) for i in range(2)]
+    eng.sync()
+    for idx in range(2):
+        q, f = _collect(sts[0], idx), _collect(sts[1], idx)
+        print(f"[stretched chunk beyond one resampler push] sample {idx}: {len(q)} int16 chunks, {len(f)} float chunks of {[c.shape[-1] for c in f]}")
+        assert all(c.dtype == torch.int16 for c in q) and all(c.dtype == torch.float32 for c in f)
+        assert [c.shape for c in q] == [c.shape for c in f] and all(c.dim() == 2 and c.shape[0] == 1 and c.shape[1] > 0 for c in f)
+        assert max(c.shape[-1] for c in f) <= 8192
+        assert torch.equal(torch.cat(f, dim=-1)[0], want[idx].cpu())
+        for got, rule in zip(q, _pcm16_rule([c[0] for c in f])):
+            assert torch.equal(got[0], rule)
+        assert len(q) == len(f) == (5, 3)[idx]
+    for st in sts:
+        st._thread.join(timeout=20)
+    assert eng._rs_used == [None] * 4 and eng._tp_used == [None] * 4
+
+
+@pytest.mark.parametrize("mode", ["16k", "speed", "speed_16k"])
+def test_streamer_live_rows_that_are_no_prefix(small, mode):
+    """a batch of 3 whose sample 1 ends after the first put while the second put still passes all three rows: the live rows 0 and 2 are
+    gathered out of the chunk batch.  Samples 0 and 2 equal the definitions over their 2400 samples, sample 1 over its 1200"""
+    eng = small.eng
+    rate, speed = (16000 if "16k" in mode else None), (0.8 if "speed" in mode else None)
+    x = torch.from_numpy(np.stack([_voice(92 + i, 2400) for i in range(3)])[:, None, :]).to(eng.device)
+    st = AudioStreamer(3, engine=eng, sample_rate=rate, speed=speed, timeout=20)
+    with torch.cuda.stream(eng.stream):
+        st.put(x[:, :, :1200], torch.tensor([0, 1, 2]))
+        st.end([1])
+        st.put(x[:, :, 1200:], torch.tensor([0, 1, 2]))
+        st.end()
+        want = []
+        for idx, n in ((0, 2400), (1, 1200), (2, 2400)):
+            y = x[idx, 0, :n]
+            y = eng.time_stretch(y, speed) if speed is not None else y
+            want.append(eng.resample(y, 24000, rate) if rate is not None else y)
+    eng.sync()
+    counts = []
+    for idx in range(3):
+        f = _collect(st, idx)
+        counts.append(len(f))
+        assert all(c.dtype == torch.float32 and c.dim() == 2 and c.shape[0] == 1 and c.shape[1] > 0 for c in f)
+        assert torch.equal(torch.cat(f, dim=-1)[0], want[idx].cpu()), (mode, idx)
+    print(f"[live rows 0 and 2 of 3, {mode}] chunks per sample: {counts}")
+    assert counts == {"16k": [3, 2, 3], "speed": [3, 2, 3], "speed_16k": [3, 2, 3]}[mode]
+    st._thread.join(timeout=20)
+    assert eng.__dict__.get("_rs_used", [None] * 4) == [None] * 4 and eng.__dict__.get("_tp_used", [None] * 4) == [None] * 4
+
+
 @pytest.mark.parametrize("mode", ["plain", "pcm16", "48k"])
 def test_streamer_without_a_speed_is_unchanged(small, mode):
     """a streamer built without `speed`, and one built with speed 1, deliver what a second streamer without the keyword delivers on the

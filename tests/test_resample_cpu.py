@@ -122,6 +122,35 @@ def test_host_class_is_chunk_invariant(src, dst):
         assert torch.equal(h.push(xs, flush=True), want)
 
 
+@pytest.mark.parametrize("src,dst", TONE_PAIRS, ids=_ids(TONE_PAIRS))
+def test_push_width_fits_the_kernel(src, dst):
+    """Resampler.take (resample.push_width): whatever the streams have taken and still hold, the width w it returns keeps every row of
+    the next push within the kernel's 8192 outputs and the chunk within its LDS beside the filter table (the two refusals of
+    vv_resample_rows, written out here as the C side has them), and it is all that remains wherever that fits"""
+    from vibevoice_amd.engine import Resampler
+    L, M, T, _ = R.design(src, dst)
+    rs = Resampler.__new__(Resampler)                    # the host arithmetic alone: no engine, no configuration
+    rs.L, rs.M, rs.T = L, M, T
+
+    def fits(totals, widths, flush):
+        return (all(R.counts(L, M, T, t, w, flush)[1] <= 8192 for t, w in zip(totals, widths))
+                and 4 * (L * (T + 1) + T + max(widths) + T // 2) <= 65536 - 64)
+    whole = 0
+    for totals in ([0, 0, 0], [3200, 0, 4097], [2999, 3001, 3000]):
+        rs.total = totals
+        for most in (0, 1, T // 2, 3200, 4000, 4096, 4097, 6400, 8192, 12801, 16000, 20000, 70000):
+            for flush in (False, True):
+                rem = [most, most // 2, max(most - 1, 0)]
+                w = rs.take([0, 1, 2], rem, flush)
+                assert w == R.push_width(L, M, T, totals, rem, flush)
+                assert 0 <= w <= most and (w > 0 or most == 0), (totals, most, flush, w)
+                assert fits(totals, [min(r, w) for r in rem], flush), (totals, most, flush, w)
+                if fits(totals, rem, flush):
+                    assert w == most
+                    whole += 1
+    assert 0 < whole < 3 * 13 * 2                         # both answers occur for every pair
+
+
 def _drain(st, idx):
     out = []
     while True:

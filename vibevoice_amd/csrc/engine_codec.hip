@@ -498,6 +498,71 @@ extern "C" int vv_codec_reset(vv_ctx* ctx, void* stream, int slot) {
     return 0;
 }
 
+// ------------------------------------------------------------------ streaming row stages: what the resampler and the tempo change share
+// A stage keeps chunk-continuous streams (vv_ctx::RowStage) and takes up to 16 rows per push, one stream each.  `fn` is the entry
+// point's name: every refusal carries it.  `s` is null where the configuration is not set.  A third stage calls the same three.
+
+// streams back to their first sample: launch(ids, n) zeroes the device state of up to 16 of them, clear(id) the stage's own host state
+template <class Launch, class Clear>
+static int stage_reset(vv_ctx* ctx, const char* fn, vv_ctx::RowStage* s, int cfg, int n, const int* stream_ids_host, Launch launch, Clear clear) {
+    if (!s) return fail(ctx, "%s: configuration %d is not set", fn, cfg);
+    std::vector<int> ids;
+    if (!stream_ids_host) { for (int i = 0; i < s->n_streams; ++i) ids.push_back(i); }
+    else {
+        if (n < 1) return fail(ctx, "%s: n = %d must be >= 1", fn, n);
+        ids.assign(stream_ids_host, stream_ids_host + n);
+    }
+    for (int id : ids)
+        if (id < 0 || id >= s->n_streams) return fail(ctx, "%s: stream id %d out of range [0,%d)", fn, id, s->n_streams);
+    for (size_t i0 = 0; i0 < ids.size(); i0 += 16)
+        VVCHK(launch(ids.data() + i0, (int)std::min<size_t>(16, ids.size() - i0)));
+    for (int id : ids) { s->total[id] = 0; s->flushed[id] = 0; clear(id); }
+    return 0;
+}
+
+// The refusals of a push that do not depend on the stage, in the order the entry points make them: head() once, then per row stream(),
+// input() and open(), the stage's own checks between them where it has some.  A refusal has recorded its text and returns -1.
+struct RowCheck {
+    vv_ctx* ctx; const char* fn; const vv_ctx::RowStage* s; const float* audio_dev; int ld_in;
+    int head(int cfg, int n, const void* rows_host, const void* out_dev, const int* n_out_host, int out_fmt) const {
+        if (!s) return fail(ctx, "%s: configuration %d is not set", fn, cfg);
+        if (n < 1 || n > 16) return fail(ctx, "%s: n = %d must be in [1,16]", fn, n);
+        if (!rows_host || !out_dev || !n_out_host) return fail(ctx, "%s: null rows / out / n_out pointer", fn);
+        if (out_fmt != 0 && out_fmt != 1) return fail(ctx, "%s: out_fmt = %d must be 0 (fp32) or 1 (int16)", fn, out_fmt);
+        return 0;
+    }
+    template <class Row>
+    int stream(const Row* rows, int i) const {
+        const Row& q = rows[i];
+        if (q.stream < 0 || q.stream >= s->n_streams) return fail(ctx, "%s: row %d: stream id %d out of range [0,%d)", fn, i, q.stream, s->n_streams);
+        for (int j = 0; j < i; ++j)
+            if (rows[j].stream == q.stream) return fail(ctx, "%s: stream %d is named twice (rows %d and %d)", fn, q.stream, j, i);
+        if (q.n_in < 0) return fail(ctx, "%s: row %d: n_in = %d must be >= 0", fn, i, q.n_in);
+        return 0;
+    }
+    int input(int i, int n_in) const {
+        if (n_in > ld_in || (n_in > 0 && !audio_dev)) return fail(ctx, "%s: row %d: n_in = %d exceeds the input rows (ld_in = %d)", fn, i, n_in, ld_in);
+        return 0;
+    }
+    int open(int stream) const {
+        if (s->flushed[stream]) return fail(ctx, "%s: stream %d has been flushed; reset it before its next push", fn, stream);
+        return 0;
+    }
+};
+
+// the end of a push: the unused rows of the kernel's argument repeat row 0, launch() runs it, and only then do the streams move on
+template <class Row, class KRows, class Launch>
+static int stage_launch(vv_ctx* ctx, vv_ctx::RowStage& s, const Row* rows_host, int n, KRows& kr, int* n_out_host, Launch launch) {
+    for (int i = n; i < 16; ++i) kr.r[i] = kr.r[0];
+    VVCHK(launch());
+    for (int i = 0; i < n; ++i) {
+        s.total[rows_host[i].stream] += rows_host[i].n_in;
+        if (rows_host[i].flush) s.flushed[rows_host[i].stream] = 1;
+        n_out_host[i] = kr.r[i].n_out;
+    }
+    return 0;
+}
+
 // ------------------------------------------------------------------ audio at another sample rate (kernels: resample.hip)
 // Outputs a stream has emitted once `total` input samples have arrived: every m whose newest input sample, index
 // (m * M + D) / L with D = (L * T - 2) / 2, is below total.  vibevoice_amd/resample.py (emitted) is the same arithmetic.
@@ -535,42 +600,26 @@ extern "C" int vv_resampler_set(vv_ctx* ctx, int rs, int L, int M, int T, const 
 
 extern "C" int vv_resampler_reset(vv_ctx* ctx, void* stream, int rs, int n, const int* stream_ids_host) {
     VV_SHARED;
-    hipStream_t st = (hipStream_t)stream;
-    if (rs < 0 || rs >= vv_ctx::N_RESAMPLERS || !ctx->rs[rs].coef) return fail(ctx, "vv_resampler_reset: configuration %d is not set", rs);
-    vv_ctx::Resampler& r = ctx->rs[rs];
-    std::vector<int> ids;
-    if (!stream_ids_host) { for (int i = 0; i < r.n_streams; ++i) ids.push_back(i); }
-    else {
-        if (n < 1) return fail(ctx, "vv_resampler_reset: n = %d must be >= 1", n);
-        ids.assign(stream_ids_host, stream_ids_host + n);
-    }
-    for (int id : ids)
-        if (id < 0 || id >= r.n_streams) return fail(ctx, "vv_resampler_reset: stream id %d out of range [0,%d)", id, r.n_streams);
-    for (size_t i0 = 0; i0 < ids.size(); i0 += 16)
-        VVCHK(vv_resample_reset_launch(r.hist, r.T, r.n_streams, ids.data() + i0, (int)std::min<size_t>(16, ids.size() - i0), st));
-    for (int id : ids) { r.total[id] = 0; r.flushed[id] = 0; }
-    return 0;
+    vv_ctx::Resampler* r = rs >= 0 && rs < vv_ctx::N_RESAMPLERS && ctx->rs[rs].coef ? &ctx->rs[rs] : nullptr;
+    return stage_reset(ctx, "vv_resampler_reset", r, rs, n, stream_ids_host,
+                       [&](const int* ids, int k) { return vv_resample_reset_launch(r->hist, r->T, r->n_streams, ids, k, (hipStream_t)stream); }, [](int) {});
 }
 
 extern "C" int vv_resample_rows(vv_ctx* ctx, void* stream, int rs, int n, const vv_resample_row* rows_host, const float* audio_dev, int ld_in,
                                 void* out_dev, int ld_out, int out_fmt, int* n_out_host) {
     VV_SHARED;
-    if (rs < 0 || rs >= vv_ctx::N_RESAMPLERS || !ctx->rs[rs].coef) return fail(ctx, "vv_resample_rows: configuration %d is not set", rs);
-    vv_ctx::Resampler& r = ctx->rs[rs];
-    if (n < 1 || n > 16) return fail(ctx, "vv_resample_rows: n = %d must be in [1,16]", n);
-    if (!rows_host || !out_dev || !n_out_host) return fail(ctx, "vv_resample_rows: null rows / out / n_out pointer");
-    if (out_fmt != 0 && out_fmt != 1) return fail(ctx, "vv_resample_rows: out_fmt = %d must be 0 (fp32) or 1 (int16)", out_fmt);
+    vv_ctx::Resampler* rp = rs >= 0 && rs < vv_ctx::N_RESAMPLERS && ctx->rs[rs].coef ? &ctx->rs[rs] : nullptr;
+    const RowCheck ck{ctx, "vv_resample_rows", rp, audio_dev, ld_in};
+    VVTRY(ck.head(rs, n, rows_host, out_dev, n_out_host, out_fmt));
+    vv_ctx::Resampler& r = *rp;
     VVRsRows kr;
     memset(&kr, 0, sizeof(kr));
     int max_in = 0;
     for (int i = 0; i < n; ++i) {
         const vv_resample_row& q = rows_host[i];
-        if (q.stream < 0 || q.stream >= r.n_streams) return fail(ctx, "vv_resample_rows: row %d: stream id %d out of range [0,%d)", i, q.stream, r.n_streams);
-        for (int j = 0; j < i; ++j)
-            if (rows_host[j].stream == q.stream) return fail(ctx, "vv_resample_rows: stream %d is named twice (rows %d and %d)", q.stream, j, i);
-        if (q.n_in < 0) return fail(ctx, "vv_resample_rows: row %d: n_in = %d must be >= 0", i, q.n_in);
-        if (q.n_in > ld_in || (q.n_in > 0 && !audio_dev)) return fail(ctx, "vv_resample_rows: row %d: n_in = %d exceeds the input rows (ld_in = %d)", i, q.n_in, ld_in);
-        if (r.flushed[q.stream]) return fail(ctx, "vv_resample_rows: stream %d has been flushed; reset it before its next push", q.stream);
+        VVTRY(ck.stream(rows_host, i));
+        VVTRY(ck.input(i, q.n_in));
+        VVTRY(ck.open(q.stream));
         const int64_t before = r.total[q.stream], after = before + q.n_in;
         const int64_t m0 = rs_emitted(before, r.L, r.M, r.T);
         const int64_t m1 = q.flush ? (after * r.L + r.M - 1) / r.M : rs_emitted(after, r.L, r.M, r.T);
@@ -585,14 +634,8 @@ extern "C" int vv_resample_rows(vv_ctx* ctx, void* stream, int rs, int n, const 
     if (vv_resample_lds_bytes(r.L, r.T, max_in) > 65536 - 64)
         return fail(ctx, "vv_resample_rows: a chunk of %d samples does not fit the kernel's LDS beside the %d x %d table; push at most %d at a time",
                     max_in, r.L, r.T, (65536 - 64) / 4 - r.L * (r.T + 1) - r.T - r.T / 2);
-    for (int i = n; i < 16; ++i) kr.r[i] = kr.r[0];
-    VVCHK(vv_resample_rows_launch(&kr, n, r.L, r.M, r.T, r.coef, r.hist, r.n_streams, audio_dev, ld_in, out_dev, ld_out, out_fmt, (hipStream_t)stream));
-    for (int i = 0; i < n; ++i) {
-        r.total[rows_host[i].stream] += rows_host[i].n_in;
-        if (rows_host[i].flush) r.flushed[rows_host[i].stream] = 1;
-        n_out_host[i] = kr.r[i].n_out;
-    }
-    return 0;
+    return stage_launch(ctx, r, rows_host, n, kr, n_out_host, [&] {
+        return vv_resample_rows_launch(&kr, n, r.L, r.M, r.T, r.coef, r.hist, r.n_streams, audio_dev, ld_in, out_dev, ld_out, out_fmt, (hipStream_t)stream); });
 }
 
 extern "C" int vv_resample_once(vv_ctx* ctx, void* stream, int L, int M, int T, const float* coef_dev, int n, int n_in, const float* audio_dev,
@@ -645,49 +688,34 @@ extern "C" int vv_tempo_set(vv_ctx* ctx, int tp, const float* window_host, int n
 
 extern "C" int vv_tempo_reset(vv_ctx* ctx, void* stream, int tp, int n, const int* stream_ids_host) {
     VV_SHARED;
-    hipStream_t st = (hipStream_t)stream;
-    if (tp < 0 || tp >= vv_ctx::N_TEMPOS || !ctx->tp[tp].hist) return fail(ctx, "vv_tempo_reset: configuration %d is not set", tp);
-    vv_ctx::Tempo& t = ctx->tp[tp];
-    std::vector<int> ids;
-    if (!stream_ids_host) { for (int i = 0; i < t.n_streams; ++i) ids.push_back(i); }
-    else {
-        if (n < 1) return fail(ctx, "vv_tempo_reset: n = %d must be >= 1", n);
-        ids.assign(stream_ids_host, stream_ids_host + n);
-    }
-    for (int id : ids)
-        if (id < 0 || id >= t.n_streams) return fail(ctx, "vv_tempo_reset: stream id %d out of range [0,%d)", id, t.n_streams);
-    for (size_t i0 = 0; i0 < ids.size(); i0 += 16)
-        VVCHK(vv_tempo_reset_launch(t.hist, t.dstate, t.n_streams, ids.data() + i0, (int)std::min<size_t>(16, ids.size() - i0), st));
-    for (int id : ids) { t.total[id] = 0; t.P[id] = 0; t.Q[id] = 0; t.flushed[id] = 0; }
-    return 0;
+    vv_ctx::Tempo* t = tp >= 0 && tp < vv_ctx::N_TEMPOS && ctx->tp[tp].hist ? &ctx->tp[tp] : nullptr;
+    return stage_reset(ctx, "vv_tempo_reset", t, tp, n, stream_ids_host,
+                       [&](const int* ids, int k) { return vv_tempo_reset_launch(t->hist, t->dstate, t->n_streams, ids, k, (hipStream_t)stream); },
+                       [&](int id) { t->P[id] = 0; t->Q[id] = 0; });
 }
 
 extern "C" int vv_tempo_rows(vv_ctx* ctx, void* stream, int tp, int n, const vv_tempo_row* rows_host, const float* audio_dev, int ld_in,
                              void* out_dev, int ld_out, int out_fmt, int* n_out_host, int* offsets_dev, int ld_off) {
     VV_SHARED;
-    if (tp < 0 || tp >= vv_ctx::N_TEMPOS || !ctx->tp[tp].hist) return fail(ctx, "vv_tempo_rows: configuration %d is not set", tp);
-    vv_ctx::Tempo& t = ctx->tp[tp];
-    if (n < 1 || n > 16) return fail(ctx, "vv_tempo_rows: n = %d must be in [1,16]", n);
-    if (!rows_host || !out_dev || !n_out_host) return fail(ctx, "vv_tempo_rows: null rows / out / n_out pointer");
-    if (out_fmt != 0 && out_fmt != 1) return fail(ctx, "vv_tempo_rows: out_fmt = %d must be 0 (fp32) or 1 (int16)", out_fmt);
+    vv_ctx::Tempo* t_ = tp >= 0 && tp < vv_ctx::N_TEMPOS && ctx->tp[tp].hist ? &ctx->tp[tp] : nullptr;
+    const RowCheck ck{ctx, "vv_tempo_rows", t_, audio_dev, ld_in};
+    VVTRY(ck.head(tp, n, rows_host, out_dev, n_out_host, out_fmt));
+    vv_ctx::Tempo& t = *t_;
     VVTpRows kr;
     memset(&kr, 0, sizeof(kr));
     for (int i = 0; i < n; ++i) {
         const vv_tempo_row& q = rows_host[i];
-        if (q.stream < 0 || q.stream >= t.n_streams) return fail(ctx, "vv_tempo_rows: row %d: stream id %d out of range [0,%d)", i, q.stream, t.n_streams);
-        for (int j = 0; j < i; ++j)
-            if (rows_host[j].stream == q.stream) return fail(ctx, "vv_tempo_rows: stream %d is named twice (rows %d and %d)", q.stream, j, i);
-        if (q.n_in < 0) return fail(ctx, "vv_tempo_rows: row %d: n_in = %d must be >= 0", i, q.n_in);
+        VVTRY(ck.stream(rows_host, i));
         if (q.n_in > VV_TP_MAX_IN) {
             fail(ctx, "vv_tempo_rows: row %d brings %d samples, one push takes at most %d per row; split it", i, q.n_in, VV_TP_MAX_IN);
             return VV_TEMPO_OVER_CAPACITY;
         }
-        if (q.n_in > ld_in || (q.n_in > 0 && !audio_dev)) return fail(ctx, "vv_tempo_rows: row %d: n_in = %d exceeds the input rows (ld_in = %d)", i, q.n_in, ld_in);
+        VVTRY(ck.input(i, q.n_in));
         if (!tp_speed_ok(q.P, q.Q)) return fail(ctx, "vv_tempo_rows: row %d: speed %d / %d must lie in [1/2, 2] with a denominator of at most 100", i, q.P, q.Q);
         if (t.P[q.stream] && (t.P[q.stream] != q.P || t.Q[q.stream] != q.Q))
             return fail(ctx, "vv_tempo_rows: stream %d runs at speed %d / %d since its first push; reset it before it changes to %d / %d", q.stream,
                         t.P[q.stream], t.Q[q.stream], q.P, q.Q);
-        if (t.flushed[q.stream]) return fail(ctx, "vv_tempo_rows: stream %d has been flushed; reset it before its next push", q.stream);
+        VVTRY(ck.open(q.stream));
         const int64_t before = t.total[q.stream], after = before + q.n_in;
         const int64_t k0 = tp_emitted(before, q.P, q.Q), total = (after * q.Q + q.P - 1) / q.P;
         const int64_t k1 = q.flush ? (total + VV_TP_HS - 1) / VV_TP_HS : tp_emitted(after, q.P, q.Q);
@@ -701,15 +729,10 @@ extern "C" int vv_tempo_rows(vv_ctx* ctx, void* stream, int tp, int n, const vv_
         kr.r[i].k0 = k0; kr.r[i].base = before - VV_TP_HIST; kr.r[i].stream = q.stream; kr.r[i].n_in = q.n_in;
         kr.r[i].nblk = (int)(k1 - k0); kr.r[i].n_out = (int)n_out; kr.r[i].P = q.P; kr.r[i].Q = q.Q;
     }
-    for (int i = n; i < 16; ++i) kr.r[i] = kr.r[0];
-    VVCHK(vv_tempo_rows_launch(&kr, n, t.window, t.hist, t.dstate, t.n_streams, audio_dev, ld_in, out_dev, ld_out, out_fmt, offsets_dev, ld_off,
-                               (hipStream_t)stream));
-    for (int i = 0; i < n; ++i) {
-        const int id = rows_host[i].stream;
-        t.total[id] += rows_host[i].n_in; t.P[id] = rows_host[i].P; t.Q[id] = rows_host[i].Q;
-        if (rows_host[i].flush) t.flushed[id] = 1;
-        n_out_host[i] = kr.r[i].n_out;
-    }
+    VVTRY(stage_launch(ctx, t, rows_host, n, kr, n_out_host, [&] {
+        return vv_tempo_rows_launch(&kr, n, t.window, t.hist, t.dstate, t.n_streams, audio_dev, ld_in, out_dev, ld_out, out_fmt, offsets_dev, ld_off,
+                                    (hipStream_t)stream); }));
+    for (int i = 0; i < n; ++i) { t.P[rows_host[i].stream] = rows_host[i].P; t.Q[rows_host[i].stream] = rows_host[i].Q; }
     return 0;
 }
 

@@ -175,18 +175,18 @@ struct vv_ctx {
     struct LoraBase { void* snap; size_t bytes; bool merged; };
     std::map<int, LoraBase> lora_base;
     int64_t lora_base_bytes = 0;      // vv_stat 7
-    // streaming resamplers (vv_resampler_set, engine_codec.hip; kernels: resample.hip): the filter, one history row of T samples per
-    // stream on the device, and on the host each stream's input total (what the next push's outputs are counted from) and whether it
-    // has been flushed.  This context's own, a shared child's included; the buffers are dalloc()s, released by vv_destroy.
-    struct Resampler { int L = 0, M = 0, T = 0, n_streams = 0; float* coef = nullptr; float* hist = nullptr;
-                       std::vector<int64_t> total; std::vector<char> flushed; };
+    // what a streaming row stage (engine_codec.hip) keeps of each of its streams on the host: its input total (what the next push's
+    // outputs are counted from) and whether it has been flushed
+    struct RowStage { int n_streams = 0; std::vector<int64_t> total; std::vector<char> flushed; };
+    // streaming resamplers (vv_resampler_set, engine_codec.hip; kernels: resample.hip): the filter and one history row of T samples per
+    // stream on the device.  This context's own, a shared child's included; the buffers are dalloc()s, released by vv_destroy.
+    struct Resampler : RowStage { int L = 0, M = 0, T = 0; float* coef = nullptr; float* hist = nullptr; };
     static constexpr int N_RESAMPLERS = 4;
     Resampler rs[N_RESAMPLERS];
     // streaming tempo changes (vv_tempo_set, engine_codec.hip; kernels: tempo.hip): the window table, per stream VV_TP_HIST history samples
-    // and its last block's offset on the device, and on the host its input total, its speed P / Q (fixed by its first push, 0 before) and
-    // whether it has been flushed.  Kept like the resamplers.
-    struct Tempo { int n_streams = 0; float* window = nullptr; float* hist = nullptr; int* dstate = nullptr;
-                   std::vector<int64_t> total; std::vector<int> P, Q; std::vector<char> flushed; };
+    // and its last block's offset on the device, and on the host its speed P / Q (fixed by its first push, 0 before).  Kept like the
+    // resamplers.
+    struct Tempo : RowStage { float* window = nullptr; float* hist = nullptr; int* dstate = nullptr; std::vector<int> P, Q; };
     static constexpr int N_TEMPOS = 4;
     Tempo tp[N_TEMPOS];
     int64_t launches = 0;

@@ -428,24 +428,15 @@ __global__ void vv_kv_zero_v_tail_kernel(__bf16* __restrict__ vc, const VVRow* _
     }
 }
 
-// 16-bit PCM of one chunk per workgroup, the arithmetic of the reference's convert_to_16_bit_wav (demo/gradio_demo.py:1058-1073):
-// peak = max|x|; if peak > 1: x /= peak (fp32, IEEE division); (x * 32767) truncated toward zero to int16.
+// 16-bit PCM of one chunk per workgroup: the rule of vv_device.h (vv_block_peak, vv_pcm16_of)
 __global__ __launch_bounds__(256) void vv_pcm16_kernel(const float* __restrict__ x, short* __restrict__ out, int samples) {
     const float* xr = x + (size_t)blockIdx.x * samples;
     short* orow = out + (size_t)blockIdx.x * samples;
     float mx = 0.f;
     for (int i = threadIdx.x; i < samples; i += 256) mx = fmaxf(mx, fabsf(xr[i]));
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
     __shared__ float wmx[4];
-    if ((threadIdx.x & 63) == 0) wmx[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    const float peak = fmaxf(fmaxf(wmx[0], wmx[1]), fmaxf(wmx[2], wmx[3]));
-    for (int i = threadIdx.x; i < samples; i += 256) {
-        float v = xr[i];
-        if (peak > 1.0f) v = __fdiv_rn(v, peak);
-        orow[i] = (short)(int)__fmul_rn(v, 32767.0f);
-    }
+    const float peak = vv_block_peak<4>(mx, wmx);
+    for (int i = threadIdx.x; i < samples; i += 256) orow[i] = vv_pcm16_of(xr[i], peak);
 }
 
 // adaLN input rows for every solver step at once: out[i*rows + r] = SiLU(cond_proj[r] + t_emb[i])  (float4 lanes)

@@ -7,8 +7,7 @@
 // table [L][T + 1] (odd phase stride: lanes at different phases hit different banks), the stream's T history samples, the chunk and
 // T / 2 zeros (read by a flush only) in LDS; after the barrier it writes the stream's new history (the last T staged samples: every
 // read of the old row is done) and each thread forms up to 8 outputs, j = thread + 1024 * i, in registers.  Float rows are stored
-// as they are; 16-bit rows with the arithmetic of vv_pcm16_kernel (misc.hip) over the resampled chunk: peak = max|y|, y / peak (IEEE)
-// where peak > 1, (y * 32767) truncated toward zero -- the same launch, the peak reduced through LDS.
+// as they are; 16-bit rows with the rule of vv_device.h (vv_block_peak, vv_pcm16_of) over the resampled chunk, in the same launch.
 // The rows travel by value in the kernel arguments (VVRsRows, vv_common.h); a row's stream is distinct from every other row's.
 //
 // vv_resample_once_kernel (stateless, whole signals): outputs tiled over workgroups, coefficients and input read from global memory.
@@ -60,23 +59,10 @@ __global__ __launch_bounds__(RS_THREADS) void vv_resample_rows_kernel(VVRsRows r
         for (int i = 0; i < RS_PER; ++i) { const int j = tid + i * RS_THREADS; if (j < r.n_out) orow[j] = acc[i]; }
         return;
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-    if ((tid & 63) == 0) wmx[tid >> 6] = mx;
-    __syncthreads();
-    float peak = 0.f;
-#pragma unroll
-    for (int w = 0; w < RS_THREADS / 64; ++w) peak = fmaxf(peak, wmx[w]);
+    const float peak = vv_block_peak<RS_THREADS / 64>(mx, wmx);
     short* orow = (short*)out + (size_t)blockIdx.x * ld_out;
 #pragma unroll
-    for (int i = 0; i < RS_PER; ++i) {
-        const int j = tid + i * RS_THREADS;
-        if (j < r.n_out) {
-            float v = acc[i];
-            if (peak > 1.0f) v = __fdiv_rn(v, peak);
-            orow[j] = (short)(int)__fmul_rn(v, 32767.0f);
-        }
-    }
+    for (int i = 0; i < RS_PER; ++i) { const int j = tid + i * RS_THREADS; if (j < r.n_out) orow[j] = vv_pcm16_of(acc[i], peak); }
 }
 
 __global__ __launch_bounds__(256) void vv_resample_once_kernel(int L, int M, int T, const float* __restrict__ coef, int n_in, int n_out,

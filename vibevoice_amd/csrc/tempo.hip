@@ -13,7 +13,7 @@
 // vv_tempo_rows_kernel (streaming, chunk-continuous): one workgroup per row of the push, the rows by value in the kernel arguments
 // (VVTpRows, vv_common.h).  The staged stretch is [the stream's VV_TP_HIST history samples | the chunk | zeros]; the new history (the
 // last VV_TP_HIST samples that have arrived) and delta of the row's last block go back with ordinary stores.  16-bit rows take the
-// arithmetic of vv_pcm16_kernel (misc.hip) over the row's stretched chunk: the peak first, then the same samples again.
+// rule of vv_device.h (vv_block_peak, vv_pcm16_of) over the row's stretched chunk: the peak first, then the same samples again.
 // vv_tempo_once_kernel (stateless, whole signals): one workgroup per signal, the signal staged a tile at a time.
 #include "vv_common.h"
 #include "vv_device.h"
@@ -126,19 +126,9 @@ __global__ __launch_bounds__(TP_THREADS) void vv_tempo_rows_kernel(VVTpRows rows
     }
     float mx = 0.f;
     for (int o = tid; o < r.n_out; o += TP_THREADS) mx = fmaxf(mx, fabsf(tp_sample(lds, o)));
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-    if ((tid & 63) == 0) lds.wmx[tid >> 6] = mx;
-    __syncthreads();
-    float peak = 0.f;
-#pragma unroll
-    for (int wv = 0; wv < TP_WAVES; ++wv) peak = fmaxf(peak, lds.wmx[wv]);
+    const float peak = vv_block_peak<TP_WAVES>(mx, lds.wmx);
     short* orow = (short*)out + (size_t)blockIdx.x * ld_out;
-    for (int o = tid; o < r.n_out; o += TP_THREADS) {
-        float v = tp_sample(lds, o);
-        if (peak > 1.0f) v = __fdiv_rn(v, peak);
-        orow[o] = (short)(int)__fmul_rn(v, 32767.0f);
-    }
+    for (int o = tid; o < r.n_out; o += TP_THREADS) orow[o] = vv_pcm16_of(tp_sample(lds, o), peak);
 }
 
 // Block k reads the signal from a_{k-1} - DELTA at the earliest and below hi(k) = max(a_k, a_{k-1} + HS) + DELTA + N (a_k + d + N and

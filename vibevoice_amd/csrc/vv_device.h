@@ -1,4 +1,4 @@
-// vv_device.h -- the device arithmetic every kernel file shares (gfx950 only): wave reductions, activations, the fp32 -> bf16
+// vv_device.h -- the device arithmetic every kernel file shares (gfx950 only): wave reductions, the 16-bit PCM rule, activations, the fp32 -> bf16
 // term split, the packed-tile element index and the sampler's guidance + solver update.  Include it after vv_common.h.
 // Everything here is __device__ __forceinline__: a kernel compiles to the same instructions as with the expression written out.
 #pragma once
@@ -30,6 +30,27 @@ __device__ __forceinline__ float vv_wave_sum_dpp(float v) {
     const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(x, 32));
     const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(x, 48));
     return (r0 + r1) + (r2 + r3);
+}
+
+// ---- 16-bit PCM of one chunk per workgroup ------------------------------------------
+// The arithmetic of the reference's convert_to_16_bit_wav (demo/gradio_demo.py:1058-1073): peak = max|x| over the chunk; where
+// peak > 1, x / peak (fp32, IEEE division); (x * 32767) truncated toward zero.  vv_block_peak: the largest of the threads' own maxima
+// (each >= 0) in a workgroup of WAVES full waves, through wmx, WAVES words of the caller's LDS; one barrier, every thread gets the peak.
+// fmaxf is exact, so the order of the reduction is free; the division, the product and the truncation below are the rule.
+template <int WAVES>
+__device__ __forceinline__ float vv_block_peak(float mx, float* wmx) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    if ((threadIdx.x & 63) == 0) wmx[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    float peak = 0.f;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) peak = fmaxf(peak, wmx[w]);
+    return peak;
+}
+__device__ __forceinline__ short vv_pcm16_of(float v, float peak) {
+    if (peak > 1.0f) v = __fdiv_rn(v, peak);
+    return (short)(int)__fmul_rn(v, 32767.0f);
 }
 
 // ---- activations ---------------------------------------------------------------

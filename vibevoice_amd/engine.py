@@ -547,16 +547,40 @@ class Engine:
         self._chk(self.lib.vv_audio_to_pcm16(self._ctx, self._sp(stream), n, samples, self._p(audio), self._p(pcm_out)),
                   "vv_audio_to_pcm16")
 
-    # ------------------------------------------------------------------ audio at another sample rate (resample.py, csrc/resample.hip)
+    # ------------------------------------------------------------------ streaming row stages and their whole-signal forms
+    _STAGE_USED = {"resampler": "_rs_used", "tempo": "_tp_used"}
+
+    def _take_stage_slot(self, kind, make):
+        """make(k) for the first free k of this engine's four `kind` configurations; the stage's close() gives k back"""
+        used = self.__dict__.setdefault(self._STAGE_USED[kind], [None] * 4)
+        for k in range(len(used)):
+            if used[k] is None:
+                used[k] = s = make(k)
+                return s
+        raise EngineError(f"Engine.{kind}: all 4 {kind} configurations of this engine are in use; close() one")
+
+    def _whole(self, what, audio, n_out, run, stream, aux_cols=0):
+        """Whole signals through a stateless kernel: audio [samples] or [n, samples] as contiguous fp32 rows on the engine's device,
+        run(hipStream_t, rows, samples, x, out, aux) per 65535 rows (the grid's limit), out and the int32 aux (aux_cols > 0) offset to
+        the tile's first row -> (out [..., n_out] fp32, aux [n, aux_cols] or None)"""
+        x = audio.detach().to(device=self.device, dtype=torch.float32)
+        if x.dim() not in (1, 2):
+            raise ValueError(f"Engine.{what}: audio is [samples] or [n, samples], got {tuple(audio.shape)}")
+        x2 = x.reshape(-1, x.shape[-1]).contiguous()
+        n, n_in = x2.shape
+        out = torch.empty((n, n_out), dtype=torch.float32, device=self.device)
+        aux = torch.zeros((n, aux_cols), dtype=torch.int32, device=self.device) if aux_cols else None
+        if n and n_in:
+            st = self._sp(stream if stream is not None else torch.cuda.current_stream(self.device))
+            for i0 in range(0, n, 65535):
+                run(st, min(65535, n - i0), n_in, x2[i0:], out[i0:], aux[i0:] if aux is not None else None)
+        return out.reshape(x.shape[:-1] + (n_out,)), aux
+
+    # audio at another sample rate (resample.py, csrc/resample.hip)
     def resampler(self, src_rate: int, dst_rate: int, n_streams: int) -> "Resampler":
         """A streaming resampler src_rate -> dst_rate with n_streams independent streams, in one of this engine's four resampler
         configurations (close() it to give the configuration back)."""
-        used = self.__dict__.setdefault("_rs_used", [None] * 4)
-        for k in range(len(used)):
-            if used[k] is None:
-                used[k] = r = Resampler(self, k, src_rate, dst_rate, n_streams)
-                return r
-        raise EngineError("Engine.resampler: all 4 resampler configurations of this engine are in use; close() one")
+        return self._take_stage_slot("resampler", lambda k: Resampler(self, k, src_rate, dst_rate, n_streams))
 
     def resample(self, audio: torch.Tensor, src_rate: int, dst_rate: int, stream=None) -> torch.Tensor:
         """Whole signals at another rate: audio [samples] or [n, samples] (any float dtype, any device) -> fp32 on the engine's device,
@@ -564,35 +588,21 @@ class Engine:
         the current torch stream of the device, the one that produced a device tensor)."""
         from . import resample as _rs
         L, M, T, coef = _rs.design(src_rate, dst_rate)
-        x = audio.detach().to(device=self.device, dtype=torch.float32)
-        if x.dim() not in (1, 2):
-            raise ValueError(f"Engine.resample: audio is [samples] or [n, samples], got {tuple(audio.shape)}")
-        x2 = x.reshape(-1, x.shape[-1]).contiguous()
-        n, n_in = x2.shape
-        n_out = _rs.total_out(n_in, L, M)
-        out = torch.empty((n, n_out), dtype=torch.float32, device=self.device)
-        if n and n_in:
+        n_out = _rs.total_out(int(audio.shape[-1]), L, M) if audio.dim() else 0
+
+        def run(st, nn, n_in, x, out, _):
             cache = self.__dict__.setdefault("_rs_coef", {})
             cd = cache.get((L, M, T))
             if cd is None:
                 cd = cache[(L, M, T)] = torch.from_numpy(np.array(coef)).to(self.device)
-            st = stream if stream is not None else torch.cuda.current_stream(self.device)
-            for i0 in range(0, n, 65535):
-                nn = min(65535, n - i0)
-                self._chk(self.lib.vv_resample_once(self._ctx, self._sp(st), L, M, T, self._p(cd), nn, n_in, self._p(x2[i0:]), n_in,
-                                                    self._p(out[i0:]), n_out), "vv_resample_once")
-        return out.reshape(x.shape[:-1] + (n_out,))
+            self._chk(self.lib.vv_resample_once(self._ctx, st, L, M, T, self._p(cd), nn, n_in, self._p(x), n_in, self._p(out), n_out), "vv_resample_once")
+        return self._whole("resample", audio, n_out, run, stream)[0]
 
-    # ------------------------------------------------------------------ speaking rate (tempo.py, csrc/tempo.hip)
+    # speaking rate (tempo.py, csrc/tempo.hip)
     def tempo(self, n_streams: int) -> "Tempo":
         """A streaming tempo change with n_streams independent streams, each at its own speed, in one of this engine's four tempo
         configurations (close() it to give the configuration back)."""
-        used = self.__dict__.setdefault("_tp_used", [None] * 4)
-        for k in range(len(used)):
-            if used[k] is None:
-                used[k] = t = Tempo(self, k, n_streams)
-                return t
-        raise EngineError("Engine.tempo: all 4 tempo configurations of this engine are in use; close() one")
+        return self._take_stage_slot("tempo", lambda k: Tempo(self, k, n_streams))
 
     def _tempo_window(self):
         from . import tempo as _tp
@@ -608,24 +618,14 @@ class Engine:
         -> (out, offsets), offsets int32 [..., blocks]: the offset the search chose for each block of 240 output samples."""
         from . import tempo as _tp
         P, Q = _tp.ratio(speed)
-        x = audio.detach().to(device=self.device, dtype=torch.float32)
-        if x.dim() not in (1, 2):
-            raise ValueError(f"Engine.time_stretch: audio is [samples] or [n, samples], got {tuple(audio.shape)}")
-        x2 = x.reshape(-1, x.shape[-1]).contiguous()
-        n, n_in = x2.shape
-        n_out = _tp.total_out(n_in, P, Q)
+        n_out = _tp.total_out(int(audio.shape[-1]), P, Q) if audio.dim() else 0
         nblk = -(-n_out // _tp.HS)
-        out = torch.empty((n, n_out), dtype=torch.float32, device=self.device)
-        offs = torch.zeros((n, max(nblk, 1)), dtype=torch.int32, device=self.device) if return_offsets else None
-        if n and n_in:
-            w = self._tempo_window()
-            st = stream if stream is not None else torch.cuda.current_stream(self.device)
-            for i0 in range(0, n, 65535):
-                nn = min(65535, n - i0)
-                self._chk(self.lib.vv_tempo_once(self._ctx, self._sp(st), self._p(w), P, Q, nn, n_in, self._p(x2[i0:]), n_in, self._p(out[i0:]),
-                                                 n_out, self._p(offs[i0:]) if offs is not None else None, max(nblk, 1)), "vv_tempo_once")
-        out = out.reshape(x.shape[:-1] + (n_out,))
-        return (out, offs[:, :nblk].reshape(x.shape[:-1] + (nblk,))) if return_offsets else out
+
+        def run(st, nn, n_in, x, out, offs):
+            self._chk(self.lib.vv_tempo_once(self._ctx, st, self._p(self._tempo_window()), P, Q, nn, n_in, self._p(x), n_in, self._p(out), n_out,
+                                             self._p(offs) if offs is not None else None, max(nblk, 1)), "vv_tempo_once")
+        out, offs = self._whole("time_stretch", audio, n_out, run, stream, aux_cols=max(nblk, 1) if return_offsets else 0)
+        return (out, offs[:, :nblk].reshape(out.shape[:-1] + (nblk,))) if return_offsets else out
 
     def codec_reset(self, slot: int):
         self._chk(self.lib.vv_codec_reset(self._ctx, self._s, slot), "vv_codec_reset")
@@ -939,18 +939,99 @@ class TempoCapacityError(EngineError):
     push it in pieces."""
 
 
-class Tempo:
+class _RowStage:
+    """What the streaming row stages share (Tempo, Resampler; a third stage derives from this too): n_streams chunk-continuous streams in
+    one of the engine's configurations, pushed up to 16 rows a launch.  A stage supplies KIND (Engine._STAGE_USED), its row struct ROW
+    and how push() fills it, its C entry points ROWS_FN / RESET_FN, counts(), max_out() and take()."""
+    KIND = ROW = ROWS_FN = RESET_FN = None
+    NO_ROWS = ()                                          # the launches of a push that names no stream
+
+    def __init__(self, engine: Engine, slot: int, n_streams: int):
+        self.engine, self.slot, self.n_streams = engine, slot, int(n_streams)
+        self.total = [0] * self.n_streams                 # input samples each stream has taken (the C side keeps the same figures)
+
+    def take(self, ids: Sequence[int], remaining: Sequence[int], flush: bool = False) -> int:
+        """input samples per row the next push accepts from rows that still have remaining[i] for stream ids[i]: a longer chunk goes in
+        pieces of this width (host integers)"""
+        raise NotImplementedError
+
+    def _args(self, audio, stream_ids, flush, n_in, **more):
+        """push()'s arguments checked and spread over the rows -> (ids, samples, n_in per row, flush per row, *more per row)"""
+        e, name = self.engine, type(self).__name__
+        ids = [int(i) for i in stream_ids]
+        n = len(ids)
+        samples = 0 if audio is None else int(audio.shape[-1])
+        if audio is not None:
+            if audio.dim() != 2 or audio.dtype != torch.float32 or not audio.is_contiguous() or audio.device != e.device or audio.shape[0] < n:
+                raise ValueError(f"{name}.push: audio is a contiguous fp32 [n >= {n}, samples] tensor on {e.device}")
+        nin = [samples] * n if n_in is None else [int(v) for v in n_in]
+        fl = [bool(flush)] * n if isinstance(flush, (bool, int)) else [bool(v) for v in flush]
+        rest = [[v] * n if not hasattr(v, "__len__") else list(v) for v in more.values()]
+        if any(len(v) != n for v in [nin, fl] + rest):
+            names = ["n_in", "flush"] + list(more)
+            raise ValueError(f"{name}.push: {', '.join(names[:-1])} and {names[-1]} name one value per row")
+        return (ids, samples, nin, fl, *rest)
+
+    def _out(self, out, n, nin, pcm16):
+        """push()'s output rows: the caller's, checked, or new ones of max_out() columns"""
+        e, dt = self.engine, torch.int16 if pcm16 else torch.float32
+        if out is None:
+            return torch.empty((max(n, 1), self.max_out(max(nin, default=0))), dtype=dt, device=e.device)
+        if out.dim() != 2 or out.dtype != dt or not out.is_contiguous() or out.device != e.device or out.shape[0] < n:
+            raise ValueError(f"{type(self).__name__}.push: out is a contiguous {dt} [n >= {n}, capacity] tensor on {e.device}")
+        return out
+
+    def _refused(self, rc):
+        self.engine._chk(rc, self.ROWS_FN)
+
+    def _launch(self, audio, samples, ids, nin, rows, out, pcm16, stream, extra=lambda i0: (), took=lambda i: None):
+        """One ROWS_FN launch per 16 rows on `stream` (default: the device's current torch stream), the pointers offset to the launch's
+        first row; extra(i0): the stage's further arguments; took(i) after the launch that took row i -> the rows' counts"""
+        e, n, cap = self.engine, len(ids), int(out.shape[1])
+        st = e._sp(stream if stream is not None else torch.cuda.current_stream(e.device))
+        cnts = (C.c_int * max(n, 1))()
+        for i0 in range(0, n, 16) or self.NO_ROWS:
+            nn = min(16, n - i0)
+            a = C.c_void_p(audio.data_ptr() + i0 * samples * 4) if audio is not None else C.c_void_p()
+            o = C.c_void_p(out.data_ptr() + i0 * cap * out.element_size())
+            self._refused(getattr(e.lib, self.ROWS_FN)(e._ctx, st, self.slot, nn, C.cast(C.byref(rows, i0 * C.sizeof(self.ROW)), C.POINTER(self.ROW)),
+                                                       a, samples, o, cap, int(pcm16), C.cast(C.byref(cnts, i0 * 4), C.POINTER(C.c_int)), *extra(i0)))
+            for i in range(i0, i0 + nn):
+                self.total[ids[i]] += nin[i]
+                took(i)
+        return [int(cnts[i]) for i in range(n)]
+
+    def reset(self, ids: Optional[Sequence[int]] = None, stream=None):
+        """streams `ids` (default: all) back to their first sample: history zeroed on `stream`, totals 0, flush marks cleared"""
+        e = self.engine
+        st = e._sp(stream if stream is not None else torch.cuda.current_stream(e.device))
+        arr = None if ids is None else (C.c_int * max(1, len(ids)))(*[int(i) for i in ids])
+        e._chk(getattr(e.lib, self.RESET_FN)(e._ctx, st, self.slot, 0 if ids is None else len(ids), arr), self.RESET_FN)
+        for i in range(self.n_streams) if ids is None else ids:
+            self._cleared(int(i))
+
+    def _cleared(self, stream_id):
+        self.total[stream_id] = 0
+
+    def close(self):
+        """give the engine's configuration back (its device buffers are released when the configuration is set again or the engine closes)"""
+        used = getattr(self.engine, Engine._STAGE_USED[self.KIND], None)
+        if used is not None and used[self.slot] is self:
+            used[self.slot] = None
+
+
+class Tempo(_RowStage):
     """One streaming tempo configuration of an engine (Engine.tempo): n_streams chunk-continuous streams at 24 kHz, each at the speed
-    of its first push until its reset.  What a stream delivers does not depend on how its input was cut into pushes
-    (vibevoice_amd/tempo.py): the concatenation of its pushes and its flush equals Engine.time_stretch() of the concatenated input, bit
-    for bit in float mode, ceil(n * Q / P) samples.  delay_samples: the input samples (640, 26.7 ms) a stream holds back at most until
-    its next push; max_in: the input samples one row of a push may bring."""
+    of its first push until its reset (which clears the speed with the rest).  What a stream delivers does not depend on how its input
+    was cut into pushes (vibevoice_amd/tempo.py): the concatenation of its pushes and its flush equals Engine.time_stretch() of the
+    concatenated input, bit for bit in float mode, ceil(n * Q / P) samples.  delay_samples: the input samples (640, 26.7 ms) a stream
+    holds back at most until its next push; max_in: the input samples one row of a push may bring."""
+    KIND, ROW, ROWS_FN, RESET_FN = "tempo", _lib.VVTempoRow, "vv_tempo_rows", "vv_tempo_reset"
 
     def __init__(self, engine: Engine, slot: int, n_streams: int):
         from . import tempo as _tp
-        self.engine, self.slot, self.n_streams = engine, slot, int(n_streams)
+        super().__init__(engine, slot, n_streams)
         self.delay_samples, self.max_in = _tp.delay_samples(), 7680
-        self.total = [0] * self.n_streams                 # input samples each stream has taken (the C side keeps the same figures)
         self.ratio = [None] * self.n_streams              # (P, Q) of each stream, None before its first push
         w = np.ascontiguousarray(_tp.window())
         engine._chk(engine.lib.vv_tempo_set(engine._ctx, slot, C.c_void_p(w.ctypes.data), self.n_streams, engine._s), "vv_tempo_set")
@@ -966,6 +1047,9 @@ class Tempo:
         block that starts 880 input samples or more before its total, and a signal of n samples yields at most 2 n"""
         return 2 * (int(n_in) + 880) + 1
 
+    def take(self, ids, remaining, flush=False):
+        return min(self.max_in, max(remaining))
+
     def push(self, audio: Optional[torch.Tensor], stream_ids: Sequence[int], speeds, flush=False, out: Optional[torch.Tensor] = None,
              n_in=None, stream=None, pcm16: bool = False, return_offsets: bool = False):
         """Row i of audio [n, samples] (contiguous fp32 on the engine's device; None where no row brings samples) goes to stream
@@ -978,81 +1062,42 @@ class Tempo:
         (default: the device's current torch stream); the counts are host integers, nothing waits for the device.  A row beyond the
         launch's capacity raises TempoCapacityError before anything ran."""
         from . import tempo as _tp
-        e = self.engine
-        ids = [int(i) for i in stream_ids]
-        n = len(ids)
-        samples = 0 if audio is None else int(audio.shape[-1])
-        if audio is not None:
-            if audio.dim() != 2 or audio.dtype != torch.float32 or not audio.is_contiguous() or audio.device != e.device or audio.shape[0] < n:
-                raise ValueError(f"Tempo.push: audio is a contiguous fp32 [n >= {n}, samples] tensor on {e.device}")
-        nin = [samples] * n if n_in is None else [int(v) for v in n_in]
-        fl = [bool(flush)] * n if isinstance(flush, (bool, int)) else [bool(v) for v in flush]
-        sp = [speeds] * n if not hasattr(speeds, "__len__") else list(speeds)
-        if len(nin) != n or len(fl) != n or len(sp) != n:
-            raise ValueError("Tempo.push: n_in, flush and speeds name one value per row")
+        ids, samples, nin, fl, sp = self._args(audio, stream_ids, flush, n_in, speeds=speeds)
         pq = [_tp.ratio(v) for v in sp]
-        dt = torch.int16 if pcm16 else torch.float32
-        if out is None:
-            out = torch.empty((max(n, 1), self.max_out(max(nin, default=0))), dtype=dt, device=e.device)
-        elif out.dim() != 2 or out.dtype != dt or not out.is_contiguous() or out.device != e.device or out.shape[0] < n:
-            raise ValueError(f"Tempo.push: out is a contiguous {dt} [n >= {n}, capacity] tensor on {e.device}")
-        cap = int(out.shape[1])
-        ld_off = -(-cap // _tp.HS)
-        offs = torch.zeros((max(n, 1), ld_off), dtype=torch.int32, device=e.device) if return_offsets else None
-        st = stream if stream is not None else torch.cuda.current_stream(e.device)
-        cnts = (C.c_int * max(n, 1))()
-        rows = (_lib.VVTempoRow * max(n, 1))()
+        n, out = len(ids), self._out(out, len(ids), nin, pcm16)
+        ld_off = -(-int(out.shape[1]) // _tp.HS)
+        offs = torch.zeros((max(n, 1), ld_off), dtype=torch.int32, device=out.device) if return_offsets else None
+        rows = (self.ROW * max(n, 1))()
         for i in range(n):
             rows[i].stream, rows[i].n_in, rows[i].flush, rows[i].P, rows[i].Q = ids[i], nin[i], int(fl[i]), pq[i][0], pq[i][1]
-        for i0 in range(0, n, 16):
-            nn = min(16, n - i0)
-            a = C.c_void_p(audio.data_ptr() + i0 * samples * 4) if audio is not None else C.c_void_p()
-            o = C.c_void_p(out.data_ptr() + i0 * cap * out.element_size())
-            f = C.c_void_p(offs.data_ptr() + i0 * ld_off * 4) if offs is not None else C.c_void_p()
-            rc = e.lib.vv_tempo_rows(e._ctx, e._sp(st), self.slot, nn, C.cast(C.byref(rows, i0 * C.sizeof(_lib.VVTempoRow)), C.POINTER(_lib.VVTempoRow)),
-                                     a, samples, o, cap, int(pcm16), C.cast(C.byref(cnts, i0 * 4), C.POINTER(C.c_int)), f, ld_off)
-            if rc == _lib.TEMPO_OVER_CAPACITY:
-                raise TempoCapacityError(f"Tempo.push: {e._err()}")
-            e._chk(rc, "vv_tempo_rows")
-            for i in range(i0, i0 + nn):
-                self.total[ids[i]] += nin[i]
-                self.ratio[ids[i]] = pq[i]
-        res = [int(cnts[i]) for i in range(n)]
+        res = self._launch(audio, samples, ids, nin, rows, out, pcm16, stream,
+                           extra=lambda i0: (C.c_void_p(offs.data_ptr() + i0 * ld_off * 4) if offs is not None else C.c_void_p(), ld_off),
+                           took=lambda i: self.ratio.__setitem__(ids[i], pq[i]))
         return (out, res, offs) if return_offsets else (out, res)
 
-    def reset(self, ids: Optional[Sequence[int]] = None, stream=None):
-        """streams `ids` (default: all) back to their first sample: history zeroed on `stream`, totals 0, speeds and flush marks cleared"""
-        e = self.engine
-        st = stream if stream is not None else torch.cuda.current_stream(e.device)
-        if ids is None:
-            e._chk(e.lib.vv_tempo_reset(e._ctx, e._sp(st), self.slot, 0, None), "vv_tempo_reset")
-            self.total, self.ratio = [0] * self.n_streams, [None] * self.n_streams
-            return
-        arr = (C.c_int * max(1, len(ids)))(*[int(i) for i in ids])
-        e._chk(e.lib.vv_tempo_reset(e._ctx, e._sp(st), self.slot, len(ids), arr), "vv_tempo_reset")
-        for i in ids:
-            self.total[int(i)], self.ratio[int(i)] = 0, None
+    def _refused(self, rc):
+        if rc == _lib.TEMPO_OVER_CAPACITY:
+            raise TempoCapacityError(f"Tempo.push: {self.engine._err()}")
+        super()._refused(rc)
 
-    def close(self):
-        """give the engine's configuration back (its device buffers are released when the configuration is set again or the engine closes)"""
-        used = getattr(self.engine, "_tp_used", None)
-        if used is not None and used[self.slot] is self:
-            used[self.slot] = None
+    def _cleared(self, stream_id):
+        self.total[stream_id], self.ratio[stream_id] = 0, None
 
 
-class Resampler:
+class Resampler(_RowStage):
     """One streaming resampler configuration of an engine (Engine.resampler): n_streams chunk-continuous streams src_rate -> dst_rate.
     What a stream delivers does not depend on how its input was cut into pushes (vibevoice_amd/resample.py): the concatenation of its
     pushes and its flush equals Engine.resample() of the concatenated input, bit for bit in float mode, ceil(n * L / M) samples.
     taps: filter taps per output sample; delay_samples: the input samples (taps / 2) a stream holds back until its next push."""
+    KIND, ROW, ROWS_FN, RESET_FN = "resampler", _lib.VVResampleRow, "vv_resample_rows", "vv_resampler_reset"
+    NO_ROWS = (0,)                                        # one launch, which vv_resample_rows refuses by name (Tempo.push returns no counts)
 
     def __init__(self, engine: Engine, slot: int, src_rate: int, dst_rate: int, n_streams: int):
         from . import resample as _rs
-        self.engine, self.slot = engine, slot
-        self.src_rate, self.dst_rate, self.n_streams = int(src_rate), int(dst_rate), int(n_streams)
+        super().__init__(engine, slot, n_streams)
+        self.src_rate, self.dst_rate = int(src_rate), int(dst_rate)
         self.L, self.M, self.T, coef = _rs.design(src_rate, dst_rate)
         self.taps, self.delay_samples = self.T, _rs.delay_samples(self.T)
-        self.total = [0] * self.n_streams                 # input samples each stream has taken (the C side keeps the same figures)
         c = np.ascontiguousarray(coef)
         engine._chk(engine.lib.vv_resampler_set(engine._ctx, slot, self.L, self.M, self.T, C.c_void_p(c.ctypes.data), self.n_streams,
                                                 engine._s), "vv_resampler_set")
@@ -1066,6 +1111,10 @@ class Resampler:
         """upper bound of what any push of up to n_in samples emits, the flush included"""
         return -((-(int(n_in) + self.delay_samples + 1) * self.L) // self.M) + 1
 
+    def take(self, ids, remaining, flush=False):
+        from . import resample as _rs
+        return _rs.push_width(self.L, self.M, self.T, [self.total[i] for i in ids], remaining, flush)
+
     def push(self, audio: Optional[torch.Tensor], stream_ids: Sequence[int], flush=False, out: Optional[torch.Tensor] = None,
              pcm16: bool = False, n_in=None, stream=None):
         """Row i of audio [n, samples] (contiguous fp32 on the engine's device; None where no row brings samples) goes to stream
@@ -1074,53 +1123,9 @@ class Resampler:
         under pcm16 (the arithmetic of Engine.audio_to_pcm16 over the row's resampled chunk, in the same launch).  out: a contiguous
         [>= n, capacity] tensor of that dtype to write into (default: a new one of max_out(samples) columns).  One launch per 16 rows
         on `stream` (default: the device's current torch stream); the counts are host integers, nothing waits for the device."""
-        e = self.engine
-        ids = [int(i) for i in stream_ids]
-        n = len(ids)
-        samples = 0 if audio is None else int(audio.shape[-1])
-        if audio is not None:
-            if audio.dim() != 2 or audio.dtype != torch.float32 or not audio.is_contiguous() or audio.device != e.device or audio.shape[0] < n:
-                raise ValueError(f"Resampler.push: audio is a contiguous fp32 [n >= {n}, samples] tensor on {e.device}")
-        nin = [samples] * n if n_in is None else [int(v) for v in n_in]
-        fl = [bool(flush)] * n if isinstance(flush, (bool, int)) else [bool(v) for v in flush]
-        if len(nin) != n or len(fl) != n:
-            raise ValueError("Resampler.push: n_in and flush name one value per row")
-        dt = torch.int16 if pcm16 else torch.float32
-        if out is None:
-            out = torch.empty((max(n, 1), self.max_out(max(nin, default=0))), dtype=dt, device=e.device)
-        elif out.dim() != 2 or out.dtype != dt or not out.is_contiguous() or out.device != e.device or out.shape[0] < n:
-            raise ValueError(f"Resampler.push: out is a contiguous {dt} [n >= {n}, capacity] tensor on {e.device}")
-        st = stream if stream is not None else torch.cuda.current_stream(e.device)
-        cnts = (C.c_int * max(n, 1))()
-        rows = (_lib.VVResampleRow * max(n, 1))()
+        ids, samples, nin, fl = self._args(audio, stream_ids, flush, n_in)
+        n, out = len(ids), self._out(out, len(ids), nin, pcm16)
+        rows = (self.ROW * max(n, 1))()
         for i in range(n):
             rows[i].stream, rows[i].n_in, rows[i].flush = ids[i], nin[i], int(fl[i])
-        cap = int(out.shape[1])
-        for i0 in range(0, max(n, 1), 16):
-            nn = min(16, n - i0)
-            a = C.c_void_p(audio.data_ptr() + i0 * samples * 4) if audio is not None else C.c_void_p()
-            o = C.c_void_p(out.data_ptr() + i0 * cap * out.element_size())
-            e._chk(e.lib.vv_resample_rows(e._ctx, e._sp(st), self.slot, nn, C.cast(C.byref(rows, i0 * C.sizeof(_lib.VVResampleRow)), C.POINTER(_lib.VVResampleRow)),
-                                          a, samples, o, cap, int(pcm16), C.cast(C.byref(cnts, i0 * 4), C.POINTER(C.c_int))), "vv_resample_rows")
-            for i in range(i0, i0 + nn):
-                self.total[ids[i]] += nin[i]
-        return out, [int(cnts[i]) for i in range(n)]
-
-    def reset(self, ids: Optional[Sequence[int]] = None, stream=None):
-        """streams `ids` (default: all) back to their first sample: history zeroed on `stream`, totals 0, flush marks cleared"""
-        e = self.engine
-        st = stream if stream is not None else torch.cuda.current_stream(e.device)
-        if ids is None:
-            e._chk(e.lib.vv_resampler_reset(e._ctx, e._sp(st), self.slot, 0, None), "vv_resampler_reset")
-            self.total = [0] * self.n_streams
-            return
-        arr = (C.c_int * max(1, len(ids)))(*[int(i) for i in ids])
-        e._chk(e.lib.vv_resampler_reset(e._ctx, e._sp(st), self.slot, len(ids), arr), "vv_resampler_reset")
-        for i in ids:
-            self.total[int(i)] = 0
-
-    def close(self):
-        """give the engine's configuration back (its device buffers are released when the configuration is set again or the engine closes)"""
-        used = getattr(self.engine, "_rs_used", None)
-        if used is not None and used[self.slot] is self:
-            used[self.slot] = None
+        return out, self._launch(audio, samples, ids, nin, rows, out, pcm16, stream)

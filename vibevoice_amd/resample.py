@@ -87,6 +87,21 @@ def counts(L, M, T, total_in, n_in, flush=False):
     return m0, m1 - m0
 
 
+# What one push of the device kernel takes per row, mirrored from the C side (vv_resample_rows refuses more of either): at most
+# MAX_OUT outputs (VV_RS_MAX_OUT, csrc/vv_common.h), and the filter table [L][T + 1], the T history samples, the chunk and T / 2 zeros
+# within LDS_BYTES of LDS (vv_resample_lds_bytes, csrc/resample.hip).
+MAX_OUT, LDS_BYTES = 8192, 65536 - 64
+
+
+def push_width(L, M, T, totals, remaining, flush=False):
+    """input samples per row the next push accepts from rows that still have remaining[i] for a stream that has taken totals[i]: all of
+    them where that fits the kernel, else a width that fits whatever the streams' state"""
+    lds_max = LDS_BYTES // 4 - L * (T + 1) - T - T // 2
+    if max(remaining) <= lds_max and all(counts(L, M, T, t, r, flush)[1] <= MAX_OUT for t, r in zip(totals, remaining)):
+        return max(remaining)
+    return max(1, min((MAX_OUT - 1) * M // L - T // 2 - 1, lds_max))
+
+
 def _outputs(coef, L, M, T, buf, first_index, m0, n_out, xp):
     """y[m0 .. m0 + n_out) from buf, which holds x[first_index ...] (zeros where the signal has none); xp: numpy or torch"""
     m = np.arange(m0, m0 + n_out, dtype=np.int64)

@@ -20,12 +20,16 @@ resample.HostResampler on the host.  Stream id = sample index.
 
 `speed=S` (a float in [0.5, 2.0], or one per sample index; anything but 1) changes the speaking rate and keeps the pitch: put() runs the
 chunk batch through the engine's tempo stage (Engine.tempo, csrc/tempo.hip: WSOLA, vibevoice_amd/tempo.py is the definition) on the
-producing stream, at 24 kHz, IN FRONT of whatever follows it today -- the resampler, else the 16-bit conversion (over each row's
-stretched chunk), else the copy; float chunks arrive as fp32.  Chunk-continuous like the resampler: per sample, the concatenated
+producing stream, at 24 kHz; float chunks arrive as fp32.  Chunk-continuous like the resampler: per sample, the concatenated
 chunks equal Engine.time_stretch() of the concatenated input (then Engine.resample() of that, under sample_rate), ceil(n / S) samples,
 bit for bit in float mode.  A sample holds back at most 640 input samples (26.7 ms) until its next chunk; a put that completes no
 block of 240 delivers nothing for that row; end(indices) flushes the tempo tail, then the resampler's.  Device chunks need an engine
-(as above), CPU chunks go through tempo.HostTempo.  A chunk too long for one launch is pushed in pieces and arrives as several.
+(as above), CPU chunks go through tempo.HostTempo.
+
+The device stages form one chain (self._stages, _put_device): the tempo change, then the resampler, whichever exist, each an engine
+row stage (engine._RowStage) pushed on the producing stream; the last one writes the ring slot's staging, as int16 under pcm16 (over
+each row's own chunk), and with no stage the 16-bit conversion does, else the chunk itself is copied.  A chunk longer than one push of
+a stage takes (stage.take()) is pushed in pieces and arrives as several.
 
 The drain thread exits when every sample has ended (or on close()); its pinned ring goes back to a process-wide pool.
 """
@@ -105,7 +109,7 @@ class AudioStreamer:
         self.sample_rate = SOURCE_RATE if sample_rate is None else int(sample_rate)
         self._rs = None                            # Engine.resampler (device chunks), one stream per sample index
         self._rs_host = {}                         # sample index -> resample.HostResampler (CPU chunks)
-        self._rs_stream = None                     # the producing stream of the last resampled put: the tails are flushed on it
+        self._prod = None                          # the producing stream of the last device put: the tails are flushed on it
         self._lead = ()                            # a chunk's dimensions between the row and the samples, kept for the tail
         if self.sample_rate != SOURCE_RATE:
             eng = engine if engine is not None else pcm16
@@ -115,13 +119,15 @@ class AudioStreamer:
             eng = engine if engine is not None else pcm16
             if eng is not None:
                 self._tp = eng.tempo(batch_size)
+        # the device stages between a chunk and the ring, in the order they run; a further stage takes its place in this list
+        self._stages = [st for st in (self._tp, self._rs) if st is not None]
         self.stop_signal = stop_signal
         self.timeout = timeout
         self.audio_queues = [self._make_queue() for _ in range(batch_size)]
         self.finished_flags = [False for _ in range(batch_size)]
         self._pcm_engine = pcm16                  # vibevoice_amd.Engine (or None: chunks keep the producer's dtype)
         self._ring = [None] * ring_slots          # pinned host buffers, allocated on first use (shape of the first chunk)
-        self._pcm_dev = [None] * ring_slots       # device int16 staging per ring slot (pcm16 mode)
+        self._pcm_dev = [None] * ring_slots       # device staging per ring slot: what the last stage, or the 16-bit conversion, writes
         self._copy_stream = None                  # D2H copies run here: the module's copy stream of the chunks' device
         self._free = Queue()
         for i in range(ring_slots):
@@ -157,21 +163,10 @@ class AudioStreamer:
         if self.sample_rate != SOURCE_RATE and self._rs is None:
             raise ValueError(f"AudioStreamer(sample_rate={self.sample_rate}): device chunks are resampled on the device and need an engine "
                              "(pcm16=engine for 16-bit chunks, engine=engine for float chunks)")
-        if self._speeds is not None:
-            if self._tp is None:
-                raise ValueError("AudioStreamer(speed=...): device chunks are stretched on the device and need an engine "
-                                 "(pcm16=engine for 16-bit chunks, engine=engine for float chunks)")
-            self._put_tempo(audio_chunks, live)
-            return
-        slot = self._free.get()                                    # back-pressure only if the consumer is > ring_slots behind
-        with self._lock:                                           # the drain thread hands the ring back to the pool under this lock
-            if self._closed:
-                self._free.put(slot)
-                return
-            if self._rs is not None:
-                self._put_resampled(audio_chunks, live, slot)
-            else:
-                self._put_slot(audio_chunks, live, slot)
+        if self._speeds is not None and self._tp is None:
+            raise ValueError("AudioStreamer(speed=...): device chunks are stretched on the device and need an engine "
+                             "(pcm16=engine for 16-bit chunks, engine=engine for float chunks)")
+        self._put_device(audio_chunks, live)
 
     def _host_chunk(self, idx, chunk):
         """a CPU chunk of sample idx (None: its flush) at the streamer's speed and rate, None where it completes no output sample"""
@@ -199,54 +194,106 @@ class AudioStreamer:
             return None
         return y.reshape(self._lead + (y.shape[0],))
 
-    def _put_resampled(self, audio_chunks, live, slot, flush=False):
-        """One Resampler.push for the live rows (audio_chunks None: their flush), then the ring copy of _put_slot; the work item carries
-        each row's sample count."""
-        rs, pcm = self._rs, self._pcm_engine is not None
-        dev = rs.engine.device
-        ids = [idx for _, idx in live]
-        n = len(live)
+    def _put_device(self, audio_chunks, live, flush=False):
+        """The live rows of a device chunk batch (audio_chunks None: their flush) through the stage chain on the producing stream, then
+        the ring.  Every stage but the last writes an fp32 temporary there; the last one writes the slot's staging, as int16 under pcm16
+        (the launch converts, over each row's own chunk), with each row's count in the work item; one ring slot and one work item per
+        last-stage launch that delivers.  A chunk longer than a stage's push takes (stage.take()) goes in pieces and arrives as several.
+        No stages: the chunk batch itself is the source of the ring copy, behind Engine.audio_to_pcm16 into the staging under pcm16."""
+        pcm = self._pcm_engine
         if audio_chunks is not None:
             src = audio_chunks.detach()
             self._lead = tuple(src.shape[1:-1])
+            self._prod = torch.cuda.current_stream(src.device)
+        prod = self._prod
+        if not self._stages:
+            n, rows = src.shape[0], [(row, idx, None) for row, idx in live]
+            if pcm is None:
+                self._with_slot(lambda slot: self._ring_copy(src, rows, slot, prod))
+                return
+            # int16 on device, on the producing stream, before the copy (demo/gradio_demo.py:1058-1073 per chunk)
+            flat = src.reshape(n, -1).to(torch.float32).contiguous()
+
+            def convert(slot):
+                pd = self._staging(slot, n, flat.shape[1], torch.int16, src.device, exact=True)
+                pcm.audio_to_pcm16(flat, pd[:n], stream=prod)
+                self._ring_copy(pd[:n].view((n,) + tuple(src.shape[1:])), rows, slot, prod)
+            self._with_slot(convert)
+            return
+        flat = None
+        if audio_chunks is not None:
             flat = src.reshape(src.shape[0], -1).to(torch.float32)
-            if [row for row, _ in live] != list(range(n)):
+            if [row for row, _ in live] != list(range(len(live))):
                 flat = flat[[row for row, _ in live]]
             flat = flat.contiguous()
-            samples = flat.shape[1]
-            self._rs_stream = torch.cuda.current_stream(dev)
-        else:
-            flat, samples = None, 0
-        prod = self._rs_stream if self._rs_stream is not None else torch.cuda.current_stream(dev)
-        cap, dt = rs.max_out(samples), torch.int16 if pcm else torch.float32
-        pd = self._staging(slot, n, cap, dt, dev)
-        with torch.cuda.stream(prod):
-            _, cnts = rs.push(flat, ids, flush=flush, out=pd, pcm16=pcm, n_in=None if flat is not None else [0] * n, stream=prod)
-        self._ring_copy(pd, ids, cnts, slot, prod)
+        if prod is None:                                   # a flush with no put before it
+            prod = torch.cuda.current_stream(self._stages[0].engine.device)
+        n = len(live)
+        self._through(0, flat, [0 if flat is None else flat.shape[1]] * n, [idx for _, idx in live], flush, prod)
 
-    def _ring_copy(self, pd, ids, cnts, slot, prod):
-        """rows [0, len(ids)) of the device staging pd, cnts[i] samples each, to the slot's pinned buffer behind the producing stream"""
-        n, dt, dev = len(ids), pd.dtype, pd.device
+    def _through(self, k, x, counts, ids, flush, prod):
+        """rows x (fp32 [n, >= max(counts)], None where no row has samples), counts[i] samples for stream ids[i], through stage k and
+        the stages behind it; flush: these are the streams' last samples.  False once the streamer is closed"""
+        stage, n, ends = self._stages[k], len(ids), k == len(self._stages) - 1
+        dev = stage.engine.device
+        kw = {"speeds": [self._speeds[idx] for idx in ids]} if stage is self._tp else {}
+        dt = torch.int16 if ends and self._pcm_engine is not None else torch.float32
+        at = 0
+        while True:                                        # one push, but for a chunk longer than it takes
+            rem = [max(c - at, 0) for c in counts]
+            w = stage.take(ids, rem, flush)
+            final = w >= max(rem)
+
+            def push(out):
+                with torch.cuda.stream(prod):
+                    return stage.push(x if at == 0 or x is None else x[:, at:].contiguous(), ids, flush=flush and final, out=out,
+                                      pcm16=dt == torch.int16, n_in=[min(r, w) for r in rem], stream=prod, **kw)[1]
+            if ends:
+                def deliver(slot):
+                    pd = self._staging(slot, n, stage.max_out(w), dt, dev)
+                    cnts = push(pd)
+                    self._ring_copy(pd[:n], [(i, idx, cnts[i]) for i, idx in enumerate(ids)], slot, prod)
+                if not self._with_slot(deliver):
+                    return False
+            else:
+                with torch.cuda.stream(prod):
+                    td = torch.empty((n, stage.max_out(w)), dtype=dt, device=dev)      # this stream's: the next stage reads it there
+                ct = push(td)
+                # no sample completed: nothing for the next stage, nothing to deliver
+                if (any(ct) or (flush and final)) and not self._through(k + 1, td, ct, ids, flush and final, prod):
+                    return False
+            if final:
+                return True
+            at += w
+
+    def _ring_copy(self, src, rows, slot, prod):
+        """the device rows src to the slot's pinned buffer behind the producing stream; rows: (row of src, sample index, samples of the row
+        that count or None: the row as it is) for the drain thread"""
         buf = self._ring[slot]
-        if buf is None or buf.dim() != 2 or buf.shape[1] != pd.shape[1] or buf.shape[0] < n or buf.dtype != dt:
+        if buf is None or buf.shape[1:] != src.shape[1:] or buf.shape[0] < src.shape[0] or buf.dtype != src.dtype:
             if buf is not None:
                 _pinned_give([buf])
-            buf = _pinned_take((max(n, self.batch_size), pd.shape[1]), dt)
+            buf = _pinned_take((max(src.shape[0], self.batch_size),) + tuple(src.shape[1:]), src.dtype)
             self._ring[slot] = buf
+        # The D2H copy runs on the streamer's OWN stream, ordered behind the producer by an event: the drain thread then waits on an
+        # event of a stream that never enters hipGraph capture.  (Waiting on an event of the producing stream raced with the
+        # engine's stream captures -- hipEventSynchronize refuses an event whose stream is capturing, hipErrorCapturedEvent --
+        # whenever a new graph key was captured while a chunk was still in flight.)
         if self._copy_stream is None:
-            self._copy_stream = _copy_stream_for(dev)
+            self._copy_stream = _copy_stream_for(src.device)
         ready = torch.cuda.Event()
         ready.record(prod)
         self._copy_stream.wait_event(ready)
         with torch.cuda.stream(self._copy_stream):
-            buf[:n].copy_(pd[:n], non_blocking=True)              # whole rows: both sides contiguous, one asynchronous copy
-        pd.record_stream(self._copy_stream)
+            buf[:src.shape[0]].copy_(src, non_blocking=True)       # staged rows are whole rows: both sides contiguous, one asynchronous copy
+        src.record_stream(self._copy_stream)
         ev = torch.cuda.Event()
         ev.record(self._copy_stream)
-        self._work.put(("rslot", [(i, idx, cnts[i]) for i, idx in enumerate(ids)], slot, ev, self._lead))
+        self._work.put(("slot", rows, slot, ev, self._lead))
 
     def _with_slot(self, fn):
-        """fn(slot) with a free ring slot, under the lock the drain thread hands the ring back under; False once the streamer is closed"""
+        """fn(slot) with a free ring slot (back-pressure only if the consumer is > ring_slots behind), under the lock the drain thread
+        hands the ring back under; False once the streamer is closed"""
         slot = self._free.get()
         with self._lock:
             if self._closed:
@@ -255,118 +302,13 @@ class AudioStreamer:
             fn(slot)
             return True
 
-    def _staging(self, slot, n, cap, dt, dev):
+    def _staging(self, slot, n, cap, dt, dev, exact=False):
+        """the slot's device staging with at least n rows of at least (exact: exactly) cap columns"""
         pd = self._pcm_dev[slot]
-        if pd is None or pd.shape[0] < n or pd.shape[1] < cap or pd.dtype != dt:
+        if pd is None or pd.shape[0] < n or pd.dtype != dt or (pd.shape[1] != cap if exact else pd.shape[1] < cap):
             pd = torch.empty((max(n, self.batch_size), cap), dtype=dt, device=dev)
             self._pcm_dev[slot] = pd
         return pd
-
-    def _rs_width(self, ids, rem, flush):
-        """how many of the rows' remaining stretched samples (rem[i] for stream ids[i]) the next Resampler.push takes: all of them where
-        that fits the kernel -- at most 8192 outputs per row, the chunk within its LDS beside the filter table (vv_resample_rows
-        refuses more) -- else a width that fits whatever the streams' state"""
-        rs = self._rs
-        lds_max = (65536 - 64) // 4 - rs.L * (rs.T + 1) - rs.T - rs.T // 2
-        if max(rem) <= lds_max and all(rs.counts(i, r, flush) <= 8192 for i, r in zip(ids, rem)):
-            return max(rem)
-        return max(1, min(8191 * rs.M // rs.L - rs.T // 2 - 1, lds_max))
-
-    def _put_tempo(self, audio_chunks, live, flush=False):
-        """Tempo.push for the live rows (audio_chunks None: their flush), then what follows today on the stretched rows with their
-        per-row counts: the resampler push, else nothing more (the tempo launch converts to 16 bits itself); one ring slot and one work
-        item per launch that delivers.  A chunk longer than one launch takes goes in pieces."""
-        tp, rs, pcm = self._tp, self._rs, self._pcm_engine is not None
-        dev = tp.engine.device
-        ids = [idx for _, idx in live]
-        n = len(live)
-        speeds = [self._speeds[idx] for idx in ids]
-        if audio_chunks is not None:
-            src = audio_chunks.detach()
-            self._lead = tuple(src.shape[1:-1])
-            flat = src.reshape(src.shape[0], -1).to(torch.float32)
-            if [row for row, _ in live] != list(range(n)):
-                flat = flat[[row for row, _ in live]]
-            flat = flat.contiguous()
-            samples = flat.shape[1]
-            self._rs_stream = torch.cuda.current_stream(dev)
-        else:
-            flat, samples = None, 0
-        prod = self._rs_stream if self._rs_stream is not None else torch.cuda.current_stream(dev)
-        dt = torch.int16 if pcm else torch.float32
-        for c0 in range(0, max(samples, 1), tp.max_in):
-            w = min(tp.max_in, samples - c0)
-            piece = flat[:, c0:c0 + w].contiguous() if flat is not None else None      # the whole chunk but for one longer than a launch takes
-            last = c0 + w >= samples
-            tcap = tp.max_out(w)
-            if rs is None:
-                def stage(slot):
-                    pd = self._staging(slot, n, tcap, dt, dev)
-                    with torch.cuda.stream(prod):
-                        _, cnts = tp.push(piece, ids, speeds, flush=flush and last, out=pd, n_in=[w] * n, stream=prod, pcm16=pcm)
-                    self._ring_copy(pd, ids, cnts, slot, prod)
-                if not self._with_slot(stage):
-                    return
-                continue
-            with torch.cuda.stream(prod):
-                td = torch.empty((n, tcap), dtype=torch.float32, device=dev)       # this stream's: the resampler push below reads it there
-                _, ct = tp.push(piece, ids, speeds, flush=flush and last, out=td, n_in=[w] * n, stream=prod)
-            if not any(ct) and not (flush and last):
-                continue                                 # no block completed: nothing for the resampler, nothing to deliver
-            at = 0
-            while True:                                # one resampler push, but for a stretched chunk longer than it takes
-                rem = [max(c - at, 0) for c in ct]
-                wr = self._rs_width(ids, rem, flush and last)
-                final = wr >= max(rem)
-                nin = [min(r, wr) for r in rem]
-
-                def stage(slot):
-                    pd = self._staging(slot, n, rs.max_out(wr), dt, dev)
-                    with torch.cuda.stream(prod):
-                        _, cnts = rs.push(td if at == 0 else td[:, at:].contiguous(), ids, flush=flush and last and final, out=pd, pcm16=pcm,
-                                          n_in=nin, stream=prod)
-                    self._ring_copy(pd, ids, cnts, slot, prod)
-                if not self._with_slot(stage):
-                    return
-                if final:
-                    break
-                at += wr
-
-    def _put_slot(self, audio_chunks, live, slot):
-        src = audio_chunks.detach()
-        if self._pcm_engine is not None:
-            # int16 on device, on the producing stream, before the copy (demo/gradio_demo.py:1058-1073 per chunk)
-            n = src.shape[0]
-            flat = src.reshape(n, -1).to(torch.float32).contiguous()
-            pd = self._pcm_dev[slot]
-            if pd is None or pd.shape[0] < n or pd.shape[1] != flat.shape[1]:
-                pd = torch.empty((max(n, self.batch_size), flat.shape[1]), dtype=torch.int16, device=src.device)
-                self._pcm_dev[slot] = pd
-            self._pcm_engine.audio_to_pcm16(flat, pd[:n], stream=torch.cuda.current_stream(src.device))
-            src = pd[:n].view((n,) + tuple(audio_chunks.shape[1:]))
-        need = src.shape
-        buf = self._ring[slot]
-        if buf is None or buf.shape[1:] != need[1:] or buf.shape[0] < need[0] or buf.dtype != src.dtype:
-            if buf is not None:
-                _pinned_give([buf])
-            buf = _pinned_take((max(need[0], self.batch_size),) + tuple(need[1:]), src.dtype)
-            self._ring[slot] = buf
-        # The D2H copy runs on the streamer's OWN stream, ordered behind the producer by an event: the drain thread then waits on an
-        # event of a stream that never enters hipGraph capture.  (Waiting on an event of the producing stream raced with the
-        # engine's stream captures -- hipEventSynchronize refuses an event whose stream is capturing, hipErrorCapturedEvent --
-        # whenever a new graph key was captured while a chunk was still in flight.)
-        prod = torch.cuda.current_stream(audio_chunks.device)
-        if self._copy_stream is None:
-            self._copy_stream = _copy_stream_for(audio_chunks.device)
-        ready = torch.cuda.Event()
-        ready.record(prod)
-        self._copy_stream.wait_event(ready)
-        with torch.cuda.stream(self._copy_stream):
-            buf[:need[0]].copy_(src, non_blocking=True)
-        src.record_stream(self._copy_stream)
-        ev = torch.cuda.Event()
-        ev.record(self._copy_stream)
-        self._work.put(("slot", live, slot, ev, need[0]))
 
     def end(self, sample_indices=None):
         if sample_indices is None:
@@ -381,24 +323,15 @@ class AudioStreamer:
             self._work.put(("end", idx, None, None, None))       # ordered after that sample's pending chunks
 
     def _flush_tails(self, idxs):
-        """the samples the resampler still holds for these sample indices, as a last chunk each, in front of their stop signals"""
+        """the samples the stages still hold for these sample indices, as last chunks, in front of their stop signals"""
         for idx in idxs:
             tail = self._host_chunk(idx, None)
             if tail is not None:
                 self._work.put(("chunk", idx, tail, None, None))
-        if self._tp is not None:                 # the tempo tail first, then (in the same pass) the resampler's
-            live = [(row, idx) for row, idx in enumerate(i for i in idxs if self._tp.total[i] > 0)]
+        if self._stages:                         # the first stage's tail runs through the ones behind it, whose own follow in the same pass
+            live = list(enumerate(i for i in idxs if self._stages[0].total[i] > 0))
             if live:
-                self._put_tempo(None, live, flush=True)
-            return
-        live = [(row, idx) for row, idx in enumerate(i for i in idxs if self._rs is not None and self._rs.total[i] > 0)]
-        for i0 in range(0, len(live), 16):
-            slot = self._free.get()
-            with self._lock:
-                if self._closed:
-                    self._free.put(slot)
-                    return
-                self._put_resampled(None, [(r - i0, idx) for r, idx in live[i0:i0 + 16]], slot, flush=True)
+                self._put_device(None, live, flush=True)
 
     def close(self):
         """Stop the drain thread and release the pinned ring (also happens by itself once every sample has ended)."""
@@ -426,17 +359,13 @@ class AudioStreamer:
             kind, a, b, ev, n = self._work.get()
             if kind is _CLOSE:
                 break
-            if kind == "slot":
-                ev.synchronize()
-                buf = self._ring[b]
-                for row, idx in a:
-                    self._deliver(idx, buf[row].clone())
-                self._free.put(b)
-            elif kind == "rslot":
+            if kind == "slot":                           # a: (ring row, sample index, samples or None: the whole row), n: the lead shape
                 ev.synchronize()
                 buf = self._ring[b]
                 for row, idx, cnt in a:
-                    if cnt:
+                    if cnt is None:
+                        self._deliver(idx, buf[row].clone())
+                    elif cnt:
                         self._deliver(idx, buf[row, :cnt].clone().reshape(n + (cnt,)))
                 self._free.put(b)
             elif kind == "chunk":
@@ -456,7 +385,7 @@ class AudioStreamer:
                 item = self._work.get_nowait()
             except _q.Empty:
                 break
-            if item[0] in ("slot", "rslot"):
+            if item[0] == "slot":
                 item[3].synchronize()
                 self._free.put(item[2])                  # a producer still blocked in _free.get() wakes up, sees _closed, returns
         with self._lock:
