@@ -3,7 +3,7 @@
 //   lm   ws_rows attn_splits Hkv tile3_ok attn2_ok p16_ok n_rows (cache pos) x n_rows
 //          ->  rc fused contiguous [route attn attn_S attn_groups zero_v_tail key_mode key_split kv_positions]   (rc 0 only)
 //   head rows n_steps HF HL MODW p16_ok p16_shift ada_p mod_all head_tail has_coef
-//          ->  ada sh_tiles layers, then the final stage of every step
+//          ->  ada sh_tiles layers solver_step, then the final stage of every step
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -26,7 +26,7 @@ int main() {
             int rows, steps, HF, HL, MODW, p16, sh, adap, modall, tail, coef;
             if (scanf("%d %d %d %d %d %d %d %d %d %d %d", &rows, &steps, &HF, &HL, &MODW, &p16, &sh, &adap, &modall, &tail, &coef) != 11) return 1;
             const VVHeadPlan p = vv_head_plan(rows, steps, HF, HL, MODW, VVHeadCaps{p16 != 0, sh != 0, adap != 0, modall != 0, tail != 0}, coef != 0);
-            printf("%d %d %d", p.ada, (int)p.sh_tiles, p.layers);
+            printf("%d %d %d %d", p.ada, (int)p.sh_tiles, p.layers, (int)p.solver_step);
             for (int i = 0; i < steps; ++i) printf(" %d", vv_head_final(p, i));
             printf("\n");
         } else return 1;

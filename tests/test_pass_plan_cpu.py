@@ -140,9 +140,10 @@ def head(rows, n_steps=5, HF=384, HL=2, MODW=1024, p16=True, shift=True, ada_p=T
 
 
 def check_head(probe, cases):
-    """cases: (probe line, (ada, sh_tiles, layers, [final stage per step]))"""
+    """cases: (probe line, (ada, sh_tiles, layers, [final stage per step])); solver_step is false for every plan of a shipped table and
+    for vv_head_forward's -- all this probe asks for (the general table's plans: test_solver_family_cpu.py)"""
     got = probe([c for c, _ in cases])
-    fails = [(line, want, r) for (line, want), r in zip(cases, got) if (r[0], r[1], r[2], r[3:]) != want]
+    fails = [(line, want, r) for (line, want), r in zip(cases, got) if (r[0], r[1], r[2], r[4:]) != want or r[3] != 0]
     assert not fails, fails
 
 
@@ -175,6 +176,7 @@ def test_head_adaln_route(probe):
     got = probe([head(2, n_steps=16), head(2, n_steps=17), head(16, n_steps=2), head(16, n_steps=3), head(8, MODW=1022),
                  head(8, ada_p=False), head(8, mod_all=False), head(8)])
     assert [ada(r) for r in got] == [ADA_ROWS16, ADA_TILE, ADA_ROWS16, ADA_TILE, ADA_ROWS16, ADA_ROWS16, ADA_PER_STEP, ADA_TILE], got
+    assert not any(r[3] for r in got), got         # solver_step: none of these is a general table's plan
 
 
 # ---- what the GPU tests say they run ----

@@ -217,7 +217,7 @@ def test_generate_under_third_order_is_the_table_sampler_run_by_hand(model):
 
 # ---------------------------------------------------------------- the head's route under a general table (csrc/pass_plan.h)
 def test_head_plan_under_a_general_table(tmp_path):
-    """vv_head_plan(..., general): the modulations stay batched and the layers keep their route, as for the shipped samplers; no
+    """vv_head_plan(..., solver_step): the modulations stay batched and the layers keep their route, as for the shipped samplers; no
     seam, no packed shift tiles (they serve the P16 CFG epilogue alone), and every step ends with the final layer's plain store."""
     import subprocess
     from vibevoice_amd import build as vvbuild
@@ -237,6 +237,7 @@ def test_head_plan_under_a_general_table(tmp_path):
     for c, shipped, general in zip(cases, lines[0::2], lines[1::2]):
         assert general[0] == shipped[0] and general[2] == shipped[2], (c, shipped, general)        # ada, layers
         assert general[1] == 0 and general[3] == 0 and general[4] == FINAL_GEMM, (c, general)
-        assert general[5:] == [FINAL_GEMM] * c[1], (c, general)
+        assert general[5] == 1 and shipped[5] == 0, (c, shipped, general)                          # solver_step: solver.hip ends the step
+        assert general[6:] == [FINAL_GEMM] * c[1], (c, general)
         seams += shipped[3]
     assert seams == 2          # the shipped plan of the two-row bf16 cases takes the seam: the probe distinguishes the two plans

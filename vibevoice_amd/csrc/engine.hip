@@ -339,12 +339,11 @@ static int create_impl(const vv_config* cfg, vv_ctx* parent, vv_ctx** out) {
     const int R2 = 16;
     ctx->cproj = (float*)dalloc(ctx, (size_t)R2 * H * 4);
     ctx->mod = (float*)dalloc(ctx, (size_t)R2 * MODW * 4);
-    ctx->zz = (float*)dalloc(ctx, (size_t)R2 * L * 4);
-    ctx->x0p = (float*)dalloc(ctx, (size_t)R2 * L * 4);
-    ctx->xh = (float*)dalloc(ctx, (size_t)R2 * H * 4);
-    ctx->zz2 = (float*)dalloc(ctx, (size_t)R2 * L * 4);
-    ctx->x0p2 = (float*)dalloc(ctx, (size_t)R2 * L * 4);
-    ctx->xh2 = (float*)dalloc(ctx, (size_t)R2 * H * 4);
+    for (HeadGen& g : ctx->hg) {      // m2 waits for the first general schedule
+        g.zz = (float*)dalloc(ctx, (size_t)R2 * L * 4);
+        g.x0p = (float*)dalloc(ctx, (size_t)R2 * L * 4);
+        g.xh = (float*)dalloc(ctx, (size_t)R2 * H * 4);
+    }
     // decode rows of the bf16 mode: final layer + solver update + next in-projection as one launch (headtail.hip)
     ctx->head_tail = c.xsplit == 1 && L == 64 && (H % 32) == 0 && vv_head_tail_init() == 0;
     if (const char* e = getenv("VVHIP_SOLVER_FUSE"); e && e[0] == '0') ctx->solver_fuse = false;      // A/B: update kernel + the in-projection GEMM

@@ -81,6 +81,10 @@ struct CodecNet {
 
 struct GraphEntry { hipGraphExec_t exec; uint64_t last_use; };
 
+// One generation of the diffusion sampler's state (headtail.hip, solver.hip: a solver step reads one and writes the other): the head's
+// in-projection, the noisy latent, the previous x0 and -- null until the first general schedule -- the x0 before that
+struct HeadGen { float *xh = nullptr, *zz = nullptr, *x0p = nullptr, *m2 = nullptr; };
+
 }  // namespace vv_engine
 using namespace vv_engine;      // this header is internal to the engine*.hip units
 
@@ -129,19 +133,16 @@ struct vv_ctx {
     std::vector<HLayer> hl;
     void *h_in = nullptr, *h_cond = nullptr, *h_t0 = nullptr, *h_t2 = nullptr, *h_ada = nullptr, *h_out = nullptr;
     int n_steps = 0;
+    // coef: the installed table, 64 rows of 8 floats: {a, s, cs, c0, c1, cn, 0, 0} shipped, {a, s, cs, c0, c1, c2, cn, 0} general
     float *temb = nullptr, *coef = nullptr, *tvals = nullptr;
     bool sde_on = false;                   // the schedule table carries variance-noise scales (sde-dpmsolver++)
+    bool general_on = false;               // the table is a general one (vv_set_schedule_general; solver.hip ends every step)
     float* mod_all = nullptr; size_t mod_all_bytes = 0;
     float* ada_in = nullptr;
     void* ada_p = nullptr;                 // the same rows as packed bf16 MFMA fragments (bf16 mode: one tile GEMM for all steps)
-    float *cproj = nullptr, *mod = nullptr, *zz = nullptr, *x0p = nullptr, *xh = nullptr, *hact = nullptr, *eps = nullptr;
-    // second generation of the sampler's state (headtail.hip: a solver step reads one generation and writes the other)
-    float *zz2 = nullptr, *x0p2 = nullptr, *xh2 = nullptr;
+    float *cproj = nullptr, *mod = nullptr, *hact = nullptr, *eps = nullptr;
+    HeadGen hg[2];                  // the sampler's state: a solver step reads generation g and writes g ^ 1
     bool head_tail = false;         // the fused seam (headtail.hip); off in the exact modes or when its LDS size is refused
-    // the general solver table (vv_set_schedule_general; solver.hip): 8-float rows, the second-previous x0 in two generations.
-    // Allocated by the first general schedule; general_on says which of `coef` / `coef8` the installed table is
-    float *coef8 = nullptr, *m2a = nullptr, *m2b = nullptr;
-    bool general_on = false;
     bool solver_fuse = true;        // the step end carries the next in-projection where solver.hip's rule allows (VVHIP_SOLVER_FUSE=0: never)
     float *tmp1 = nullptr, *tmp2 = nullptr;
     // connectors
@@ -275,7 +276,7 @@ int gemm_tl(vv_ctx* ctx, VVGemm g, hipStream_t st);
 //           kernel is in the graph).  device: the row table (cache, position), x, the KV caches, the (cos, sin) table (rebuilt in
 //           place in front of the graph after an upload), inv_freq.  by value: nothing else.
 //           test_lm_replays_follow_the_row_table, test_replays_after_an_upload
-//   samp: sde:  key: n, cond / noise / step-noise / output pointers, CFG_SCALE.  device: conditions, noise, the schedule's rows.
+//   samp: sde:  key: n, cond / noise / step-noise / output pointers, CFG_SCALE.  device: conditions, noise, the rows of ctx->coef, ctx->hg.
 //           by value: STEP COUNT, TABLE OFFSETS, THE PER-STEP MODULATION BUFFERS (a longer schedule reallocates them), sde_on --
 //           dropped by vv_set_schedule / vv_set_schedule_sde.  test_sampler_graphs_follow_the_schedule, test_replays_after_an_upload
 //   rows:   as samp: / sde:, with the POINTER of the per-row scales in the key and the scales on the device.

@@ -2,7 +2,7 @@
 #include "engine_ctx.h"
 #include "pass_plan.h"
 
-// width 5 / 6: the shipped tables (rows of ctx->coef);  8: a general table (rows of ctx->coef8), stochastic as the caller says
+// width 5 / 6: the shipped tables;  8: a general table, stochastic as the caller says.  All of them are rows of ctx->coef, 8 floats each
 static int set_schedule(vv_ctx* ctx, int n_steps, const float* t, const float* coef, int width, void* stream, bool stochastic = false) {
     VV_SHARED;
     hipStream_t st = (hipStream_t)stream;
@@ -10,27 +10,23 @@ static int set_schedule(vv_ctx* ctx, int n_steps, const float* t, const float* c
     const int H = ctx->H;
     if (!ctx->temb) {
         ctx->temb = (float*)dalloc(ctx, (size_t)64 * H * 4);
-        ctx->coef = (float*)dalloc(ctx, 64 * 6 * 4);
+        ctx->coef = (float*)dalloc(ctx, 64 * 8 * 4);
         ctx->tvals = (float*)dalloc(ctx, 64 * 4);
     }
     const bool general = width == 8;
-    if (general && !ctx->coef8) {
-        ctx->coef8 = (float*)dalloc(ctx, 64 * 8 * 4);
-        ctx->m2a = (float*)dalloc(ctx, (size_t)8 * ctx->c.latent_dim * 4);
-        ctx->m2b = (float*)dalloc(ctx, (size_t)8 * ctx->c.latent_dim * 4);
-        if (!ctx->coef8 || !ctx->m2a || !ctx->m2b) return fail(ctx, "vv_set_schedule_general: out of device memory");
+    if (general && !ctx->hg[0].m2) {
+        for (HeadGen& g : ctx->hg) g.m2 = (float*)dalloc(ctx, (size_t)8 * ctx->c.latent_dim * 4);
+        if (!ctx->hg[0].m2 || !ctx->hg[1].m2) return fail(ctx, "vv_set_schedule_general: out of device memory");
     }
-    float rows6[64 * 6];
+    float rows[64 * 8] = {};                      // a shipped row's 5 or 6 values, zeros after them; a general row as given
     for (int i = 0; i < n_steps; ++i)
-        for (int j = 0; j < 6; ++j) rows6[i * 6 + j] = (j < width) ? coef[i * width + j] : 0.f;
+        for (int j = 0; j < width; ++j) rows[i * 8 + j] = coef[i * width + j];
     // by the API used, not by the values: a one-step stochastic schedule has sigma_t = 0 on its only step (all noise scales
     // zero) and must still be sampled through vv_diffusion_sample_sde, as the reference runs it (a noise-free first-order step)
     ctx->sde_on = general ? stochastic : (width == 6);
     ctx->general_on = general;
     HIPCHK(ctx, hipStreamSynchronize(st));
-    if (general) HIPCHK(ctx, hipMemcpy(ctx->coef8, coef, (size_t)n_steps * 8 * 4, hipMemcpyHostToDevice));
-    else
-    HIPCHK(ctx, hipMemcpy(ctx->coef, rows6, (size_t)n_steps * 6 * 4, hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(ctx->coef, rows, (size_t)n_steps * 8 * 4, hipMemcpyHostToDevice));
     HIPCHK(ctx, hipMemcpy(ctx->tvals, t, (size_t)n_steps * 4, hipMemcpyHostToDevice));
     // t_emb[i] = W2 . silu(W1 . sinusoid(t_i))   (TimestepEmbedder, modular_vibevoice_diffusion_head.py:66-93)
     VVCHK(vv_tfreq_launch(ctx->tvals, ctx->tmp2, n_steps, st));
@@ -77,38 +73,49 @@ extern "C" int vv_set_schedule_sde(vv_ctx* ctx, int n_steps, const float* t, con
     return set_schedule(ctx, n_steps, t, coef6, 6, stream);
 }
 
-// coef8: n_steps rows {a, s, cs, c0, c1, c2, cn, 0} (vibevoice_amd/schedule.py: make_general_table); sampled by vv_diffusion_sample_general
-extern "C" int vv_set_schedule_general(vv_ctx* ctx, int n_steps, const float* t, const float* coef8, int stochastic, void* stream) {
-    return set_schedule(ctx, n_steps, t, coef8, 8, stream, stochastic != 0);
+// coef: n_steps rows {a, s, cs, c0, c1, c2, cn, 0} (vibevoice_amd/schedule.py: make_general_table); sampled by vv_diffusion_sample_general
+extern "C" int vv_set_schedule_general(vv_ctx* ctx, int n_steps, const float* t, const float* coef, int stochastic, void* stream) {
+    return set_schedule(ctx, n_steps, t, coef, 8, stream, stochastic != 0);
 }
 
-static VVHeadPlan head_plan(const vv_ctx* ctx, int rows, int n_steps, bool has_coef, bool general = false) {
+// has_coef: a sampler's plan, which ends its steps as the installed table says (general_on: solver.hip's launch)
+static VVHeadPlan head_plan(const vv_ctx* ctx, int rows, int n_steps, bool has_coef) {
     return vv_head_plan(rows, n_steps, ctx->HF, ctx->c.head_layers, ctx->MODW,
-                        {ctx->p16_ok, ctx->p16_shift != nullptr, ctx->ada_p != nullptr, ctx->mod_all_bytes != 0, ctx->head_tail}, has_coef, general);
+                        {ctx->p16_ok, ctx->p16_shift != nullptr, ctx->ada_p != nullptr, ctx->mod_all_bytes != 0, ctx->head_tail}, has_coef,
+                        has_coef && ctx->general_on);
 }
 
-// one head evaluation on 2n rows, solver step `step` of the plan; mod/xh/hact/eps are ctx scratch. temb = t-embedding row for this step.
-static int head_eval(vv_ctx* ctx, hipStream_t st, const VVHeadPlan& p, int step, const float* zrows, const float* temb_row, float* eps_out,
-                     const float* coef = nullptr, float cfg = 0.f, const float* mod_ready = nullptr, const float* sde_noise = nullptr,
-                     const unsigned char* sh_tiles = nullptr, int gen = 0, bool have_x = false, const float* cfg_rows = nullptr) {
-    // cfg_rows: [rows / 2] one guidance scale per utterance on the device, read by the final layer's epilogue in place of cfg (null: cfg)
-    // gen / have_x (sampler, decode rows, bf16 mode): the step's state is generation `gen` (xh / zz / x0p or their second copies);
-    // have_x: the previous step's seam launch already produced this step's in-projection; a step whose final stage is the seam ends with
-    // the fused launch (final layer + CFG + solver update + the NEXT step's in-projection, written to the other generation)
+// How a shipped sampler's step ends inside the head (an epilogue of the final layer, or the seam): the step's row of ctx->coef, the
+// guidance scale or cfg_rows [rows / 2], one per utterance on the device and read in its place, the step's variance noise or null
+struct StepEnd { const float* coef; float cfg; const float *cfg_rows, *noise; };
+// One head evaluation: solver step `step` of the plan, on the plan's rows
+struct HeadStep {
+    int step;
+    const float *z, *temb, *mod;        // the rows the in-projection reads, the t-embedding row, the modulation rows (null: evaluated here)
+    const unsigned char* sh_tiles;      // the step's packed shift tiles (VV_FINAL_P16_CFG), else null
+    float* eps_out;                     // where the GEMM dispatcher's final layer stores
+    const HeadGen &cur, &nxt;           // the generation the step reads (xh: its in-projection) and the one a seam writes
+    bool have_x;                        // the previous step's end left this step's in-projection in cur.xh
+    const StepEnd* end;                 // null: a plain final layer (vv_head_forward; a general table, whose step end is solver.hip's launch)
+};
+
+// mod / hact are ctx scratch.  < 0: failure;  1: the step ended with the seam (final layer + CFG + solver update + the NEXT step's
+// in-projection, all written to s.nxt);  0: otherwise
+static int head_eval(vv_ctx* ctx, hipStream_t st, const VVHeadPlan& p, const HeadStep& s) {
     const vv_config& c = ctx->c;
-    const int rows = p.rows, final_stage = vv_head_final(p, step);
+    const int rows = p.rows, final_stage = vv_head_final(p, s.step);
     const int H = ctx->H, L = c.latent_dim, HL = c.head_layers, HF = ctx->HF, MODW = ctx->MODW;
-    const float* mod = mod_ready ? mod_ready : ctx->mod;
-    float* const xh = gen ? ctx->xh2 : ctx->xh;
-    float* const zcur = gen ? ctx->zz2 : ctx->zz;
-    float* const x0cur = gen ? ctx->x0p2 : ctx->x0p;
-    if (!mod_ready) {
+    const float* mod = s.mod ? s.mod : ctx->mod;
+    const StepEnd end = s.end ? *s.end : StepEnd{};
+    auto put_end = [&](auto& a) { a.coef = end.coef; a.cfg = end.cfg; a.n_cfg = rows / 2; a.sde_noise = end.noise; a.cfg_rows = end.cfg_rows; };
+    float* const xh = s.cur.xh;
+    if (!s.mod) {
         VVGemm ga = mk_gemm(ctx->h_ada, ctx->cproj, ctx->mod, rows, MODW, H, H, MODW);
-        ga.pro = VV_PRO_ADD_SILU; ga.addvec = temb_row; ga.nt = 1;
+        ga.pro = VV_PRO_ADD_SILU; ga.addvec = s.temb; ga.nt = 1;
         GEMM(ga);
     }
-    if (!have_x) {
-        VVGemm gi = mk_gemm(ctx->h_in, zrows, xh, rows, H, L, L, H);
+    if (!s.have_x) {
+        VVGemm gi = mk_gemm(ctx->h_in, s.z, xh, rows, H, L, L, H);
         GEMM(gi);
         nan_probe(ctx, st, "in-proj xh", xh, (size_t)rows * H);
     }
@@ -156,9 +163,8 @@ static int head_eval(vv_ctx* ctx, hipStream_t st, const VVHeadPlan& p, int step,
         ctx->launches += 1;
         VVGemv16p af = p16_args(ctx->h_out, nullptr, ctx->p16_x, nullptr, nullptr, rows, L, H, L);
         af.ssq_in = ctx->ssq_a; af.ssq_tiles = H / 16; af.eps = c.head_eps;
-        af.Xs = (const u32x4*)(sh_tiles + (size_t)HL * ctx->p16_shift_tile);
-        af.z = zcur; af.x0p = x0cur; af.coef = coef; af.cfg = cfg; af.n_cfg = rows / 2; af.sde_noise = sde_noise;
-        af.cfg_rows = cfg_rows;
+        af.Xs = (const u32x4*)(s.sh_tiles + (size_t)HL * ctx->p16_shift_tile);
+        af.z = s.cur.zz; af.x0p = s.cur.x0p; put_end(af);
         VVCHK(p16_go(ctx, st, af, VV_EPI_CFG_DPM, 3));
         return 0;
     }
@@ -167,9 +173,8 @@ static int head_eval(vv_ctx* ctx, hipStream_t st, const VVHeadPlan& p, int step,
         t.Wout = (const u32x4*)ctx->h_out; t.Win = (const u32x4*)ctx->h_in; t.bin = nullptr;
         t.X = xh; t.xa = ctx->xh_parts + (size_t)(HL & 1) * 2 * xps; t.n_xa = xp; t.part_stride = xps;
         t.sc = fb + H; t.sh = fb; t.ld_mod = MODW;
-        t.Xout = gen ? ctx->xh : ctx->xh2;
-        t.z_in = zcur; t.x0p_in = x0cur; t.z_out = gen ? ctx->zz : ctx->zz2; t.x0p_out = gen ? ctx->x0p : ctx->x0p2;
-        t.coef = coef; t.cfg = cfg; t.n_cfg = rows / 2; t.sde_noise = sde_noise; t.cfg_rows = cfg_rows;
+        t.Xout = s.nxt.xh;
+        t.z_in = s.cur.zz; t.x0p_in = s.cur.x0p; t.z_out = s.nxt.zz; t.x0p_out = s.nxt.x0p; put_end(t);
         t.T = rows; t.H = H; t.L = L; t.eps = c.head_eps;
         if (vv_head_tail_ok(&t)) {
             ctx->launches++;
@@ -180,41 +185,70 @@ static int head_eval(vv_ctx* ctx, hipStream_t st, const VVHeadPlan& p, int step,
                                            [=](hipStream_t s2) { return vv_head_tail_launch(&tc, s2); }});
             }
             VVCHK(vv_head_tail_launch(&t, st));
-            return 1;          // the next step's in-projection is done (generation gen ^ 1)
+            return 1;          // the next step's in-projection is done (in s.nxt)
         }
     }
-    VVGemm gf = mk_gemm(ctx->h_out, xh, eps_out, rows, L, H, H, L);
+    VVGemm gf = mk_gemm(ctx->h_out, xh, s.eps_out, rows, L, H, H, L);
     gf.pro = VV_PRO_RMS_MOD; gf.nw = nullptr; gf.eps = c.head_eps; gf.mod_shift = fb; gf.mod_scale = fb + H; gf.ld_mod = MODW;
     gf.xa = ctx->xh_parts + (size_t)(HL & 1) * 2 * xps; gf.n_xa = xp; gf.part_stride = xps;
     if (final_stage != VV_FINAL_GEMM) {   // CFG + DPM-Solver++ update fused into the epilogue: the noisy latent is rewritten in place
-        gf.epi = VV_EPI_CFG_DPM; gf.z = zcur; gf.x0p = x0cur; gf.coef = coef; gf.cfg = cfg; gf.n_cfg = rows / 2;
-        gf.sde_noise = sde_noise; gf.cfg_rows = cfg_rows;
+        gf.epi = VV_EPI_CFG_DPM; gf.z = s.cur.zz; gf.x0p = s.cur.x0p; put_end(gf);
     }
     GEMM(gf);
     return 0;
 }
 
-// general: the installed table is a general one (rows of ctx->coef8): a step is the head with a plain final layer, then solver.hip's launch
-static int sample_body(vv_ctx* ctx, hipStream_t st, int n, const float* cond, const float* noise, float cfg, float* latent_out,
-                       const float* step_noise = nullptr, const float* cfg_rows = nullptr, bool general = false) {
-    const vv_config& c = ctx->c;
-    const int H = ctx->H, L = c.latent_dim;
-    const int rows = 2 * n;
-    ctx->seam_launches = 0;
-    ctx->solver_fused = 0;
+// what one sampler call asks for, whichever entry point it came through: step_noise / cfg_rows null where the call has none
+struct SampleReq { int n; const float *cond, *noise, *step_noise; float cfg; const float* cfg_rows; float* out; };
+// how a step ended.  rc < 0: failure;  1: the next step's in-projection is done;  0: otherwise.  flipped: its result is in the other generation
+struct StepDone { int rc; bool flipped; };
+
+// a shipped table: the step ends inside the head, in an epilogue of the final layer (the state is rewritten in place) or -- decode rows,
+// bf16 mode, every step but the last -- in the fused seam (headtail.hip), which leaves the next step's state in the other generation
+static StepDone step_shipped(vv_ctx* ctx, hipStream_t st, const VVHeadPlan& p, const SampleReq& r, HeadStep s) {
+    const StepEnd end{ctx->coef + s.step * 8, r.cfg, r.cfg_rows,
+                      r.step_noise ? r.step_noise + (size_t)s.step * r.n * ctx->c.latent_dim : nullptr};
+    s.end = &end;
+    const int hr = head_eval(ctx, st, p, s);
+    return {hr, hr == 1};
+}
+
+// a general table: the head (plain final layer -> eps), then ONE launch: CFG + the table-driven update of s.cur into s.nxt and, on every
+// step but the last, the next step's in-projection where solver.hip's rule holds (else the next head_eval does its own)
+static StepDone step_general(vv_ctx* ctx, hipStream_t st, const VVHeadPlan& p, const SampleReq& r, const HeadStep& s) {
+    const int L = ctx->c.latent_dim;
+    if (head_eval(ctx, st, p, s) < 0) return {-1, false};
+    VVSolverStep v{};
+    v.eps = s.eps_out; v.coef = ctx->coef + s.step * 8; v.cfg = r.cfg; v.cfg_rows = r.cfg_rows; v.n = r.n; v.L = L;
+    v.noise = r.step_noise ? r.step_noise + (size_t)s.step * r.n * L : nullptr;
+    v.z_in = s.cur.zz; v.m1_in = s.cur.x0p; v.m2_in = s.cur.m2;
+    v.z_out = s.nxt.zz; v.m1_out = s.nxt.x0p; v.m2_out = s.nxt.m2;
+    if (s.step + 1 < p.n_steps && ctx->solver_fuse) { v.Win = (const u32x4*)ctx->h_in; v.Xout = s.nxt.xh; v.H = ctx->H; v.xs = ctx->c.xsplit; }
+    ctx->launches++;
+    const int sr = vv_solver_step_launch(&v, st);
+    if (sr == VV_RC_NO_FORM) return {fail(ctx, "vv_diffusion_sample_general: solver.hip has no form for n = %d, latent_dim = %d", r.n, L), false};
+    if (sr < 0) return {fail(ctx, "%s:%d launch failed (%d): hip error %d (%s)", __FILE__, __LINE__, sr, g_vv_launch_err, hipGetErrorString((hipError_t)g_vv_launch_err)), false};
+    if (sr == 1) ctx->solver_fused++;
+    return {sr == 1, true};
+}
+
+static int sample_body(vv_ctx* ctx, hipStream_t st, const SampleReq& r) {
+    const int H = ctx->H, L = ctx->c.latent_dim, HL = ctx->c.head_layers;
+    const int n = r.n, rows = 2 * n;
+    ctx->seam_launches = ctx->solver_fused = 0;
     ctx->probe_names.clear();
-    nan_probe(ctx, st, "cond (input)", cond, (size_t)rows * H);
-    nan_probe(ctx, st, "noise (input)", noise, (size_t)n * L);
+    nan_probe(ctx, st, "cond (input)", r.cond, (size_t)rows * H);
+    nan_probe(ctx, st, "noise (input)", r.noise, (size_t)n * L);
     // both CFG halves see the same noisy latent (modeling_vibevoice_inference.py:703-704)
-    VVCHK(vv_sampler_init_launch(noise, ctx->zz, ctx->x0p, n * L, st));
-    VVGemm gc = mk_gemm(ctx->h_cond, cond, ctx->cproj, rows, H, H, H, H);
+    VVCHK(vv_sampler_init_launch(r.noise, ctx->hg[0].zz, ctx->hg[0].x0p, n * L, st));
+    VVGemm gc = mk_gemm(ctx->h_cond, r.cond, ctx->cproj, rows, H, H, H, H);
     gc.nt = 1;
     GEMM(gc);
     // adaLN modulations depend on (cond, t) only, not on the evolving latent: evaluate them for ALL solver steps
     // up front, <=16 rows per GEMM, so the (3*layers+2)*H x H modulation matrix is streamed ceil(2nN/16) times per
     // frame instead of N times (the reference recomputes it inside every head call)
     const int MODW = ctx->MODW;
-    const VVHeadPlan p = head_plan(ctx, rows, ctx->n_steps, true, general);
+    const VVHeadPlan p = head_plan(ctx, rows, ctx->n_steps, true);
     const bool batch_ada = p.ada != VV_ADA_PER_STEP;
     if (batch_ada) {
         // SiLU(cond + t) for all (step, row) pairs in one small launch: the GEMM workgroups (one per 16 output features,
@@ -240,116 +274,90 @@ static int sample_body(vv_ctx* ctx, hipStream_t st, int n, const float* cond, co
         // the shift rows of every (solver step, layer) -- and the final layer's -- as packed bf16 tiles, one launch per frame:
         // tile (i, l) = rows [i * rows, (i + 1) * rows) of mod_all, columns [l * 3H, l * 3H + H).  Only the final layer's tile (l == HL) is read
         ctx->launches++;
-        VVCHK(vv_pack16_tiles_launch(ctx->mod_all, MODW, (int64_t)rows * MODW, ctx->c.head_layers + 1, (int64_t)3 * H, ctx->p16_shift,
-                                     (int64_t)ctx->p16_shift_tile, rows, H, ctx->n_steps * (ctx->c.head_layers + 1), st));
+        VVCHK(vv_pack16_tiles_launch(ctx->mod_all, MODW, (int64_t)rows * MODW, HL + 1, (int64_t)3 * H, ctx->p16_shift,
+                                     (int64_t)ctx->p16_shift_tile, rows, H, ctx->n_steps * (HL + 1), st));
     }
     int gen = 0; bool have_x = false;
     for (int i = 0; i < ctx->n_steps; ++i) {
-        const float* mod_i = batch_ada ? ctx->mod_all + (size_t)i * rows * MODW : nullptr;
-        const float* sn = step_noise ? step_noise + (size_t)i * n * L : nullptr;
-        const unsigned char* sht = p.sh_tiles ? (const unsigned char*)ctx->p16_shift + (size_t)i * (ctx->c.head_layers + 1) * ctx->p16_shift_tile : nullptr;
-        if (general) {
-            // head (plain final layer -> eps), then ONE launch: CFG + table-driven update of generation gen into gen ^ 1 and, on every
-            // step but the last, the next step's in-projection where solver.hip's rule holds (else the next head_eval does its own)
-            if (head_eval(ctx, st, p, i, gen ? ctx->zz2 : ctx->zz, ctx->temb + (size_t)i * H, ctx->eps, nullptr, 0.f, mod_i, nullptr, nullptr,
-                          gen, have_x) < 0) return -1;
-            VVSolverStep s{};
-            s.eps = ctx->eps; s.coef = ctx->coef8 + i * 8; s.cfg = cfg; s.cfg_rows = cfg_rows; s.noise = sn; s.n = n; s.L = L;
-            s.z_in = gen ? ctx->zz2 : ctx->zz; s.m1_in = gen ? ctx->x0p2 : ctx->x0p; s.m2_in = gen ? ctx->m2b : ctx->m2a;
-            s.z_out = gen ? ctx->zz : ctx->zz2; s.m1_out = gen ? ctx->x0p : ctx->x0p2; s.m2_out = gen ? ctx->m2a : ctx->m2b;
-            if (i + 1 < ctx->n_steps && ctx->solver_fuse) { s.Win = (const u32x4*)ctx->h_in; s.Xout = gen ? ctx->xh : ctx->xh2; s.H = H; s.xs = c.xsplit; }
-            ctx->launches++;
-            const int sr = vv_solver_step_launch(&s, st);
-            if (sr == VV_RC_NO_FORM) return fail(ctx, "vv_diffusion_sample_general: solver.hip has no form for n = %d, latent_dim = %d", n, L);
-            if (sr < 0) return fail(ctx, "%s:%d launch failed (%d): hip error %d (%s)", __FILE__, __LINE__, sr, g_vv_launch_err, hipGetErrorString((hipError_t)g_vv_launch_err));
-            have_x = (sr == 1);
-            if (have_x) ctx->solver_fused++;
-            gen ^= 1;
-            if (ctx->probe_on) { char nm[64]; snprintf(nm, 64, "step %d z (general)", i); nan_probe(ctx, st, nm, gen ? ctx->zz2 : ctx->zz, (size_t)rows * L); }
-            continue;
-        }
-        // decode rows, bf16 mode: every step but the last ends with the fused seam (final layer + CFG + solver update + the next step's
-        // in-projection, headtail.hip), which leaves the next step's state in the other generation of (xh, zz, x0p)
-        const int hr = head_eval(ctx, st, p, i, gen ? ctx->zz2 : ctx->zz, ctx->temb + (size_t)i * H, ctx->eps, ctx->coef + i * 6, cfg, mod_i, sn, sht,
-                                 gen, have_x, cfg_rows);
-        if (hr < 0) return -1;
+        const HeadGen& cur = ctx->hg[gen];
+        const HeadStep s{.step = i, .z = cur.zz, .temb = ctx->temb + (size_t)i * H,
+                         .mod = batch_ada ? ctx->mod_all + (size_t)i * rows * MODW : nullptr,
+                         .sh_tiles = p.sh_tiles ? (const unsigned char*)ctx->p16_shift + (size_t)i * (HL + 1) * ctx->p16_shift_tile : nullptr,
+                         .eps_out = ctx->eps, .cur = cur, .nxt = ctx->hg[gen ^ 1], .have_x = have_x, .end = nullptr};
+        const StepDone d = p.solver_step ? step_general(ctx, st, p, r, s) : step_shipped(ctx, st, p, r, s);
+        if (d.rc < 0) return -1;
+        have_x = d.rc == 1;
+        gen ^= d.flipped;
         if (ctx->probe_on) {
+            const HeadGen& now = ctx->hg[gen];      // where the step left its result
             char nm[64];
-            snprintf(nm, 64, "step %d z%s", i, hr == 1 ? " (seam, next gen)" : ""); nan_probe(ctx, st, nm, (gen ^ (hr == 1)) ? ctx->zz2 : ctx->zz, (size_t)rows * L);
-            snprintf(nm, 64, "step %d x0p", i); nan_probe(ctx, st, nm, (gen ^ (hr == 1)) ? ctx->x0p2 : ctx->x0p, (size_t)n * L);
-            if (hr == 1) { snprintf(nm, 64, "step %d next xh", i); nan_probe(ctx, st, nm, (gen ^ 1) ? ctx->xh2 : ctx->xh, (size_t)rows * H); }
+            snprintf(nm, 64, "step %d z%s", i, p.solver_step ? " (general)" : have_x ? " (seam, next gen)" : ""); nan_probe(ctx, st, nm, now.zz, (size_t)rows * L);
+            if (!p.solver_step) { snprintf(nm, 64, "step %d x0p", i); nan_probe(ctx, st, nm, now.x0p, (size_t)n * L); }
+            if (!p.solver_step && have_x) { snprintf(nm, 64, "step %d next xh", i); nan_probe(ctx, st, nm, now.xh, (size_t)rows * H); }
         }
-        have_x = (hr == 1);
-        if (have_x) gen ^= 1;
     }
-    VVCHK(vv_copy_launch(latent_out, gen ? ctx->zz2 : ctx->zz, (size_t)n * L * 4, st));
+    VVCHK(vv_copy_launch(r.out, ctx->hg[gen].zz, (size_t)n * L * 4, st));
     return 0;
 }
 
+// The tail of every sampler entry point, behind its own checks and its key: eager, captured or replayed, then the NaN probe's report
+static int run_sampler(vv_ctx* ctx, hipStream_t st, const char* key, const SampleReq& r) {
+    ctx->launches = 0;
+    const int rc = graphed(ctx, key, st, [&]() { return sample_body(ctx, st, r); });
+    nan_probe_report(ctx, st, key);
+    return rc;
+}
+
 extern "C" int vv_diffusion_sample(vv_ctx* ctx, void* stream, int n, const float* cond_dev, const float* noise_dev, float cfg_scale, float* latent_out_dev) {
-    hipStream_t st = (hipStream_t)stream;
     if (ctx->n_steps < 1) return fail(ctx, "vv_set_schedule has not been called");
     if (n < 1 || n > 8) return fail(ctx, "vv_diffusion_sample: n must be in [1,8]");
     if (ctx->general_on) return fail(ctx, "the installed table is a general one (vv_set_schedule_general): sample with vv_diffusion_sample_general");
     if (ctx->sde_on) return fail(ctx, "the schedule is stochastic (vv_set_schedule_sde): sample with vv_diffusion_sample_sde and its per-step noise");
-    ctx->launches = 0;
     char key[128]; snprintf(key, 128, "samp:%d:%p:%p:%p:%a", n, (const void*)cond_dev, (const void*)noise_dev, (void*)latent_out_dev, cfg_scale);
-    const int rc = graphed(ctx, key, st, [&]() { return sample_body(ctx, st, n, cond_dev, noise_dev, cfg_scale, latent_out_dev); });
-    nan_probe_report(ctx, st, key);
-    return rc;
+    return run_sampler(ctx, (hipStream_t)stream, key, {n, cond_dev, noise_dev, nullptr, cfg_scale, nullptr, latent_out_dev});
 }
 
 // The stochastic solver: step_noise_dev = [n_steps][n][latent_dim] fp32, the variance noise scheduler.step() draws per solver step
 // (dpm_solver.py:994-997; the reference draws [2n][latent] and only the first n rows reach the next step, :703-704).
 extern "C" int vv_diffusion_sample_sde(vv_ctx* ctx, void* stream, int n, const float* cond_dev, const float* noise_dev,
                                        const float* step_noise_dev, float cfg_scale, float* latent_out_dev) {
-    hipStream_t st = (hipStream_t)stream;
     if (ctx->n_steps < 1) return fail(ctx, "vv_set_schedule_sde has not been called");
     if (n < 1 || n > 8) return fail(ctx, "vv_diffusion_sample_sde: n must be in [1,8]");
     if (ctx->general_on) return fail(ctx, "the installed table is a general one (vv_set_schedule_general): sample with vv_diffusion_sample_general");
     if (!ctx->sde_on) return fail(ctx, "the schedule is deterministic (vv_set_schedule): sample with vv_diffusion_sample");
     if (!step_noise_dev) return fail(ctx, "vv_diffusion_sample_sde: step_noise is null");
-    ctx->launches = 0;
     char key[160]; snprintf(key, 160, "sde:%d:%p:%p:%p:%p:%a", n, (const void*)cond_dev, (const void*)noise_dev, (const void*)step_noise_dev,
                             (void*)latent_out_dev, cfg_scale);
-    return graphed(ctx, key, st, [&]() { return sample_body(ctx, st, n, cond_dev, noise_dev, cfg_scale, latent_out_dev, step_noise_dev); });
+    return run_sampler(ctx, (hipStream_t)stream, key, {n, cond_dev, noise_dev, step_noise_dev, cfg_scale, nullptr, latent_out_dev});
 }
 
 // Either sampler with one guidance scale per utterance, cfg_rows_dev [n] fp32.  The kernels read the values at run time: the graph key
 // holds the POINTER, so rewriting the buffer between calls replays the same captured graph.
 extern "C" int vv_diffusion_sample_rows(vv_ctx* ctx, void* stream, int n, const float* cond_dev, const float* noise_dev,
                                         const float* step_noise_dev, const float* cfg_rows_dev, float* latent_out_dev) {
-    hipStream_t st = (hipStream_t)stream;
     if (ctx->n_steps < 1) return fail(ctx, "vv_set_schedule / vv_set_schedule_sde has not been called");
     if (n < 1 || n > 8) return fail(ctx, "vv_diffusion_sample_rows: n must be in [1,8]");
     if (ctx->general_on) return fail(ctx, "the installed table is a general one (vv_set_schedule_general): sample with vv_diffusion_sample_general");
     if (!cfg_rows_dev) return fail(ctx, "vv_diffusion_sample_rows: cfg_rows is null");
     if (ctx->sde_on && !step_noise_dev) return fail(ctx, "the schedule is stochastic (vv_set_schedule_sde): vv_diffusion_sample_rows needs its per-step noise");
     if (!ctx->sde_on && step_noise_dev) return fail(ctx, "the schedule is deterministic (vv_set_schedule): vv_diffusion_sample_rows takes no step noise");
-    ctx->launches = 0;
     char key[192]; snprintf(key, 192, "rows:%d:%p:%p:%p:%p:%p", n, (const void*)cond_dev, (const void*)noise_dev, (const void*)step_noise_dev,
                             (const void*)cfg_rows_dev, (void*)latent_out_dev);
-    const int rc = graphed(ctx, key, st, [&]() { return sample_body(ctx, st, n, cond_dev, noise_dev, 0.f, latent_out_dev, step_noise_dev, cfg_rows_dev); });
-    nan_probe_report(ctx, st, key);
-    return rc;
+    return run_sampler(ctx, (hipStream_t)stream, key, {n, cond_dev, noise_dev, step_noise_dev, 0.f, cfg_rows_dev, latent_out_dev});
 }
 
 // The sampler under a general table (vv_set_schedule_general): one guidance scale, or cfg_rows_dev [n] read at run time (the key
 // holds the POINTER); step_noise_dev as the table's kind demands.  Its own graph family, dropped by every vv_set_schedule* call.
 extern "C" int vv_diffusion_sample_general(vv_ctx* ctx, void* stream, int n, const float* cond_dev, const float* noise_dev,
                                            const float* step_noise_dev, float cfg_scale, const float* cfg_rows_dev, float* latent_out_dev) {
-    hipStream_t st = (hipStream_t)stream;
     if (ctx->n_steps < 1) return fail(ctx, "vv_set_schedule_general has not been called");
     if (n < 1 || n > 8) return fail(ctx, "vv_diffusion_sample_general: n must be in [1,8]");
     if (!ctx->general_on) return fail(ctx, "the installed table is a shipped one (vv_set_schedule / vv_set_schedule_sde): sample with vv_diffusion_sample, _sde or _rows");
     if (ctx->sde_on && !step_noise_dev) return fail(ctx, "the general table is stochastic: vv_diffusion_sample_general needs its per-step noise");
     if (!ctx->sde_on && step_noise_dev) return fail(ctx, "the general table is deterministic: vv_diffusion_sample_general takes no step noise");
-    ctx->launches = 0;
     char key[224]; snprintf(key, 224, "gen:%d:%p:%p:%p:%p:%p:%a", n, (const void*)cond_dev, (const void*)noise_dev, (const void*)step_noise_dev,
                             (const void*)cfg_rows_dev, (void*)latent_out_dev, cfg_rows_dev ? 0.f : cfg_scale);
-    const int rc = graphed(ctx, key, st, [&]() { return sample_body(ctx, st, n, cond_dev, noise_dev, cfg_scale, latent_out_dev, step_noise_dev, cfg_rows_dev, true); });
-    nan_probe_report(ctx, st, key);
-    return rc;
+    return run_sampler(ctx, (hipStream_t)stream, key, {n, cond_dev, noise_dev, step_noise_dev, cfg_scale, cfg_rows_dev, latent_out_dev});
 }
 
 extern "C" int vv_head_forward(vv_ctx* ctx, void* stream, int n, const float* noisy_dev, const float* t_host, const float* cond_dev, float* out_dev) {
@@ -366,7 +374,9 @@ extern "C" int vv_head_forward(vv_ctx* ctx, void* stream, int n, const float* no
     VVCHK(vv_silu_launch(ctx->tmp1, H, st));
     VVGemm g2 = mk_gemm(ctx->h_t2, ctx->tmp1, ctx->tmp1 + H, 1, H, H, H, H); GEMM(g2);
     VVGemm gc = mk_gemm(ctx->h_cond, cond_dev, ctx->cproj, n, H, H, H, H); GEMM(gc);
-    if (head_eval(ctx, st, head_plan(ctx, n, 1, false), 0, noisy_dev, ctx->tmp1 + H, out_dev)) return -1;
+    const HeadStep s{.step = 0, .z = noisy_dev, .temb = ctx->tmp1 + H, .mod = nullptr, .sh_tiles = nullptr, .eps_out = out_dev,
+                     .cur = ctx->hg[0], .nxt = ctx->hg[1], .have_x = false, .end = nullptr};
+    if (head_eval(ctx, st, head_plan(ctx, n, 1, false), s)) return -1;
     HIPCHK(ctx, hipStreamSynchronize(st));
     return 0;
 }

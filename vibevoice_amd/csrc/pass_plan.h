@@ -103,12 +103,13 @@ struct VVHeadPlan {
     int layers;                 // VV_HEAD_*
     bool seam;                  // decode rows, bf16 mode: every step but the last ends with the fused seam
     int final_stage;            // VV_FINAL_* of a step that does not
+    bool solver_step;           // the general solver table: a step ends with solver.hip's launch behind the final layer's plain store
 };
 
 // has_coef: the call has solver coefficients (the samplers; vv_head_forward has none and evaluates the head once)
-// general: the general solver table (vv_diffusion_sample_general): the modulations stay batched and the layers are chosen as for
+// solver_step: the general solver table (vv_diffusion_sample_general): the modulations stay batched and the layers are chosen as for
 // has_coef, but every step ends with the final layer's plain store -- the update is solver.hip's launch, never an epilogue or the seam
-inline VVHeadPlan vv_head_plan(int rows, int n_steps, int HF, int HL, int MODW, const VVHeadCaps& c, bool has_coef, bool general = false) {
+inline VVHeadPlan vv_head_plan(int rows, int n_steps, int HF, int HL, int MODW, const VVHeadCaps& c, bool has_coef, bool solver_step = false) {
     VVHeadPlan p;
     p.rows = rows; p.n_steps = n_steps;
     const bool batch_ada = has_coef && c.mod_all;
@@ -118,7 +119,8 @@ inline VVHeadPlan vv_head_plan(int rows, int n_steps, int HF, int HL, int MODW, 
     p.layers = vv_p16_rows(rows) && c.p16_ok && (HF % 32) == 0 ? VV_HEAD_P16 : VV_HEAD_GEMV;
     p.seam = has_coef && rows == 2 && c.head_tail;
     p.final_stage = p.layers == VV_HEAD_P16 && p.sh_tiles && has_coef && HL > 0 ? VV_FINAL_P16_CFG : has_coef ? VV_FINAL_GEMM_CFG : VV_FINAL_GEMM;
-    if (general) { p.sh_tiles = false; p.seam = false; p.final_stage = VV_FINAL_GEMM; }      // the packed shift tiles serve VV_FINAL_P16_CFG alone
+    p.solver_step = solver_step;
+    if (solver_step) { p.sh_tiles = false; p.seam = false; p.final_stage = VV_FINAL_GEMM; }      // the packed shift tiles serve VV_FINAL_P16_CFG alone
     return p;
 }
 inline int vv_head_final(const VVHeadPlan& p, int step) { return p.seam && step + 1 < p.n_steps ? VV_FINAL_SEAM : p.final_stage; }

@@ -122,6 +122,9 @@ class Engine:
         # a dedicated non-default stream: hipGraph capture is illegal on the null stream
         self.stream = torch.cuda.Stream(device=self.device)
         self.shared_from = share_from
+        self.max_ctx = (cfg.max_ctx + 127) // 128 * 128
+        self._n_steps = None
+        self.general_solver, self.stochastic, self.n_solver_steps = False, False, 0      # what set_num_steps leaves
         if share_from is not None:
             if share_from.device != self.device:
                 raise EngineError("a shared engine lives on its owner's device")
@@ -132,15 +135,11 @@ class Engine:
                     self.lib.vv_destroy(self._ctx)
                     self._ctx = C.c_void_p()
                 raise EngineError("vv_create_shared failed: " + msg)
-            self.max_ctx = (cfg.max_ctx + 127) // 128 * 128
-            self._n_steps = None
             self._loaded = set(share_from._loaded)
             return
         rc = self.lib.vv_create(C.byref(c), C.byref(self._ctx))
         if rc != 0:
             raise EngineError("vv_create failed: " + self._err())
-        self.max_ctx = (cfg.max_ctx + 127) // 128 * 128
-        self._n_steps = None
         self._loaded = set()
         # HF Qwen2RotaryEmbedding inv_freq, computed exactly as transformers does
         d = cfg.lm_head_dim
@@ -298,15 +297,13 @@ class Engine:
         if general:
             tv, coef = _schedule.make_general_table(cfg, n_steps, t_cast_bf16)
             stochastic = algorithm_type == "sde-dpmsolver++"
-            self._chk(self.lib.vv_set_schedule_general(self._ctx, len(tv), tv.ctypes.data_as(C.POINTER(C.c_float)),
-                                                       np.ascontiguousarray(coef).ctypes.data_as(C.POINTER(C.c_float)), int(stochastic),
-                                                       self._s), "vv_set_schedule_general")
         else:
             tv, coef = _schedule.make_table(n_steps, t_cast_bf16, algorithm_type)
             stochastic = coef.shape[1] == 6
-            fn, name = ((self.lib.vv_set_schedule_sde, "vv_set_schedule_sde") if stochastic else (self.lib.vv_set_schedule, "vv_set_schedule"))
-            self._chk(fn(self._ctx, n_steps, tv.ctypes.data_as(C.POINTER(C.c_float)),
-                         np.ascontiguousarray(coef).ctypes.data_as(C.POINTER(C.c_float)), self._s), name)
+        name = "vv_set_schedule_general" if general else "vv_set_schedule_sde" if stochastic else "vv_set_schedule"
+        fp = C.POINTER(C.c_float)
+        self._chk(getattr(self.lib, name)(self._ctx, len(tv), tv.ctypes.data_as(fp), np.ascontiguousarray(coef).ctypes.data_as(fp),
+                                          *((int(stochastic),) if general else ()), self._s), name)
         self._n_steps = key
         self.n_solver_steps = len(tv)
         self.stochastic = stochastic
@@ -469,32 +466,22 @@ class Engine:
         cfg_scale: one float for every row, or a 1-D fp32 device tensor of n guidance scales, one per utterance row.  The kernels read
         the tensor at run time and the graph is keyed by its address: rewrite the same buffer between calls and nothing is re-captured."""
         rows = isinstance(cfg_scale, torch.Tensor)
-        if getattr(self, "general_solver", False):          # routed by the installed table (set_num_steps(..., solver=...))
-            if rows and (cfg_scale.dim() != 1 or cfg_scale.shape[0] != n or cfg_scale.dtype != torch.float32 or cfg_scale.device != self.device
-                         or not cfg_scale.is_contiguous()):
-                raise ValueError(f"diffusion_sample: a per-row cfg_scale is a contiguous 1-D fp32 tensor of n = {n} entries on {self.device}")
-            if step_noise is not None:
-                assert step_noise.dtype == torch.float32 and step_noise.is_contiguous() and step_noise.shape[1] == n
-                assert step_noise.shape[0] >= self.n_solver_steps
-            self._chk(self.lib.vv_diffusion_sample_general(self._ctx, self._s, n, self._p(cond), self._p(noise), self._p(step_noise),
-                                                           0.0 if rows else float(cfg_scale), self._p(cfg_scale) if rows else C.c_void_p(),
-                                                           self._p(latent_out)), "vv_diffusion_sample_general")
-            return
-        if isinstance(cfg_scale, torch.Tensor):
-            if (cfg_scale.dim() != 1 or cfg_scale.shape[0] != n or cfg_scale.dtype != torch.float32 or cfg_scale.device != self.device
-                    or not cfg_scale.is_contiguous()):
-                raise ValueError(f"diffusion_sample: a per-row cfg_scale is a contiguous 1-D fp32 tensor of n = {n} entries on {self.device}")
-            if step_noise is not None:
-                assert step_noise.dtype == torch.float32 and step_noise.is_contiguous() and step_noise.shape[1] == n
-            self._chk(self.lib.vv_diffusion_sample_rows(self._ctx, self._s, n, self._p(cond), self._p(noise), self._p(step_noise),
-                                                        self._p(cfg_scale), self._p(latent_out)), "vv_diffusion_sample_rows")
-        elif step_noise is None:
-            self._chk(self.lib.vv_diffusion_sample(self._ctx, self._s, n, self._p(cond), self._p(noise),
-                                                   float(cfg_scale), self._p(latent_out)), "vv_diffusion_sample")
-        else:
+        if rows and (cfg_scale.dim() != 1 or cfg_scale.shape[0] != n or cfg_scale.dtype != torch.float32 or cfg_scale.device != self.device
+                     or not cfg_scale.is_contiguous()):
+            raise ValueError(f"diffusion_sample: a per-row cfg_scale is a contiguous 1-D fp32 tensor of n = {n} entries on {self.device}")
+        if step_noise is not None:      # every entry point reads n_solver_steps rows of n latents
             assert step_noise.dtype == torch.float32 and step_noise.is_contiguous() and step_noise.shape[1] == n
-            self._chk(self.lib.vv_diffusion_sample_sde(self._ctx, self._s, n, self._p(cond), self._p(noise), self._p(step_noise),
-                                                       float(cfg_scale), self._p(latent_out)), "vv_diffusion_sample_sde")
+            assert step_noise.shape[0] >= self.n_solver_steps
+        head, sn, out = (self._ctx, self._s, n, self._p(cond), self._p(noise)), self._p(step_noise), self._p(latent_out)
+        if self.general_solver:         # routed by the installed table (set_num_steps(..., solver=...))
+            name, args = "vv_diffusion_sample_general", (sn, 0.0 if rows else float(cfg_scale), self._p(cfg_scale) if rows else C.c_void_p(), out)
+        elif rows:
+            name, args = "vv_diffusion_sample_rows", (sn, self._p(cfg_scale), out)
+        elif step_noise is None:
+            name, args = "vv_diffusion_sample", (float(cfg_scale), out)
+        else:
+            name, args = "vv_diffusion_sample_sde", (sn, float(cfg_scale), out)
+        self._chk(getattr(self.lib, name)(*head, *args), name)
 
     def head_forward(self, noisy: torch.Tensor, t: float, cond: torch.Tensor, out: torch.Tensor):
         n = noisy.shape[0]
