@@ -333,6 +333,31 @@ int vv_tempo_rows(vv_ctx* ctx, void* stream, int tp, int n, const vv_tempo_row* 
  * window_dev [480] on the device; offsets_dev as above.  Bit-identical to the same signal pushed and flushed through vv_tempo_rows. */
 int vv_tempo_once(vv_ctx* ctx, void* stream, const float* window_dev, int P, int Q, int n, int n_in, const float* audio_dev, int ld_in,
                   float* out_dev, int ld_out, int* offsets_dev, int ld_off);
+/* ---- output level: a streaming gain and look-ahead peak limiter (vibevoice_amd/level.py defines it).  A: look-ahead and ramp, H: hold,
+ * in samples; g: the gain, c: the ceiling.  u = fl(g x) (non-finite: 0), r = 1 where |u| <= c else fl(c / |u|), q = floor(r 2^20),
+ * h[j] = min q[j - H .. j + A - 1], S[i] = sum h[i - A + 1 .. i], a = fl(float(S) / float(A 2^20)), y = clamp(fl(a u), -c, c): no
+ * output exceeds c, and a stream that never reaches c passes as fl(g x) bit for bit.  As many outputs as inputs.  What a stream emits
+ * does not depend on how its input was cut into pushes: a push emits every output whose A - 1 samples of look-ahead have arrived, the
+ * flush emits the rest.
+ * vv_level_set: configuration lv (0..3) of this context: A in [1,2047], H >= 0, H + 3 A - 3 < 8128, ceiling in (0,1], n_streams streams
+ * at their first sample.  Replaces what lv held.  Synchronous. */
+int vv_level_set(vv_ctx* ctx, int lv, int A, int H, float ceiling, int n_streams, void* stream);
+/* Back to the state after vv_level_set for n streams (stream_ids_host == NULL: all of them): history zeroed by a kernel on `stream`,
+ * input total 0, gain and flush mark cleared. */
+int vv_level_reset(vv_ctx* ctx, void* stream, int lv, int n, const int* stream_ids_host);
+/* One push of n <= 16 rows, ONE launch on `stream`: row i = n_in samples at audio_dev + i * ld_in for stream rows_host[i].stream
+ * (distinct) at gain rows_host[i].gain in (0,16] (a stream keeps the gain of its first push until its reset), flush != 0: the stream's
+ * last push.  Its outputs go to out_dev + i * ld_out (elements): out_fmt 0 = fp32, 1 = int16 with the arithmetic of vv_audio_to_pcm16
+ * over the row's own output (whose peak is <= ceiling <= 1: its rescale never fires).  n_out_host [n]: what each row emitted, computed
+ * on the host from the streams' input totals (no sync).  Refused with a message, nothing written, no state changed: as
+ * vv_resample_rows, a stream whose gain changes, and a row of more than 8128 - (H + 3 A - 3) input samples. */
+typedef struct vv_level_row { int stream; int n_in; int flush; float gain; } vv_level_row;
+int vv_level_rows(vv_ctx* ctx, void* stream, int lv, int n, const vv_level_row* rows_host, const float* audio_dev, int ld_in, void* out_dev,
+                  int ld_out, int out_fmt, int* n_out_host);
+/* Stateless: n whole signals of n_in samples (audio_dev + i * ld_in) -> n_in fp32 samples each (out_dev + i * ld_out).  Bit-identical
+ * to the same signal pushed and flushed through vv_level_rows. */
+int vv_level_once(vv_ctx* ctx, void* stream, int A, int H, float gain, float ceiling, int n, int n_in, const float* audio_dev, int ld_in,
+                  float* out_dev, int ld_out);
 /* acoustic_cache.set_to_zero + semantic_cache.set_to_zero for a slot (:542-546) */
 int vv_codec_reset(vv_ctx* ctx, void* stream, int slot);
 /* acoustic_connector(latent) [+ semantic_connector(sem)] (:667-669, :161); sem_dev may be NULL */

@@ -60,6 +60,11 @@ class VVTempoRow(C.Structure):
     _fields_ = [("stream", C.c_int), ("n_in", C.c_int), ("flush", C.c_int), ("P", C.c_int), ("Q", C.c_int)]
 
 
+class VVLevelRow(C.Structure):
+    """vv_level_row (include/vvhip.h): the stream, the input samples, the flush mark and the gain of one row of vv_level_rows"""
+    _fields_ = [("stream", C.c_int), ("n_in", C.c_int), ("flush", C.c_int), ("gain", C.c_float)]
+
+
 GEMV_REFUSED = 1     # VV_GEMV_REFUSED
 TEMPO_OVER_CAPACITY = 3     # VV_TEMPO_OVER_CAPACITY
 _SIGS = {
@@ -113,6 +118,10 @@ _SIGS = {
     "vv_tempo_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(VVTempoRow), _P, C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_int), _P,
                                 C.c_int]),
     "vv_tempo_once": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, _P, C.c_int]),
+    "vv_level_set": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P]),
+    "vv_level_reset": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "vv_level_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(VVLevelRow), _P, C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "vv_level_once": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int]),
     "vv_codec_reset": (C.c_int, [_P, _P, C.c_int]),
     "vv_connect": (C.c_int, [_P, _P, C.c_int, _P, _P, _P]),
     "vv_packed_bytes": (C.c_int64, [C.c_int, C.c_int]),

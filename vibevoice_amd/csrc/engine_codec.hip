@@ -498,7 +498,7 @@ extern "C" int vv_codec_reset(vv_ctx* ctx, void* stream, int slot) {
     return 0;
 }
 
-// ------------------------------------------------------------------ streaming row stages: what the resampler and the tempo change share
+// ------------------------------------------------------------------ streaming row stages: what the resampler, the tempo change and the level share
 // A stage keeps chunk-continuous streams (vv_ctx::RowStage) and takes up to 16 rows per push, one stream each.  `fn` is the entry
 // point's name: every refusal carries it.  `s` is null where the configuration is not set.  A third stage calls the same three.
 
@@ -747,5 +747,88 @@ extern "C" int vv_tempo_once(vv_ctx* ctx, void* stream, const float* window_dev,
         return fail(ctx, "vv_tempo_once: %lld blocks per row, the offset rows hold %d", (long long)((total + VV_TP_HS - 1) / VV_TP_HS), ld_off);
     if (!window_dev || !audio_dev || !out_dev) return fail(ctx, "vv_tempo_once: null window / audio / out pointer");
     VVCHK(vv_tempo_once_launch(window_dev, P, Q, n, n_in, audio_dev, ld_in, out_dev, ld_out, offsets_dev, ld_off, (hipStream_t)stream));
+    return 0;
+}
+
+// ------------------------------------------------------------------ output level (kernels: level.hip; vibevoice_amd/level.py defines it)
+// Outputs a stream has emitted before its flush once `total` input samples have arrived: every sample whose A - 1 samples of look-ahead
+// are there.  vibevoice_amd/level.py (emitted) is the same arithmetic.
+static int64_t lv_emitted(int64_t total, int A) { return std::max<int64_t>(0, total - (A - 1)); }
+
+static bool lv_params_ok(int A, int H, float c) {
+    return A >= 1 && A <= VV_LV_MAX_A && H >= 0 && (int64_t)H + 3 * (int64_t)A - 3 < VV_LV_BUF && c > 0.f && c <= 1.0f;
+}
+static bool lv_gain_ok(float g) { return g > 0.f && g <= 16.0f; }       // a NaN compares false
+
+extern "C" int vv_level_set(vv_ctx* ctx, int lv, int A, int H, float ceiling, int n_streams, void* stream) {
+    VV_SHARED;
+    if (lv < 0 || lv >= vv_ctx::N_LEVELS) return fail(ctx, "vv_level_set: configuration %d out of range [0,%d)", lv, vv_ctx::N_LEVELS);
+    if (!lv_params_ok(A, H, ceiling))
+        return fail(ctx, "vv_level_set: A = %d must be in [1,%d], H = %d >= 0 with H + 3 A - 3 < %d, ceiling = %g in (0,1]", A, VV_LV_MAX_A, H, VV_LV_BUF,
+                    (double)ceiling);
+    if (n_streams < 1 || n_streams > 65536) return fail(ctx, "vv_level_set: n_streams = %d must be in [1,65536]", n_streams);
+    vv_ctx::Level& l = ctx->lv[lv];
+    HIPCHK(ctx, hipStreamSynchronize((hipStream_t)stream));      // pushes that still read what is replaced
+    dfree(ctx, l.hist);
+    l = vv_ctx::Level();
+    // one word more than the rows: a configuration with H + 2 A - 2 = 0 still holds a buffer, which marks it as set
+    float* hist = (float*)dalloc(ctx, ((size_t)n_streams * (H + 2 * A - 2) + 1) * 4, true);
+    if (!hist) return -1;
+    l.A = A; l.H = H; l.c = ceiling; l.n_streams = n_streams; l.hist = hist;
+    l.total.assign(n_streams, 0); l.flushed.assign(n_streams, 0); l.gain.assign(n_streams, 0.f);
+    return 0;
+}
+
+extern "C" int vv_level_reset(vv_ctx* ctx, void* stream, int lv, int n, const int* stream_ids_host) {
+    VV_SHARED;
+    vv_ctx::Level* l = lv >= 0 && lv < vv_ctx::N_LEVELS && ctx->lv[lv].hist ? &ctx->lv[lv] : nullptr;
+    return stage_reset(ctx, "vv_level_reset", l, lv, n, stream_ids_host,
+                       [&](const int* ids, int k) { return vv_level_reset_launch(l->hist, l->H + 2 * l->A - 2, l->n_streams, ids, k, (hipStream_t)stream); },
+                       [&](int id) { l->gain[id] = 0.f; });
+}
+
+extern "C" int vv_level_rows(vv_ctx* ctx, void* stream, int lv, int n, const vv_level_row* rows_host, const float* audio_dev, int ld_in,
+                             void* out_dev, int ld_out, int out_fmt, int* n_out_host) {
+    VV_SHARED;
+    vv_ctx::Level* lp = lv >= 0 && lv < vv_ctx::N_LEVELS && ctx->lv[lv].hist ? &ctx->lv[lv] : nullptr;
+    const RowCheck ck{ctx, "vv_level_rows", lp, audio_dev, ld_in};
+    VVTRY(ck.head(lv, n, rows_host, out_dev, n_out_host, out_fmt));
+    vv_ctx::Level& l = *lp;
+    const int nh = l.H + 2 * l.A - 2, max_in = VV_LV_BUF - nh - (l.A - 1);
+    VVLvRows kr;
+    memset(&kr, 0, sizeof(kr));
+    for (int i = 0; i < n; ++i) {
+        const vv_level_row& q = rows_host[i];
+        VVTRY(ck.stream(rows_host, i));
+        VVTRY(ck.input(i, q.n_in));
+        if (q.n_in > max_in) return fail(ctx, "vv_level_rows: row %d brings %d samples, one push takes at most %d per row; push it in pieces", i, q.n_in, max_in);
+        if (!lv_gain_ok(q.gain)) return fail(ctx, "vv_level_rows: row %d: gain %g must lie in (0,16]", i, (double)q.gain);
+        if (l.gain[q.stream] != 0.f && l.gain[q.stream] != q.gain)
+            return fail(ctx, "vv_level_rows: stream %d runs at gain %g since its first push; reset it before it changes to %g", q.stream,
+                        (double)l.gain[q.stream], (double)q.gain);
+        VVTRY(ck.open(q.stream));
+        const int64_t before = l.total[q.stream], after = before + q.n_in;
+        const int64_t o0 = lv_emitted(before, l.A), o1 = q.flush ? after : lv_emitted(after, l.A);
+        const int64_t n_out = o1 - o0;
+        if (n_out > ld_out) return fail(ctx, "vv_level_rows: row %d emits %lld samples, the output rows hold %d", i, (long long)n_out, ld_out);
+        kr.r[i].stream = q.stream; kr.r[i].n_in = q.n_in; kr.r[i].n_out = (int)n_out; kr.r[i].b0 = (int)(o0 - before + nh); kr.r[i].gain = q.gain;
+    }
+    VVTRY(stage_launch(ctx, l, rows_host, n, kr, n_out_host, [&] {
+        return vv_level_rows_launch(&kr, n, l.A, l.H, l.c, l.hist, l.n_streams, audio_dev, ld_in, out_dev, ld_out, out_fmt, (hipStream_t)stream); }));
+    for (int i = 0; i < n; ++i) l.gain[rows_host[i].stream] = rows_host[i].gain;
+    return 0;
+}
+
+extern "C" int vv_level_once(vv_ctx* ctx, void* stream, int A, int H, float gain, float ceiling, int n, int n_in, const float* audio_dev, int ld_in,
+                             float* out_dev, int ld_out) {
+    VV_SHARED;
+    if (!lv_params_ok(A, H, ceiling))
+        return fail(ctx, "vv_level_once: A = %d must be in [1,%d], H = %d >= 0 with H + 3 A - 3 < %d, ceiling = %g in (0,1]", A, VV_LV_MAX_A, H, VV_LV_BUF,
+                    (double)ceiling);
+    if (!lv_gain_ok(gain)) return fail(ctx, "vv_level_once: gain %g must lie in (0,16]", (double)gain);
+    if (n < 1 || n > 65535 || n_in < 1 || n_in > ld_in) return fail(ctx, "vv_level_once: n = %d in [1,65535], n_in = %d in [1, ld_in = %d]", n, n_in, ld_in);
+    if (n_in > ld_out) return fail(ctx, "vv_level_once: %d output samples per row, the output rows hold %d", n_in, ld_out);
+    if (!audio_dev || !out_dev) return fail(ctx, "vv_level_once: null audio / out pointer");
+    VVCHK(vv_level_once_launch(A, H, gain, ceiling, n, n_in, audio_dev, ld_in, out_dev, ld_out, (hipStream_t)stream));
     return 0;
 }

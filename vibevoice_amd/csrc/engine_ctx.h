@@ -190,6 +190,11 @@ struct vv_ctx {
     struct Tempo : RowStage { float* window = nullptr; float* hist = nullptr; int* dstate = nullptr; std::vector<int> P, Q; };
     static constexpr int N_TEMPOS = 4;
     Tempo tp[N_TEMPOS];
+    // streaming output levels (vv_level_set, engine_codec.hip; kernels: level.hip): look-ahead A, hold H, ceiling c, per stream H + 2 A - 2
+    // history samples on the device and on the host its gain (fixed by its first push, 0 before).  Kept like the resamplers.
+    struct Level : RowStage { int A = 0, H = 0; float c = 0.f; float* hist = nullptr; std::vector<float> gain; };
+    static constexpr int N_LEVELS = 4;
+    Level lv[N_LEVELS];
     int64_t launches = 0;
     int64_t solver_fused = 0;         // general-path step ends that carried the next in-projection, last recorded body (vv_stat 8)
     int64_t seam_launches = 0;        // head-tail seam launches the last recorded sampler body issued (vv_stat 6; a replay keeps its capture's count)

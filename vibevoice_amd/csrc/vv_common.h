@@ -187,6 +187,14 @@ constexpr int VV_TP_PAD = 896;             // zeros behind the chunk: a flush re
 constexpr int VV_TP_BUF = VV_TP_HIST + VV_TP_MAX_IN + VV_TP_PAD;
 constexpr int VV_TP_MAX_BLOCKS = 96;       // blocks per staged buffer: a block advances >= 120 input samples, (MAX_IN + PAD) / 120 < 96
 
+// ---- streaming output level (level.hip): one row of a push, passed by value in the kernel arguments ----
+// The host keeps each stream's 64-bit input total and its gain; the row's staging buffer is [H + 2 A - 2 history | n_in chunk | A - 1
+// zeros], its first output sits at index b0 = (first output's signal index) - total + H + 2 A - 2 of it, n_out outputs follow.
+struct VVLvRow { int stream, n_in, n_out, b0; float gain; };
+struct VVLvRows { VVLvRow r[16]; };
+constexpr int VV_LV_BUF = 8128;            // samples of a row's staging buffer (two 32-bit words each in LDS; vibevoice_amd/level.py: BUF)
+constexpr int VV_LV_MAX_A = 2047;          // keeps the window sums below 2^31
+
 // Raise the dynamic-LDS limit of one or more kernels above the 64 KiB default; returns the first error.  A launcher calls it as
 // the initialiser of a function-local `static const hipError_t`: C++11 runs that initialiser once per process and makes
 // concurrent first calls wait for it (generate_interleaved and fork() drive two contexts from two host threads).

@@ -120,4 +120,9 @@ int vv_tempo_rows_launch(const VVTpRows* rows, int n, const float* window, float
 int vv_tempo_once_launch(const float* window, int P, int Q, int n, int n_in, const float* x, int ld_in, float* out, int ld_out, int* offsets,
                          int ld_off, hipStream_t s);
 int vv_tempo_reset_launch(float* hist, int* dstate, int n_streams, const int* ids, int n, hipStream_t s);
+// level.hip.  A look-ahead / ramp, H hold (samples), c the ceiling; hist [n_streams][nh], nh = H + 2 A - 2.
+int vv_level_rows_launch(const VVLvRows* rows, int n, int A, int H, float c, float* hist, int n_streams, const float* x, int ld_in, void* out,
+                         int ld_out, int pcm16, hipStream_t s);
+int vv_level_once_launch(int A, int H, float g, float c, int n, int n_in, const float* x, int ld_in, float* out, int ld_out, hipStream_t s);
+int vv_level_reset_launch(float* hist, int nh, int n_streams, const int* ids, int n, hipStream_t s);
 }

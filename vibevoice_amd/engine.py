@@ -535,7 +535,7 @@ class Engine:
                   "vv_audio_to_pcm16")
 
     # ------------------------------------------------------------------ streaming row stages and their whole-signal forms
-    _STAGE_USED = {"resampler": "_rs_used", "tempo": "_tp_used"}
+    _STAGE_USED = {"resampler": "_rs_used", "tempo": "_tp_used", "level": "_lv_used"}
 
     def _take_stage_slot(self, kind, make):
         """make(k) for the first free k of this engine's four `kind` configurations; the stage's close() gives k back"""
@@ -613,6 +613,27 @@ class Engine:
                                              self._p(offs) if offs is not None else None, max(nblk, 1)), "vv_tempo_once")
         out, offs = self._whole("time_stretch", audio, n_out, run, stream, aux_cols=max(nblk, 1) if return_offsets else 0)
         return (out, offs[:, :nblk].reshape(out.shape[:-1] + (nblk,))) if return_offsets else out
+
+    # output level (level.py, csrc/level.hip)
+    def level(self, n_streams: int, rate: int = 24000, ceiling_db: float = -1.0) -> "Level":
+        """A streaming gain and look-ahead peak limiter at `rate` Hz under the ceiling `ceiling_db`, with n_streams independent streams,
+        each at its own volume, in one of this engine's four level configurations (close() it to give the configuration back)."""
+        return self._take_stage_slot("level", lambda k: Level(self, k, n_streams, rate, ceiling_db))
+
+    def apply_level(self, audio: torch.Tensor, volume_db: float = 0.0, ceiling_db: float = -1.0, rate: int = 24000, stream=None) -> torch.Tensor:
+        """Whole signals at another level: audio [samples] or [n, samples] (at `rate` Hz, any float dtype, any device) -> fp32 on the
+        engine's device, as many samples: volume_db of gain, then a look-ahead peak limiter that keeps every sample within ceiling_db
+        of full scale (5 ms of look-ahead and ramp, 50 ms of hold), the definition of vibevoice_amd/level.py.  A signal that never
+        reaches the ceiling comes back as fl(gain * x) bit for bit.  Stateless; runs on `stream` (default: the current torch stream
+        of the device)."""
+        from . import level as _lv
+        A, H = _lv.params(rate)
+        g, c = float(_lv.gain_of(volume_db)), float(_lv.ceiling_of(ceiling_db))
+        n_out = int(audio.shape[-1]) if audio.dim() else 0
+
+        def run(st, nn, n_in, x, out, _):
+            self._chk(self.lib.vv_level_once(self._ctx, st, A, H, g, c, nn, n_in, self._p(x), n_in, self._p(out), n_out), "vv_level_once")
+        return self._whole("apply_level", audio, n_out, run, stream)[0]
 
     def codec_reset(self, slot: int):
         self._chk(self.lib.vv_codec_reset(self._ctx, self._s, slot), "vv_codec_reset")
@@ -927,7 +948,7 @@ class TempoCapacityError(EngineError):
 
 
 class _RowStage:
-    """What the streaming row stages share (Tempo, Resampler; a third stage derives from this too): n_streams chunk-continuous streams in
+    """What the streaming row stages share (Tempo, Resampler, Level): n_streams chunk-continuous streams in
     one of the engine's configurations, pushed up to 16 rows a launch.  A stage supplies KIND (Engine._STAGE_USED), its row struct ROW
     and how push() fills it, its C entry points ROWS_FN / RESET_FN, counts(), max_out() and take()."""
     KIND = ROW = ROWS_FN = RESET_FN = None
@@ -1115,4 +1136,54 @@ class Resampler(_RowStage):
         rows = (self.ROW * max(n, 1))()
         for i in range(n):
             rows[i].stream, rows[i].n_in, rows[i].flush = ids[i], nin[i], int(fl[i])
+        return out, self._launch(audio, samples, ids, nin, rows, out, pcm16, stream)
+
+
+class Level(_RowStage):
+    """One streaming level configuration of an engine (Engine.level): n_streams chunk-continuous streams at `rate` Hz under one ceiling,
+    each at the volume of its first push until its reset (which clears the volume with the rest).  What a stream delivers does not
+    depend on how its input was cut into pushes (vibevoice_amd/level.py): the concatenation of its pushes and its flush equals
+    Engine.apply_level() of the concatenated input, bit for bit in float mode, as many samples.  delay_samples: the input samples
+    (A - 1, 5 ms less one) a stream holds back until its next push; max_in: the input samples one row of a push may bring."""
+    KIND, ROW, ROWS_FN, RESET_FN = "level", _lib.VVLevelRow, "vv_level_rows", "vv_level_reset"
+    NO_ROWS = (0,)                                        # one launch, which vv_level_rows refuses by name
+
+    def __init__(self, engine: Engine, slot: int, n_streams: int, rate: int = 24000, ceiling_db: float = -1.0):
+        from . import level as _lv
+        super().__init__(engine, slot, n_streams)
+        self.rate, self.ceiling_db = int(rate), float(ceiling_db)
+        self.A, self.H = _lv.params(rate)
+        self.ceiling = float(_lv.ceiling_of(ceiling_db))
+        self.delay_samples, self.max_in = _lv.delay_samples(self.A), _lv.push_width(self.A, self.H)
+        engine._chk(engine.lib.vv_level_set(engine._ctx, slot, self.A, self.H, self.ceiling, self.n_streams, engine._s), "vv_level_set")
+
+    def counts(self, stream_id: int, n_in: int, flush: bool = False) -> int:
+        """samples a push of n_in samples to stream_id would emit now (host integers, no device sync)"""
+        from . import level as _lv
+        return _lv.counts(self.A, self.total[stream_id], n_in, flush)[1]
+
+    def max_out(self, n_in: int) -> int:
+        """upper bound of what any push of up to n_in samples emits, the flush included"""
+        return int(n_in) + self.delay_samples
+
+    def take(self, ids, remaining, flush=False):
+        return min(self.max_in, max(remaining))
+
+    def push(self, audio: Optional[torch.Tensor], stream_ids: Sequence[int], volumes_db=0.0, flush=False, out: Optional[torch.Tensor] = None,
+             n_in=None, stream=None, pcm16: bool = False):
+        """Row i of audio [n, samples] (contiguous fp32 on the engine's device; None where no row brings samples) goes to stream
+        stream_ids[i] (distinct) at volumes_db[i] (or one volume for all rows; a stream keeps the volume of its first push); n_in:
+        samples of each row that count (default: all), flush: bool or one per row -- a stream's last push, after which it takes no
+        more until reset().  -> (out, counts): out[i, :counts[i]] is what row i emitted, fp32, or int16 under pcm16 (the arithmetic of
+        Engine.audio_to_pcm16 over the row's own output, in the same launch; its rescale never fires, the peak is within the
+        ceiling).  out: a contiguous [>= n, capacity] tensor of that dtype to write into (default: a new one of max_out(samples)
+        columns).  One launch per 16 rows on `stream` (default: the device's current torch stream); the counts are host integers,
+        nothing waits for the device.  A row of more than max_in samples is refused: push it in pieces of take()."""
+        from . import level as _lv
+        ids, samples, nin, fl, vols = self._args(audio, stream_ids, flush, n_in, volumes_db=volumes_db)
+        gains = [float(_lv.gain_of(v)) for v in vols]
+        n, out = len(ids), self._out(out, len(ids), nin, pcm16)
+        rows = (self.ROW * max(n, 1))()
+        for i in range(n):
+            rows[i].stream, rows[i].n_in, rows[i].flush, rows[i].gain = ids[i], nin[i], int(fl[i]), gains[i]
         return out, self._launch(audio, samples, ids, nin, rows, out, pcm16, stream)

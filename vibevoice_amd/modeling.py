@@ -593,6 +593,13 @@ class _AudioRates:
         time_stretch(out.speech_outputs[0], 1.2); in front of resample_audio where both are wanted.  generate() itself has no rate input."""
         return self.engine.time_stretch(audio, speed)
 
+    def apply_level(self, audio: torch.Tensor, volume_db: float = 0.0, ceiling_db: float = -1.0, rate: int = 24000) -> torch.Tensor:
+        """audio [samples] or [n, samples] at `rate` Hz -> fp32 on the engine's device, as many samples: volume_db of gain (-40 .. +24),
+        then a look-ahead peak limiter that keeps every sample within ceiling_db (-20 .. 0) of full scale (Engine.apply_level).  For
+        speech_outputs after the fact -- apply_level(out.speech_outputs[0], 6.0); behind time_stretch and resample_audio where those
+        are wanted, at the rate they deliver.  generate() itself has no level input."""
+        return self.engine.apply_level(audio, volume_db, ceiling_db, int(rate))
+
 
 class VibeVoiceForConditionalGenerationInference(_AudioRates):
     """Drop-in for the reference class on the generate() path, backed by libvvhip.so."""

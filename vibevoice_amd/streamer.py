@@ -26,7 +26,16 @@ bit for bit in float mode.  A sample holds back at most 640 input samples (26.7 
 block of 240 delivers nothing for that row; end(indices) flushes the tempo tail, then the resampler's.  Device chunks need an engine
 (as above), CPU chunks go through tempo.HostTempo.
 
-The device stages form one chain (self._stages, _put_device): the tempo change, then the resampler, whichever exist, each an engine
+`volume_db=V` (a float in [-40, +24], or one per sample index) and `ceiling_db=C` (in [-20, 0]) set the output level: a gain and a
+look-ahead peak limiter (Engine.level, csrc/level.hip; vibevoice_amd/level.py is the definition), the last stage, at the delivered rate.
+The stage exists when ceiling_db is given or any volume_db is not 0 (the ceiling is then -1 dB unless given; an index at 0 dB still gets
+the limiter); float chunks arrive as fp32.  Chunk-continuous like the other two: per sample, the concatenated chunks equal
+Engine.apply_level() of what the stages in front deliver, as many samples, bit for bit in float mode.  No delivered sample exceeds
+the ceiling, so under pcm16 the per-chunk rescale of the 16-bit rule never fires for such a stream: a loud passage is turned down
+smoothly across chunk boundaries.  A sample holds back 5 ms less one sample until its next chunk; end(indices) flushes that tail last.
+Device chunks need an engine (as above), CPU chunks go through level.HostLevel.
+
+The device stages form one chain (self._stages, _put_device): the tempo change, the resampler, the level, whichever exist, each an engine
 row stage (engine._RowStage) pushed on the producing stream; the last one writes the ring slot's staging, as int16 under pcm16 (over
 each row's own chunk), and with no stage the 16-bit conversion does, else the chunk itself is copied.  A chunk longer than one push of
 a stage takes (stage.take()) is pushed in pieces and arrives as several.
@@ -99,10 +108,31 @@ def _speeds_of(speed, batch_size):
     return speeds
 
 
+def _volumes_of(volume_db, ceiling_db, batch_size):
+    """AudioStreamer's level arguments as (one volume in dB per sample index, the ceiling in dB); None where they ask for no level
+    stage (no ceiling, and no volume or 0 dB everywhere)"""
+    from .level import DEFAULT_CEILING_DB, ceiling_of, gain_of
+    vols = [0.0] * batch_size
+    if volume_db is not None:
+        vols = [float(volume_db)] * batch_size if not hasattr(volume_db, "__len__") else [float(v) for v in volume_db]
+        if len(vols) != batch_size:
+            raise ValueError(f"AudioStreamer(volume_db=...): one value, or one per sample index ({batch_size}), got {len(vols)}")
+        for v in vols:
+            gain_of(v)                                        # refuses what lies outside [-40, +24]
+    if ceiling_db is None and all(v == 0.0 for v in vols):
+        return None
+    ceiling = DEFAULT_CEILING_DB if ceiling_db is None else float(ceiling_db)
+    ceiling_of(ceiling)                                       # refuses what lies outside [-20, 0]
+    return vols, ceiling
+
+
 class AudioStreamer:
     def __init__(self, batch_size: int, stop_signal=None, timeout: Optional[float] = None, ring_slots: int = 8, pcm16=None,
-                 sample_rate: Optional[int] = None, engine=None, speed=None):
+                 sample_rate: Optional[int] = None, engine=None, speed=None, volume_db=None, ceiling_db=None):
         self.batch_size = batch_size
+        self._level = _volumes_of(volume_db, ceiling_db, batch_size)    # (volumes in dB, one per sample index; ceiling in dB), or None
+        self._lv = None                            # Engine.level (device chunks), one stream per sample index
+        self._lv_host = {}                         # sample index -> level.HostLevel (CPU chunks)
         self._speeds = _speeds_of(speed, batch_size)   # one per sample index, or None: no tempo stage anywhere
         self._tp = None                            # Engine.tempo (device chunks), one stream per sample index
         self._tp_host = {}                         # sample index -> tempo.HostTempo (CPU chunks)
@@ -119,8 +149,12 @@ class AudioStreamer:
             eng = engine if engine is not None else pcm16
             if eng is not None:
                 self._tp = eng.tempo(batch_size)
+        if self._level is not None:
+            eng = engine if engine is not None else pcm16
+            if eng is not None:
+                self._lv = eng.level(batch_size, rate=self.sample_rate, ceiling_db=self._level[1])
         # the device stages between a chunk and the ring, in the order they run; a further stage takes its place in this list
-        self._stages = [st for st in (self._tp, self._rs) if st is not None]
+        self._stages = [st for st in (self._tp, self._rs, self._lv) if st is not None]
         self.stop_signal = stop_signal
         self.timeout = timeout
         self.audio_queues = [self._make_queue() for _ in range(batch_size)]
@@ -154,7 +188,7 @@ class AudioStreamer:
         if not audio_chunks.is_cuda:
             for row, idx in live:
                 chunk = audio_chunks[row].detach().clone()
-                if self.sample_rate != SOURCE_RATE or self._speeds is not None:
+                if self.sample_rate != SOURCE_RATE or self._speeds is not None or self._level is not None:
                     chunk = self._host_chunk(idx, chunk)
                     if chunk is None:
                         continue
@@ -166,10 +200,13 @@ class AudioStreamer:
         if self._speeds is not None and self._tp is None:
             raise ValueError("AudioStreamer(speed=...): device chunks are stretched on the device and need an engine "
                              "(pcm16=engine for 16-bit chunks, engine=engine for float chunks)")
+        if self._level is not None and self._lv is None:
+            raise ValueError("AudioStreamer(volume_db=... / ceiling_db=...): device chunks are levelled on the device and need an engine "
+                             "(pcm16=engine for 16-bit chunks, engine=engine for float chunks)")
         self._put_device(audio_chunks, live)
 
     def _host_chunk(self, idx, chunk):
-        """a CPU chunk of sample idx (None: its flush) at the streamer's speed and rate, None where it completes no output sample"""
+        """a CPU chunk of sample idx (None: its flush) at the streamer's speed, rate and level, None where it completes no output sample"""
         flush = chunk is None
         y = None
         if not flush:
@@ -190,6 +227,14 @@ class AudioStreamer:
                     return None
                 h = self._rs_host[idx] = HostResampler(SOURCE_RATE, self.sample_rate)
             y = h.push(y if y is not None else torch.zeros(0), flush=flush)
+        if self._level is not None:
+            from .level import HostLevel
+            lv = self._lv_host.get(idx)
+            if lv is None:
+                if y is None:
+                    return None
+                lv = self._lv_host[idx] = HostLevel(self._level[0][idx], self._level[1], self.sample_rate)
+            y = lv.push(y if y is not None else torch.zeros(0), flush=flush)
         if y is None or not y.shape[0]:
             return None
         return y.reshape(self._lead + (y.shape[0],))
@@ -237,6 +282,8 @@ class AudioStreamer:
         stage, n, ends = self._stages[k], len(ids), k == len(self._stages) - 1
         dev = stage.engine.device
         kw = {"speeds": [self._speeds[idx] for idx in ids]} if stage is self._tp else {}
+        if stage is self._lv:
+            kw = {"volumes_db": [self._level[0][idx] for idx in ids]}
         dt = torch.int16 if ends and self._pcm_engine is not None else torch.float32
         at = 0
         while True:                                        # one push, but for a chunk longer than it takes
@@ -316,7 +363,7 @@ class AudioStreamer:
         else:
             idxs = [int(i.item()) if torch.is_tensor(i) else int(i) for i in sample_indices]
         idxs = [idx for idx in dict.fromkeys(idxs) if idx < self.batch_size and not self.finished_flags[idx]]
-        if (self.sample_rate != SOURCE_RATE or self._speeds is not None) and idxs and not self._closed:
+        if (self.sample_rate != SOURCE_RATE or self._speeds is not None or self._level is not None) and idxs and not self._closed:
             self._flush_tails(idxs)
         for idx in idxs:
             self.finished_flags[idx] = True
@@ -396,6 +443,8 @@ class AudioStreamer:
                 self._rs.close()                         # the engine's resampler configuration is free for the next streamer
             if self._tp is not None:
                 self._tp.close()                         # ... and its tempo configuration
+            if self._lv is not None:
+                self._lv.close()                         # ... and its level configuration
 
     # ---- consumer side ----
     def __iter__(self):
@@ -460,10 +509,10 @@ class AsyncAudioStreamer(AudioStreamer):
         async for chunk in streamer.get_stream(0): ...      async for batch in streamer: ..."""
 
     def __init__(self, batch_size: int, stop_signal=None, timeout: Optional[float] = None, ring_slots: int = 8, pcm16=None,
-                 sample_rate: Optional[int] = None, engine=None, speed=None):
+                 sample_rate: Optional[int] = None, engine=None, speed=None, volume_db=None, ceiling_db=None):
         self.loop = asyncio.get_running_loop()
         super().__init__(batch_size, stop_signal, timeout, ring_slots=ring_slots, pcm16=pcm16, sample_rate=sample_rate, engine=engine,
-                         speed=speed)
+                         speed=speed, volume_db=volume_db, ceiling_db=ceiling_db)
 
     def _make_queue(self):
         return asyncio.Queue()
