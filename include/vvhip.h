@@ -409,6 +409,18 @@ typedef struct vv_gemv_case_args {
     const float* cfg_rows;      /* VV_EPI_CFG_DPM: [n_cfg] one guidance scale per utterance row, or NULL (cfg for every row) */
 } vv_gemv_case_args;
 int vv_gemv_case(void* stream, const vv_gemv_case_args* args, int xsplit, int* form_out);
+/* W13: the lossless 13-bit twin of a packed bf16 matrix (format: vibevoice_amd/w13.py, csrc/vv_w13.h), N % 16 == 0, K % 128 == 0.
+ * vv_w13_twin_bytes: size of a twin (planes, then per tile row a scale word and an ok word, then the folded ok word), 0 for a shape
+ * without one.  vv_w13_pack_matrix: packed_dev (a vv_pack_matrix output) -> twin_dev; the kernel decodes what it wrote and compares
+ * it with the source bit for bit -- that is the ok word.  vv_w13_unpack_matrix: twin_dev -> packed fragments (the same decoder).
+ * vv_w13_gemv_case: ONE launch of the W13 form (mr rows, wpb waves; csrc/gemv_plan.h: vv_gemv_w13_forms) on the operands of args:
+ * over the twins (twin_dev, twin2_dev for SwiGLU's second matrix), or with twin_dev == NULL the same form over the bf16 fragments --
+ * the two must agree bit for bit.  Returns VV_GEMV_REFUSED where the form or the shape does not exist.  New surface (tests); the
+ * engine keeps twins of the diffusion head's gate / up / down matrices itself (VVHIP_W13=0: none). */
+int64_t vv_w13_twin_bytes(int N, int K);
+int vv_w13_pack_matrix(void* stream, const void* packed_dev, void* twin_dev, int N, int K);
+int vv_w13_unpack_matrix(void* stream, const void* twin_dev, void* packed_dev, int N, int K);
+int vv_w13_gemv_case(void* stream, const vv_gemv_case_args* args, const void* twin_dev, const void* twin2_dev, int mr, int wpb);
 /* The prompt-prefill GEMM (bf16-activation mode): x_dev fp32 [T][K] is packed (RMS-normalised when nw_dev != NULL) into
  * xp_scratch (vv_packed_bytes(T, K)); epi 0/1/4 (store / bias / residual) -> fp32 y_dev [T][N]; epi 3 (SwiGLU: w = gate,
  * w2 = up) -> packed bf16 in yp_scratch (vv_packed_bytes(T, N), zero-initialised), unpacked into y_dev.  K % 8 == 0, N % 4 == 0.
@@ -444,7 +456,10 @@ int vv_profile_replay_family(vv_ctx* ctx, void* stream, int family, int reps, in
  * replay keeps the count of its capture;
  * 7: bytes of device memory held by the base snapshots of LoRA-merged parameters (vv_lora_merge);
  * 8: step ends of the general sampler (vv_diffusion_sample_general) that carried the next step's in-projection in the same launch,
- * in the last recorded sampler body -- n_steps - 1 where solver.hip's rule holds, 0 where the update ran alone */
+ * in the last recorded sampler body -- n_steps - 1 where solver.hip's rule holds, 0 where the update ran alone;
+ * 9: matrices of the diffusion head (gate, up and down of every layer) that a one-utterance sampler streams as W13 now: their twins
+ * decoded exactly on the device; gate and up of a layer count together or not at all.  0 with VVHIP_W13=0, in the exact modes and at
+ * widths without whole groups */
 int64_t vv_stat(vv_ctx* ctx, int what);
 
 #pragma GCC visibility pop

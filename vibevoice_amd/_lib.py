@@ -135,6 +135,10 @@ _SIGS = {
     "vv_gemm_raw": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                               _P, C.c_float, _P, _P, C.c_int, C.c_int, C.c_int]),
     "vv_gemv_case": (C.c_int, [_P, C.POINTER(VVGemvCase), C.c_int, C.POINTER(C.c_int)]),
+    "vv_w13_twin_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "vv_w13_pack_matrix": (C.c_int, [_P, _P, _P, C.c_int, C.c_int]),
+    "vv_w13_unpack_matrix": (C.c_int, [_P, _P, _P, C.c_int, C.c_int]),
+    "vv_w13_gemv_case": (C.c_int, [_P, C.POINTER(VVGemvCase), _P, _P, C.c_int, C.c_int]),
     "vv_gemm3_raw": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_float, _P, _P, _P, _P]),
     "vv_profile_begin": (C.c_int, [_P]),
     "vv_profile_end": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -2,6 +2,7 @@
 // capture / replay cache, connectors.  The op orchestration lives in engine_lm / engine_head / engine_codec / engine_prof.hip,
 // the device-resident LoRA adapters (base snapshots, merge, reset, read-back) in engine_lora.hip.
 #include "engine_ctx.h"
+#include "vv_w13.h"
 
 // declared (and explained) in engine_ctx.h; defined here and nowhere else
 thread_local char g_err[512] = "";
@@ -325,14 +326,23 @@ static int create_impl(const vv_config* cfg, vv_ctx* parent, vv_ctx** out) {
     ctx->h_t2 = alloc_packed(ctx, H, H); add_mat(ctx, "head.t_embedder.mlp.2.weight", H, H, ctx->h_t2, 0);
     ctx->h_ada = alloc_packed(ctx, MODW, H);
     ctx->hl.resize(HL);
+    // W13 twins of the layers' matrices (+13/16 of their bytes): bf16 mode, whole 4-k-tile groups.  A shared context has its parent's
+    {
+        const char* e = getenv("VVHIP_W13");      // 0: the A/B arm -- no twins, no new launches
+        ctx->w13_on = parent ? parent->w13_on : !(e && e[0] == '0') && c.xsplit == 1 && vv_w13_shape_ok(HF, H) && vv_w13_shape_ok(H, HF);
+    }
+    auto twin = [&](int N, int K) {
+        if (ctx->w13_on) ctx->w.back().w13 = walloc(ctx, (size_t)vv_w13_bytes(N, K));
+        return (int)ctx->w.size() - 1;
+    };
     for (int l = 0; l < HL; ++l) {
         char nm[128]; snprintf(nm, 128, "head.layers.%d.", l);
         std::string p(nm);
         ctx->hl[l].norm = add_vec(ctx, p + "norm.weight", H);
         add_mat(ctx, p + "adaLN_modulation.1.weight", 3 * H, H, ctx->h_ada, l * 3 * H / 16);
-        ctx->hl[l].wg = alloc_packed(ctx, HF, H); add_mat(ctx, p + "ffn.gate_proj.weight", HF, H, ctx->hl[l].wg, 0);
-        ctx->hl[l].wu = alloc_packed(ctx, HF, H); add_mat(ctx, p + "ffn.up_proj.weight", HF, H, ctx->hl[l].wu, 0);
-        ctx->hl[l].wd = alloc_packed(ctx, H, HF); add_mat(ctx, p + "ffn.down_proj.weight", H, HF, ctx->hl[l].wd, 0);
+        ctx->hl[l].wg = alloc_packed(ctx, HF, H); add_mat(ctx, p + "ffn.gate_proj.weight", HF, H, ctx->hl[l].wg, 0); ctx->hl[l].ig = twin(HF, H);
+        ctx->hl[l].wu = alloc_packed(ctx, HF, H); add_mat(ctx, p + "ffn.up_proj.weight", HF, H, ctx->hl[l].wu, 0); ctx->hl[l].iu = twin(HF, H);
+        ctx->hl[l].wd = alloc_packed(ctx, H, HF); add_mat(ctx, p + "ffn.down_proj.weight", H, HF, ctx->hl[l].wd, 0); ctx->hl[l].id = twin(H, HF);
     }
     add_mat(ctx, "head.final_layer.adaLN_modulation.1.weight", 2 * H, H, ctx->h_ada, HL * 3 * H / 16);
     ctx->h_out = alloc_packed(ctx, L, H); add_mat(ctx, "head.final_layer.linear.weight", L, H, ctx->h_out, 0);
@@ -382,6 +392,7 @@ static int create_impl(const vv_config* cfg, vv_ctx* parent, vv_ctx** out) {
         for (size_t i = 0; i < ctx->w.size(); ++i) {
             if (ctx->w[i].name != parent->w[i].name || ctx->w[i].nelem != parent->w[i].nelem) { *out = ctx; return fail(ctx, "vv_create_shared: parameter table differs at '%s'", ctx->w[i].name.c_str()); }
             ctx->w[i].loaded = parent->w[i].loaded;
+            ctx->w[i].w13_ok = parent->w[i].w13_ok;
             if (ctx->w[i].name == "lm_head.weight") ctx->w[i].dev = parent->w[i].dev;
         }
         ctx->lm_head = parent->lm_head; ctx->lm_head_loaded = parent->lm_head_loaded;
@@ -494,6 +505,7 @@ extern "C" int vv_upload(vv_ctx* ctx, const char* name, const void* src, int src
     } else if (w.kind == W_MAT) {
         VVCHK(vv_pack_launch(dsrc, src_dtype, w.dev, w.N, w.K, w.pk, w.Cin, w.Cout, w.ksz, w.stride, st));
         VVTRY(lora_rebase(ctx, it->second, st));      // a parameter with a LoRA base snapshot: the upload is the new base
+        VVTRY(w13_repack(ctx, it->second, st));
     } else {
         // fp32 vectors
         const float* f32 = (const float*)dsrc;
@@ -519,6 +531,19 @@ extern "C" int vv_upload(vv_ctx* ctx, const char* name, const void* src, int src
     w.loaded = true;
     ctx->rope_ready = false;      // (cos, sin) table is rebuilt from the current inv_freq on the next decode step
     return 0;
+}
+
+int w13_repack(vv_ctx* ctx, int widx, hipStream_t st) {
+    Weight& w = ctx->w[widx];
+    if (!w.w13) return 0;
+    VVCHK(vv_w13_pack_launch(w.dev, w.w13, w.N, w.K, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    unsigned ok = 0;
+    HIPCHK(ctx, hipMemcpy(&ok, (const char*)w.w13 + vv_w13_plane_bytes(w.N, w.K) + (size_t)2 * (w.N / 16) * 4, 4, hipMemcpyDeviceToHost));
+    const bool now = ok == 1;
+    if (now == w.w13_ok) return 0;
+    w.w13_ok = now;
+    return drop_graphs(ctx, {"samp:", "sde:", "rows:", "gen:"});
 }
 
 extern "C" int vv_set_speech_factors(vv_ctx* ctx, float scaling, float bias) {
@@ -594,6 +619,14 @@ extern "C" int64_t vv_stat(vv_ctx* ctx, int what) {
         case 6: return ctx->seam_launches;        // head-tail seam launches of the last recorded sampler body
         case 8: return ctx->solver_fused;         // general-path step ends that carried the next in-projection (last recorded sampler body)
         case 7: return ctx->lora_base_bytes;      // bytes held by the base snapshots of LoRA-merged parameters
+        case 9: {                                 // head matrices a one-utterance sampler streams as W13 now (gate and up go together)
+            int64_t n = 0;
+            for (const auto& l : ctx->hl) {
+                if (ctx->w[l.ig].w13_ok && ctx->w[l.iu].w13_ok) n += 2;
+                if (ctx->w[l.id].w13_ok) n += 1;
+            }
+            return n;
+        }
         default: return (int64_t)ctx->graphs.size();
     }
 }

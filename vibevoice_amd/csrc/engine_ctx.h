@@ -33,6 +33,10 @@ struct Weight {
     int rep = 1;                // W_BIAS_REP: repeat count
     bool loaded = false;
     bool optional = false;
+    // W13 twin of a W_MAT (vv_w13.h; the diffusion head's gate / up / down matrices): packed behind every write to dev (w13_repack);
+    // w13_ok is the device's answer that the twin decodes to dev's bits -- without it the matrix keeps its bf16 launch
+    void* w13 = nullptr;
+    bool w13_ok = false;
 };
 
 struct Block {
@@ -129,7 +133,8 @@ struct vv_ctx {
     float *pm = nullptr, *pl = nullptr, *po = nullptr;
     // head
     int HF = 0, MODW = 0;
-    struct HLayer { float* norm; void *wg, *wu, *wd; };
+    struct HLayer { float* norm; void *wg, *wu, *wd; int ig, iu, id; };      // ig / iu / id: the matrices' rows of the parameter table
+    bool w13_on = false;            // the head's gate / up / down matrices have W13 twins (bf16 mode, qualifying widths; VVHIP_W13=0: none)
     std::vector<HLayer> hl;
     void *h_in = nullptr, *h_cond = nullptr, *h_t0 = nullptr, *h_t2 = nullptr, *h_ada = nullptr, *h_out = nullptr;
     int n_steps = 0;
@@ -259,6 +264,9 @@ void nan_probe(vv_ctx* ctx, hipStream_t st, const char* name, const void* p, siz
 void nan_probe_report(vv_ctx* ctx, hipStream_t st, const char* what);
 int gemm_prof(vv_ctx* ctx, const VVGemm& g, hipStream_t st);
 int lora_rebase(vv_ctx* ctx, int widx, hipStream_t st);                                                                       // engine_lora.hip
+// Behind EVERY write to a parameter's packed storage (vv_upload, the LoRA merge and reset): re-packs its W13 twin, if it has one, waits
+// and reads the device's answer.  A changed answer changes the sampler's launches: drops its graph families.  The caller holds g_dev_mu shared.
+int w13_repack(vv_ctx* ctx, int widx, hipStream_t st);                                                                        // engine.hip
 
 // One GEMM launch of an op body (`ctx` and `st` in scope).  ctx->launches counts these and what the bodies add by hand; some launches
 // (vv_copy_launch, vv_sampler_init_launch, ...) are not counted, and bench.py reports the figure as it is: do not "fix" it in passing.
@@ -284,6 +292,9 @@ int gemm_tl(vv_ctx* ctx, VVGemm g, hipStream_t st);
 //   samp: sde:  key: n, cond / noise / step-noise / output pointers, CFG_SCALE.  device: conditions, noise, the rows of ctx->coef, ctx->hg.
 //           by value: STEP COUNT, TABLE OFFSETS, THE PER-STEP MODULATION BUFFERS (a longer schedule reallocates them), sde_on --
 //           dropped by vv_set_schedule / vv_set_schedule_sde.  test_sampler_graphs_follow_the_schedule, test_replays_after_an_upload
+//           THE W13 ANSWER of the head's matrices (which of them stream their twins: a kernel choice) -- dropped by w13_repack when an
+//           upload or a LoRA merge changes it; the twins' storage never moves and is re-packed in place.
+//           test_gpu_w13.py: test_sampler_arms_agree
 //   rows:   as samp: / sde:, with the POINTER of the per-row scales in the key and the scales on the device.
 //           test_gpu_cfg_rows.py: test_graph_replay_follows_the_buffer, test_a_new_schedule_drops_the_cached_rows_graph
 //   gen:    the general solver table (vv_diffusion_sample_general).  key: n, cond / noise / step-noise / PER-ROW-SCALE / output

@@ -81,7 +81,7 @@ extern "C" int vv_set_schedule_general(vv_ctx* ctx, int n_steps, const float* t,
 // has_coef: a sampler's plan, which ends its steps as the installed table says (general_on: solver.hip's launch)
 static VVHeadPlan head_plan(const vv_ctx* ctx, int rows, int n_steps, bool has_coef) {
     return vv_head_plan(rows, n_steps, ctx->HF, ctx->c.head_layers, ctx->MODW,
-                        {ctx->p16_ok, ctx->p16_shift != nullptr, ctx->ada_p != nullptr, ctx->mod_all_bytes != 0, ctx->head_tail}, has_coef,
+                        {ctx->p16_ok, ctx->p16_shift != nullptr, ctx->ada_p != nullptr, ctx->mod_all_bytes != 0, ctx->head_tail, ctx->w13_on}, has_coef,
                         has_coef && ctx->general_on);
 }
 
@@ -144,11 +144,15 @@ static int head_eval(vv_ctx* ctx, hipStream_t st, const VVHeadPlan& p, const Hea
         float* cur = ctx->xh_parts + (size_t)(l & 1) * 2 * xps;          // parts written by layer l-1
         float* nxt = ctx->xh_parts + (size_t)((l + 1) & 1) * 2 * xps;    // parts layer l writes
         g1.xa = cur; g1.n_xa = xp; g1.part_stride = xps;
+        // a matrix whose twin the device did not find exact, or a launch without a W13 form (part tensors), keeps its bf16 launch
+        const Weight &mg = ctx->w[ctx->hl[l].ig], &mu = ctx->w[ctx->hl[l].iu], &md = ctx->w[ctx->hl[l].id];
+        if (p.w13 && mg.w13_ok && mu.w13_ok && vv_gemv_w13_form(&g1, c.xsplit) >= 0) { g1.w13 = mg.w13; g1.w13_2 = mu.w13; }
         GEMM(g1);
         VVGemm g2 = mk_gemm(ctx->hl[l].wd, ctx->hact, xh, rows, H, HF, HF, H);
         g2.epi = VV_EPI_GATED_RESID; g2.gate = base + 2 * H; g2.ld_gate = MODW; g2.nt = 1;
         g2.ya = cur; g2.n_ya = xp; g2.part_stride = xps;
         xp = ksplit_parts(ctx, g2, nxt, xps);
+        if (p.w13 && md.w13_ok && vv_gemv_w13_form(&g2, c.xsplit) >= 0) g2.w13 = md.w13;
         if (ctx->probe_on) { char nm[64]; snprintf(nm, 64, "layer %d hact (parts in %d)", l, g1.n_xa); nan_probe(ctx, st, nm, ctx->hact, (size_t)rows * HF); }
         GEMM(g2);
         if (ctx->probe_on) {

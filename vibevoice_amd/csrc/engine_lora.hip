@@ -102,6 +102,7 @@ extern "C" int vv_lora_merge(vv_ctx* ctx, void* stream, const char* name, const 
     ctx->launches++;
     VVCHK(vv_lora_merge_launch(it->second.snap, w.dev, w.N, w.K, a_dev, b_dev, r, scale, delta_bf16 ? 1 : 0, st));
     it->second.merged = true;
+    VVTRY(w13_repack(ctx, i, st));
     return 0;
 }
 
@@ -120,6 +121,7 @@ extern "C" int vv_lora_reset(vv_ctx* ctx, void* stream, const char* name) {
         ctx->launches++;
         VVCHK(vv_copy_launch(ctx->w[kv.first].dev, kv.second.snap, kv.second.bytes, st));
         kv.second.merged = false;
+        VVTRY(w13_repack(ctx, kv.first, st));
     }
     return 0;
 }

@@ -1,5 +1,6 @@
 // engine_prof.hip -- host side of libvvhip.so: per-launch profiling, the timing builds' timeline, the NaN probe, raw test entries.
 #include "engine_ctx.h"
+#include "vv_w13.h"
 
 static __global__ void vv_nan_probe_kernel(const float* __restrict__ p, int n, unsigned* __restrict__ rec) {
     unsigned cnt = 0, first = 0xffffffffu, mx = 0;
@@ -47,6 +48,7 @@ void nan_probe_report(vv_ctx* ctx, hipStream_t st, const char* what) {
 static double gemm_bytes(const VVGemm& g) {
     // algorithmic bytes of one launch: packed weights once (+ second matrix), activations in, result out (RMW epilogues twice)
     double w = (double)vv_packed_elems(g.N, g.K) * 2.0 * (g.W2 ? 2.0 : 1.0);
+    if (g.w13) w = (double)vv_w13_plane_bytes(g.N, g.K) * (g.W2 ? 2.0 : 1.0);      // the bytes actually streamed
     double x = (double)g.T * g.K * 4.0;
     double y = (double)g.T * g.N * 4.0 * ((g.epi == VV_EPI_RESID || g.epi == VV_EPI_GATED_RESID) ? 2.0 : 1.0);
     return w + x + y;
@@ -106,9 +108,7 @@ extern "C" int vv_gemm_raw(void* stream, const void* w, const void* w2, const fl
     if (g.dbg) g.nscale = nullptr;
     return vv_gemm_launch(g, xsplit, (hipStream_t)stream);
 }
-// tests: one launch of the decode GEMV kernel in the form its own launcher picks, or a refusal; no dispatcher, no stand-in kernel
-extern "C" int vv_gemv_case(void* stream, const vv_gemv_case_args* c, int xsplit, int* form_out) {
-    if (!c || xsplit < 1 || xsplit > 3) return -1;
+static VVGemm case_gemm(const vv_gemv_case_args* c) {
     VVGemm g = mk_gemm(c->W, c->X, c->Y, c->T, c->N, c->K, c->ldx, c->ldy);
     g.W2 = (const u32x4*)c->W2; g.pro = c->pro; g.epi = c->epi; g.nw = c->nw; g.eps = c->eps; g.bias = c->bias; g.nscale = c->nscale;
     g.mod_scale = c->mod_scale; g.mod_shift = c->mod_shift; g.ld_mod = c->ld_mod;
@@ -122,12 +122,33 @@ extern "C" int vv_gemv_case(void* stream, const vv_gemv_case_args* c, int xsplit
     g.dw_hist = c->dw_hist; g.dw_w = c->dw_w; g.dw_b = c->dw_b; g.dw_gamma = c->dw_gamma; g.dw_nw = c->dw_nw;
     g.dw_xout = c->dw_xout; g.dw_hnew = c->dw_hnew;
     g.nt = 1;
+    return g;
+}
+// tests: one launch of the decode GEMV kernel in the form its own launcher picks, or a refusal; no dispatcher, no stand-in kernel
+extern "C" int vv_gemv_case(void* stream, const vv_gemv_case_args* c, int xsplit, int* form_out) {
+    if (!c || xsplit < 1 || xsplit > 3) return -1;
+    VVGemm g = case_gemm(c);
     if (!vv_gemv_ok(&g)) return VV_GEMV_REFUSED;
     int form[5] = {0, 0, 0, 0, 0};
     const int r = vv_gemv_launch(g, xsplit, (hipStream_t)stream, form);
     if (r == VV_RC_NO_FORM) return VV_GEMV_REFUSED;
     if (r == 0 && form_out) for (int j = 0; j < 5; ++j) form_out[j] = form[j];
     return r;
+}
+// tests: W13 twins one matrix at a time, and one launch of a named W13 form over the twins or over the bf16 fragments
+extern "C" int64_t vv_w13_twin_bytes(int N, int K) { return vv_w13_shape_ok(N, K) ? vv_w13_bytes(N, K) : 0; }
+extern "C" int vv_w13_pack_matrix(void* stream, const void* packed_dev, void* twin_dev, int N, int K) {
+    return vv_w13_pack_launch(packed_dev, twin_dev, N, K, (hipStream_t)stream);
+}
+extern "C" int vv_w13_unpack_matrix(void* stream, const void* twin_dev, void* packed_dev, int N, int K) {
+    return vv_w13_unpack_launch(twin_dev, packed_dev, N, K, (hipStream_t)stream);
+}
+extern "C" int vv_w13_gemv_case(void* stream, const vv_gemv_case_args* c, const void* twin_dev, const void* twin2_dev, int mr, int wpb) {
+    if (!c) return -1;
+    VVGemm g = case_gemm(c);
+    g.w13 = twin_dev; g.w13_2 = twin2_dev;
+    const int r = vv_gemv_w13_form_launch(g, mr, wpb, (hipStream_t)stream);
+    return r == VV_RC_NO_FORM ? VV_GEMV_REFUSED : r;
 }
 // tests: Y = f(X) . W^T through the prefill GEMM (prefill.hip): X fp32 [T][K] is packed (optionally RMS-normalised) into xp_scratch,
 // epi STORE/BIAS/RESID write fp32 Y [T][N]; epi SWIGLU (W = gate, W2 = up) writes packed bf16 into yp_scratch, unpacked to Y.

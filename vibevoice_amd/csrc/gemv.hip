@@ -21,6 +21,7 @@
 #include "vv_common.h"
 #include "vv_device.h"
 #include "vv_launch.h"
+#include "vv_w13.h"
 
 #ifdef VV_GEMM_TIMING
 #define VV_STAMP(i) do { if (a.dbg && blockIdx.x == 0 && threadIdx.x == 0) a.dbg[i] = __builtin_amdgcn_s_memtime(); } while (0)
@@ -51,7 +52,11 @@ constexpr int U = 8;       // k-steps per batch (256 k = one float4 per lane per
 // split K over 3 workgroup columns): the three loads are issued together and summed in a fixed order.
 // SL: slot-batched rows (VVGemm::sl_*): the rows of one launch are gathered from / scattered to the streaming buffers of up
 // to 8 utterances -- one weight pass for the tokenizer stages of a whole batch.  16-row form only.
-template <int XS, int PRO, int EPI, int MR, int WPB, int PARTS = 0, int SL = 0>      // PARTS: 0 none, 1 activation side, 2 residual side
+// WF: weight format.  0: packed bf16 fragments.  1: W13 planes (vv_w13.h; pW / pW2 are the twins): only the weight loads and the
+// fragment handed to the MFMA change -- the wave K ranges, the staging batches, the order of MFMAs over k, the reduce and the epilogue
+// are those of WF = 0, so the outputs are the same bits.  A wave's K range need not start or end on a 4-k-tile group: the groups at
+// its ends are loaded whole and the k-tiles outside the range skipped (a neighbour wave of the same workgroup streams them too).
+template <int XS, int PRO, int EPI, int MR, int WPB, int PARTS = 0, int SL = 0, int WF = 0>      // PARTS: 0 none, 1 activation side, 2 residual side
 // The operands every wave needs before its first load (weight / activation bases, shape, strides) are separate leading
 // scalar parameters: with -mllvm -amdgpu-kernarg-preload-count=16 the dispatcher delivers them in SGPRs at wave launch,
 // so the first addresses do not wait for a scalar-cache round trip; the rest of VVGemm is fetched by one s_load batch.
@@ -67,6 +72,7 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemv_kernel(const u32x4* __restri
     constexpr bool FOLD = (PRO == VV_PRO_RMS_MOD) && MR <= 4;
     constexpr int NOP = (PRO == VV_PRO_RMS_MOD && !FOLD) ? 2 : 1;
     constexpr int MRS = FOLD ? 2 * MR : MR;         // staged B columns: activation rows, then (folded form) their shift rows
+    static_assert(WF == 0 || (XS == 1 && NOP == 1 && MR <= 4 && PARTS == 0 && SL == 0), "W13 forms: bf16 mode, decode rows, one operand");
     // one (k-step, k-group) plane of the staging tile = MR rows x 16 B; the 16-row form pads it by 16 B so that the planes
     // one staging store touches fall into different bank groups (unpadded: 256-B stride = the same 4 banks, 16-way conflict)
     constexpr int GSB = MRS * 16 + (MR == 16 ? 16 : 0);
@@ -106,6 +112,19 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemv_kernel(const u32x4* __restri
 
     const u32x4* wbase = pW + (size_t)tile * k_tiles * 64 + lane;
     const u32x4* wbase2 = DUAL ? pW2 + (size_t)tile * k_tiles * 64 + lane : nullptr;
+    // W13: this tile row's groups in the twin's planes, and its scale word behind them (gridDim.x = the matrix's tile rows)
+    const unsigned char* gbase = reinterpret_cast<const unsigned char*>(pW) + (size_t)tile * (k_tiles >> 2) * VV_W13_GROUP;
+    const unsigned char* gbase2 = reinterpret_cast<const unsigned char*>(pW2) + (size_t)tile * (k_tiles >> 2) * VV_W13_GROUP;
+    // groups in flight per stream: one weight batch (two streams: see the single-buffered bf16 form below), one and a half for one
+    // stream (a fourth slot costs the 8-wave form its second resident workgroup per CU: 134 VGPRs)
+    constexpr int RG = WF ? (DUAL ? 2 : 3) : 1;
+    const unsigned g_lo = kt0 >> 2, g_hi = (kt1 + 3) >> 2, ph = kt0 & 3;
+    VVW13Raw raw[RG][NM];
+    auto g_load = [&](unsigned g, VVW13Raw (&dst)[NM]) {
+        g = min(g, g_hi - 1);                              // clamped: a group past the range re-reads the last one, MFMAs skipped
+        dst[0] = vv_w13_load(gbase + g * VV_W13_GROUP, lane);
+        if constexpr (DUAL) dst[1] = vv_w13_load(gbase2 + g * VV_W13_GROUP, lane);
+    };
 
     // slot-batched rows: per-row activation offsets (wave-uniform), computed once
     unsigned xoff_sl[SL ? MR : 1];
@@ -169,7 +188,14 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemv_kernel(const u32x4* __restri
     };
     // ---- first activation batch and first weight batch go out before anything else ----
     XR R;
-    u32x4 wA[U][NM], wB[U][NM];
+    u32x4 wA[WF ? 1 : U][NM], wB[WF ? 1 : U][NM];
+    if constexpr (WF) {
+        if (has_k) {
+            x_load(kt0, R);
+#pragma unroll
+            for (int q = 0; q < RG; ++q) g_load(g_lo + q, raw[q]);
+        }
+    } else
     if (has_k) { x_load(kt0, R); w_load(kt0, wA); }      // x first: its wait must not drag the weight stream along
     __builtin_amdgcn_sched_barrier(0);
     VV_STAMP(1);
@@ -314,6 +340,68 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemv_kernel(const u32x4* __restri
         }
     };
 
+    if constexpr (WF) {
+        float wscale[NM];
+        {
+            const size_t tail = (size_t)gridDim.x * (k_tiles >> 2) * VV_W13_GROUP;
+            wscale[0] = vv_w13_scale(reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned char*>(pW) + tail)[tile]);
+            if constexpr (DUAL) wscale[1] = vv_w13_scale(reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned char*>(pW2) + tail)[tile]);
+        }
+        if (has_k) {
+            x_stage(kt0, R);
+            VV_STAMP(2);
+            const unsigned klen = kt1 - kt0;
+            // k-tile j of the wave (0 = kt0) sits in staging slot j & 7 of activation batch j >> 3, exactly as in the bf16 form
+            auto mma1 = [&](const u32x4 (&f)[NM][4], int t, unsigned slot) {
+                u32x4 xf = u32x4{0u, 0u, 0u, 0u};
+                if (frow < MRS) xf = *reinterpret_cast<const u32x4*>(stg + (size_t)(slot * 4 + fq) * GSB + frow * 16);
+                const bf16x8 xb = __builtin_bit_cast(bf16x8, xf);
+#pragma unroll
+                for (int i = 0; i < NM; ++i)
+                    acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, f[i][t]), xb, acc[i], 0, 0, 0);
+            };
+            // weight batch i = groups g_lo + 2i, + 1 = k-tiles 8i - ph .. 8i + 7 - ph of the wave: the first ph of them belong to the
+            // activation batch i - 1 still staged, the others to batch i, staged between the two
+            auto wstep = [&](unsigned i, auto s0c, auto s1c) {      // s0, s1: the raw slots of the batch's two groups
+                constexpr int sl[2] = {decltype(s0c)::value, decltype(s1c)::value};
+#pragma unroll
+                for (int gi = 0; gi < 2; ++gi) {
+                    u32x4 f[NM][4];
+                    if (gi == 0) {
+                        if (ph > 0 && i > 0) {      // a range that starts inside a group (narrow models): decoded for these k-tiles alone
+#pragma unroll
+                            for (int m = 0; m < NM; ++m) vv_w13_unpack(raw[sl[0]][m], wscale[m], f[m]);
+#pragma unroll
+                            for (int t = 0; t < 3; ++t)
+                                if ((unsigned)t < ph && 8 * i + t - ph < klen) mma1(f, t, 8 + t - ph);
+                        }
+                        if (i > 0 && 8 * i < klen) x_stage(kt0 + 8 * i, R);
+                        if (8 * (i + 1) < klen) x_load(kt0 + 8 * (i + 1), R);
+                    }
+#pragma unroll
+                    for (int m = 0; m < NM; ++m) vv_w13_unpack(raw[sl[gi]][m], wscale[m], f[m]);
+                    const unsigned gn = g_lo + 2 * i + gi + RG;
+                    if (gn < g_hi) g_load(gn, raw[sl[gi]]);      // the slot's next group goes out before this one's MFMAs
+#pragma unroll
+                    for (int t = 0; t < 4; ++t)
+                        if ((unsigned)t >= (gi == 0 ? ph : 0u) && 8 * i + 4 * gi + t - ph < klen) mma1(f, t, 4 * gi + t - ph);
+                }
+            };
+            const unsigned n_wb = (ph + klen + 7) >> 3;
+            using S0 = std::integral_constant<int, 0>; using S1 = std::integral_constant<int, 1>; using S2 = std::integral_constant<int, 2>;
+            if constexpr (RG == 2) {
+#pragma unroll 1
+                for (unsigned i = 0; i < n_wb; ++i) wstep(i, S0{}, S1{});
+            } else {
+#pragma unroll 1
+                for (unsigned i = 0; i < n_wb; i += 3) {
+                    wstep(i, S0{}, S1{});
+                    if (i + 1 < n_wb) wstep(i + 1, S2{}, S0{});
+                    if (i + 2 < n_wb) wstep(i + 2, S1{}, S2{});
+                }
+            }
+        }
+    } else
     if (has_k) {
         x_stage(kt0, R);
         VV_STAMP(2);
@@ -455,6 +543,14 @@ static constexpr std::array<GemvKernel, sizeof...(J)> gemv_kernel_table(std::ind
 }
 static const auto gemv_kernels = gemv_kernel_table(std::make_index_sequence<VV_GF_COUNT * VV_GEMV_MAX_PAIRS * VV_GEMV_MAX_XS>{});
 
+// the W13 forms of gemv_plan.h: [form][0] its bf16 instantiation (one of the table above), [form][1] the one that streams the twins
+template <size_t... J>
+static constexpr std::array<std::array<GemvKernel, 2>, sizeof...(J)> gemv_w13_table(std::index_sequence<J...>) {
+    return {{{vv_gemv_kernel<1, vv_gemv_w13_forms[J].pro, vv_gemv_w13_forms[J].epi, vv_gemv_w13_forms[J].mr, vv_gemv_w13_forms[J].wpb, 0, 0, 0>,
+              vv_gemv_kernel<1, vv_gemv_w13_forms[J].pro, vv_gemv_w13_forms[J].epi, vv_gemv_w13_forms[J].mr, vv_gemv_w13_forms[J].wpb, 0, 0, 1>}...}};
+}
+static const auto gemv_w13_kernels = gemv_w13_table(std::make_index_sequence<VV_GEMV_W13_FORMS>{});
+
 static GemvKernel gemv_kernel(const VVGemvForm& form, int pro, int epi) {
     for (int f = 0; f < VV_GF_COUNT; ++f) {
         const VVGemvFamily& fam = vv_gemv_families[f];
@@ -471,8 +567,26 @@ extern "C" int vv_gemv_launch(VVGemm a, int xs, hipStream_t s, int* form) {
     if (a.epi == VV_EPI_SWIGLU && !a.W2) return -1;
     VVGemvPlan p;
     if (!vv_gemv_plan(&a, xs, &p)) return VV_RC_NO_FORM;
-    const GemvKernel k = gemv_kernel(p.form, a.pro, a.epi);      // never null: the plan and the table read the same declaration
+    GemvKernel k = gemv_kernel(p.form, a.pro, a.epi);      // never null: the plan and the table read the same declaration
+    if (a.w13) {            // the caller asked for the twins: a W13 form of this very plan exists (vv_gemv_w13_form), or the call is refused
+        const int wi = vv_gemv_w13_form(&a, xs);
+        if (wi < 0 || (a.epi == VV_EPI_SWIGLU && !a.w13_2)) return VV_RC_NO_FORM;
+        k = gemv_w13_kernels[wi][1];
+        a.W = (const u32x4*)a.w13; a.W2 = (const u32x4*)a.w13_2;
+    }
     if (form) { form[0] = p.form.xs; form[1] = p.form.mr; form[2] = p.form.wpb; form[3] = p.form.parts; form[4] = p.form.sl; }
     hipLaunchKernelGGL(k, p.grid, dim3(p.form.wpb * 64), 0, s, a.W, a.W2, a.X, a.Y, a.nw, a.T, a.N, a.K, a.ldx, a.ldy, a);
+    return vv_launch_rc(0);
+}
+
+// tests: the named W13 form (mr, wpb) on this launch, streaming the twins (a.w13) or, without them, the bf16 fragments: the two
+// instantiations that must agree bit for bit, whatever form the plan would give the shape
+extern "C" int vv_gemv_w13_form_launch(VVGemm a, int mr, int wpb, hipStream_t s) {
+    if (a.epi == VV_EPI_SWIGLU && (!a.W2 || (a.w13 && !a.w13_2))) return -1;
+    const int wi = vv_gemv_w13_find(a.pro, a.epi, mr, wpb);
+    if (wi < 0 || !vv_gemv_eligible(&a) || !vv_gemv_w13_shape(&a, 1) || a.T > mr) return VV_RC_NO_FORM;
+    const GemvKernel k = gemv_w13_kernels[wi][a.w13 ? 1 : 0];
+    if (a.w13) { a.W = (const u32x4*)a.w13; a.W2 = (const u32x4*)a.w13_2; }
+    hipLaunchKernelGGL(k, dim3(a.N / 16, 1), dim3(wpb * 64), 0, s, a.W, a.W2, a.X, a.Y, a.nw, a.T, a.N, a.K, a.ldx, a.ldy, a);
     return vv_launch_rc(0);
 }

@@ -152,6 +152,31 @@ inline bool vv_gemv_plan(const VVGemm* a, int xs, VVGemvPlan* out) {
     return true;
 }
 
+// ---- W13 forms (vv_w13.h): the instantiations of vv_gemv_kernel that stream a matrix's 13-bit twin -- the diffusion head's gate/up and
+// down projections of one utterance, in the forms the plan above gives them (wide outputs, and the default form of narrow models).
+// A W13 form keeps the wave K ranges, the staging, the MFMA order and the reduce of its bf16 form: same bits, 13/16 of the bytes.
+struct VVGemvW13Form { int pro, epi, mr, wpb; };
+inline constexpr VVGemvW13Form vv_gemv_w13_forms[] = {
+    {VV_PRO_RMS_MOD, VV_EPI_SWIGLU, 2, 4}, {VV_PRO_RMS_MOD, VV_EPI_SWIGLU, 4, 8}, {VV_PRO_NONE, VV_EPI_GATED_RESID, 4, 8}};
+constexpr int VV_GEMV_W13_FORMS = sizeof(vv_gemv_w13_forms) / sizeof(vv_gemv_w13_forms[0]);
+inline int vv_gemv_w13_find(int pro, int epi, int mr, int wpb) {
+    for (int i = 0; i < VV_GEMV_W13_FORMS; ++i) {
+        const VVGemvW13Form& f = vv_gemv_w13_forms[i];
+        if (f.pro == pro && f.epi == epi && f.mr == mr && f.wpb == wpb) return i;
+    }
+    return -1;
+}
+// what a W13 form asks of a launch beyond its bf16 form: bf16 mode, whole 4-k-tile groups and 16-feature tiles, no part tensors
+inline bool vv_gemv_w13_shape(const VVGemm* a, int xs) {
+    return xs == 1 && (a->K & 127) == 0 && (a->N & 15) == 0 && a->T <= 4 && a->kgrid <= 1 && a->n_xa == 0 && a->n_ya == 0 && a->sl_n == 0;
+}
+// index of the W13 form of this launch (the form vv_gemv_plan picks for it, streaming twins), or -1: the launch stays bf16
+inline int vv_gemv_w13_form(const VVGemm* a, int xs) {
+    VVGemvPlan p;
+    if (!vv_gemv_w13_shape(a, xs) || !vv_gemv_plan(a, xs, &p) || p.form.parts || p.form.sl) return -1;
+    return vv_gemv_w13_find(a->pro, a->epi, p.form.mr, p.form.wpb);
+}
+
 // ---- the MFMA tile GEMM (tile.hip): its pairs and its eligibility ----
 constexpr int VV_TILE_BM = 64;          // rows per workgroup
 #define VV_TILE_COMBOS(X)                                                                      \

@@ -94,7 +94,8 @@ enum { VV_FINAL_P16_CFG,        // final layer over the packed operand the last 
        VV_FINAL_GEMM };         // ... with a plain store (no solver coefficients: vv_head_forward)
 
 // what the context offers: the batch-decode buffers, the packed shift tiles, the packed adaLN operand, the batched modulations, the seam
-struct VVHeadCaps { bool p16_ok, p16_shift, ada_p, mod_all, head_tail; };
+// ... and W13 twins of the layers' matrices (vv_w13.h)
+struct VVHeadCaps { bool p16_ok, p16_shift, ada_p, mod_all, head_tail, w13; };
 
 struct VVHeadPlan {
     int rows, n_steps;
@@ -104,6 +105,7 @@ struct VVHeadPlan {
     bool seam;                  // decode rows, bf16 mode: every step but the last ends with the fused seam
     int final_stage;            // VV_FINAL_* of a step that does not
     bool solver_step;           // the general solver table: a step ends with solver.hip's launch behind the final layer's plain store
+    bool w13;                   // one utterance on the GEMV route: a layer's projections stream their W13 twins where the device found them exact
 };
 
 // has_coef: the call has solver coefficients (the samplers; vv_head_forward has none and evaluates the head once)
@@ -118,6 +120,7 @@ inline VVHeadPlan vv_head_plan(int rows, int n_steps, int HF, int HL, int MODW, 
     // batch rows: normalise + modulate + pack ONCE, then both projections stream weights against packed fragments
     p.layers = vv_p16_rows(rows) && c.p16_ok && (HF % 32) == 0 ? VV_HEAD_P16 : VV_HEAD_GEMV;
     p.seam = has_coef && rows == 2 && c.head_tail;
+    p.w13 = c.w13 && p.layers == VV_HEAD_GEMV && rows <= 2;
     p.final_stage = p.layers == VV_HEAD_P16 && p.sh_tiles && has_coef && HL > 0 ? VV_FINAL_P16_CFG : has_coef ? VV_FINAL_GEMM_CFG : VV_FINAL_GEMM;
     p.solver_step = solver_step;
     if (solver_step) { p.sh_tiles = false; p.seam = false; p.final_stage = VV_FINAL_GEMM; }      // the packed shift tiles serve VV_FINAL_P16_CFG alone

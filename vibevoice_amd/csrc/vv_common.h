@@ -106,6 +106,10 @@ struct VVGemm {
     const float* dw_nw;    // [K] weight of the block's first norm
     float* dw_xout;        // [K]
     float* dw_hnew;        // [K]
+    // W13 twins of W / W2 (vv_w13.h), or null: the launch streams the twins' planes where a W13 form exists for it (gemv_plan.h:
+    // vv_gemv_w13_form) and produces the bits of the bf16 launch
+    const void* w13;
+    const void* w13_2;
 };
 
 // ---- batch decode over pre-packed activations (gemv16p.hip) ----

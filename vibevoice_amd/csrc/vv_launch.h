@@ -102,6 +102,9 @@ int vv_block1d_supported(int C);
 int vv_gemv_ok(const VVGemm* a);
 // vv_gemv_plan (gemv_plan.h) -> the kernel of that form -> launch; VV_RC_NO_FORM where the plan finds none.  form (tests): the plan's form.
 int vv_gemv_launch(VVGemm a, int xs, hipStream_t s, int* form);
+int vv_gemv_w13_form_launch(VVGemm a, int mr, int wpb, hipStream_t s);      // tests: one named W13 form, streaming the twins or (w13 null) bf16
+int vv_w13_pack_launch(const void* packed, void* twin, int N, int K, hipStream_t s);
+int vv_w13_unpack_launch(const void* twin, void* packed, int N, int K, hipStream_t s);
 int vv_tile_ok(const VVGemm* a, int xs);
 int vv_tile_launch(VVGemm a, int xs, hipStream_t s);
 int vv_lora_merge_launch(const void* base, void* dst, int N, int K, const float* a, const float* b, int r, float scale, int delta_bf16,

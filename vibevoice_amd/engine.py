@@ -672,6 +672,34 @@ class Engine:
         self.sync()
         return out
 
+    def w13_pack(self, packed: torch.Tensor, N: int, K: int) -> torch.Tensor:
+        """The W13 twin (vibevoice_amd/w13.py) of a pack_matrix output, packed and checked on the device: uint8 [vv_w13_twin_bytes]."""
+        self._shape_ints("w13_pack", N=N, K=K)
+        nbytes = int(self.lib.vv_w13_twin_bytes(N, K))
+        if nbytes == 0:
+            raise ValueError(f"w13_pack: N = {N} must be a multiple of 16 and K = {K} of 128")
+        self._dev_tensor("w13_pack", "packed", packed, int(self.lib.vv_packed_bytes(N, K)), torch.uint8)
+        twin = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        self._after_producer()
+        rc = self.lib.vv_w13_pack_matrix(self._s, C.c_void_p(packed.data_ptr()), C.c_void_p(twin.data_ptr()), N, K)
+        if rc != 0:
+            raise EngineError(f"vv_w13_pack_matrix failed ({rc})")
+        return twin
+
+    def w13_unpack(self, twin: torch.Tensor, N: int, K: int) -> torch.Tensor:
+        """A twin expanded back to packed bf16 fragments by the device decoder: uint8 [vv_packed_bytes]."""
+        self._shape_ints("w13_unpack", N=N, K=K)
+        nbytes = int(self.lib.vv_w13_twin_bytes(N, K))
+        if nbytes == 0:
+            raise ValueError(f"w13_unpack: N = {N} must be a multiple of 16 and K = {K} of 128")
+        self._dev_tensor("w13_unpack", "twin", twin, nbytes, torch.uint8)
+        out = torch.zeros(int(self.lib.vv_packed_bytes(N, K)), dtype=torch.uint8, device=self.device)
+        self._after_producer()
+        rc = self.lib.vv_w13_unpack_matrix(self._s, C.c_void_p(twin.data_ptr()), C.c_void_p(out.data_ptr()), N, K)
+        if rc != 0:
+            raise EngineError(f"vv_w13_unpack_matrix failed ({rc})")
+        return out
+
     # ------------------------------------------------------------------ device-resident LoRA adapters
     MERGE_DTYPES = ("float32", "bfloat16")
 
@@ -822,7 +850,7 @@ class Engine:
                   kgrid=0, yparts=None, xa=None, n_xa=0, ya=None, n_ya=0, part_stride=0,
                   sl_n=0, sl_T=0, sl_x=0, sl_y=0, sl_id=(),
                   dw_hist=None, dw_w=None, dw_b=None, dw_gamma=None, dw_nw=None, dw_xout=None, dw_hnew=None,
-                  xsplit=None, unaligned_ok=()):
+                  xsplit=None, unaligned_ok=(), w13_form=None, twin=None, twin2=None):
         """One launch of the decode GEMV kernel (vv_gemv_case), or a refusal.  Returns the form the launcher chose,
         (XS, MR, WPB, PARTS, SL), or None when nothing was launched (the kernel's eligibility check or its launcher refused).
 
@@ -830,7 +858,10 @@ class Engine:
         size that covers every address the kernel can form from T, N, K and the strides -- and a mismatch raises ValueError: a
         wrong argument must fail here, not as an out-of-bounds access on the GPU.  unaligned_ok names tensors whose alignment
         check is waived, for callers that test the refusal of a misaligned operand (their size is still checked).
-        Asynchronous: the caller syncs."""
+        Asynchronous: the caller syncs.
+
+        w13_form = (mr, wpb): the launch is that W13 form (vv_w13_gemv_case), over the twins (w13_pack outputs; twin2 for SwiGLU's second
+        matrix) or, with twin None, the same form over the bf16 fragments; returns the form asked for, None on a refusal."""
         ldx = K if ldx is None else ldx
         ldy = N if ldy is None else ldy
         xs = self.cfg.xsplit if xsplit is None else xsplit
@@ -883,6 +914,14 @@ class Engine:
         wbytes = int(self.lib.vv_packed_bytes(N, K))
         need("wp", wp, wbytes, torch.uint8)
         need("w2p", w2p, wbytes, torch.uint8, required=epi == self.EPI_SWIGLU)
+        if w13_form is None and (twin is not None or twin2 is not None):
+            raise ValueError("gemv_case: twins without w13_form")
+        if twin is not None or twin2 is not None:
+            tbytes = int(self.lib.vv_w13_twin_bytes(N, K))
+            if tbytes == 0:
+                raise ValueError(f"gemv_case: no W13 twin for N = {N}, K = {K}")
+            need("twin", twin, tbytes, torch.uint8)
+            need("twin2", twin2, tbytes, torch.uint8, required=epi == self.EPI_SWIGLU)
         need("x", x, x_need)
         need("y", y, y_need, required=epi != self.EPI_CFG_DPM)
         need("nw", nw, K, required=False)
@@ -933,6 +972,16 @@ class Engine:
         a.dw_hist, a.dw_w, a.dw_b, a.dw_gamma, a.dw_nw = p(dw_hist), p(dw_w), p(dw_b), p(dw_gamma), p(dw_nw)
         a.dw_xout, a.dw_hnew = p(dw_xout), p(dw_hnew)
         a.cfg_rows = p(cfg_rows)
+        if w13_form is not None:
+            mr, wpb = (int(v) for v in w13_form)
+            if xs != 1 or T > mr:
+                raise ValueError(f"gemv_case: the W13 form ({mr}, {wpb}) takes xsplit 1 and T <= {mr}")
+            rc = self.lib.vv_w13_gemv_case(self._s, C.byref(a), p(twin), p(twin2), mr, wpb)
+            if rc == _lib.GEMV_REFUSED:
+                return None
+            if rc != 0:
+                raise EngineError(f"vv_w13_gemv_case failed ({rc})")
+            return (1, mr, wpb, 0, 0)
         form = (C.c_int * 5)()
         rc = self.lib.vv_gemv_case(self._s, C.byref(a), xs, form)
         if rc == _lib.GEMV_REFUSED:
