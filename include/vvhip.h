@@ -415,8 +415,10 @@ int vv_gemv_case(void* stream, const vv_gemv_case_args* args, int xsplit, int* f
  * it with the source bit for bit -- that is the ok word.  vv_w13_unpack_matrix: twin_dev -> packed fragments (the same decoder).
  * vv_w13_gemv_case: ONE launch of the W13 form (mr rows, wpb waves; csrc/gemv_plan.h: vv_gemv_w13_forms) on the operands of args:
  * over the twins (twin_dev, twin2_dev for SwiGLU's second matrix), or with twin_dev == NULL the same form over the bf16 fragments --
- * the two must agree bit for bit.  Returns VV_GEMV_REFUSED where the form or the shape does not exist.  New surface (tests); the
- * engine keeps twins of the diffusion head's gate / up / down matrices itself (VVHIP_W13=0: none). */
+ * the two must agree bit for bit; args' W / W2 stay the bf16 fragments either way, and a tile row whose ok word in the twin is 0 streams
+ * them inside the same launch.  Returns VV_GEMV_REFUSED where the form or the shape does not exist.  New surface (tests); the engine
+ * keeps twins of the diffusion head's gate / up / down matrices and of every LM layer's QKV / o / gate / up / down matrices itself
+ * (VVHIP_W13=head: the head's alone; VVHIP_W13=0: none). */
 int64_t vv_w13_twin_bytes(int N, int K);
 int vv_w13_pack_matrix(void* stream, const void* packed_dev, void* twin_dev, int N, int K);
 int vv_w13_unpack_matrix(void* stream, const void* twin_dev, void* packed_dev, int N, int K);
@@ -457,9 +459,13 @@ int vv_profile_replay_family(vv_ctx* ctx, void* stream, int family, int reps, in
  * 7: bytes of device memory held by the base snapshots of LoRA-merged parameters (vv_lora_merge);
  * 8: step ends of the general sampler (vv_diffusion_sample_general) that carried the next step's in-projection in the same launch,
  * in the last recorded sampler body -- n_steps - 1 where solver.hip's rule holds, 0 where the update ran alone;
- * 9: matrices of the diffusion head (gate, up and down of every layer) that a one-utterance sampler streams as W13 now: their twins
- * decoded exactly on the device; gate and up of a layer count together or not at all.  0 with VVHIP_W13=0, in the exact modes and at
- * widths without whole groups */
+ * 9: matrices of the diffusion head (gate, up and down of every layer) whose W13 twin decoded exactly on the device in every tile row;
+ * gate and up of a layer count together or not at all.  0 with VVHIP_W13=0, in the exact modes and at widths without whole groups.
+ * (A matrix that does not count still streams its twin: the tile rows that are not exact read bf16 inside the same launch.);
+ * 10: matrices of the LM (QKV, o, gate, up and down of every layer) that have a W13 twin: 5 x layers, or 0 with VVHIP_W13=head or 0, in
+ * the exact modes and for a matrix without whole groups;
+ * 11: tile rows (16 output features) of all twinned matrices, head and LM, that stream bf16 because the format cannot hold one of
+ * their elements (or because the matrix was never uploaded).  9 and 11 wait for the device and read the twins' ok words back */
 int64_t vv_stat(vv_ctx* ctx, int what);
 
 #pragma GCC visibility pop

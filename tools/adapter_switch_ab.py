@@ -33,14 +33,14 @@ MATS = ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o
 HBM_READ_CEILING_TBS = 6.3
 
 
-def build_model(device):
+def build_model(device, xsplit=1):
     """the 7B model with synthetic weights; returns (model, cfg, {engine name: shape} of the LM targets, host copies of layer 0's)"""
     from vibevoice_amd import synthetic
     from vibevoice_amd.configs import CONFIGS
     from vibevoice_amd.engine import Engine, map_param_name
     from vibevoice_amd.modeling import VibeVoiceForConditionalGenerationInference, engine_config_from_reference
     cfg = copy.deepcopy(CONFIGS["7b"])
-    ecfg = engine_config_from_reference(cfg, n_slots=1, max_ctx=256, use_graph=False, max_rows=16)
+    ecfg = engine_config_from_reference(cfg, n_slots=1, max_ctx=256, use_graph=False, max_rows=16, xsplit=xsplit)
     eng = Engine(ecfg, device)
     exp = eng.expected_weights()
     gen = torch.Generator(device=device)
@@ -120,6 +120,9 @@ def measure(model, shapes, host0, r, reps):
                    "set_adapter_none_device_ms": round(reset[0], 3), "set_adapter_none_wall_ms": round(reset[1], 3)},
         "base_snapshot_bytes": e.stat(7), "base_snapshot_bytes_before": snap0,
         "bytes_moved_per_switch": moved,
+        # bf16 mode: every merge and reset also re-packs the written matrix's W13 twin on the same stream (read it, write 13/16 of it)
+        "lm_matrices_with_a_w13_twin": e.stat(10),
+        "twin_bytes_written_per_switch": (elems * 2 * 13 // 16) if e.stat(10) else 0,
         "tb_per_s": round(moved / (statistics.median(dev_ms) * 1e-3) / 1e12, 3),
         "hbm_read_ceiling_tb_per_s": HBM_READ_CEILING_TBS,
     }
@@ -132,18 +135,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--ranks", default="8,64")
+    ap.add_argument("--xsplit", type=int, default=1, help="engine mode: 1 = bf16 activations (the bench default; the LM has W13 twins), 2 / 3 = the exact modes (none)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "adapter_switch.json"))
     args = ap.parse_args()
     from vibevoice_amd import build
     if not torch.cuda.is_available():
         raise SystemExit("tools/adapter_switch_ab.py measures on the GPU; none found")
     device = torch.device("cuda", 0)
-    model, cfg, shapes, host0 = build_model(device)
+    model, cfg, shapes, host0 = build_model(device, args.xsplit)
     out = {"tool": "tools/adapter_switch_ab.py", "library_build": build.binary_id(), "device": torch.cuda.get_device_name(0),
            "model": "7B language model, 28 layers x (q, k, v, o, gate, up, down), synthetic weights",
            "timing": "arms alternate repetition by repetition in one process; medians.  host: wall clock of one layer, scaled by 28; "
                      "device: device events on the engine stream around set_adapter() + the wall clock of the call",
-           "repetitions": args.reps, "ranks": {}}
+           "repetitions": args.reps, "xsplit": args.xsplit, "ranks": {}}
     try:
         for r in [int(v) for v in args.ranks.split(",") if v]:
             out["ranks"][str(r)] = measure(model, shapes, host0, r, args.reps)

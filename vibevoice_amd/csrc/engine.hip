@@ -245,6 +245,21 @@ static int create_impl(const vv_config* cfg, vv_ctx* parent, vv_ctx** out) {
         ctx->eos_w2 = alloc_packed(ctx, 1, H); add_mat(ctx, "eos.fc2.weight", 1, H, ctx->eos_w2, 0);
         ctx->eos_b2 = add_vec(ctx, "eos.fc2.bias", 1);
     }
+    // W13 twins (+13/16 of a matrix's bytes): bf16 mode, whole 4-k-tile groups.  The head's layers qualify together (w13_on), an LM
+    // matrix by its own shape (w13_lm).  A shared context has its parent's
+    {
+        const char* e = getenv("VVHIP_W13");      // 0: no twins, no new launches; head: the diffusion head's alone (the A/B arms)
+        const bool on = !(e && e[0] == '0') && c.xsplit == 1;
+        ctx->w13_on = parent ? parent->w13_on : on && vv_w13_shape_ok(c.head_ffn, H) && vv_w13_shape_ok(H, c.head_ffn);
+        ctx->w13_lm = parent ? parent->w13_lm : on && !(e && !strcmp(e, "head"));
+    }
+    // the twin of the matrix [N][K] at src, shared by the n_par parameters registered last (q / k / v are parts of one QKV matrix)
+    auto twin = [&](bool want, bool lm, const void* src, int N, int K, int n_par = 1) -> void* {
+        if (!want || !vv_w13_shape_ok(N, K)) return nullptr;
+        ctx->twins.push_back({walloc(ctx, (size_t)vv_w13_bytes(N, K)), src, N, K, lm});
+        for (int j = 0; j < n_par; ++j) ctx->w[ctx->w.size() - 1 - j].twin = (int)ctx->twins.size() - 1;
+        return ctx->twins.back().planes;
+    };
     ctx->layers.resize(c.lm_layers);
     for (int l = 0; l < c.lm_layers; ++l) {
         auto& L = ctx->layers[l];
@@ -257,13 +272,14 @@ static int create_impl(const vv_config* cfg, vv_ctx* parent, vv_ctx** out) {
         add_mat(ctx, p + "self_attn.q_proj.weight", Hq * D, H, L.wqkv, 0);
         add_mat(ctx, p + "self_attn.k_proj.weight", Hkv * D, H, L.wqkv, Hq * D / 16);
         add_mat(ctx, p + "self_attn.v_proj.weight", Hkv * D, H, L.wqkv, (Hq + Hkv) * D / 16);
+        L.tqkv = twin(ctx->w13_lm, true, L.wqkv, QKV, H, 3);
         add_vec(ctx, p + "self_attn.q_proj.bias", Hq * D, L.bqkv);
         add_vec(ctx, p + "self_attn.k_proj.bias", Hkv * D, L.bqkv + Hq * D);
         add_vec(ctx, p + "self_attn.v_proj.bias", Hkv * D, L.bqkv + (Hq + Hkv) * D);
-        L.wo = alloc_packed(ctx, H, Hq * D); add_mat(ctx, p + "self_attn.o_proj.weight", H, Hq * D, L.wo, 0);
-        L.wg = alloc_packed(ctx, I, H); add_mat(ctx, p + "mlp.gate_proj.weight", I, H, L.wg, 0);
-        L.wu = alloc_packed(ctx, I, H); add_mat(ctx, p + "mlp.up_proj.weight", I, H, L.wu, 0);
-        L.wd = alloc_packed(ctx, H, I); add_mat(ctx, p + "mlp.down_proj.weight", H, I, L.wd, 0);
+        L.wo = alloc_packed(ctx, H, Hq * D); add_mat(ctx, p + "self_attn.o_proj.weight", H, Hq * D, L.wo, 0); L.to = twin(ctx->w13_lm, true, L.wo, H, Hq * D);
+        L.wg = alloc_packed(ctx, I, H); add_mat(ctx, p + "mlp.gate_proj.weight", I, H, L.wg, 0); L.tg = twin(ctx->w13_lm, true, L.wg, I, H);
+        L.wu = alloc_packed(ctx, I, H); add_mat(ctx, p + "mlp.up_proj.weight", I, H, L.wu, 0); L.tu = twin(ctx->w13_lm, true, L.wu, I, H);
+        L.wd = alloc_packed(ctx, H, I); add_mat(ctx, p + "mlp.down_proj.weight", H, I, L.wd, 0); L.td = twin(ctx->w13_lm, true, L.wd, H, I);
     }
     const int n_caches = 2 * c.n_slots;
     ctx->head_stride = (int64_t)c.max_ctx * D;
@@ -326,13 +342,8 @@ static int create_impl(const vv_config* cfg, vv_ctx* parent, vv_ctx** out) {
     ctx->h_t2 = alloc_packed(ctx, H, H); add_mat(ctx, "head.t_embedder.mlp.2.weight", H, H, ctx->h_t2, 0);
     ctx->h_ada = alloc_packed(ctx, MODW, H);
     ctx->hl.resize(HL);
-    // W13 twins of the layers' matrices (+13/16 of their bytes): bf16 mode, whole 4-k-tile groups.  A shared context has its parent's
-    {
-        const char* e = getenv("VVHIP_W13");      // 0: the A/B arm -- no twins, no new launches
-        ctx->w13_on = parent ? parent->w13_on : !(e && e[0] == '0') && c.xsplit == 1 && vv_w13_shape_ok(HF, H) && vv_w13_shape_ok(H, HF);
-    }
-    auto twin = [&](int N, int K) {
-        if (ctx->w13_on) ctx->w.back().w13 = walloc(ctx, (size_t)vv_w13_bytes(N, K));
+    auto htwin = [&](const void* src, int N, int K) {
+        twin(ctx->w13_on, false, src, N, K);
         return (int)ctx->w.size() - 1;
     };
     for (int l = 0; l < HL; ++l) {
@@ -340,9 +351,9 @@ static int create_impl(const vv_config* cfg, vv_ctx* parent, vv_ctx** out) {
         std::string p(nm);
         ctx->hl[l].norm = add_vec(ctx, p + "norm.weight", H);
         add_mat(ctx, p + "adaLN_modulation.1.weight", 3 * H, H, ctx->h_ada, l * 3 * H / 16);
-        ctx->hl[l].wg = alloc_packed(ctx, HF, H); add_mat(ctx, p + "ffn.gate_proj.weight", HF, H, ctx->hl[l].wg, 0); ctx->hl[l].ig = twin(HF, H);
-        ctx->hl[l].wu = alloc_packed(ctx, HF, H); add_mat(ctx, p + "ffn.up_proj.weight", HF, H, ctx->hl[l].wu, 0); ctx->hl[l].iu = twin(HF, H);
-        ctx->hl[l].wd = alloc_packed(ctx, H, HF); add_mat(ctx, p + "ffn.down_proj.weight", H, HF, ctx->hl[l].wd, 0); ctx->hl[l].id = twin(H, HF);
+        ctx->hl[l].wg = alloc_packed(ctx, HF, H); add_mat(ctx, p + "ffn.gate_proj.weight", HF, H, ctx->hl[l].wg, 0); ctx->hl[l].ig = htwin(ctx->hl[l].wg, HF, H);
+        ctx->hl[l].wu = alloc_packed(ctx, HF, H); add_mat(ctx, p + "ffn.up_proj.weight", HF, H, ctx->hl[l].wu, 0); ctx->hl[l].iu = htwin(ctx->hl[l].wu, HF, H);
+        ctx->hl[l].wd = alloc_packed(ctx, H, HF); add_mat(ctx, p + "ffn.down_proj.weight", H, HF, ctx->hl[l].wd, 0); ctx->hl[l].id = htwin(ctx->hl[l].wd, H, HF);
     }
     add_mat(ctx, "head.final_layer.adaLN_modulation.1.weight", 2 * H, H, ctx->h_ada, HL * 3 * H / 16);
     ctx->h_out = alloc_packed(ctx, L, H); add_mat(ctx, "head.final_layer.linear.weight", L, H, ctx->h_out, 0);
@@ -392,7 +403,6 @@ static int create_impl(const vv_config* cfg, vv_ctx* parent, vv_ctx** out) {
         for (size_t i = 0; i < ctx->w.size(); ++i) {
             if (ctx->w[i].name != parent->w[i].name || ctx->w[i].nelem != parent->w[i].nelem) { *out = ctx; return fail(ctx, "vv_create_shared: parameter table differs at '%s'", ctx->w[i].name.c_str()); }
             ctx->w[i].loaded = parent->w[i].loaded;
-            ctx->w[i].w13_ok = parent->w[i].w13_ok;
             if (ctx->w[i].name == "lm_head.weight") ctx->w[i].dev = parent->w[i].dev;
         }
         ctx->lm_head = parent->lm_head; ctx->lm_head_loaded = parent->lm_head_loaded;
@@ -534,16 +544,21 @@ extern "C" int vv_upload(vv_ctx* ctx, const char* name, const void* src, int src
 }
 
 int w13_repack(vv_ctx* ctx, int widx, hipStream_t st) {
-    Weight& w = ctx->w[widx];
-    if (!w.w13) return 0;
-    VVCHK(vv_w13_pack_launch(w.dev, w.w13, w.N, w.K, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    unsigned ok = 0;
-    HIPCHK(ctx, hipMemcpy(&ok, (const char*)w.w13 + vv_w13_plane_bytes(w.N, w.K) + (size_t)2 * (w.N / 16) * 4, 4, hipMemcpyDeviceToHost));
-    const bool now = ok == 1;
-    if (now == w.w13_ok) return 0;
-    w.w13_ok = now;
-    return drop_graphs(ctx, {"samp:", "sde:", "rows:", "gen:"});
+    const Weight& w = ctx->w[widx];
+    if (w.twin < 0) return 0;
+    W13Twin& t = ctx->twins[w.twin];            // the matrix the parameter is part of (q / k / v: the layer's QKV): its own tile rows alone
+    const int tile0 = (int)(((const char*)w.dev - (const char*)t.src) / ((int64_t)(t.K / 32) * 1024));
+    VVCHK(vv_w13_pack_rows_launch(t.src, t.planes, t.N, t.K, tile0, w.N / 16, st));
+    t.exact = -1;                               // the host's copy of the folded word is stale: the next sampler call reads it again
+    return 0;
+}
+
+// statistics only: the ok words of a twin's tile rows, or (folded) the one word that says all of them are set, as the device holds them now
+static bool w13_ok_words(const W13Twin& t, std::vector<unsigned>& ok, bool folded) {
+    const int n_tiles = t.N / 16;
+    ok.resize(folded ? 1 : n_tiles);
+    return hipMemcpy(ok.data(), (const char*)t.planes + vv_w13_plane_bytes(t.N, t.K) + (size_t)(folded ? 2 * n_tiles : n_tiles) * 4, ok.size() * 4,
+                     hipMemcpyDeviceToHost) == hipSuccess;
 }
 
 extern "C" int vv_set_speech_factors(vv_ctx* ctx, float scaling, float bias) {
@@ -619,12 +634,32 @@ extern "C" int64_t vv_stat(vv_ctx* ctx, int what) {
         case 6: return ctx->seam_launches;        // head-tail seam launches of the last recorded sampler body
         case 8: return ctx->solver_fused;         // general-path step ends that carried the next in-projection (last recorded sampler body)
         case 7: return ctx->lora_base_bytes;      // bytes held by the base snapshots of LoRA-merged parameters
-        case 9: {                                 // head matrices a one-utterance sampler streams as W13 now (gate and up go together)
-            int64_t n = 0;
-            for (const auto& l : ctx->hl) {
-                if (ctx->w[l.ig].w13_ok && ctx->w[l.iu].w13_ok) n += 2;
-                if (ctx->w[l.id].w13_ok) n += 1;
+        case 9: case 11: {                        // the twins' ok words, read back now (the launches never need them on the host)
+            VV_SHARED;
+            if (hipDeviceSynchronize() != hipSuccess) return -1;
+            std::vector<unsigned> tail;
+            if (what == 11) {                     // tile rows of twinned matrices that stream bf16
+                int64_t n = 0;
+                for (const W13Twin& t : ctx->twins) {
+                    if (!w13_ok_words(t, tail, false)) return -1;
+                    for (unsigned v : tail) n += v == 0;
+                }
+                return n;
             }
+            auto exact = [&](int widx) {          // the folded word: every tile row of the matrix is held by its twin
+                const int ti = ctx->w[widx].twin;
+                return ti >= 0 && w13_ok_words(ctx->twins[ti], tail, true) && tail[0] == 1;
+            };
+            int64_t n = 0;                        // head matrices exact in every tile row; gate and up of a layer count together
+            for (const auto& l : ctx->hl) {
+                if (exact(l.ig) && exact(l.iu)) n += 2;
+                if (exact(l.id)) n += 1;
+            }
+            return n;
+        }
+        case 10: {                                // LM matrices (QKV, o, gate, up, down of every layer) that have a twin
+            int64_t n = 0;
+            for (const W13Twin& t : ctx->twins) n += t.lm;
             return n;
         }
         default: return (int64_t)ctx->graphs.size();

@@ -33,11 +33,15 @@ struct Weight {
     int rep = 1;                // W_BIAS_REP: repeat count
     bool loaded = false;
     bool optional = false;
-    // W13 twin of a W_MAT (vv_w13.h; the diffusion head's gate / up / down matrices): packed behind every write to dev (w13_repack);
-    // w13_ok is the device's answer that the twin decodes to dev's bits -- without it the matrix keeps its bf16 launch
-    void* w13 = nullptr;
-    bool w13_ok = false;
+    int twin = -1;              // W_MAT: row of vv_ctx::twins of the W13 twin this parameter's storage is part of, or none
 };
+
+// W13 twin of one packed matrix (vv_w13.h): the diffusion head's gate / up / down and the LM layers' QKV / o / gate / up / down.  Packed
+// behind every write to the matrix (w13_repack); the launches read per tile row whether the twin holds it (gemv.hip: WF), so the host
+// never needs the device's answer.  A twin never packed is all zero: every tile row streams bf16.
+// exact / used (the head's twins): the folded ok word as the host last read it (-1: written since, not read), and the answer the
+// sampler's graphs were built with.  An exact twin takes the launch without the fall-back (VVGemm::w13_exact); see head_w13_resolve.
+struct W13Twin { void* planes; const void* src; int N, K; bool lm; int exact = -1, used = -1; };
 
 struct Block {
     int C;
@@ -101,7 +105,7 @@ struct vv_ctx {
     std::map<std::string, int> widx;
     int H, D, Hq, Hkv, I, QKV;
     // LM params
-    struct Layer { float *ln1, *ln2, *bqkv; void *wqkv, *wo, *wg, *wu, *wd; };
+    struct Layer { float *ln1, *ln2, *bqkv; void *wqkv, *wo, *wg, *wu, *wd; void *tqkv, *to, *tg, *tu, *td; };      // t*: W13 twins, or null
     std::vector<Layer> layers;
     float *lm_norm = nullptr, *inv_freq = nullptr;
     int ws_rows = 0;
@@ -134,7 +138,10 @@ struct vv_ctx {
     // head
     int HF = 0, MODW = 0;
     struct HLayer { float* norm; void *wg, *wu, *wd; int ig, iu, id; };      // ig / iu / id: the matrices' rows of the parameter table
-    bool w13_on = false;            // the head's gate / up / down matrices have W13 twins (bf16 mode, qualifying widths; VVHIP_W13=0: none)
+    // W13 twins (bf16 mode, qualifying widths): w13_on the head's gate / up / down matrices, w13_lm the LM layers' five as well.
+    // VVHIP_W13=0: none; VVHIP_W13=head: the head's alone
+    bool w13_on = false, w13_lm = false;
+    std::vector<W13Twin> twins;
     std::vector<HLayer> hl;
     void *h_in = nullptr, *h_cond = nullptr, *h_t0 = nullptr, *h_t2 = nullptr, *h_ada = nullptr, *h_out = nullptr;
     int n_steps = 0;
@@ -264,8 +271,9 @@ void nan_probe(vv_ctx* ctx, hipStream_t st, const char* name, const void* p, siz
 void nan_probe_report(vv_ctx* ctx, hipStream_t st, const char* what);
 int gemm_prof(vv_ctx* ctx, const VVGemm& g, hipStream_t st);
 int lora_rebase(vv_ctx* ctx, int widx, hipStream_t st);                                                                       // engine_lora.hip
-// Behind EVERY write to a parameter's packed storage (vv_upload, the LoRA merge and reset): re-packs its W13 twin, if it has one, waits
-// and reads the device's answer.  A changed answer changes the sampler's launches: drops its graph families.  The caller holds g_dev_mu shared.
+// Behind EVERY write to a parameter's packed storage (vv_upload, the LoRA merge and reset): re-packs the W13 twin it is part of, if
+// any, on the same stream.  Enqueue only: no wait, no read-back, no graph is dropped (the twins' storage never moves and the kernels
+// read the ok words themselves).  The caller holds g_dev_mu shared.
 int w13_repack(vv_ctx* ctx, int widx, hipStream_t st);                                                                        // engine.hip
 
 // One GEMM launch of an op body (`ctx` and `st` in scope).  ctx->launches counts these and what the bodies add by hand; some launches
@@ -292,9 +300,9 @@ int gemm_tl(vv_ctx* ctx, VVGemm g, hipStream_t st);
 //   samp: sde:  key: n, cond / noise / step-noise / output pointers, CFG_SCALE.  device: conditions, noise, the rows of ctx->coef, ctx->hg.
 //           by value: STEP COUNT, TABLE OFFSETS, THE PER-STEP MODULATION BUFFERS (a longer schedule reallocates them), sde_on --
 //           dropped by vv_set_schedule / vv_set_schedule_sde.  test_sampler_graphs_follow_the_schedule, test_replays_after_an_upload
-//           THE W13 ANSWER of the head's matrices (which of them stream their twins: a kernel choice) -- dropped by w13_repack when an
-//           upload or a LoRA merge changes it; the twins' storage never moves and is re-packed in place.
-//           test_gpu_w13.py: test_sampler_arms_agree
+//           W13 twins: storage that never moves, re-packed in place behind every write; which tile rows stream them is read from the
+//           device by the launch itself.  by value: WHETHER EACH HEAD TWIN IS EXACT (the launch without the fall-back) -- read back at
+//           the first sampler call after a write to the matrix (head_w13_resolve), which drops the four families when an answer changed.  test_gpu_w13.py: test_sampler_arms_agree; test_gpu_w13_lm.py (the lm: family too)
 //   rows:   as samp: / sde:, with the POINTER of the per-row scales in the key and the scales on the device.
 //           test_gpu_cfg_rows.py: test_graph_replay_follows_the_buffer, test_a_new_schedule_drops_the_cached_rows_graph
 //   gen:    the general solver table (vv_diffusion_sample_general).  key: n, cond / noise / step-noise / PER-ROW-SCALE / output

@@ -1,6 +1,7 @@
 // engine_head.hip -- host side of libvvhip.so: the diffusion head: schedule tables, one head evaluation, the sampler.
 #include "engine_ctx.h"
 #include "pass_plan.h"
+#include "vv_w13.h"
 
 // width 5 / 6: the shipped tables;  8: a general table, stochastic as the caller says.  All of them are rows of ctx->coef, 8 floats each
 static int set_schedule(vv_ctx* ctx, int n_steps, const float* t, const float* coef, int width, void* stream, bool stochastic = false) {
@@ -144,15 +145,18 @@ static int head_eval(vv_ctx* ctx, hipStream_t st, const VVHeadPlan& p, const Hea
         float* cur = ctx->xh_parts + (size_t)(l & 1) * 2 * xps;          // parts written by layer l-1
         float* nxt = ctx->xh_parts + (size_t)((l + 1) & 1) * 2 * xps;    // parts layer l writes
         g1.xa = cur; g1.n_xa = xp; g1.part_stride = xps;
-        // a matrix whose twin the device did not find exact, or a launch without a W13 form (part tensors), keeps its bf16 launch
-        const Weight &mg = ctx->w[ctx->hl[l].ig], &mu = ctx->w[ctx->hl[l].iu], &md = ctx->w[ctx->hl[l].id];
-        if (p.w13 && mg.w13_ok && mu.w13_ok && vv_gemv_w13_form(&g1, c.xsplit) >= 0) { g1.w13 = mg.w13; g1.w13_2 = mu.w13; }
+        // a launch without a W13 form (part tensors) keeps its bf16 launch; a tile row its twin cannot hold streams bf16 inside the W13 one
+        const int tg = ctx->w[ctx->hl[l].ig].twin, tu = ctx->w[ctx->hl[l].iu].twin, td = ctx->w[ctx->hl[l].id].twin;
+        if (p.w13 && tg >= 0 && tu >= 0 && vv_gemv_w13_form(&g1, c.xsplit) >= 0) {
+            g1.w13 = ctx->twins[tg].planes; g1.w13_2 = ctx->twins[tu].planes;
+            g1.w13_exact = ctx->twins[tg].exact == 1 && ctx->twins[tu].exact == 1;
+        }
         GEMM(g1);
         VVGemm g2 = mk_gemm(ctx->hl[l].wd, ctx->hact, xh, rows, H, HF, HF, H);
         g2.epi = VV_EPI_GATED_RESID; g2.gate = base + 2 * H; g2.ld_gate = MODW; g2.nt = 1;
         g2.ya = cur; g2.n_ya = xp; g2.part_stride = xps;
         xp = ksplit_parts(ctx, g2, nxt, xps);
-        if (p.w13 && md.w13_ok && vv_gemv_w13_form(&g2, c.xsplit) >= 0) g2.w13 = md.w13;
+        if (p.w13 && td >= 0 && vv_gemv_w13_form(&g2, c.xsplit) >= 0) { g2.w13 = ctx->twins[td].planes; g2.w13_exact = ctx->twins[td].exact == 1; }
         if (ctx->probe_on) { char nm[64]; snprintf(nm, 64, "layer %d hact (parts in %d)", l, g1.n_xa); nan_probe(ctx, st, nm, ctx->hact, (size_t)rows * HF); }
         GEMM(g2);
         if (ctx->probe_on) {
@@ -304,9 +308,29 @@ static int sample_body(vv_ctx* ctx, hipStream_t st, const SampleReq& r) {
     return 0;
 }
 
+// In front of every head evaluation, outside any capture: the folded ok words of the head's twins that were written since the host last
+// read them (an upload, a LoRA merge or reset; a new context).  One stream wait and one 4-byte copy per such twin, once per write, not
+// per call.  An exact twin takes the launch without the fall-back; that is a kernel choice, so a changed answer drops the sampler's
+// graph families.  The caller holds g_dev_mu shared.
+static int head_w13_resolve(vv_ctx* ctx, hipStream_t st) {
+    if (!ctx->w13_on) return 0;
+    bool changed = false, waited = false;
+    for (W13Twin& t : ctx->twins) {
+        if (t.lm || t.exact >= 0) continue;
+        if (!waited) { HIPCHK(ctx, hipStreamSynchronize(st)); waited = true; }
+        unsigned ok = 0;
+        HIPCHK(ctx, hipMemcpy(&ok, (const char*)t.planes + vv_w13_plane_bytes(t.N, t.K) + (size_t)2 * (t.N / 16) * 4, 4, hipMemcpyDeviceToHost));
+        t.exact = ok == 1;
+        if (t.used >= 0 && t.used != t.exact) changed = true;
+        t.used = t.exact;
+    }
+    return changed ? drop_graphs(ctx, {"samp:", "sde:", "rows:", "gen:"}) : 0;
+}
+
 // The tail of every sampler entry point, behind its own checks and its key: eager, captured or replayed, then the NaN probe's report
 static int run_sampler(vv_ctx* ctx, hipStream_t st, const char* key, const SampleReq& r) {
     ctx->launches = 0;
+    { VV_SHARED; VVTRY(head_w13_resolve(ctx, st)); }
     const int rc = graphed(ctx, key, st, [&]() { return sample_body(ctx, st, r); });
     nan_probe_report(ctx, st, key);
     return rc;
@@ -370,6 +394,7 @@ extern "C" int vv_head_forward(vv_ctx* ctx, void* stream, int n, const float* no
     if (n < 1 || n > 16) return fail(ctx, "vv_head_forward: n must be in [1,16]");
     const int H = ctx->H;
     for (int i = 1; i < n; ++i) if (t_host[i] != t_host[0]) return fail(ctx, "vv_head_forward: all rows must share one timestep");
+    VVTRY(head_w13_resolve(ctx, st));
     float* tdev = ctx->tmp2 + 63 * 256;     // scratch
     HIPCHK(ctx, hipStreamSynchronize(st));
     HIPCHK(ctx, hipMemcpy(tdev + 128, t_host, 4, hipMemcpyHostToDevice));

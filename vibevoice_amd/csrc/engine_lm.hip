@@ -144,6 +144,10 @@ static int lm_gemv_layer(vv_ctx* ctx, hipStream_t st, int R, int l, int l1, cons
     VVGemm g = mk_gemm(L.wqkv, ctx->h, ctx->qkv, R, QKV, H, H, QKV);
     g.pro = VV_PRO_RMS; g.nw = L.ln1; g.eps = c.lm_eps; g.epi = VV_EPI_BIAS; g.bias = L.bqkv; g.nt = 1;
     g.xa = ctx->h_parts; g.n_xa = hp; g.part_stride = hps;
+    // W13: a launch streams its matrix's twin where the plan's form of it has a W13 instantiation (7B widths: QKV, gate/up and down;
+    // o keeps bf16, below)
+    const auto w13 = [&](const VVGemm& a, const void* t) { return p.w13 && t && vv_gemv_w13_form(&a, c.xsplit) >= 0; };
+    if (w13(g, L.tqkv)) g.w13 = L.tqkv;
     GEMM(g);
     if (p.attn == VV_ATTN_FUSED) {
         VVTRY(lm_decode_attn(ctx, st, R, l, p, nullptr));
@@ -169,14 +173,18 @@ static int lm_gemv_layer(vv_ctx* ctx, hipStream_t st, int R, int l, int l1, cons
     VVGemm go = mk_gemm(L.wo, ctx->attn, ctx->h, R, H, Hq * D, Hq * D, H);
     go.epi = VV_EPI_RESID; go.nt = 1;
     go.ya = ctx->h_parts; go.n_ya = hp; go.part_stride = hps;     // o_proj folds the parts back: h is whole again
+    // o keeps its bf16 launch although the residual form has a W13 instantiation: 25.7 MB at 7B is too short a stream for the decode to
+    // pay (6.94 us bf16 against 7.21 us W13 per launch, profiles/w13_lm_ab.json); its twin exists and is kept packed, unused
     GEMM(go);
     hp = 0;
     VVGemm gm = mk_gemm(L.wg, ctx->h, ctx->act, R, I, H, H, I);
     gm.W2 = (const u32x4*)L.wu; gm.pro = VV_PRO_RMS; gm.nw = L.ln2; gm.eps = c.lm_eps; gm.epi = VV_EPI_SWIGLU; gm.nt = 1;
+    if (L.tu && w13(gm, L.tg)) { gm.w13 = L.tg; gm.w13_2 = L.tu; }
     GEMM(gm);
     VVGemm gd = mk_gemm(L.wd, ctx->act, ctx->h, R, H, I, I, H);
     gd.epi = VV_EPI_RESID; gd.nt = 1;
     if (l + 1 < l1) hp = ksplit_parts(ctx, gd, ctx->h_parts, hps);     // the last layer leaves h whole for the final norm
+    if (w13(gd, L.td)) gd.w13 = L.td;
     GEMM(gd);
     return 0;
 }
@@ -235,7 +243,7 @@ extern "C" int vv_lm_forward_range(vv_ctx* ctx, void* stream, int n_rows, const 
         ctx->rope_ready = true;
     }
     VVLmPlan plan;
-    if (vv_lm_pass_plan(pin, n_rows, {ctx->ws_rows, ctx->c.attn_splits, ctx->Hkv, ctx->tile3_ok, ctx->attn2_ok, ctx->p16_ok}, &plan))
+    if (vv_lm_pass_plan(pin, n_rows, {ctx->ws_rows, ctx->c.attn_splits, ctx->Hkv, ctx->tile3_ok, ctx->attn2_ok, ctx->p16_ok, ctx->w13_lm}, &plan))
         return fail(ctx, "a launch of %d rows must be consecutive positions of one cache (decode / ragged launches take <= %d rows)", n_rows, ctx->ws_rows);
     char key[160]; snprintf(key, 160, "lm:%d:%p:%p:%d:%d:%d:%d:%d", n_rows, (const void*)x_in_dev, (void*)hidden_out_dev, l0, l1, final_norm,
                             plan.key_mode, plan.key_split);

@@ -52,10 +52,15 @@ constexpr int U = 8;       // k-steps per batch (256 k = one float4 per lane per
 // split K over 3 workgroup columns): the three loads are issued together and summed in a fixed order.
 // SL: slot-batched rows (VVGemm::sl_*): the rows of one launch are gathered from / scattered to the streaming buffers of up
 // to 8 utterances -- one weight pass for the tokenizer stages of a whole batch.  16-row form only.
-// WF: weight format.  0: packed bf16 fragments.  1: W13 planes (vv_w13.h; pW / pW2 are the twins): only the weight loads and the
-// fragment handed to the MFMA change -- the wave K ranges, the staging batches, the order of MFMAs over k, the reduce and the epilogue
-// are those of WF = 0, so the outputs are the same bits.  A wave's K range need not start or end on a 4-k-tile group: the groups at
-// its ends are loaded whole and the k-tiles outside the range skipped (a neighbour wave of the same workgroup streams them too).
+// WF: weight format.  0: packed bf16 fragments.  1, 2: W13 planes (vv_w13.h; pW / pW2 are the twins, a.W / a.W2 the bf16 fragments): only
+// the weight loads and the fragment handed to the MFMA change -- the wave K ranges, the staging batches, the order of MFMAs over k, the
+// reduce and the epilogue are those of WF = 0, so the outputs are the same bits.  A wave's K range need not start or end on a 4-k-tile
+// group: the groups at its ends are loaded whole and the k-tiles outside the range skipped (a neighbour wave of the same workgroup
+// streams them too).  A tile row whose ok word is 0 (an element outside the format's span; a twin never packed) is one workgroup: it
+// drops the groups it loaded and runs the bf16 loop of WF = 0 over a.W / a.W2 -- a workgroup-uniform branch only such rows pay for.
+// That is WF = 2.  WF = 1 is the same stream without the ok word, the branch and the bf16 loop, for twins the host knows to be exact in
+// every tile row (VVGemm::w13_exact; the diffusion head's matrices, re-read 20 times per step): the fall-back's presence alone costs
+// the head's gate/up launch 0.4 us (profiles/w13_lm_ab.json), which an exact twin need not pay.
 template <int XS, int PRO, int EPI, int MR, int WPB, int PARTS = 0, int SL = 0, int WF = 0>      // PARTS: 0 none, 1 activation side, 2 residual side
 // The operands every wave needs before its first load (weight / activation bases, shape, strides) are separate leading
 // scalar parameters: with -mllvm -amdgpu-kernarg-preload-count=16 the dispatcher delivers them in SGPRs at wave launch,
@@ -89,7 +94,7 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemv_kernel(const u32x4* __restri
     if constexpr (EPI == VV_EPI_CFG_DPM) asm volatile("" ::"s"(a.sde_noise), "s"(a.cfg_rows));
     VV_STAMP(0);
     VV_BSTAMP(0);
-    const int lane = threadIdx.x & 63;
+    int lane = threadIdx.x & 63;      // WF = 1: re-derived, with frow / fq / kk / st_off, in a tile row that falls back (see there)
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     // 16-row form: grid.y walks 16-row tiles of a tall activation (tokenizer stages, prefill chunks)
     const int t_base = (MR == 16) ? (int)blockIdx.y * 16 : 0;
@@ -105,13 +110,14 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemv_kernel(const u32x4* __restri
     const unsigned kt0 = kb0 + wave * kper;
     const unsigned kt1 = min(kb1, kt0 + kper);
     const bool has_k = kt0 < kt1;
-    const int frow = lane & 15, fq = lane >> 4;
+    int frow = lane & 15, fq = lane >> 4;
     unsigned char* stg = stg_all + (size_t)wave * (NOP * XS * U * 4 * GSB);
-    const unsigned kk = lane * 4;
-    const unsigned st_off = ((kk >> 5) * 4 + ((kk & 31) >> 3)) * GSB + (kk & 7) * 2;
+    unsigned kk = lane * 4;
+    unsigned st_off = ((kk >> 5) * 4 + ((kk & 31) >> 3)) * GSB + (kk & 7) * 2;
 
-    const u32x4* wbase = pW + (size_t)tile * k_tiles * 64 + lane;
-    const u32x4* wbase2 = DUAL ? pW2 + (size_t)tile * k_tiles * 64 + lane : nullptr;
+    // WF = 1: the bf16 fragments are a.W / a.W2, and only a tile row that falls back forms these addresses
+    const u32x4* wbase = WF ? nullptr : pW + (size_t)tile * k_tiles * 64 + lane;
+    const u32x4* wbase2 = DUAL && !WF ? pW2 + (size_t)tile * k_tiles * 64 + lane : nullptr;
     // W13: this tile row's groups in the twin's planes, and its scale word behind them (gridDim.x = the matrix's tile rows)
     const unsigned char* gbase = reinterpret_cast<const unsigned char*>(pW) + (size_t)tile * (k_tiles >> 2) * VV_W13_GROUP;
     const unsigned char* gbase2 = reinterpret_cast<const unsigned char*>(pW2) + (size_t)tile * (k_tiles >> 2) * VV_W13_GROUP;
@@ -188,7 +194,7 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemv_kernel(const u32x4* __restri
     };
     // ---- first activation batch and first weight batch go out before anything else ----
     XR R;
-    u32x4 wA[WF ? 1 : U][NM], wB[WF ? 1 : U][NM];
+    u32x4 wA[U][NM], wB[U][NM];      // WF = 1: live in a tile row that falls back alone
     if constexpr (WF) {
         if (has_k) {
             x_load(kt0, R);
@@ -342,63 +348,138 @@ __global__ __launch_bounds__(WPB * 64) void vv_gemv_kernel(const u32x4* __restri
 
     if constexpr (WF) {
         float wscale[NM];
-        {
-            const size_t tail = (size_t)gridDim.x * (k_tiles >> 2) * VV_W13_GROUP;
-            wscale[0] = vv_w13_scale(reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned char*>(pW) + tail)[tile]);
-            if constexpr (DUAL) wscale[1] = vv_w13_scale(reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned char*>(pW2) + tail)[tile]);
-        }
-        if (has_k) {
-            x_stage(kt0, R);
-            VV_STAMP(2);
-            const unsigned klen = kt1 - kt0;
-            // k-tile j of the wave (0 = kt0) sits in staging slot j & 7 of activation batch j >> 3, exactly as in the bf16 form
-            auto mma1 = [&](const u32x4 (&f)[NM][4], int t, unsigned slot) {
-                u32x4 xf = u32x4{0u, 0u, 0u, 0u};
-                if (frow < MRS) xf = *reinterpret_cast<const u32x4*>(stg + (size_t)(slot * 4 + fq) * GSB + frow * 16);
-                const bf16x8 xb = __builtin_bit_cast(bf16x8, xf);
+        // the W13 weight stream of a wave with K: the raw slots hold its first groups, the activations of its first batch are staged;
+        // Rx: the registers of the batches that follow
+        auto w13_loop = [&](XR& Rx) {
+        const unsigned klen = kt1 - kt0;
+        // k-tile j of the wave (0 = kt0) sits in staging slot j & 7 of activation batch j >> 3, exactly as in the bf16 form
+        auto mma1 = [&](const u32x4 (&f)[NM][4], int t, unsigned slot) {
+            u32x4 xf = u32x4{0u, 0u, 0u, 0u};
+            if (frow < MRS) xf = *reinterpret_cast<const u32x4*>(stg + (size_t)(slot * 4 + fq) * GSB + frow * 16);
+            const bf16x8 xb = __builtin_bit_cast(bf16x8, xf);
 #pragma unroll
-                for (int i = 0; i < NM; ++i)
-                    acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, f[i][t]), xb, acc[i], 0, 0, 0);
-            };
-            // weight batch i = groups g_lo + 2i, + 1 = k-tiles 8i - ph .. 8i + 7 - ph of the wave: the first ph of them belong to the
-            // activation batch i - 1 still staged, the others to batch i, staged between the two
-            auto wstep = [&](unsigned i, auto s0c, auto s1c) {      // s0, s1: the raw slots of the batch's two groups
-                constexpr int sl[2] = {decltype(s0c)::value, decltype(s1c)::value};
+            for (int i = 0; i < NM; ++i)
+                acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, f[i][t]), xb, acc[i], 0, 0, 0);
+        };
+        // weight batch i = groups g_lo + 2i, + 1 = k-tiles 8i - ph .. 8i + 7 - ph of the wave: the first ph of them belong to the
+        // activation batch i - 1 still staged, the others to batch i, staged between the two
+        auto wstep = [&](unsigned i, auto s0c, auto s1c) {      // s0, s1: the raw slots of the batch's two groups
+            constexpr int sl[2] = {decltype(s0c)::value, decltype(s1c)::value};
 #pragma unroll
-                for (int gi = 0; gi < 2; ++gi) {
-                    u32x4 f[NM][4];
-                    if (gi == 0) {
-                        if (ph > 0 && i > 0) {      // a range that starts inside a group (narrow models): decoded for these k-tiles alone
+            for (int gi = 0; gi < 2; ++gi) {
+                u32x4 f[NM][4];
+                if (gi == 0) {
+                    if (ph > 0 && i > 0) {      // a range that starts inside a group (narrow models): decoded for these k-tiles alone
 #pragma unroll
-                            for (int m = 0; m < NM; ++m) vv_w13_unpack(raw[sl[0]][m], wscale[m], f[m]);
+                        for (int m = 0; m < NM; ++m) vv_w13_unpack(raw[sl[0]][m], wscale[m], f[m]);
 #pragma unroll
-                            for (int t = 0; t < 3; ++t)
-                                if ((unsigned)t < ph && 8 * i + t - ph < klen) mma1(f, t, 8 + t - ph);
-                        }
-                        if (i > 0 && 8 * i < klen) x_stage(kt0 + 8 * i, R);
-                        if (8 * (i + 1) < klen) x_load(kt0 + 8 * (i + 1), R);
+                        for (int t = 0; t < 3; ++t)
+                            if ((unsigned)t < ph && 8 * i + t - ph < klen) mma1(f, t, 8 + t - ph);
                     }
+                    if (i > 0 && 8 * i < klen) x_stage(kt0 + 8 * i, Rx);
+                    if (8 * (i + 1) < klen) x_load(kt0 + 8 * (i + 1), Rx);
+                }
 #pragma unroll
-                    for (int m = 0; m < NM; ++m) vv_w13_unpack(raw[sl[gi]][m], wscale[m], f[m]);
-                    const unsigned gn = g_lo + 2 * i + gi + RG;
-                    if (gn < g_hi) g_load(gn, raw[sl[gi]]);      // the slot's next group goes out before this one's MFMAs
+                for (int m = 0; m < NM; ++m) vv_w13_unpack(raw[sl[gi]][m], wscale[m], f[m]);
+                const unsigned gn = g_lo + 2 * i + gi + RG;
+                if (gn < g_hi) g_load(gn, raw[sl[gi]]);      // the slot's next group goes out before this one's MFMAs
 #pragma unroll
-                    for (int t = 0; t < 4; ++t)
-                        if ((unsigned)t >= (gi == 0 ? ph : 0u) && 8 * i + 4 * gi + t - ph < klen) mma1(f, t, 4 * gi + t - ph);
+                for (int t = 0; t < 4; ++t)
+                    if ((unsigned)t >= (gi == 0 ? ph : 0u) && 8 * i + 4 * gi + t - ph < klen) mma1(f, t, 4 * gi + t - ph);
+            }
+        };
+        const unsigned n_wb = (ph + klen + 7) >> 3;
+        using S0 = std::integral_constant<int, 0>; using S1 = std::integral_constant<int, 1>; using S2 = std::integral_constant<int, 2>;
+        if constexpr (RG == 2) {
+#pragma unroll 1
+            for (unsigned i = 0; i < n_wb; ++i) wstep(i, S0{}, S1{});
+        } else {
+#pragma unroll 1
+            for (unsigned i = 0; i < n_wb; i += 3) {
+                wstep(i, S0{}, S1{});
+                if (i + 1 < n_wb) wstep(i + 1, S2{}, S0{});
+                if (i + 2 < n_wb) wstep(i + 2, S1{}, S2{});
+            }
+        }
+        };
+        if constexpr (WF == 1) {        // every tile row of the twin(s) is known to be exact: no ok word is read, no bf16 loop exists
+            {
+                const size_t tail = (size_t)gridDim.x * (k_tiles >> 2) * VV_W13_GROUP;
+                wscale[0] = vv_w13_scale(reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned char*>(pW) + tail)[tile]);
+                if constexpr (DUAL) wscale[1] = vv_w13_scale(reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned char*>(pW2) + tail)[tile]);
+            }
+            if (has_k) {
+                x_stage(kt0, R);
+                VV_STAMP(2);
+                w13_loop(R);
+            }
+        } else {
+            unsigned w13_ok;            // the tile row's ok word(s), fetched with its scale word(s): one scalar batch
+            {
+                const unsigned n_tiles = (unsigned)pN >> 4;      // = gridDim.x, from a preloaded argument: no round trip in front of the batch
+                const size_t tail = (size_t)n_tiles * (k_tiles >> 2) * VV_W13_GROUP;
+                const unsigned* t1 = reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned char*>(pW) + tail);
+                unsigned sw[NM];
+                sw[0] = t1[tile];
+                w13_ok = t1[n_tiles + tile];
+                if constexpr (DUAL) {
+                    const unsigned* t2 = reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned char*>(pW2) + tail);
+                    sw[1] = t2[tile];
+                    w13_ok &= t2[n_tiles + tile];
+                    asm volatile("" ::"s"(sw[1]));
+                }
+                // all of them in SGPRs here, under the first activation batch still in flight: left alone the compiler sinks the scale
+                // load behind the branch on the ok word, a scalar round trip in front of the weight loop of every launch
+                asm volatile("" ::"s"(sw[0]), "s"(w13_ok));
+#pragma unroll
+                for (int m = 0; m < NM; ++m) wscale[m] = vv_w13_scale(sw[m]);
+            }
+            if (has_k) x_stage(kt0, R);
+            VV_STAMP(2);
+            // a tile row that falls back: the bf16 weight stream of WF = 0 below, statement for statement (wA holds the batch at kt0, the
+            // activations of that batch are staged; Rx: the registers of the batches that follow).  Kept textually apart from it: with the
+            // WF = 0 loop routed through this lambda the register allocation of 44 bf16 forms moved by 1-8 VGPRs and one of them lost a wave.
+            auto w_stream = [&](XR& Rx) {
+                if constexpr (DUAL) {
+#pragma unroll 1
+                    for (unsigned ktb = kt0; ktb < kt1; ktb += U) {
+                        const bool n1 = ktb + U < kt1;
+                        if (n1) x_load(ktb + U, Rx);
+                        mma(ktb, wA);
+                        if (n1) { w_load(ktb + U, wA); x_stage(ktb + U, Rx); }
+                    }
+                } else
+#pragma unroll 1
+                for (unsigned ktb = kt0; ktb < kt1; ktb += 2 * U) {
+                    const bool n1 = ktb + U < kt1, n2 = ktb + 2 * U < kt1;
+                    if (n1) { x_load(ktb + U, Rx); w_load(ktb + U, wB); }
+                    mma(ktb, wA);
+                    if (n1) x_stage(ktb + U, Rx);
+                    if (n2) { x_load(ktb + 2 * U, Rx); w_load(ktb + 2 * U, wA); }
+                    if (n1) mma(ktb + U, wB);
+                    if (n2) x_stage(ktb + 2 * U, Rx);
                 }
             };
-            const unsigned n_wb = (ph + klen + 7) >> 3;
-            using S0 = std::integral_constant<int, 0>; using S1 = std::integral_constant<int, 1>; using S2 = std::integral_constant<int, 2>;
-            if constexpr (RG == 2) {
-#pragma unroll 1
-                for (unsigned i = 0; i < n_wb; ++i) wstep(i, S0{}, S1{});
-            } else {
-#pragma unroll 1
-                for (unsigned i = 0; i < n_wb; i += 3) {
-                    wstep(i, S0{}, S1{});
-                    if (i + 1 < n_wb) wstep(i + 1, S2{}, S0{});
-                    if (i + 2 < n_wb) wstep(i + 2, S1{}, S2{});
+            // Registers: both arms below keep the activations of their later batches in registers of their own (Rf; Rw, a copy of R), and the
+            // fall-back arm derives its lane constants afresh behind an opaque copy.  With R or those constants shared between the arms the
+            // compiler holds them across the W13 loop as well: +18 VGPRs on the 8-wave forms, one resident workgroup per CU less.  Rw starts
+            // as a copy of R rather than undefined: with nothing in it the next batch's activation loads were scheduled behind the weight
+            // groups of the trip, and the wait for them (vmcnt 16 -> 4) drained the weight stream once per batch: +0.35 us on a head gate/up
+            // launch.  The fall-back arm is marked unlikely so that block placement and allocation favour the W13 loop.
+            if (__builtin_expect(w13_ok == 0, 0)) {          // this tile row streams bf16: the groups in flight are dropped, the weight stream starts over
+                if (has_k) {
+                    asm volatile("" : "+v"(lane));
+                    frow = lane & 15; fq = lane >> 4; kk = lane * 4;
+                    st_off = ((kk >> 5) * 4 + ((kk & 31) >> 3)) * GSB + (kk & 7) * 2;
+                    wbase = a.W + (size_t)tile * k_tiles * 64 + lane;
+                    if constexpr (DUAL) wbase2 = a.W2 + (size_t)tile * k_tiles * 64 + lane;
+                    w_load(kt0, wA);
+                    XR Rf;
+                    w_stream(Rf);
                 }
+            } else if (has_k) {
+                XR Rw = R;      // a copy, not R itself: see above
+                w13_loop(Rw);
             }
         }
     } else
@@ -543,11 +624,13 @@ static constexpr std::array<GemvKernel, sizeof...(J)> gemv_kernel_table(std::ind
 }
 static const auto gemv_kernels = gemv_kernel_table(std::make_index_sequence<VV_GF_COUNT * VV_GEMV_MAX_PAIRS * VV_GEMV_MAX_XS>{});
 
-// the W13 forms of gemv_plan.h: [form][0] its bf16 instantiation (one of the table above), [form][1] the one that streams the twins
+// the W13 forms of gemv_plan.h: [form][0] its bf16 instantiation (one of the table above), [form][1] the one that streams twins known
+// to be exact, [form][2] the one that streams twins and falls back to bf16 per tile row
 template <size_t... J>
-static constexpr std::array<std::array<GemvKernel, 2>, sizeof...(J)> gemv_w13_table(std::index_sequence<J...>) {
+static constexpr std::array<std::array<GemvKernel, 3>, sizeof...(J)> gemv_w13_table(std::index_sequence<J...>) {
     return {{{vv_gemv_kernel<1, vv_gemv_w13_forms[J].pro, vv_gemv_w13_forms[J].epi, vv_gemv_w13_forms[J].mr, vv_gemv_w13_forms[J].wpb, 0, 0, 0>,
-              vv_gemv_kernel<1, vv_gemv_w13_forms[J].pro, vv_gemv_w13_forms[J].epi, vv_gemv_w13_forms[J].mr, vv_gemv_w13_forms[J].wpb, 0, 0, 1>}...}};
+              vv_gemv_kernel<1, vv_gemv_w13_forms[J].pro, vv_gemv_w13_forms[J].epi, vv_gemv_w13_forms[J].mr, vv_gemv_w13_forms[J].wpb, 0, 0, 1>,
+              vv_gemv_kernel<1, vv_gemv_w13_forms[J].pro, vv_gemv_w13_forms[J].epi, vv_gemv_w13_forms[J].mr, vv_gemv_w13_forms[J].wpb, 0, 0, 2>}...}};
 }
 static const auto gemv_w13_kernels = gemv_w13_table(std::make_index_sequence<VV_GEMV_W13_FORMS>{});
 
@@ -571,11 +654,12 @@ extern "C" int vv_gemv_launch(VVGemm a, int xs, hipStream_t s, int* form) {
     if (a.w13) {            // the caller asked for the twins: a W13 form of this very plan exists (vv_gemv_w13_form), or the call is refused
         const int wi = vv_gemv_w13_form(&a, xs);
         if (wi < 0 || (a.epi == VV_EPI_SWIGLU && !a.w13_2)) return VV_RC_NO_FORM;
-        k = gemv_w13_kernels[wi][1];
-        a.W = (const u32x4*)a.w13; a.W2 = (const u32x4*)a.w13_2;
+        k = gemv_w13_kernels[wi][a.w13_exact ? 1 : 2];
     }
     if (form) { form[0] = p.form.xs; form[1] = p.form.mr; form[2] = p.form.wpb; form[3] = p.form.parts; form[4] = p.form.sl; }
-    hipLaunchKernelGGL(k, p.grid, dim3(p.form.wpb * 64), 0, s, a.W, a.W2, a.X, a.Y, a.nw, a.T, a.N, a.K, a.ldx, a.ldy, a);
+    // a W13 form takes the twins as its leading (preloaded) pointers; a.W / a.W2 stay the bf16 fragments of tile rows that fall back
+    hipLaunchKernelGGL(k, p.grid, dim3(p.form.wpb * 64), 0, s, a.w13 ? (const u32x4*)a.w13 : a.W, a.w13 ? (const u32x4*)a.w13_2 : a.W2, a.X, a.Y, a.nw,
+                       a.T, a.N, a.K, a.ldx, a.ldy, a);
     return vv_launch_rc(0);
 }
 
@@ -585,8 +669,8 @@ extern "C" int vv_gemv_w13_form_launch(VVGemm a, int mr, int wpb, hipStream_t s)
     if (a.epi == VV_EPI_SWIGLU && (!a.W2 || (a.w13 && !a.w13_2))) return -1;
     const int wi = vv_gemv_w13_find(a.pro, a.epi, mr, wpb);
     if (wi < 0 || !vv_gemv_eligible(&a) || !vv_gemv_w13_shape(&a, 1) || a.T > mr) return VV_RC_NO_FORM;
-    const GemvKernel k = gemv_w13_kernels[wi][a.w13 ? 1 : 0];
-    if (a.w13) { a.W = (const u32x4*)a.w13; a.W2 = (const u32x4*)a.w13_2; }
-    hipLaunchKernelGGL(k, dim3(a.N / 16, 1), dim3(wpb * 64), 0, s, a.W, a.W2, a.X, a.Y, a.nw, a.T, a.N, a.K, a.ldx, a.ldy, a);
+    const GemvKernel k = gemv_w13_kernels[wi][a.w13 ? (a.w13_exact ? 1 : 2) : 0];
+    hipLaunchKernelGGL(k, dim3(a.N / 16, 1), dim3(wpb * 64), 0, s, a.w13 ? (const u32x4*)a.w13 : a.W, a.w13 ? (const u32x4*)a.w13_2 : a.W2, a.X, a.Y, a.nw,
+                       a.T, a.N, a.K, a.ldx, a.ldy, a);
     return vv_launch_rc(0);
 }

@@ -153,11 +153,14 @@ inline bool vv_gemv_plan(const VVGemm* a, int xs, VVGemvPlan* out) {
 }
 
 // ---- W13 forms (vv_w13.h): the instantiations of vv_gemv_kernel that stream a matrix's 13-bit twin -- the diffusion head's gate/up and
-// down projections of one utterance, in the forms the plan above gives them (wide outputs, and the default form of narrow models).
+// down projections of one utterance, in the forms the plan above gives them (wide outputs, and the default form of narrow models), and
+// the four projections of an LM layer at 7B widths (QKV and gate/up: wide outputs, 2 rows; o and down: the default form).
 // A W13 form keeps the wave K ranges, the staging, the MFMA order and the reduce of its bf16 form: same bits, 13/16 of the bytes.
+// A tile row the format cannot hold streams bf16 inside the same launch (gemv.hip: WF), so a twin serves its matrix whatever it holds.
 struct VVGemvW13Form { int pro, epi, mr, wpb; };
 inline constexpr VVGemvW13Form vv_gemv_w13_forms[] = {
-    {VV_PRO_RMS_MOD, VV_EPI_SWIGLU, 2, 4}, {VV_PRO_RMS_MOD, VV_EPI_SWIGLU, 4, 8}, {VV_PRO_NONE, VV_EPI_GATED_RESID, 4, 8}};
+    {VV_PRO_RMS_MOD, VV_EPI_SWIGLU, 2, 4}, {VV_PRO_RMS_MOD, VV_EPI_SWIGLU, 4, 8}, {VV_PRO_NONE, VV_EPI_GATED_RESID, 4, 8},
+    {VV_PRO_RMS, VV_EPI_BIAS, 2, 4}, {VV_PRO_RMS, VV_EPI_SWIGLU, 2, 4}, {VV_PRO_NONE, VV_EPI_RESID, 4, 8}};
 constexpr int VV_GEMV_W13_FORMS = sizeof(vv_gemv_w13_forms) / sizeof(vv_gemv_w13_forms[0]);
 inline int vv_gemv_w13_find(int pro, int epi, int mr, int wpb) {
     for (int i = 0; i < VV_GEMV_W13_FORMS; ++i) {

@@ -26,7 +26,7 @@ enum { VV_LM_PREFILL, VV_LM_P16, VV_LM_GEMV };                       // the laye
 enum { VV_ATTN_FUSED, VV_ATTN_PREFILL4, VV_ATTN_SPLIT_MERGE };       // the attention inside it
 
 // what the context offers a pass
-struct VVLmCaps { int ws_rows, attn_splits, Hkv; bool tile3_ok, attn2_ok, p16_ok; };
+struct VVLmCaps { int ws_rows, attn_splits, Hkv; bool tile3_ok, attn2_ok, p16_ok; bool w13 = false; };      // w13: the layers' matrices have W13 twins (vv_w13.h)
 
 struct VVLmPlan {
     bool fused;                 // every row a different cache: RoPE + append + attention in one launch
@@ -37,6 +37,7 @@ struct VVLmPlan {
     bool zero_v_tail;           // the pass reaches vv_attn_prefill4: the V tail past the chunk is zeroed once for every layer
     int key_mode, key_split;    // the graph key's last two fields
     int64_t kv_positions;       // cached positions the rows attend, summed (the profile window's byte count)
+    bool w13 = false;           // one utterance (<= 2 rows) on the GEMV route: a layer's projections stream their W13 twins where a form exists
 };
 
 // rows: n_rows validated (cache, pos) pairs.  0: *p is the pass;  -1: a ragged launch of more than ws_rows rows (fused and
@@ -78,6 +79,7 @@ inline int vv_lm_pass_plan(const VVRow* rows, int n_rows, const VVLmCaps& c, VVL
     p->zero_v_tail = p->route == VV_LM_PREFILL || chunk_attn;
     p->key_mode = fused ? 1 : (contiguous ? 2 : 0);
     p->key_split = chunk_attn ? 0 : S;
+    p->w13 = c.w13 && p->route == VV_LM_GEMV && n_rows <= 2;
     return 0;
 }
 
@@ -105,7 +107,7 @@ struct VVHeadPlan {
     bool seam;                  // decode rows, bf16 mode: every step but the last ends with the fused seam
     int final_stage;            // VV_FINAL_* of a step that does not
     bool solver_step;           // the general solver table: a step ends with solver.hip's launch behind the final layer's plain store
-    bool w13;                   // one utterance on the GEMV route: a layer's projections stream their W13 twins where the device found them exact
+    bool w13;                   // one utterance on the GEMV route: a layer's projections stream their W13 twins
 };
 
 // has_coef: the call has solver coefficients (the samplers; vv_head_forward has none and evaluates the head once)

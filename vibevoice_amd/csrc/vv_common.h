@@ -110,6 +110,9 @@ struct VVGemm {
     // vv_gemv_w13_form) and produces the bits of the bf16 launch
     const void* w13;
     const void* w13_2;
+    // the caller knows that every tile row of the twin(s) is exact (the folded ok word, read on the host): the launch takes the
+    // instantiation that reads no ok word and holds no bf16 loop (gemv.hip: WF = 1); 0: the one with the per-tile-row fall-back (WF = 2)
+    int w13_exact;
 };
 
 // ---- batch decode over pre-packed activations (gemv16p.hip) ----

@@ -104,6 +104,7 @@ int vv_gemv_ok(const VVGemm* a);
 int vv_gemv_launch(VVGemm a, int xs, hipStream_t s, int* form);
 int vv_gemv_w13_form_launch(VVGemm a, int mr, int wpb, hipStream_t s);      // tests: one named W13 form, streaming the twins or (w13 null) bf16
 int vv_w13_pack_launch(const void* packed, void* twin, int N, int K, hipStream_t s);
+int vv_w13_pack_rows_launch(const void* packed, void* twin, int N, int K, int tile0, int tiles, hipStream_t s);      // the tile rows tile0 .. tile0 + tiles - 1 alone
 int vv_w13_unpack_launch(const void* twin, void* packed, int N, int K, hipStream_t s);
 int vv_tile_ok(const VVGemm* a, int xs);
 int vv_tile_launch(VVGemm a, int xs, hipStream_t s);

@@ -10,10 +10,10 @@ constexpr int PACK_WAVES = 4;
 
 // One workgroup per 16-feature tile row: Emax over the row, then wave w packs groups w, w + 4, ...; every packed group is decoded
 // again with vv_w13_unpack and compared with the source bit for bit -- the answer is ok[tile], whatever the host thinks of the rule.
-__global__ __launch_bounds__(PACK_WAVES * 64) void vv_w13_pack_kernel(const u32x4* __restrict__ W, unsigned char* __restrict__ out, int n_tiles, int k_tiles) {
+__global__ __launch_bounds__(PACK_WAVES * 64) void vv_w13_pack_kernel(const u32x4* __restrict__ W, unsigned char* __restrict__ out, int n_tiles, int k_tiles, int tile0) {
     __shared__ unsigned red[PACK_WAVES];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned tile = blockIdx.x;
+    const unsigned tile = blockIdx.x + tile0;      // the launch covers the tile rows tile0 .. tile0 + gridDim.x - 1 of the matrix
     const int groups = k_tiles >> 2;
     const u32x4* src = W + (size_t)tile * k_tiles * 64;
     unsigned emax = 0;
@@ -114,12 +114,16 @@ __global__ __launch_bounds__(PACK_WAVES * 64) void vv_w13_unpack_kernel(const un
 
 // packed: the matrix's bf16 fragments (vv_pack_launch's output); twin: vv_w13_bytes(N, K) bytes.  The folded ok word is the twin's last
 // word but three: vv_w13_ok_offset
-extern "C" int vv_w13_pack_launch(const void* packed, void* twin, int N, int K, hipStream_t s) {
-    if (!vv_w13_shape_ok(N, K)) return VV_RC_NO_FORM;
+// tile0, tiles: the tile rows to pack (a parameter that is one part of the matrix: q, k or v of a QKV matrix); the fold covers all rows
+extern "C" int vv_w13_pack_rows_launch(const void* packed, void* twin, int N, int K, int tile0, int tiles, hipStream_t s) {
+    if (!vv_w13_shape_ok(N, K) || tile0 < 0 || tiles < 1 || tile0 + tiles > N / 16) return VV_RC_NO_FORM;
     const int n_tiles = N / 16, k_tiles = K / 32;
-    hipLaunchKernelGGL(vv_w13_pack_kernel, dim3(n_tiles), dim3(PACK_WAVES * 64), 0, s, (const u32x4*)packed, (unsigned char*)twin, n_tiles, k_tiles);
+    hipLaunchKernelGGL(vv_w13_pack_kernel, dim3(tiles), dim3(PACK_WAVES * 64), 0, s, (const u32x4*)packed, (unsigned char*)twin, n_tiles, k_tiles, tile0);
     hipLaunchKernelGGL(vv_w13_fold_kernel, dim3(1), dim3(256), 0, s, reinterpret_cast<unsigned*>((unsigned char*)twin + vv_w13_plane_bytes(N, K)), n_tiles);
     return vv_launch_rc(0);
+}
+extern "C" int vv_w13_pack_launch(const void* packed, void* twin, int N, int K, hipStream_t s) {
+    return vv_w13_pack_rows_launch(packed, twin, N, K, 0, N / 16, s);
 }
 extern "C" int vv_w13_unpack_launch(const void* twin, void* packed, int N, int K, hipStream_t s) {
     if (!vv_w13_shape_ok(N, K)) return VV_RC_NO_FORM;
