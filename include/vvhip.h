@@ -358,6 +358,42 @@ int vv_level_rows(vv_ctx* ctx, void* stream, int lv, int n, const vv_level_row* 
  * to the same signal pushed and flushed through vv_level_rows. */
 int vv_level_once(vv_ctx* ctx, void* stream, int A, int H, float gain, float ceiling, int n, int n_in, const float* audio_dev, int ld_in,
                   float* out_dev, int ld_out);
+/* ---- loudness: BS.1770 segment energies and a causal adaptive leveller at 24 kHz (vibevoice_amd/loudness.py defines them).  S = 2400
+ * samples a segment, hq the 2400 integer taps of the K-weighting (impulse response times 2^24).  xq = rint(fl(clamp(x, -8, 8) 2^20)),
+ * non-finite x: 0; z[i] = sum hq[k] xq[i - k], exact (|z| < 2^49, evaluated in fp64); zs = z >> 28; E[m] = sum of zs^2 over segment m:
+ * E / (S 2^32) is the segment's mean square.  Leveller: a segment counts if E >= 120856803 (-50 LUFS); with M30 / c30 the sum and
+ * number of the last <= 30 counted segments and M4 the sum of the last 4, w[m] = w[m-1] while c30 < 4, else
+ * clamp(sqrt(t / max(float(M30 >> 8) / float(c30 S 2^24), float(M4 >> 8) / float(4 S 2^24))), 10^(-24/20), wmax), every operation one
+ * fp32 rounding; w[-1] = w[-2] = g0; sample k of segment m: y = fl(fl(w[m-2] + fl(fl(w[m-1] - w[m-2]) fl(k / S))) x).  As many outputs
+ * as inputs, none held back; what a stream emits does not depend on how its input was cut into pushes.
+ * vv_loud_set: configuration ld (0..3) of this context: taps_host [2400] int32 = hq, n_streams streams at their first sample.  Replaces
+ * what ld held.  Synchronous. */
+int vv_loud_set(vv_ctx* ctx, int ld, const int* taps_host, int n_streams, void* stream);
+/* Back to the state after vv_loud_set for n streams (stream_ids_host == NULL: all of them): inputs, energies and gains zeroed by a kernel
+ * on `stream`, input total 0, parameters and flush mark cleared. */
+int vv_loud_reset(vv_ctx* ctx, void* stream, int ld, int n, const int* stream_ids_host);
+/* One push of n <= 16 rows, TWO kernel launches on `stream` (the FIR over tiles of 320 samples x rows, then one workgroup per row that
+ * closes segments and applies the gains): row i = n_in <= 3200 samples at audio_dev + i * ld_in for stream rows_host[i].stream
+ * (distinct) with t = float32(10^((target + 0.691) / 10)) in (0,1), g0 in (0,16], wmax in [1,16] (a stream keeps the parameters of its
+ * first push until its reset), flush != 0: the stream's last push (it emits nothing extra).  n_in fp32 outputs go to
+ * out_dev + i * ld_out; n_out_host [n] = n_in.  Refused with a message, nothing written, no state changed: as vv_resample_rows, a stream
+ * whose parameters change, a row of more than 3200 samples, and out_fmt = 1 (the stage is never the last one). */
+typedef struct vv_loud_row { int stream; int n_in; int flush; float t; float g0; float wmax; } vv_loud_row;
+int vv_loud_rows(vv_ctx* ctx, void* stream, int ld, int n, const vv_loud_row* rows_host, const float* audio_dev, int ld_in, void* out_dev,
+                 int ld_out, int out_fmt, int* n_out_host);
+/* Stateless: the energies E[i][m], m < n_in / 2400, of n whole signals of n_in samples (audio_dev + i * ld_in) as int64 at
+ * energies_dev + i * ld_e, and the same sums at 16 times the resolution, F[i][m] = sum (z >> 24)^2 < 2^62 (F / (S 2^40) is the mean
+ * square: what the meter reads, so that the floor of zs does not show at -60 LUFS), at fine_dev + i * ld_f.  Either pointer may be NULL,
+ * not both.  taps_dev [2400]: hq as fp64 on the device; the call does not inspect it.  The bounds E < 2^54 and F < 2^62 (and the exactness
+ * of z) are those of the K-weighting taps, sum |hq| = 3.25 2^24: vv_loud_set admits a tap sum up to 2^30 for the exactness of z in the
+ * leveller alone, and a caller that passes other taps here owns the range of the int64 sums. */
+int vv_loud_energy(vv_ctx* ctx, void* stream, const double* taps_dev, int n, int n_in, const float* audio_dev, int ld_in,
+                   long long* energies_dev, int ld_e, long long* fine_dev, int ld_f);
+/* Stateless: n whole signals of any length through the leveller -> n_in fp32 samples each (out_dev + i * ld_out) and, where gain_dev is
+ * not NULL, the gain of every sample (gain_dev + i * ld_gain).  energies_dev [n][ld_e >= n_in / 2400]: room for the energies, which the
+ * call leaves there.  Bit-identical to the same signal pushed through vv_loud_rows. */
+int vv_loud_once(vv_ctx* ctx, void* stream, const double* taps_dev, float t, float g0, float wmax, int n, int n_in, const float* audio_dev,
+                 int ld_in, float* out_dev, int ld_out, float* gain_dev, int ld_gain, long long* energies_dev, int ld_e);
 /* acoustic_cache.set_to_zero + semantic_cache.set_to_zero for a slot (:542-546) */
 int vv_codec_reset(vv_ctx* ctx, void* stream, int slot);
 /* acoustic_connector(latent) [+ semantic_connector(sem)] (:667-669, :161); sem_dev may be NULL */

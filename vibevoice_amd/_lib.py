@@ -65,6 +65,11 @@ class VVLevelRow(C.Structure):
     _fields_ = [("stream", C.c_int), ("n_in", C.c_int), ("flush", C.c_int), ("gain", C.c_float)]
 
 
+class VVLoudRow(C.Structure):
+    """vv_loud_row (include/vvhip.h): the stream, the input samples, the flush mark and t, g0, wmax of one row of vv_loud_rows"""
+    _fields_ = [("stream", C.c_int), ("n_in", C.c_int), ("flush", C.c_int), ("t", C.c_float), ("g0", C.c_float), ("wmax", C.c_float)]
+
+
 GEMV_REFUSED = 1     # VV_GEMV_REFUSED
 TEMPO_OVER_CAPACITY = 3     # VV_TEMPO_OVER_CAPACITY
 _SIGS = {
@@ -122,6 +127,11 @@ _SIGS = {
     "vv_level_reset": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "vv_level_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(VVLevelRow), _P, C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "vv_level_once": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int]),
+    "vv_loud_set": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),
+    "vv_loud_reset": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "vv_loud_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(VVLoudRow), _P, C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "vv_loud_energy": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, _P, C.c_int]),
+    "vv_loud_once": (C.c_int, [_P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, _P, C.c_int, _P, C.c_int]),
     "vv_codec_reset": (C.c_int, [_P, _P, C.c_int]),
     "vv_connect": (C.c_int, [_P, _P, C.c_int, _P, _P, _P]),
     "vv_packed_bytes": (C.c_int64, [C.c_int, C.c_int]),

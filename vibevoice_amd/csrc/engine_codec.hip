@@ -498,9 +498,9 @@ extern "C" int vv_codec_reset(vv_ctx* ctx, void* stream, int slot) {
     return 0;
 }
 
-// ------------------------------------------------------------------ streaming row stages: what the resampler, the tempo change and the level share
+// ------------------------------------------------------------------ streaming row stages: what the resampler, the tempo change, the level and the loudness leveller share
 // A stage keeps chunk-continuous streams (vv_ctx::RowStage) and takes up to 16 rows per push, one stream each.  `fn` is the entry
-// point's name: every refusal carries it.  `s` is null where the configuration is not set.  A third stage calls the same three.
+// point's name: every refusal carries it.  `s` is null where the configuration is not set.  Every stage calls the same three.
 
 // streams back to their first sample: launch(ids, n) zeroes the device state of up to 16 of them, clear(id) the stage's own host state
 template <class Launch, class Clear>
@@ -830,5 +830,99 @@ extern "C" int vv_level_once(vv_ctx* ctx, void* stream, int A, int H, float gain
     if (n_in > ld_out) return fail(ctx, "vv_level_once: %d output samples per row, the output rows hold %d", n_in, ld_out);
     if (!audio_dev || !out_dev) return fail(ctx, "vv_level_once: null audio / out pointer");
     VVCHK(vv_level_once_launch(A, H, gain, ceiling, n, n_in, audio_dev, ld_in, out_dev, ld_out, (hipStream_t)stream));
+    return 0;
+}
+
+// ------------------------------------------------------------------ loudness (kernels: loudness.hip; vibevoice_amd/loudness.py defines it)
+// The leveller holds nothing back: a push emits as many samples as it brings, the flush none.
+extern "C" int vv_loud_set(vv_ctx* ctx, int ld, const int* taps_host, int n_streams, void* stream) {
+    VV_SHARED;
+    if (ld < 0 || ld >= vv_ctx::N_LOUDS) return fail(ctx, "vv_loud_set: configuration %d out of range [0,%d)", ld, vv_ctx::N_LOUDS);
+    if (n_streams < 1 || n_streams > 65536) return fail(ctx, "vv_loud_set: n_streams = %d must be in [1,65536]", n_streams);
+    if (!taps_host) return fail(ctx, "vv_loud_set: null tap table");
+    std::vector<double> h(VV_LD_T);
+    double sum = 0.0;
+    for (int k = 0; k < VV_LD_T; ++k) { h[k] = (double)taps_host[k]; sum += std::fabs(h[k]); }
+    // |z| <= 2^23 sum |hq| must stay below 2^53 for the fp64 sums to be exact; the K-weighting's is 3.25 2^24
+    if (sum >= 1073741824.0) return fail(ctx, "vv_loud_set: the taps' absolute sum %.0f must stay below 2^30", sum);
+    vv_ctx::Loud& l = ctx->loud[ld];
+    HIPCHK(ctx, hipStreamSynchronize((hipStream_t)stream));      // pushes that still read what is replaced
+    dfree(ctx, l.taps); dfree(ctx, l.hist); dfree(ctx, l.state); dfree(ctx, l.part);
+    l = vv_ctx::Loud();
+    double* taps = (double*)dalloc(ctx, (size_t)VV_LD_T * 8, false);
+    int* hist = (int*)dalloc(ctx, (size_t)n_streams * VV_LD_T * 4, true);
+    VVLdState* state = (VVLdState*)dalloc(ctx, (size_t)n_streams * sizeof(VVLdState), true);
+    long long* part = (long long*)dalloc(ctx, (size_t)n_streams * VV_LD_MAX_TILES * 2 * 8, true);
+    if (!taps || !hist || !state || !part || hipMemcpy(taps, h.data(), (size_t)VV_LD_T * 8, hipMemcpyHostToDevice) != hipSuccess) {
+        dfree(ctx, taps); dfree(ctx, hist); dfree(ctx, state); dfree(ctx, part);
+        return fail(ctx, "vv_loud_set: allocating the state or uploading the taps failed");
+    }
+    l.n_streams = n_streams; l.taps = taps; l.hist = hist; l.state = state; l.part = part;
+    l.total.assign(n_streams, 0); l.flushed.assign(n_streams, 0);
+    l.t.assign(n_streams, 0.f); l.g0.assign(n_streams, 0.f); l.wmax.assign(n_streams, 0.f);
+    return 0;
+}
+
+extern "C" int vv_loud_reset(vv_ctx* ctx, void* stream, int ld, int n, const int* stream_ids_host) {
+    VV_SHARED;
+    vv_ctx::Loud* l = ld >= 0 && ld < vv_ctx::N_LOUDS && ctx->loud[ld].hist ? &ctx->loud[ld] : nullptr;
+    return stage_reset(ctx, "vv_loud_reset", l, ld, n, stream_ids_host,
+                       [&](const int* ids, int k) { return vv_loud_reset_launch(l->hist, l->state, l->n_streams, ids, k, (hipStream_t)stream); },
+                       [&](int id) { l->t[id] = 0.f; l->g0[id] = 0.f; l->wmax[id] = 0.f; });
+}
+
+extern "C" int vv_loud_rows(vv_ctx* ctx, void* stream, int ld, int n, const vv_loud_row* rows_host, const float* audio_dev, int ld_in,
+                            void* out_dev, int ld_out, int out_fmt, int* n_out_host) {
+    VV_SHARED;
+    vv_ctx::Loud* lp = ld >= 0 && ld < vv_ctx::N_LOUDS && ctx->loud[ld].hist ? &ctx->loud[ld] : nullptr;
+    const RowCheck ck{ctx, "vv_loud_rows", lp, audio_dev, ld_in};
+    VVTRY(ck.head(ld, n, rows_host, out_dev, n_out_host, out_fmt));
+    if (out_fmt != 0) return fail(ctx, "vv_loud_rows: out_fmt = 1 (int16) is not served: the leveller is never the last stage, a level stage follows it");
+    vv_ctx::Loud& l = *lp;
+    VVLdRows kr;
+    memset(&kr, 0, sizeof(kr));
+    for (int i = 0; i < n; ++i) {
+        const vv_loud_row& q = rows_host[i];
+        VVTRY(ck.stream(rows_host, i));
+        VVTRY(ck.input(i, q.n_in));
+        if (q.n_in > VV_LD_MAX_IN)
+            return fail(ctx, "vv_loud_rows: row %d brings %d samples, one push takes at most %d per row; push it in pieces", i, q.n_in, VV_LD_MAX_IN);
+        if (!vv_ld_params_ok(q.t, q.g0, q.wmax))
+            return fail(ctx, "vv_loud_rows: row %d: t = %g must lie in (0,1), g0 = %g in (0,16], wmax = %g in [1,16]", i, (double)q.t, (double)q.g0, (double)q.wmax);
+        if (l.t[q.stream] != 0.f && (l.t[q.stream] != q.t || l.g0[q.stream] != q.g0 || l.wmax[q.stream] != q.wmax))
+            return fail(ctx, "vv_loud_rows: stream %d runs at t = %g, g0 = %g, wmax = %g since its first push; reset it before they change", q.stream,
+                        (double)l.t[q.stream], (double)l.g0[q.stream], (double)l.wmax[q.stream]);
+        VVTRY(ck.open(q.stream));
+        if (q.n_in > ld_out) return fail(ctx, "vv_loud_rows: row %d emits %d samples, the output rows hold %d", i, q.n_in, ld_out);
+        const int64_t before = l.total[q.stream];
+        kr.r[i].stream = q.stream; kr.r[i].n_in = q.n_in; kr.r[i].n_out = q.n_in; kr.r[i].k0 = (int)(before % VV_LD_S); kr.r[i].h0 = (int)(before % VV_LD_T);
+        kr.r[i].first = before == 0; kr.r[i].t = q.t; kr.r[i].g0 = q.g0; kr.r[i].wmax = q.wmax;
+    }
+    VVTRY(stage_launch(ctx, l, rows_host, n, kr, n_out_host, [&] {
+        return vv_loud_rows_launch(&kr, n, l.taps, l.hist, l.state, l.part, l.n_streams, audio_dev, ld_in, (float*)out_dev, ld_out, (hipStream_t)stream); }));
+    for (int i = 0; i < n; ++i) { l.t[rows_host[i].stream] = rows_host[i].t; l.g0[rows_host[i].stream] = rows_host[i].g0; l.wmax[rows_host[i].stream] = rows_host[i].wmax; }
+    return 0;
+}
+
+extern "C" int vv_loud_energy(vv_ctx* ctx, void* stream, const double* taps_dev, int n, int n_in, const float* audio_dev, int ld_in,
+                              long long* energies_dev, int ld_e, long long* fine_dev, int ld_f) {
+    VV_SHARED;
+    if (n < 1 || n > 65535 || n_in < 1 || n_in > ld_in) return fail(ctx, "vv_loud_energy: n = %d in [1,65535], n_in = %d in [1, ld_in = %d]", n, n_in, ld_in);
+    if ((energies_dev && n_in / VV_LD_S > ld_e) || (fine_dev && n_in / VV_LD_S > ld_f))
+        return fail(ctx, "vv_loud_energy: %d segments per row, the energy rows hold %d", n_in / VV_LD_S, energies_dev && n_in / VV_LD_S > ld_e ? ld_e : ld_f);
+    if (!taps_dev || !audio_dev || (n_in >= VV_LD_S && !energies_dev && !fine_dev)) return fail(ctx, "vv_loud_energy: null taps / audio / energies pointer");
+    VVCHK(vv_loud_energy_launch(taps_dev, n, n_in, audio_dev, ld_in, energies_dev, ld_e, fine_dev, ld_f, (hipStream_t)stream));
+    return 0;
+}
+
+extern "C" int vv_loud_once(vv_ctx* ctx, void* stream, const double* taps_dev, float t, float g0, float wmax, int n, int n_in, const float* audio_dev,
+                            int ld_in, float* out_dev, int ld_out, float* gain_dev, int ld_gain, long long* energies_dev, int ld_e) {
+    VV_SHARED;
+    if (!vv_ld_params_ok(t, g0, wmax)) return fail(ctx, "vv_loud_once: t = %g must lie in (0,1), g0 = %g in (0,16], wmax = %g in [1,16]", (double)t, (double)g0, (double)wmax);
+    if (n < 1 || n > 65535 || n_in < 1 || n_in > ld_in) return fail(ctx, "vv_loud_once: n = %d in [1,65535], n_in = %d in [1, ld_in = %d]", n, n_in, ld_in);
+    if (n_in > ld_out || (gain_dev && n_in > ld_gain)) return fail(ctx, "vv_loud_once: %d output samples per row, the output rows hold %d", n_in, gain_dev ? std::min(ld_out, ld_gain) : ld_out);
+    if (n_in / VV_LD_S > ld_e) return fail(ctx, "vv_loud_once: %d segments per row, the energy rows hold %d", n_in / VV_LD_S, ld_e);
+    if (!taps_dev || !audio_dev || !out_dev || (n_in >= VV_LD_S && !energies_dev)) return fail(ctx, "vv_loud_once: null taps / audio / out / energies pointer");
+    VVCHK(vv_loud_once_launch(taps_dev, t, g0, wmax, n, n_in, audio_dev, ld_in, out_dev, ld_out, gain_dev, ld_gain, energies_dev, ld_e, (hipStream_t)stream));
     return 0;
 }

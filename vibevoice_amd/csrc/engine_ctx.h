@@ -207,6 +207,13 @@ struct vv_ctx {
     struct Level : RowStage { int A = 0, H = 0; float c = 0.f; float* hist = nullptr; std::vector<float> gain; };
     static constexpr int N_LEVELS = 4;
     Level lv[N_LEVELS];
+    // streaming loudness levellers (vv_loud_set, engine_codec.hip; kernels: loudness.hip): the taps as fp64, per stream a ring of VV_LD_T
+    // quantised inputs, a VVLdState and the FIR launch's tile sums on the device, and on the host its parameters t, g0, wmax (fixed by its
+    // first push, t = 0 before).  Kept like the resamplers.
+    struct Loud : RowStage { double* taps = nullptr; int* hist = nullptr; VVLdState* state = nullptr; long long* part = nullptr;
+                             std::vector<float> t, g0, wmax; };
+    static constexpr int N_LOUDS = 4;
+    Loud loud[N_LOUDS];
     int64_t launches = 0;
     int64_t solver_fused = 0;         // general-path step ends that carried the next in-projection, last recorded body (vv_stat 8)
     int64_t seam_launches = 0;        // head-tail seam launches the last recorded sampler body issued (vv_stat 6; a replay keeps its capture's count)

@@ -202,6 +202,28 @@ struct VVLvRows { VVLvRow r[16]; };
 constexpr int VV_LV_BUF = 8128;            // samples of a row's staging buffer (two 32-bit words each in LDS; vibevoice_amd/level.py: BUF)
 constexpr int VV_LV_MAX_A = 2047;          // keeps the window sums below 2^31
 
+// ---- streaming loudness leveller (loudness.hip): one row of a push, passed by value in the kernel arguments ----
+// The host keeps each stream's 64-bit input total and its parameters; of the total the kernels need k0 = total % VV_LD_S, the position of
+// the row's first sample in its open segment, h0 = total % VV_LD_T, that sample's slot in the stream's ring of quantised inputs, and
+// first = (total == 0): the stream's gains are g0 and its state counts as empty.  n_out = n_in: the stage holds nothing back.
+struct VVLdRow { int stream, n_in, n_out, k0, h0, first; float t, g0, wmax; };
+struct VVLdRows { VVLdRow r[16]; };
+constexpr int VV_LD_S = 2400;              // samples of a segment (vibevoice_amd/loudness.py: S)
+constexpr int VV_LD_T = 2400;              // taps of the K-weighting FIR; a stream's ring holds as many quantised inputs, T - 1 of them live
+constexpr int VV_LD_RING = 30;             // counted segments the slow mean looks back over
+constexpr int VV_LD_MAX_IN = 3200;         // input samples one row of a push may bring (loudness.py: MAX_IN): at most 2 segments close
+constexpr int VV_LD_TILE = 320;            // outputs of one FIR workgroup: 64 lanes x 5
+constexpr int VV_LD_MAX_TILES = VV_LD_MAX_IN / VV_LD_TILE;
+constexpr long long VV_LD_GATE = 120856803LL;   // EG = floor(S 2^32 10^((-50 + 0.691) / 10)) (loudness.py: EG)
+// what a stream keeps on the device besides its ring of inputs: the open segment's running sum, the ring of counted energies (the next
+// one goes to e[head]; count of them are live) and the last two wanted gains
+struct VVLdState { long long acc; long long e[VV_LD_RING]; int head, count; float w1, w2; };
+// the ranges of a stream's parameters, for the entry points (engine_codec.hip) and the launchers (loudness.hip) alike: t of a target in
+// [-36, -10] LUFS, g0 of [-24, +24] dB, wmax of [0, 24] dB; a NaN compares false
+static inline bool vv_ld_params_ok(float t, float g0, float wmax) {
+    return t > 0.f && t < 1.0f && g0 > 0.f && g0 <= 16.0f && wmax >= 1.0f && wmax <= 16.0f;
+}
+
 // Raise the dynamic-LDS limit of one or more kernels above the 64 KiB default; returns the first error.  A launcher calls it as
 // the initialiser of a function-local `static const hipError_t`: C++11 runs that initialiser once per process and makes
 // concurrent first calls wait for it (generate_interleaved and fork() drive two contexts from two host threads).

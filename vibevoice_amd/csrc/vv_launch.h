@@ -129,4 +129,13 @@ int vv_level_rows_launch(const VVLvRows* rows, int n, int A, int H, float c, flo
                          int ld_out, int pcm16, hipStream_t s);
 int vv_level_once_launch(int A, int H, float g, float c, int n, int n_in, const float* x, int ld_in, float* out, int ld_out, hipStream_t s);
 int vv_level_reset_launch(float* hist, int nh, int n_streams, const int* ids, int n, hipStream_t s);
+// loudness.hip.  taps [VV_LD_T] the integer taps as fp64; hist [n_streams][VV_LD_T] each stream's ring of quantised inputs, state [n_streams],
+// part [n_streams][VV_LD_MAX_TILES][2] the FIR launch's sums for the apply launch.  E [n][ld_e]: segment energies, F [n][ld_f]: the same at 16 times
+// the resolution, sum (z >> 24)^2 (either may be null).
+int vv_loud_rows_launch(const VVLdRows* rows, int n, const double* taps, int* hist, VVLdState* state, long long* part, int n_streams, const float* x,
+                        int ld_in, float* out, int ld_out, hipStream_t s);
+int vv_loud_energy_launch(const double* taps, int n, int n_in, const float* x, int ld_in, long long* E, int ld_e, long long* F, int ld_f, hipStream_t s);
+int vv_loud_once_launch(const double* taps, float t, float g0, float wmax, int n, int n_in, const float* x, int ld_in, float* out, int ld_out,
+                        float* gain, int ld_gain, long long* E, int ld_e, hipStream_t s);
+int vv_loud_reset_launch(int* hist, VVLdState* state, int n_streams, const int* ids, int n, hipStream_t s);
 }

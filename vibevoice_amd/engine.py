@@ -535,7 +535,7 @@ class Engine:
                   "vv_audio_to_pcm16")
 
     # ------------------------------------------------------------------ streaming row stages and their whole-signal forms
-    _STAGE_USED = {"resampler": "_rs_used", "tempo": "_tp_used", "level": "_lv_used"}
+    _STAGE_USED = {"resampler": "_rs_used", "tempo": "_tp_used", "level": "_lv_used", "loudness": "_ld_used"}
 
     def _take_stage_slot(self, kind, make):
         """make(k) for the first free k of this engine's four `kind` configurations; the stage's close() gives k back"""
@@ -634,6 +634,75 @@ class Engine:
         def run(st, nn, n_in, x, out, _):
             self._chk(self.lib.vv_level_once(self._ctx, st, A, H, g, c, nn, n_in, self._p(x), n_in, self._p(out), n_out), "vv_level_once")
         return self._whole("apply_level", audio, n_out, run, stream)[0]
+
+    # loudness (loudness.py, csrc/loudness.hip)
+    def loudness(self, n_streams: int) -> "Loudness":
+        """A streaming adaptive leveller at 24 kHz with n_streams independent streams, each with its own target, in one of this engine's
+        four loudness configurations (close() it to give the configuration back)."""
+        return self._take_stage_slot("loudness", lambda k: Loudness(self, k, n_streams))
+
+    def _loud_taps(self):
+        from . import loudness as _ld
+        w = self.__dict__.get("_ld_taps")
+        if w is None:
+            w = self.__dict__["_ld_taps"] = torch.from_numpy(_ld.taps().astype(np.float64)).to(self.device)
+        return w
+
+    def segment_energies(self, audio: torch.Tensor, stream=None, fine: bool = False) -> torch.Tensor:
+        """The K-weighted energy of every complete 100 ms segment: audio [samples] or [n, samples] (24 kHz, any float dtype, any device)
+        -> int64 [..., samples // 2400] on the engine's device, E / (2400 * 2**32) a segment's mean square: the definition of
+        vibevoice_amd/loudness.py, integer for integer.  fine: F, the same sums at 16 times the resolution, F / (2400 * 2**40) the
+        mean square (what measure_loudness reads).  Stateless; runs on `stream` (default: the device's current torch stream)."""
+        from . import loudness as _ld
+        x = audio.detach().to(device=self.device, dtype=torch.float32)
+        if x.dim() not in (1, 2):
+            raise ValueError(f"Engine.segment_energies: audio is [samples] or [n, samples], got {tuple(audio.shape)}")
+        x2 = x.reshape(-1, x.shape[-1]).contiguous()
+        n, n_in = x2.shape
+        n_seg = n_in // _ld.S
+        E = torch.empty((n, n_seg), dtype=torch.int64, device=self.device)
+        if n and n_seg:
+            st = self._sp(stream if stream is not None else torch.cuda.current_stream(self.device))
+            for i0 in range(0, n, 65535):
+                e = (None, 0, self._p(E[i0:]), n_seg) if fine else (self._p(E[i0:]), n_seg, None, 0)
+                self._chk(self.lib.vv_loud_energy(self._ctx, st, self._p(self._loud_taps()), min(65535, n - i0), n_in, self._p(x2[i0:]), n_in, *e),
+                          "vv_loud_energy")
+        return E.reshape(x.shape[:-1] + (n_seg,))
+
+    def measure_loudness(self, audio: torch.Tensor, stream=None) -> torch.Tensor:
+        """The ITU-R BS.1770-4 loudness in LUFS of audio [samples] or [n, samples] at 24 kHz -> a float64 CPU tensor, one value per row
+        (a scalar tensor for a 1-D signal); -inf for a signal with no 400 ms block over -70 LUFS or shorter than 400 ms.  The device
+        delivers the segment energies, the gating runs on the host over a few numbers per second of audio (this call waits for them)."""
+        from . import loudness as _ld
+        F = self.segment_energies(audio, stream, fine=True)
+        n_rows = int(np.prod(F.shape[:-1]))                         # explicit: a signal under one segment has rows of no energies
+        rows = F.reshape(n_rows, F.shape[-1]).cpu().tolist()        # the copy waits for the producing stream
+        return torch.tensor([_ld.gated(r, fine=True) for r in rows], dtype=torch.float64).reshape(F.shape[:-1])
+
+    def apply_loudness(self, audio: torch.Tensor, target_lufs: float = -16.0, start_db: float = 0.0, max_boost_db: float = 12.0,
+                       return_gain: bool = False, stream=None):
+        """Whole signals through the adaptive leveller: audio [samples] or [n, samples] (24 kHz, any float dtype, any device) -> fp32 on
+        the engine's device, as many samples, brought towards target_lufs (-36 .. -10) by a gain that follows the loudness of the last
+        three seconds of speech (and of the last 400 ms where that is louder), starts at start_db (-24 .. +24) and stays within
+        [-24 dB, max_boost_db]: the definition of vibevoice_amd/loudness.py, bit for bit.  No limiter: a boost can pass full scale, run
+        apply_level behind it.  return_gain: -> (out, gain), the gain of every sample.  Stateless; runs on `stream`."""
+        from . import loudness as _ld
+        t, g0, wmax = float(_ld.target_of(target_lufs)), float(_ld.start_of(start_db)), float(_ld.boost_of(max_boost_db))
+        n_out = int(audio.shape[-1]) if audio.dim() else 0
+        n_seg = max(n_out // _ld.S, 1)
+        gains = []
+
+        def run(st, nn, n_in, x, out, _):
+            E = torch.empty((nn, n_seg), dtype=torch.int64, device=self.device)
+            g = torch.empty((nn, n_out), dtype=torch.float32, device=self.device) if return_gain else None
+            gains.append(g)
+            self._chk(self.lib.vv_loud_once(self._ctx, st, self._p(self._loud_taps()), t, g0, wmax, nn, n_in, self._p(x), n_in, self._p(out), n_out,
+                                            self._p(g) if g is not None else None, n_out, self._p(E), n_seg), "vv_loud_once")
+        out = self._whole("apply_loudness", audio, n_out, run, stream)[0]
+        if not return_gain:
+            return out
+        g = torch.cat(gains) if gains else torch.empty((0, n_out), dtype=torch.float32, device=self.device)
+        return out, g.reshape(out.shape)
 
     def codec_reset(self, slot: int):
         self._chk(self.lib.vv_codec_reset(self._ctx, self._s, slot), "vv_codec_reset")
@@ -997,7 +1066,7 @@ class TempoCapacityError(EngineError):
 
 
 class _RowStage:
-    """What the streaming row stages share (Tempo, Resampler, Level): n_streams chunk-continuous streams in
+    """What the streaming row stages share (Loudness, Tempo, Resampler, Level): n_streams chunk-continuous streams in
     one of the engine's configurations, pushed up to 16 rows a launch.  A stage supplies KIND (Engine._STAGE_USED), its row struct ROW
     and how push() fills it, its C entry points ROWS_FN / RESET_FN, counts(), max_out() and take()."""
     KIND = ROW = ROWS_FN = RESET_FN = None
@@ -1235,4 +1304,53 @@ class Level(_RowStage):
         rows = (self.ROW * max(n, 1))()
         for i in range(n):
             rows[i].stream, rows[i].n_in, rows[i].flush, rows[i].gain = ids[i], nin[i], int(fl[i]), gains[i]
+        return out, self._launch(audio, samples, ids, nin, rows, out, pcm16, stream)
+
+
+class Loudness(_RowStage):
+    """One streaming loudness configuration of an engine (Engine.loudness): n_streams chunk-continuous adaptive levellers at 24 kHz,
+    each with the target, start gain and upper bound of its first push until its reset (which clears them with the rest).  What a stream
+    delivers does not depend on how its input was cut into pushes (vibevoice_amd/loudness.py): the concatenation of its pushes equals
+    Engine.apply_loudness() of the concatenated input, bit for bit, as many samples; nothing is held back (delay_samples = 0) and the
+    flush emits nothing.  max_in: the input samples one row of a push may bring.  fp32 only: a level stage follows this one."""
+    KIND, ROW, ROWS_FN, RESET_FN = "loudness", _lib.VVLoudRow, "vv_loud_rows", "vv_loud_reset"
+    NO_ROWS = (0,)                                        # one launch, which vv_loud_rows refuses by name
+
+    def __init__(self, engine: Engine, slot: int, n_streams: int):
+        from . import loudness as _ld
+        super().__init__(engine, slot, n_streams)
+        self.rate, self.delay_samples, self.max_in = _ld.RATE, 0, _ld.push_width()
+        h = np.ascontiguousarray(_ld.taps())
+        engine._chk(engine.lib.vv_loud_set(engine._ctx, slot, C.c_void_p(h.ctypes.data), self.n_streams, engine._s), "vv_loud_set")
+
+    def counts(self, stream_id: int, n_in: int, flush: bool = False) -> int:
+        """samples a push of n_in samples to stream_id would emit now: as many as it brings"""
+        from . import loudness as _ld
+        return _ld.counts(self.total[stream_id], n_in, flush)[1]
+
+    def max_out(self, n_in: int) -> int:
+        """what a push of up to n_in samples emits at most: n_in (at least one column: a flush that brings nothing still names rows)"""
+        return max(int(n_in), 1)
+
+    def take(self, ids, remaining, flush=False):
+        return min(self.max_in, max(remaining))
+
+    def push(self, audio: Optional[torch.Tensor], stream_ids: Sequence[int], targets_lufs, start_db=0.0, max_boost_db=12.0, flush=False,
+             out: Optional[torch.Tensor] = None, n_in=None, stream=None, pcm16: bool = False):
+        """Row i of audio [n, samples] (contiguous fp32 on the engine's device; None where no row brings samples) goes to stream
+        stream_ids[i] (distinct) with targets_lufs[i], start_db[i] and max_boost_db[i] (or one value for all rows; a stream keeps the
+        parameters of its first push); n_in: samples of each row that count (default: all), flush: bool or one per row -- a stream's
+        last push, after which it takes no more until reset().  -> (out, counts): out[i, :counts[i]] is what row i emitted, fp32,
+        counts[i] = n_in[i].  out: a contiguous fp32 [>= n, capacity] tensor to write into (default: a new one).  Two kernel launches per
+        16 rows on `stream` (default: the device's current torch stream); nothing waits for the device.  A row of more than max_in
+        samples is refused: push it in pieces of take().  pcm16 is refused by name: the stage is never the last one."""
+        from . import loudness as _ld
+        ids, samples, nin, fl, tg, sd, mb = self._args(audio, stream_ids, flush, n_in, targets_lufs=targets_lufs, start_db=start_db,
+                                                       max_boost_db=max_boost_db)
+        par = [(float(_ld.target_of(a)), float(_ld.start_of(b)), float(_ld.boost_of(c))) for a, b, c in zip(tg, sd, mb)]
+        n, out = len(ids), self._out(out, len(ids), nin, pcm16)
+        rows = (self.ROW * max(n, 1))()
+        for i in range(n):
+            rows[i].stream, rows[i].n_in, rows[i].flush = ids[i], nin[i], int(fl[i])
+            rows[i].t, rows[i].g0, rows[i].wmax = par[i]
         return out, self._launch(audio, samples, ids, nin, rows, out, pcm16, stream)

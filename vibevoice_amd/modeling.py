@@ -600,6 +600,43 @@ class _AudioRates:
         are wanted, at the rate they deliver.  generate() itself has no level input."""
         return self.engine.apply_level(audio, volume_db, ceiling_db, int(rate))
 
+    def measure_loudness(self, audio: torch.Tensor) -> torch.Tensor:
+        """The ITU-R BS.1770-4 loudness in LUFS of audio [samples] or [n, samples] at 24 kHz -> a float64 CPU tensor, one value per row;
+        -inf for silence and for less than 400 ms (Engine.measure_loudness).  For speech_outputs, and for a voice sample: its reading
+        tells AudioStreamer(loudness_start_db=target - reading) where to start."""
+        return self.engine.measure_loudness(audio)
+
+    def normalize_loudness(self, audio: torch.Tensor, target_lufs: float = -16.0, ceiling_db: float = -1.0) -> torch.Tensor:
+        """audio [samples] at 24 kHz -> fp32 on the engine's device at target_lufs (-16 for podcasts, -23 for broadcast): one fixed gain
+        of target_lufs - measure_loudness(audio) dB, then the peak limiter of apply_level under ceiling_db.  Where the limiter engages
+        the result reads below the target.  [n, samples]: each row by its own measurement.  Refused by name: a signal that reads -inf
+        (silence, or shorter than 400 ms) and a gain outside apply_level's -40 .. +24 dB."""
+        from . import level as _lv
+        from . import loudness as _ld
+        target = _ld._range("target_lufs", target_lufs, _ld.MIN_TARGET, _ld.MAX_TARGET, "LUFS")
+        measured = self.measure_loudness(audio).reshape(-1).tolist()
+        vols = []
+        for i, m in enumerate(measured):
+            if m == float("-inf"):
+                raise ValueError(f"normalize_loudness: signal {i} reads -inf LUFS (silence, or shorter than 400 ms): there is no gain that "
+                                 "brings it to a target")
+            vol = target - m
+            if not (_lv.MIN_VOLUME_DB <= vol <= _lv.MAX_VOLUME_DB):
+                raise ValueError(f"normalize_loudness: signal {i} reads {m:.2f} LUFS; target_lufs = {target} asks for volume_db = {vol:.2f}, "
+                                 f"outside apply_level's [{_lv.MIN_VOLUME_DB}, {_lv.MAX_VOLUME_DB}] dB")
+            vols.append(vol)
+        if audio.dim() == 1:
+            return self.apply_level(audio, vols[0], ceiling_db)
+        rows = audio.reshape(-1, audio.shape[-1])
+        return torch.stack([self.apply_level(rows[i], vols[i], ceiling_db) for i in range(len(vols))]).reshape(audio.shape)
+
+    def apply_loudness(self, audio: torch.Tensor, target_lufs: float = -16.0, start_db: float = 0.0, max_boost_db: float = 12.0,
+                       return_gain: bool = False):
+        """audio [samples] or [n, samples] at 24 kHz -> fp32 on the engine's device, as many samples, through the adaptive leveller
+        AudioStreamer(loudness_lufs=...) runs while the audio is produced (Engine.apply_loudness): the gain follows the speaker.  No
+        limiter: run apply_level behind it.  generate() itself has no loudness input."""
+        return self.engine.apply_loudness(audio, target_lufs, start_db, max_boost_db, return_gain=return_gain)
+
 
 class VibeVoiceForConditionalGenerationInference(_AudioRates):
     """Drop-in for the reference class on the generate() path, backed by libvvhip.so."""

@@ -35,7 +35,16 @@ the ceiling, so under pcm16 the per-chunk rescale of the 16-bit rule never fires
 smoothly across chunk boundaries.  A sample holds back 5 ms less one sample until its next chunk; end(indices) flushes that tail last.
 Device chunks need an engine (as above), CPU chunks go through level.HostLevel.
 
-The device stages form one chain (self._stages, _put_device): the tempo change, the resampler, the level, whichever exist, each an engine
+`loudness_lufs=T` (a float in [-36, -10], or one per sample index) brings each sample towards T LUFS (ITU-R BS.1770) while it is produced:
+a causal adaptive leveller (Engine.loudness, csrc/loudness.hip; vibevoice_amd/loudness.py is the definition), the first stage, at
+24 kHz, in front of the tempo change.  Its gain follows the loudness of the last three seconds of speech, comes down within 400 ms of a
+louder speaker, starts at `loudness_start_db` (default 0 dB: the first 400 ms of speech pass at that gain) and never exceeds
+`max_boost_db` (default 12); the two are refused without a target.  It holds nothing back and its flush adds nothing.  A boost can pass
+full scale, so such a streamer always has a level stage behind it (ceiling -1 dB unless ceiling_db is given): no delivered sample
+exceeds the ceiling.  Chunk-continuous: per sample, what reaches the next stage equals Engine.apply_loudness() of the concatenated
+input, bit for bit.  Device chunks need an engine (as above), CPU chunks go through loudness.HostLoudness.
+
+The device stages form one chain (self._stages, _put_device): the leveller, the tempo change, the resampler, the level, whichever exist, each an engine
 row stage (engine._RowStage) pushed on the producing stream; the last one writes the ring slot's staging, as int16 under pcm16 (over
 each row's own chunk), and with no stage the 16-bit conversion does, else the chunk itself is copied.  A chunk longer than one push of
 a stage takes (stage.take()) is pushed in pieces and arrives as several.
@@ -126,10 +135,39 @@ def _volumes_of(volume_db, ceiling_db, batch_size):
     return vols, ceiling
 
 
+def _loudness_of(loudness_lufs, loudness_start_db, max_boost_db, batch_size):
+    """AudioStreamer's loudness arguments as (targets in LUFS, start gains in dB, upper bounds in dB), one per sample index each; None
+    where there is no target.  The other two alone are refused."""
+    from .loudness import DEFAULT_BOOST_DB, boost_of, start_of, target_of
+    if loudness_lufs is None:
+        for name, v in (("loudness_start_db", loudness_start_db), ("max_boost_db", max_boost_db)):
+            if v is not None:
+                raise ValueError(f"AudioStreamer({name}=...) belongs to loudness_lufs=..., which is not given")
+        return None
+    cols = []
+    for name, v, default, check in (("loudness_lufs", loudness_lufs, None, target_of), ("loudness_start_db", loudness_start_db, 0.0, start_of),
+                                    ("max_boost_db", max_boost_db, DEFAULT_BOOST_DB, boost_of)):
+        v = default if v is None else v
+        col = [float(v)] * batch_size if not hasattr(v, "__len__") else [float(u) for u in v]
+        if len(col) != batch_size:
+            raise ValueError(f"AudioStreamer({name}=...): one value, or one per sample index ({batch_size}), got {len(col)}")
+        for u in col:
+            check(u)                                          # refuses what lies outside the parameter's range, by name
+        cols.append(col)
+    return tuple(cols)
+
+
 class AudioStreamer:
     def __init__(self, batch_size: int, stop_signal=None, timeout: Optional[float] = None, ring_slots: int = 8, pcm16=None,
-                 sample_rate: Optional[int] = None, engine=None, speed=None, volume_db=None, ceiling_db=None):
+                 sample_rate: Optional[int] = None, engine=None, speed=None, volume_db=None, ceiling_db=None, loudness_lufs=None,
+                 loudness_start_db=None, max_boost_db=None):
         self.batch_size = batch_size
+        self._loud = _loudness_of(loudness_lufs, loudness_start_db, max_boost_db, batch_size)   # (targets, start gains, bounds) or None
+        self._ld = None                            # Engine.loudness (device chunks), one stream per sample index
+        self._ld_host = {}                         # sample index -> loudness.HostLoudness (CPU chunks)
+        if self._loud is not None and ceiling_db is None:
+            from .level import DEFAULT_CEILING_DB
+            ceiling_db = DEFAULT_CEILING_DB        # a boost can pass full scale: the leveller is always followed by the limiter
         self._level = _volumes_of(volume_db, ceiling_db, batch_size)    # (volumes in dB, one per sample index; ceiling in dB), or None
         self._lv = None                            # Engine.level (device chunks), one stream per sample index
         self._lv_host = {}                         # sample index -> level.HostLevel (CPU chunks)
@@ -145,6 +183,10 @@ class AudioStreamer:
             eng = engine if engine is not None else pcm16
             if eng is not None:                    # without one, only CPU chunks are served (resample.HostResampler); put() refuses others
                 self._rs = eng.resampler(SOURCE_RATE, self.sample_rate, batch_size)
+        if self._loud is not None:
+            eng = engine if engine is not None else pcm16
+            if eng is not None:
+                self._ld = eng.loudness(batch_size)
         if self._speeds is not None:
             eng = engine if engine is not None else pcm16
             if eng is not None:
@@ -154,7 +196,7 @@ class AudioStreamer:
             if eng is not None:
                 self._lv = eng.level(batch_size, rate=self.sample_rate, ceiling_db=self._level[1])
         # the device stages between a chunk and the ring, in the order they run; a further stage takes its place in this list
-        self._stages = [st for st in (self._tp, self._rs, self._lv) if st is not None]
+        self._stages = [st for st in (self._ld, self._tp, self._rs, self._lv) if st is not None]
         self.stop_signal = stop_signal
         self.timeout = timeout
         self.audio_queues = [self._make_queue() for _ in range(batch_size)]
@@ -194,6 +236,9 @@ class AudioStreamer:
                         continue
                 self._work.put(("chunk", idx, chunk, None, None))
             return
+        if self._loud is not None and self._ld is None:
+            raise ValueError("AudioStreamer(loudness_lufs=...): device chunks are levelled on the device and need an engine "
+                             "(pcm16=engine for 16-bit chunks, engine=engine for float chunks)")
         if self.sample_rate != SOURCE_RATE and self._rs is None:
             raise ValueError(f"AudioStreamer(sample_rate={self.sample_rate}): device chunks are resampled on the device and need an engine "
                              "(pcm16=engine for 16-bit chunks, engine=engine for float chunks)")
@@ -212,6 +257,16 @@ class AudioStreamer:
         if not flush:
             self._lead = tuple(chunk.shape[:-1])
             y = chunk.reshape(-1)
+        if self._loud is not None:
+            from .loudness import HostLoudness
+            ld = self._ld_host.get(idx)
+            if ld is None and not flush:
+                ld = self._ld_host[idx] = HostLoudness(self._loud[0][idx], self._loud[1][idx], self._loud[2][idx])
+            if ld is not None:
+                if flush:
+                    ld.flush()                                # emits nothing: it closes the stream
+                else:
+                    y = ld.push(y)
         if self._speeds is not None:
             from .tempo import HostTempo
             t = self._tp_host.get(idx)
@@ -284,6 +339,9 @@ class AudioStreamer:
         kw = {"speeds": [self._speeds[idx] for idx in ids]} if stage is self._tp else {}
         if stage is self._lv:
             kw = {"volumes_db": [self._level[0][idx] for idx in ids]}
+        if stage is self._ld:
+            kw = {"targets_lufs": [self._loud[0][idx] for idx in ids], "start_db": [self._loud[1][idx] for idx in ids],
+                  "max_boost_db": [self._loud[2][idx] for idx in ids]}
         dt = torch.int16 if ends and self._pcm_engine is not None else torch.float32
         at = 0
         while True:                                        # one push, but for a chunk longer than it takes
@@ -445,6 +503,8 @@ class AudioStreamer:
                 self._tp.close()                         # ... and its tempo configuration
             if self._lv is not None:
                 self._lv.close()                         # ... and its level configuration
+            if self._ld is not None:
+                self._ld.close()                         # ... and its loudness configuration
 
     # ---- consumer side ----
     def __iter__(self):
@@ -509,10 +569,12 @@ class AsyncAudioStreamer(AudioStreamer):
         async for chunk in streamer.get_stream(0): ...      async for batch in streamer: ..."""
 
     def __init__(self, batch_size: int, stop_signal=None, timeout: Optional[float] = None, ring_slots: int = 8, pcm16=None,
-                 sample_rate: Optional[int] = None, engine=None, speed=None, volume_db=None, ceiling_db=None):
+                 sample_rate: Optional[int] = None, engine=None, speed=None, volume_db=None, ceiling_db=None, loudness_lufs=None,
+                 loudness_start_db=None, max_boost_db=None):
         self.loop = asyncio.get_running_loop()
         super().__init__(batch_size, stop_signal, timeout, ring_slots=ring_slots, pcm16=pcm16, sample_rate=sample_rate, engine=engine,
-                         speed=speed, volume_db=volume_db, ceiling_db=ceiling_db)
+                         speed=speed, volume_db=volume_db, ceiling_db=ceiling_db, loudness_lufs=loudness_lufs,
+                         loudness_start_db=loudness_start_db, max_boost_db=max_boost_db)
 
     def _make_queue(self):
         return asyncio.Queue()
