@@ -333,6 +333,33 @@ int vv_tempo_rows(vv_ctx* ctx, void* stream, int tp, int n, const vv_tempo_row* 
  * window_dev [480] on the device; offsets_dev as above.  Bit-identical to the same signal pushed and flushed through vv_tempo_rows. */
 int vv_tempo_once(vv_ctx* ctx, void* stream, const float* window_dev, int P, int Q, int n, int n_in, const float* audio_dev, int ld_in,
                   float* out_dev, int ld_out, int* offsets_dev, int ld_off);
+/* ---- pitch: a streaming variable-ratio band-limited resampler P / Q, both terms in 1..100, P / Q in [1/2, 2], each row of a push at
+ * its own ratio over one prototype table (vibevoice_amd/pitch.py defines it).  Behind a tempo change by Q / P it moves the pitch by
+ * P / Q and keeps the duration; the formants move with the pitch.  Output m is the input at time m * P / Q, the input taken as zero
+ * outside itself: with den = max(P, Q), q = m * P / Q, a = m * P % Q, Tn = ceil(32 * den / Q) <= 64,
+ * y[m] = sum_{t = -Tn .. Tn} (Q / den) c(a, t) x[q - t], c the table at |a + t * Q| * R / den by linear interpolation, fp32 fmaf in that
+ * order; 1 / 1 is the identity (Tn = 0).  What a stream emits does not depend on how its input was cut into pushes: a push emits every
+ * output whose newest input sample q + Tn has arrived, the flush emits the rest against zeros, ceil(total * Q / P) outputs in all.
+ * vv_pitch_set: configuration pt (0..3) of this context: table_host [n_table = 32 * R + 1] fp32 in HOST memory, the non-negative half of
+ * the prototype at R <= 256 entries per zero crossing; n_streams streams at their first sample.  Replaces what pt held.  Synchronous. */
+int vv_pitch_set(vv_ctx* ctx, int pt, const float* table_host, int n_table, int R, int n_streams, void* stream);
+/* Back to the state after vv_pitch_set for n streams (stream_ids_host == NULL: all of them): history zeroed by a kernel on `stream`,
+ * input total 0, ratio and flush mark cleared. */
+int vv_pitch_reset(vv_ctx* ctx, void* stream, int pt, int n, const int* stream_ids_host);
+/* One push of n <= 16 rows, ONE launch on `stream`: row i = n_in samples at audio_dev + i * ld_in for stream rows_host[i].stream
+ * (distinct) at ratio P / Q (a stream keeps the ratio of its first push until its reset), flush != 0: the stream's last push.  Its
+ * outputs go to out_dev + i * ld_out (elements): out_fmt 0 = fp32, 1 = int16 with the arithmetic of vv_audio_to_pcm16 over the row's
+ * resampled chunk.  n_out_host [n]: what each row emitted, computed on the host from the streams' input totals (no sync).  Refused with
+ * a message, nothing written, no state changed: as vv_resample_rows, and P or Q outside 1..100 or P / Q outside [1/2, 2], a stream
+ * whose ratio changes, a row of more than 7552 input samples or one that emits more than 8192 or more than ld_out. */
+typedef struct vv_pitch_row { int stream; int n_in; int flush; int P; int Q; } vv_pitch_row;
+int vv_pitch_rows(vv_ctx* ctx, void* stream, int pt, int n, const vv_pitch_row* rows_host, const float* audio_dev, int ld_in,
+                  void* out_dev, int ld_out, int out_fmt, int* n_out_host);
+/* Stateless: n whole signals of n_in samples (audio_dev + i * ld_in), signal i at ratio pq_host[2 i] / pq_host[2 i + 1] (HOST memory)
+ * -> ceil(n_in * Q / P) fp32 samples (out_dev + i * ld_out); table_dev [n_table = 32 * R + 1] on the device.  One launch per 16 signals.
+ * Bit-identical to the same signal pushed and flushed through vv_pitch_rows. */
+int vv_pitch_once(vv_ctx* ctx, void* stream, const float* table_dev, int n_table, int R, int n, const int* pq_host, int n_in,
+                  const float* audio_dev, int ld_in, float* out_dev, int ld_out);
 /* ---- output level: a streaming gain and look-ahead peak limiter (vibevoice_amd/level.py defines it).  A: look-ahead and ramp, H: hold,
  * in samples; g: the gain, c: the ceiling.  u = fl(g x) (non-finite: 0), r = 1 where |u| <= c else fl(c / |u|), q = floor(r 2^20),
  * h[j] = min q[j - H .. j + A - 1], S[i] = sum h[i - A + 1 .. i], a = fl(float(S) / float(A 2^20)), y = clamp(fl(a u), -c, c): no

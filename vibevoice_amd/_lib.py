@@ -60,6 +60,11 @@ class VVTempoRow(C.Structure):
     _fields_ = [("stream", C.c_int), ("n_in", C.c_int), ("flush", C.c_int), ("P", C.c_int), ("Q", C.c_int)]
 
 
+class VVPitchRow(C.Structure):
+    """vv_pitch_row (include/vvhip.h): the stream, the input samples, the flush mark and the ratio P / Q of one row of vv_pitch_rows"""
+    _fields_ = [("stream", C.c_int), ("n_in", C.c_int), ("flush", C.c_int), ("P", C.c_int), ("Q", C.c_int)]
+
+
 class VVLevelRow(C.Structure):
     """vv_level_row (include/vvhip.h): the stream, the input samples, the flush mark and the gain of one row of vv_level_rows"""
     _fields_ = [("stream", C.c_int), ("n_in", C.c_int), ("flush", C.c_int), ("gain", C.c_float)]
@@ -123,6 +128,10 @@ _SIGS = {
     "vv_tempo_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(VVTempoRow), _P, C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_int), _P,
                                 C.c_int]),
     "vv_tempo_once": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, _P, C.c_int]),
+    "vv_pitch_set": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "vv_pitch_reset": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "vv_pitch_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(VVPitchRow), _P, C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "vv_pitch_once": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _P, C.c_int, _P, C.c_int]),
     "vv_level_set": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P]),
     "vv_level_reset": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "vv_level_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(VVLevelRow), _P, C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_int)]),

@@ -750,6 +750,104 @@ extern "C" int vv_tempo_once(vv_ctx* ctx, void* stream, const float* window_dev,
     return 0;
 }
 
+// ------------------------------------------------------------------ pitch (kernels: pitch.hip; vibevoice_amd/pitch.py defines it)
+// Outputs a stream has emitted before its flush once `total` input samples have arrived: every m whose newest input sample, index
+// (m * P) / Q + Tn, is below total.  vibevoice_amd/pitch.py (emitted) is the same arithmetic.
+static int64_t pt_emitted(int64_t total, int P, int Q) {
+    const int64_t room = total - vv_pt_taps(P, Q);
+    return room <= 0 ? 0 : (room * Q - 1) / P + 1;
+}
+
+extern "C" int vv_pitch_set(vv_ctx* ctx, int pt, const float* table_host, int n_table, int R, int n_streams, void* stream) {
+    VV_SHARED;
+    if (pt < 0 || pt >= vv_ctx::N_PITCHES) return fail(ctx, "vv_pitch_set: configuration %d out of range [0,%d)", pt, vv_ctx::N_PITCHES);
+    if (R < 1 || R > VV_PT_MAX_R || n_table != VV_PT_Z * R + 1)
+        return fail(ctx, "vv_pitch_set: R = %d must be in [1,%d] and n_table = %d must be %d * R + 1", R, VV_PT_MAX_R, n_table, VV_PT_Z);
+    if (n_streams < 1 || n_streams > 65536) return fail(ctx, "vv_pitch_set: n_streams = %d must be in [1,65536]", n_streams);
+    if (!table_host) return fail(ctx, "vv_pitch_set: null prototype table");
+    vv_ctx::Pitch& p = ctx->pt[pt];
+    HIPCHK(ctx, hipStreamSynchronize((hipStream_t)stream));      // pushes that still read what is replaced
+    dfree(ctx, p.table); dfree(ctx, p.hist);
+    p = vv_ctx::Pitch();
+    float* table = (float*)dalloc(ctx, (size_t)n_table * 4, false);
+    float* hist = (float*)dalloc(ctx, (size_t)n_streams * VV_PT_HIST * 4, true);
+    if (!table || !hist || hipMemcpy(table, table_host, (size_t)n_table * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        dfree(ctx, table); dfree(ctx, hist);
+        return fail(ctx, "vv_pitch_set: allocating the state or uploading the table failed");
+    }
+    p.R = R; p.n_streams = n_streams; p.table = table; p.hist = hist;
+    p.total.assign(n_streams, 0); p.P.assign(n_streams, 0); p.Q.assign(n_streams, 0); p.flushed.assign(n_streams, 0);
+    return 0;
+}
+
+extern "C" int vv_pitch_reset(vv_ctx* ctx, void* stream, int pt, int n, const int* stream_ids_host) {
+    VV_SHARED;
+    vv_ctx::Pitch* p = pt >= 0 && pt < vv_ctx::N_PITCHES && ctx->pt[pt].hist ? &ctx->pt[pt] : nullptr;
+    return stage_reset(ctx, "vv_pitch_reset", p, pt, n, stream_ids_host,
+                       [&](const int* ids, int k) { return vv_pitch_reset_launch(p->hist, p->n_streams, ids, k, (hipStream_t)stream); },
+                       [&](int id) { p->P[id] = 0; p->Q[id] = 0; });
+}
+
+extern "C" int vv_pitch_rows(vv_ctx* ctx, void* stream, int pt, int n, const vv_pitch_row* rows_host, const float* audio_dev, int ld_in,
+                             void* out_dev, int ld_out, int out_fmt, int* n_out_host) {
+    VV_SHARED;
+    vv_ctx::Pitch* pp = pt >= 0 && pt < vv_ctx::N_PITCHES && ctx->pt[pt].hist ? &ctx->pt[pt] : nullptr;
+    const RowCheck ck{ctx, "vv_pitch_rows", pp, audio_dev, ld_in};
+    VVTRY(ck.head(pt, n, rows_host, out_dev, n_out_host, out_fmt));
+    vv_ctx::Pitch& p = *pp;
+    VVPitchRows kr;
+    memset(&kr, 0, sizeof(kr));
+    for (int i = 0; i < n; ++i) {
+        const vv_pitch_row& q = rows_host[i];
+        VVTRY(ck.stream(rows_host, i));
+        VVTRY(ck.input(i, q.n_in));
+        if (q.n_in > VV_PT_MAX_IN) return fail(ctx, "vv_pitch_rows: row %d brings %d samples, one push takes at most %d per row; push it in pieces", i, q.n_in, VV_PT_MAX_IN);
+        if (!vv_pt_ratio_ok(q.P, q.Q))
+            return fail(ctx, "vv_pitch_rows: row %d: ratio %d / %d must have both terms in [1,100] and lie in [1/2, 2]", i, q.P, q.Q);
+        if (p.P[q.stream] && (p.P[q.stream] != q.P || p.Q[q.stream] != q.Q))
+            return fail(ctx, "vv_pitch_rows: stream %d runs at ratio %d / %d since its first push; reset it before it changes to %d / %d", q.stream,
+                        p.P[q.stream], p.Q[q.stream], q.P, q.Q);
+        VVTRY(ck.open(q.stream));
+        const int64_t before = p.total[q.stream], after = before + q.n_in;
+        const int64_t m0 = pt_emitted(before, q.P, q.Q);
+        const int64_t m1 = q.flush ? (after * q.Q + q.P - 1) / q.P : pt_emitted(after, q.P, q.Q);
+        const int64_t n_out = m1 - m0;
+        if (n_out > ld_out) return fail(ctx, "vv_pitch_rows: row %d emits %lld samples, the output rows hold %d", i, (long long)n_out, ld_out);
+        if (n_out > VV_PT_MAX_OUT)
+            return fail(ctx, "vv_pitch_rows: row %d emits %lld samples, one push emits at most %d per row; push it in pieces", i, (long long)n_out, VV_PT_MAX_OUT);
+        const int64_t k0 = m0 * q.P;
+        kr.r[i].stream = q.stream; kr.r[i].n_in = q.n_in; kr.r[i].n_out = (int)n_out; kr.r[i].P = q.P; kr.r[i].Q = q.Q;
+        kr.r[i].a0 = (int)(k0 % q.Q); kr.r[i].b0 = (int)(k0 / q.Q - before + VV_PT_HIST);
+    }
+    VVTRY(stage_launch(ctx, p, rows_host, n, kr, n_out_host, [&] {
+        return vv_pitch_rows_launch(&kr, n, p.table, p.R, p.hist, p.n_streams, audio_dev, ld_in, out_dev, ld_out, out_fmt, (hipStream_t)stream); }));
+    for (int i = 0; i < n; ++i) { p.P[rows_host[i].stream] = rows_host[i].P; p.Q[rows_host[i].stream] = rows_host[i].Q; }
+    return 0;
+}
+
+extern "C" int vv_pitch_once(vv_ctx* ctx, void* stream, const float* table_dev, int n_table, int R, int n, const int* pq_host, int n_in,
+                             const float* audio_dev, int ld_in, float* out_dev, int ld_out) {
+    VV_SHARED;
+    if (R < 1 || R > VV_PT_MAX_R || n_table != VV_PT_Z * R + 1)
+        return fail(ctx, "vv_pitch_once: R = %d must be in [1,%d] and n_table = %d must be %d * R + 1", R, VV_PT_MAX_R, n_table, VV_PT_Z);
+    if (n < 1 || n > 65535 || n_in < 1 || n_in > ld_in) return fail(ctx, "vv_pitch_once: n = %d in [1,65535], n_in = %d in [1, ld_in = %d]", n, n_in, ld_in);
+    if (!table_dev || !pq_host || !audio_dev || !out_dev) return fail(ctx, "vv_pitch_once: null table / ratios / audio / out pointer");
+    for (int i = 0; i < n; ++i) {
+        const int P = pq_host[2 * i], Q = pq_host[2 * i + 1];
+        if (!vv_pt_ratio_ok(P, Q)) return fail(ctx, "vv_pitch_once: signal %d: ratio %d / %d must have both terms in [1,100] and lie in [1/2, 2]", i, P, Q);
+        const int64_t n_out = ((int64_t)n_in * Q + P - 1) / P;
+        if (n_out > ld_out || n_out >= ((int64_t)1 << 31) - 256)
+            return fail(ctx, "vv_pitch_once: signal %d: %lld output samples, the output rows hold %d", i, (long long)n_out, ld_out);
+    }
+    for (int i0 = 0; i0 < n; i0 += 16) {
+        const int k = std::min(16, n - i0);
+        VVPitchRatios a;
+        for (int i = 0; i < 16; ++i) { a.P[i] = pq_host[2 * (i0 + (i < k ? i : 0))]; a.Q[i] = pq_host[2 * (i0 + (i < k ? i : 0)) + 1]; }
+        VVCHK(vv_pitch_once_launch(table_dev, R, &a, k, n_in, audio_dev + (size_t)i0 * ld_in, ld_in, out_dev + (size_t)i0 * ld_out, ld_out, (hipStream_t)stream));
+    }
+    return 0;
+}
+
 // ------------------------------------------------------------------ output level (kernels: level.hip; vibevoice_amd/level.py defines it)
 // Outputs a stream has emitted before its flush once `total` input samples have arrived: every sample whose A - 1 samples of look-ahead
 // are there.  vibevoice_amd/level.py (emitted) is the same arithmetic.

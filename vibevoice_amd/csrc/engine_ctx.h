@@ -202,6 +202,11 @@ struct vv_ctx {
     struct Tempo : RowStage { float* window = nullptr; float* hist = nullptr; int* dstate = nullptr; std::vector<int> P, Q; };
     static constexpr int N_TEMPOS = 4;
     Tempo tp[N_TEMPOS];
+    // streaming pitch resamplers (vv_pitch_set, engine_codec.hip; kernels: pitch.hip): the prototype table every ratio shares, per stream
+    // VV_PT_HIST history samples on the device and on the host its ratio P / Q (fixed by its first push, 0 before).  Kept like the resamplers.
+    struct Pitch : RowStage { int R = 0; float* table = nullptr; float* hist = nullptr; std::vector<int> P, Q; };
+    static constexpr int N_PITCHES = 4;
+    Pitch pt[N_PITCHES];
     // streaming output levels (vv_level_set, engine_codec.hip; kernels: level.hip): look-ahead A, hold H, ceiling c, per stream H + 2 A - 2
     // history samples on the device and on the host its gain (fixed by its first push, 0 before).  Kept like the resamplers.
     struct Level : RowStage { int A = 0, H = 0; float c = 0.f; float* hist = nullptr; std::vector<float> gain; };

@@ -194,6 +194,25 @@ constexpr int VV_TP_PAD = 896;             // zeros behind the chunk: a flush re
 constexpr int VV_TP_BUF = VV_TP_HIST + VV_TP_MAX_IN + VV_TP_PAD;
 constexpr int VV_TP_MAX_BLOCKS = 96;       // blocks per staged buffer: a block advances >= 120 input samples, (MAX_IN + PAD) / 120 < 96
 
+// ---- streaming pitch resampler (pitch.hip): one row of a push, passed by value in the kernel arguments, each at its own ratio ----
+// The host keeps each stream's 64-bit input total and its ratio P / Q; what the kernel needs of the total is the position of the row's
+// first output m0: with k0 = m0 * P, a0 = k0 % Q is its phase and b0 = k0 / Q - total + VV_PT_HIST the index of the input sample it
+// sits on in the row's staging buffer [VV_PT_HIST history | n_in chunk | VV_PT_MAX_TN zeros].  Output j of the push then has phase
+// (a0 + j * P) % Q and sits on index b0 + (a0 + j * P) / Q: 32-bit arithmetic whatever the stream's age.
+struct VVPitchRow { int stream, n_in, n_out, P, Q, a0, b0; };
+struct VVPitchRows { VVPitchRow r[16]; };
+struct VVPitchRatios { int P[16], Q[16]; };    // vv_pitch_once_kernel: the ratio of each of up to 16 signals of a launch
+constexpr int VV_PT_Z = 32;                // zero crossings of the prototype either side (vibevoice_amd/pitch.py: Z)
+constexpr int VV_PT_MAX_R = 256;           // table entries per crossing, at most: the table [Z R + 1] is staged in LDS
+constexpr int VV_PT_MAX_TN = 64;           // Tn = ceil(Z max(P, Q) / Q) <= 64 for P <= 2 Q: input samples a stream holds back
+constexpr int VV_PT_HIST = 2 * VV_PT_MAX_TN;   // input samples a stream keeps between pushes
+constexpr int VV_PT_MAX_IN = 7552;         // input samples one row of a push may bring (the staging buffer is LDS, beside the table)
+constexpr int VV_PT_MAX_OUT = 8192;        // outputs one row of a push may emit (1024 threads x 8 accumulators)
+// Tn of a ratio: 0 at 1 / 1, which is the identity by definition (pitch.py, "Unison")
+static inline int vv_pt_taps(int P, int Q) { return P == Q ? 0 : (VV_PT_Z * (P > Q ? P : Q) + Q - 1) / Q; }
+// the ratios a row may run at: both terms in 1..100, P / Q in [1/2, 2]
+static inline bool vv_pt_ratio_ok(int P, int Q) { return P >= 1 && P <= 100 && Q >= 1 && Q <= 100 && P <= 2 * Q && Q <= 2 * P; }
+
 // ---- streaming output level (level.hip): one row of a push, passed by value in the kernel arguments ----
 // The host keeps each stream's 64-bit input total and its gain; the row's staging buffer is [H + 2 A - 2 history | n_in chunk | A - 1
 // zeros], its first output sits at index b0 = (first output's signal index) - total + H + 2 A - 2 of it, n_out outputs follow.

@@ -124,6 +124,14 @@ int vv_tempo_rows_launch(const VVTpRows* rows, int n, const float* window, float
 int vv_tempo_once_launch(const float* window, int P, int Q, int n, int n_in, const float* x, int ld_in, float* out, int ld_out, int* offsets,
                          int ld_off, hipStream_t s);
 int vv_tempo_reset_launch(float* hist, int* dstate, int n_streams, const int* ids, int n, hipStream_t s);
+// pitch.hip.  table [VV_PT_Z * R + 1] the prototype's non-negative half, hist [n_streams][VV_PT_HIST].  _lds_bytes: what a push of n_in
+// samples per row needs of the 64 KiB a workgroup has (the launcher refuses more).
+int vv_pitch_lds_bytes(int R, int n_in);
+int vv_pitch_rows_launch(const VVPitchRows* rows, int n, const float* table, int R, float* hist, int n_streams, const float* x, int ld_in,
+                         void* out, int ld_out, int pcm16, hipStream_t s);
+int vv_pitch_once_launch(const float* table, int R, const VVPitchRatios* pq, int n, int n_in, const float* x, int ld_in, float* out, int ld_out,
+                         hipStream_t s);
+int vv_pitch_reset_launch(float* hist, int n_streams, const int* ids, int n, hipStream_t s);
 // level.hip.  A look-ahead / ramp, H hold (samples), c the ceiling; hist [n_streams][nh], nh = H + 2 A - 2.
 int vv_level_rows_launch(const VVLvRows* rows, int n, int A, int H, float c, float* hist, int n_streams, const float* x, int ld_in, void* out,
                          int ld_out, int pcm16, hipStream_t s);

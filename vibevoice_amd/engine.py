@@ -535,7 +535,7 @@ class Engine:
                   "vv_audio_to_pcm16")
 
     # ------------------------------------------------------------------ streaming row stages and their whole-signal forms
-    _STAGE_USED = {"resampler": "_rs_used", "tempo": "_tp_used", "level": "_lv_used", "loudness": "_ld_used"}
+    _STAGE_USED = {"resampler": "_rs_used", "tempo": "_tp_used", "pitch": "_pt_used", "level": "_lv_used", "loudness": "_ld_used"}
 
     def _take_stage_slot(self, kind, make):
         """make(k) for the first free k of this engine's four `kind` configurations; the stage's close() gives k back"""
@@ -613,6 +613,58 @@ class Engine:
                                              self._p(offs) if offs is not None else None, max(nblk, 1)), "vv_tempo_once")
         out, offs = self._whole("time_stretch", audio, n_out, run, stream, aux_cols=max(nblk, 1) if return_offsets else 0)
         return (out, offs[:, :nblk].reshape(out.shape[:-1] + (nblk,))) if return_offsets else out
+
+    # pitch (pitch.py, csrc/pitch.hip)
+    def pitch(self, n_streams: int) -> "Pitch":
+        """A streaming variable-ratio resampler with n_streams independent streams, each at the ratio of its own shift in semitones,
+        in one of this engine's four pitch configurations (close() it to give the configuration back).  Behind a tempo stage at
+        speed Q / P it moves the pitch and keeps the duration."""
+        return self._take_stage_slot("pitch", lambda k: Pitch(self, k, n_streams))
+
+    def _pitch_table(self):
+        from . import pitch as _pt
+        h = self.__dict__.get("_pt_table")
+        if h is None:
+            h = self.__dict__["_pt_table"] = torch.from_numpy(np.array(_pt.table())).to(self.device)
+        return h
+
+    def pitch_shift(self, audio: torch.Tensor, semitones, speed: float = 1.0, stream=None) -> torch.Tensor:
+        """Whole signals at another pitch: audio [samples] or [n, samples] (24 kHz, any float dtype, any device) -> fp32 on the engine's
+        device, moved by `semitones` in [-12, +12] and played at `speed`: time_stretch() at speed * Q / P (none where that is exactly
+        1), then pitch_resample() at P / Q = ratio(semitones), the definition of vibevoice_amd/pitch.py (shift_ref):
+        ceil(ceil(n Qt / Pt) Q / P) samples.  A resampling shifter: the formants move with the pitch.  A combined speed outside
+        [0.5, 2.0] is refused.  Stateless; runs on `stream` (default: the current torch stream of the device)."""
+        from . import pitch as _pt
+        from . import tempo as _tp
+        P, Q = _pt.ratio(semitones)
+        v = _pt.tempo_speed(speed, semitones)
+        if _tp.ratio(v) != (1, 1):
+            audio = self.time_stretch(audio, v, stream=stream)
+        if P == Q:
+            return audio.detach().to(device=self.device, dtype=torch.float32)
+        out, counts = self.pitch_resample(audio, semitones, stream=stream)
+        return out[..., :counts[0]] if counts else out
+
+    def pitch_resample(self, audio: torch.Tensor, semitones, stream=None):
+        """The pitch stage alone over whole signals: audio [samples] or [n, samples] -> (out fp32 [..., max(counts)], counts): row i
+        resampled at P / Q = ratio(semitones[i]) (or one value for all rows), counts[i] = ceil(samples * Q / P) samples of it (what lies
+        behind them is not written).  Pitch and duration both change by the ratio.  Stateless; one launch per 16 rows, each row at its own ratio."""
+        from . import pitch as _pt
+        rows = int(audio.numel() // audio.shape[-1]) if audio.dim() and audio.shape[-1] else 0
+        semis = [semitones] * rows if not hasattr(semitones, "__len__") else list(semitones)
+        if len(semis) != rows:
+            raise ValueError(f"Engine.pitch_resample: semitones names one value, or one per row ({rows}), got {len(semis)}")
+        pq = [_pt.ratio(s) for s in semis]
+        counts = [_pt.total_out(int(audio.shape[-1]), P, Q) for P, Q in pq]
+        n_out = max(counts, default=0)
+
+        def run(st, nn, n_in, x, out, _):
+            h = self._pitch_table()
+            i0 = rows - int(x.shape[0])                        # _whole hands over the tile's first row onwards
+            flat = [v for P, Q in pq[i0:i0 + nn] for v in (P, Q)]
+            self._chk(self.lib.vv_pitch_once(self._ctx, st, self._p(h), int(h.shape[0]), _pt.R, nn, (C.c_int * (2 * nn))(*flat), n_in, self._p(x),
+                                             n_in, self._p(out), n_out), "vv_pitch_once")
+        return self._whole("pitch_resample", audio, n_out, run, stream)[0], counts
 
     # output level (level.py, csrc/level.hip)
     def level(self, n_streams: int, rate: int = 24000, ceiling_db: float = -1.0) -> "Level":
@@ -1066,7 +1118,7 @@ class TempoCapacityError(EngineError):
 
 
 class _RowStage:
-    """What the streaming row stages share (Loudness, Tempo, Resampler, Level): n_streams chunk-continuous streams in
+    """What the streaming row stages share (Loudness, Tempo, Pitch, Resampler, Level): n_streams chunk-continuous streams in
     one of the engine's configurations, pushed up to 16 rows a launch.  A stage supplies KIND (Engine._STAGE_USED), its row struct ROW
     and how push() fills it, its C entry points ROWS_FN / RESET_FN, counts(), max_out() and take()."""
     KIND = ROW = ROWS_FN = RESET_FN = None
@@ -1205,6 +1257,71 @@ class Tempo(_RowStage):
         if rc == _lib.TEMPO_OVER_CAPACITY:
             raise TempoCapacityError(f"Tempo.push: {self.engine._err()}")
         super()._refused(rc)
+
+    def _cleared(self, stream_id):
+        self.total[stream_id], self.ratio[stream_id] = 0, None
+
+
+class Pitch(_RowStage):
+    """One streaming pitch configuration of an engine (Engine.pitch): n_streams chunk-continuous variable-ratio resamplers at 24 kHz, each
+    at the ratio P / Q of the shift of its first push until its reset (which clears the ratio with the rest); the rows of one launch run
+    at different ratios.  What a stream delivers does not depend on how its input was cut into pushes (vibevoice_amd/pitch.py): the
+    concatenation of its pushes and its flush equals Engine.pitch_resample() of the concatenated input, bit for bit in float mode,
+    ceil(n * Q / P) samples; a stream at 0 semitones passes bit for bit.  Pitch AND duration change by the ratio: behind a tempo stage at
+    speed Q / P (AudioStreamer(pitch=...)) the duration stays.  delay_samples: the input samples (64, 2.7 ms) a stream holds back at
+    most until its next push; max_in: the input samples one row of a push may bring."""
+    KIND, ROW, ROWS_FN, RESET_FN = "pitch", _lib.VVPitchRow, "vv_pitch_rows", "vv_pitch_reset"
+    NO_ROWS = (0,)                                        # one launch, which vv_pitch_rows refuses by name
+
+    def __init__(self, engine: Engine, slot: int, n_streams: int):
+        from . import pitch as _pt
+        super().__init__(engine, slot, n_streams)
+        self.delay_samples, self.max_in = _pt.MAX_TN, _pt.MAX_IN
+        self.ratio = [None] * self.n_streams              # (P, Q) of each stream, None before its first push
+        h = np.ascontiguousarray(_pt.table())
+        engine._chk(engine.lib.vv_pitch_set(engine._ctx, slot, C.c_void_p(h.ctypes.data), int(h.shape[0]), _pt.R, self.n_streams, engine._s),
+                    "vv_pitch_set")
+
+    def _pq(self, stream_id, semitones):
+        from . import pitch as _pt
+        return self.ratio[stream_id] or _pt.ratio(semitones)
+
+    def counts(self, stream_id: int, n_in: int, semitones=None, flush: bool = False) -> int:
+        """samples a push of n_in samples to stream_id would emit now (host integers, no device sync); semitones: for its first push"""
+        from . import pitch as _pt
+        P, Q = self._pq(stream_id, semitones)
+        return _pt.counts(P, Q, self.total[stream_id], n_in, flush)[1]
+
+    def max_out(self, n_in: int) -> int:
+        """upper bound of what any push of up to n_in samples emits at any ratio, the flush included: at most 64 held samples join the
+        chunk, and n samples yield at most 2 n"""
+        return 2 * (int(n_in) + self.delay_samples) + 1
+
+    def take(self, ids, remaining, flush=False, semitones=None):
+        """semitones: one per row, for the streams that have had no push yet (without it such a stream counts as an octave down, the
+        ratio that emits most)"""
+        from . import pitch as _pt
+        semis = [-12.0] * len(ids) if semitones is None else semitones
+        return _pt.push_width([self._pq(i, s) for i, s in zip(ids, semis)], [self.total[i] for i in ids], remaining, flush)
+
+    def push(self, audio: Optional[torch.Tensor], stream_ids: Sequence[int], semitones, flush=False, out: Optional[torch.Tensor] = None,
+             n_in=None, stream=None, pcm16: bool = False):
+        """Row i of audio [n, samples] (contiguous fp32 on the engine's device; None where no row brings samples) goes to stream
+        stream_ids[i] (distinct) at the ratio of semitones[i] (or one shift for all rows; a stream keeps the ratio of its first push);
+        n_in: samples of each row that count (default: all), flush: bool or one per row -- a stream's last push, after which it takes no
+        more until reset().  -> (out, counts): out[i, :counts[i]] is what row i emitted, fp32, or int16 under pcm16 (the arithmetic of
+        Engine.audio_to_pcm16 over the row's resampled chunk, in the same launch).  out: a contiguous [>= n, capacity] tensor of that
+        dtype to write into (default: a new one of max_out(samples) columns).  One launch per 16 rows on `stream` (default: the
+        device's current torch stream); the counts are host integers, nothing waits for the device.  A row of more than max_in
+        samples, or one that emits more than 8192, is refused: push it in pieces of take()."""
+        from . import pitch as _pt
+        ids, samples, nin, fl, semis = self._args(audio, stream_ids, flush, n_in, semitones=semitones)
+        pq = [_pt.ratio(v) for v in semis]
+        n, out = len(ids), self._out(out, len(ids), nin, pcm16)
+        rows = (self.ROW * max(n, 1))()
+        for i in range(n):
+            rows[i].stream, rows[i].n_in, rows[i].flush, rows[i].P, rows[i].Q = ids[i], nin[i], int(fl[i]), pq[i][0], pq[i][1]
+        return out, self._launch(audio, samples, ids, nin, rows, out, pcm16, stream, took=lambda i: self.ratio.__setitem__(ids[i], pq[i]))
 
     def _cleared(self, stream_id):
         self.total[stream_id], self.ratio[stream_id] = 0, None

@@ -26,6 +26,17 @@ bit for bit in float mode.  A sample holds back at most 640 input samples (26.7 
 block of 240 delivers nothing for that row; end(indices) flushes the tempo tail, then the resampler's.  Device chunks need an engine
 (as above), CPU chunks go through tempo.HostTempo.
 
+`pitch=S` (a float in [-12, +12] semitones, or one per sample index; anything but 0) moves the pitch and keeps the duration: the tempo
+stage runs each index at speed * Q / P and a variable-ratio resampler behind it (Engine.pitch, csrc/pitch.hip; vibevoice_amd/pitch.py is the
+definition) plays its output at P / Q = the fraction within 1..100 nearest to 2^(S / 12), each row of a launch at its own ratio, at 24 kHz,
+in front of the rate resampler; float chunks arrive as fp32.  A resampling shifter: the formants move with the pitch, so a few semitones
+read as the same voice higher or lower and more changes its character.  Chunk-continuous: per sample, the concatenated chunks equal
+Engine.pitch_shift(whole signal, S, speed), n / speed samples to within one and the tempo stage's rounding, bit for bit in float mode.
+An index at 0 semitones passes the stage bit for bit; a combined speed outside [0.5, 2.0] is refused, one of exactly 1 (speed 1.5 with
++7 semitones) builds no tempo stage.  A sample holds back at most 64 more input samples (2.7 ms) behind the tempo stage's; end(indices)
+flushes the tails in order: tempo, pitch, resampler, level.  Device chunks need an engine (as above), CPU chunks go through tempo.HostTempo
+and pitch.HostPitch.
+
 `volume_db=V` (a float in [-40, +24], or one per sample index) and `ceiling_db=C` (in [-20, 0]) set the output level: a gain and a
 look-ahead peak limiter (Engine.level, csrc/level.hip; vibevoice_amd/level.py is the definition), the last stage, at the delivered rate.
 The stage exists when ceiling_db is given or any volume_db is not 0 (the ceiling is then -1 dB unless given; an index at 0 dB still gets
@@ -44,7 +55,7 @@ full scale, so such a streamer always has a level stage behind it (ceiling -1 dB
 exceeds the ceiling.  Chunk-continuous: per sample, what reaches the next stage equals Engine.apply_loudness() of the concatenated
 input, bit for bit.  Device chunks need an engine (as above), CPU chunks go through loudness.HostLoudness.
 
-The device stages form one chain (self._stages, _put_device): the leveller, the tempo change, the resampler, the level, whichever exist, each an engine
+The device stages form one chain (self._stages, _put_device): the leveller, the tempo change, the pitch resampler, the rate resampler, the level, whichever exist, each an engine
 row stage (engine._RowStage) pushed on the producing stream; the last one writes the ring slot's staging, as int16 under pcm16 (over
 each row's own chunk), and with no stage the 16-bit conversion does, else the chunk itself is copied.  A chunk longer than one push of
 a stage takes (stage.take()) is pushed in pieces and arrives as several.
@@ -117,6 +128,21 @@ def _speeds_of(speed, batch_size):
     return speeds
 
 
+def _pitch_of(pitch, speed, batch_size):
+    """AudioStreamer's pitch argument as (semitones, one per sample index; the speed the tempo stage in front runs each index at,
+    speed * Q / P); None where it asks for no change (absent, or every index at the ratio 1 / 1)"""
+    if pitch is None:
+        return None
+    from .pitch import ratio, tempo_speed
+    semis = [float(pitch)] * batch_size if not hasattr(pitch, "__len__") else [float(v) for v in pitch]
+    if len(semis) != batch_size:
+        raise ValueError(f"AudioStreamer(pitch=...): one value, or one per sample index ({batch_size}), got {len(semis)}")
+    if all(p == q for p, q in map(ratio, semis)):             # ratio() refuses what lies outside [-12, +12]
+        return None
+    speeds = [1.0] * batch_size if speed is None else ([float(speed)] * batch_size if not hasattr(speed, "__len__") else [float(v) for v in speed])
+    return semis, [tempo_speed(v, s) for v, s in zip(speeds, semis)]    # refuses a combined speed outside [0.5, 2.0], naming both
+
+
 def _volumes_of(volume_db, ceiling_db, batch_size):
     """AudioStreamer's level arguments as (one volume in dB per sample index, the ceiling in dB); None where they ask for no level
     stage (no ceiling, and no volume or 0 dB everywhere)"""
@@ -160,7 +186,7 @@ def _loudness_of(loudness_lufs, loudness_start_db, max_boost_db, batch_size):
 class AudioStreamer:
     def __init__(self, batch_size: int, stop_signal=None, timeout: Optional[float] = None, ring_slots: int = 8, pcm16=None,
                  sample_rate: Optional[int] = None, engine=None, speed=None, volume_db=None, ceiling_db=None, loudness_lufs=None,
-                 loudness_start_db=None, max_boost_db=None):
+                 loudness_start_db=None, max_boost_db=None, pitch=None):
         self.batch_size = batch_size
         self._loud = _loudness_of(loudness_lufs, loudness_start_db, max_boost_db, batch_size)   # (targets, start gains, bounds) or None
         self._ld = None                            # Engine.loudness (device chunks), one stream per sample index
@@ -172,6 +198,14 @@ class AudioStreamer:
         self._lv = None                            # Engine.level (device chunks), one stream per sample index
         self._lv_host = {}                         # sample index -> level.HostLevel (CPU chunks)
         self._speeds = _speeds_of(speed, batch_size)   # one per sample index, or None: no tempo stage anywhere
+        self._pitch = None                         # semitones, one per sample index, or None: no pitch stage anywhere
+        self._pt = None                            # Engine.pitch (device chunks), one stream per sample index
+        self._pt_host = {}                         # sample index -> pitch.HostPitch (CPU chunks)
+        shifted = _pitch_of(pitch, speed, batch_size)
+        if shifted is not None:                    # the tempo stage absorbs the change of duration: it runs at speed * Q / P
+            from .tempo import ratio as _tempo_ratio
+            self._pitch = shifted[0]
+            self._speeds = shifted[1] if any(p != q for p, q in map(_tempo_ratio, shifted[1])) else None
         self._tp = None                            # Engine.tempo (device chunks), one stream per sample index
         self._tp_host = {}                         # sample index -> tempo.HostTempo (CPU chunks)
         self.sample_rate = SOURCE_RATE if sample_rate is None else int(sample_rate)
@@ -191,12 +225,16 @@ class AudioStreamer:
             eng = engine if engine is not None else pcm16
             if eng is not None:
                 self._tp = eng.tempo(batch_size)
+        if self._pitch is not None:
+            eng = engine if engine is not None else pcm16
+            if eng is not None:
+                self._pt = eng.pitch(batch_size)
         if self._level is not None:
             eng = engine if engine is not None else pcm16
             if eng is not None:
                 self._lv = eng.level(batch_size, rate=self.sample_rate, ceiling_db=self._level[1])
         # the device stages between a chunk and the ring, in the order they run; a further stage takes its place in this list
-        self._stages = [st for st in (self._ld, self._tp, self._rs, self._lv) if st is not None]
+        self._stages = [st for st in (self._ld, self._tp, self._pt, self._rs, self._lv) if st is not None]
         self.stop_signal = stop_signal
         self.timeout = timeout
         self.audio_queues = [self._make_queue() for _ in range(batch_size)]
@@ -230,7 +268,7 @@ class AudioStreamer:
         if not audio_chunks.is_cuda:
             for row, idx in live:
                 chunk = audio_chunks[row].detach().clone()
-                if self.sample_rate != SOURCE_RATE or self._speeds is not None or self._level is not None:
+                if self.sample_rate != SOURCE_RATE or self._speeds is not None or self._level is not None or self._pitch is not None:
                     chunk = self._host_chunk(idx, chunk)
                     if chunk is None:
                         continue
@@ -241,6 +279,9 @@ class AudioStreamer:
                              "(pcm16=engine for 16-bit chunks, engine=engine for float chunks)")
         if self.sample_rate != SOURCE_RATE and self._rs is None:
             raise ValueError(f"AudioStreamer(sample_rate={self.sample_rate}): device chunks are resampled on the device and need an engine "
+                             "(pcm16=engine for 16-bit chunks, engine=engine for float chunks)")
+        if self._pitch is not None and self._pt is None:
+            raise ValueError("AudioStreamer(pitch=...): device chunks are shifted on the device and need an engine "
                              "(pcm16=engine for 16-bit chunks, engine=engine for float chunks)")
         if self._speeds is not None and self._tp is None:
             raise ValueError("AudioStreamer(speed=...): device chunks are stretched on the device and need an engine "
@@ -274,6 +315,14 @@ class AudioStreamer:
                 t = self._tp_host[idx] = HostTempo(self._speeds[idx])
             if t is not None:
                 y = t.flush() if flush else t.push(y)
+        if self._pitch is not None:
+            from .pitch import HostPitch
+            p = self._pt_host.get(idx)
+            if p is None:
+                if y is None:
+                    return None
+                p = self._pt_host[idx] = HostPitch(self._pitch[idx])
+            y = p.push(y if y is not None else torch.zeros(0), flush=flush)
         if self.sample_rate != SOURCE_RATE:
             from .resample import HostResampler
             h = self._rs_host.get(idx)
@@ -337,6 +386,9 @@ class AudioStreamer:
         stage, n, ends = self._stages[k], len(ids), k == len(self._stages) - 1
         dev = stage.engine.device
         kw = {"speeds": [self._speeds[idx] for idx in ids]} if stage is self._tp else {}
+        tk = {}
+        if stage is self._pt:
+            kw = tk = {"semitones": [self._pitch[idx] for idx in ids]}
         if stage is self._lv:
             kw = {"volumes_db": [self._level[0][idx] for idx in ids]}
         if stage is self._ld:
@@ -346,7 +398,7 @@ class AudioStreamer:
         at = 0
         while True:                                        # one push, but for a chunk longer than it takes
             rem = [max(c - at, 0) for c in counts]
-            w = stage.take(ids, rem, flush)
+            w = stage.take(ids, rem, flush, **tk)
             final = w >= max(rem)
 
             def push(out):
@@ -421,7 +473,8 @@ class AudioStreamer:
         else:
             idxs = [int(i.item()) if torch.is_tensor(i) else int(i) for i in sample_indices]
         idxs = [idx for idx in dict.fromkeys(idxs) if idx < self.batch_size and not self.finished_flags[idx]]
-        if (self.sample_rate != SOURCE_RATE or self._speeds is not None or self._level is not None) and idxs and not self._closed:
+        if (self.sample_rate != SOURCE_RATE or self._speeds is not None or self._level is not None or self._pitch is not None) and idxs \
+                and not self._closed:
             self._flush_tails(idxs)
         for idx in idxs:
             self.finished_flags[idx] = True
@@ -501,6 +554,8 @@ class AudioStreamer:
                 self._rs.close()                         # the engine's resampler configuration is free for the next streamer
             if self._tp is not None:
                 self._tp.close()                         # ... and its tempo configuration
+            if self._pt is not None:
+                self._pt.close()                         # ... and its pitch configuration
             if self._lv is not None:
                 self._lv.close()                         # ... and its level configuration
             if self._ld is not None:
@@ -570,11 +625,11 @@ class AsyncAudioStreamer(AudioStreamer):
 
     def __init__(self, batch_size: int, stop_signal=None, timeout: Optional[float] = None, ring_slots: int = 8, pcm16=None,
                  sample_rate: Optional[int] = None, engine=None, speed=None, volume_db=None, ceiling_db=None, loudness_lufs=None,
-                 loudness_start_db=None, max_boost_db=None):
+                 loudness_start_db=None, max_boost_db=None, pitch=None):
         self.loop = asyncio.get_running_loop()
         super().__init__(batch_size, stop_signal, timeout, ring_slots=ring_slots, pcm16=pcm16, sample_rate=sample_rate, engine=engine,
                          speed=speed, volume_db=volume_db, ceiling_db=ceiling_db, loudness_lufs=loudness_lufs,
-                         loudness_start_db=loudness_start_db, max_boost_db=max_boost_db)
+                         loudness_start_db=loudness_start_db, max_boost_db=max_boost_db, pitch=pitch)
 
     def _make_queue(self):
         return asyncio.Queue()
