@@ -486,6 +486,34 @@ int64_t vv_w13_twin_bytes(int N, int K);
 int vv_w13_pack_matrix(void* stream, const void* packed_dev, void* twin_dev, int N, int K);
 int vv_w13_unpack_matrix(void* stream, const void* twin_dev, void* packed_dev, int N, int K);
 int vv_w13_gemv_case(void* stream, const vv_gemv_case_args* args, const void* twin_dev, const void* twin2_dev, int mr, int wpb);
+/* Exactly ONE launch of the batch-decode packed GEMV (gemv16p.hip: vv_gemv16p_kernel) through its own launcher, or a refusal.  The
+ * struct mirrors VVGemv16p (csrc/vv_common.h, field meanings there); unused operands are 0 / NULL.  W / W2 are vv_pack_matrix
+ * outputs; Xp / Xs are ONE packed 16-row activation tile each (the layout of a 16-row weight tile: ceil(K / 32) KiB); Yp is one such
+ * tile of the N output features.  epi: VV_EPI_* of vv_common.h (0 / 1 bias or store, 3 SwiGLU, 4 residual, 5 gated residual,
+ * 6 CFG + solver update); flags: 1 = RS (row scale from ssq_in), 2 = SH (second operand Xs), 4 = PK (the residual epilogue also
+ * packs the new rows and writes their sums of squares).  Returns 0 after the launch, VV_GEMV_REFUSED (nothing was launched: the
+ * shape, a missing operand, or a (epi, flags) pair without an instantiation), < 0 on a launch error.  wpb_out (optional) receives
+ * the waves per workgroup the launcher chose (4 or 8).  The caller vouches for the sizes of every buffer (Engine.gemv16p_case
+ * checks them).  New surface (tests), like vv_gemv_case; the engine reaches the kernel through its passes. */
+typedef struct vv_gemv16p_case_args {
+    const void* W; const void* W2; const void* Xp; float* Y; void* Yp; const float* bias; const float* gate;
+    int T, N, K, ldy, ld_gate;
+    const float* ssq_in; int ssq_tiles; float eps;
+    const void* Xs;
+    const float* pk_nw; const float* pk_sc; int ld_pk; float* ssq_out;
+    float* z; float* x0p; const float* coef; float cfg; int n_cfg; const float* sde_noise;
+    const float* cfg_rows;
+} vv_gemv16p_case_args;
+int vv_gemv16p_case(void* stream, const vv_gemv16p_case_args* args, int epi, int flags, int* wpb_out);
+/* One launch of the activation packers of gemv16p.hip, or a refusal (VV_GEMV_REFUSED, nothing launched).  vv_pack16_case: rows
+ * x_dev [T][ldx] fp32 (T <= 16, K % 32 == 0, K <= 8192) -> one packed 16-row tile xp_dev (K / 32 KiB, rows >= T zero); mode 1:
+ * RMSNorm with weight nw_dev (NULL: none), mode 2: adaLN-modulated RMSNorm, x^ = rs x nw (1 + sc) + sh with sc_dev / sh_dev rows of
+ * stride ld_mod.  vv_pack16_tiles_case: n_tiles plain bf16 conversions in one launch; tile j reads rows at x_dev + (j / n_inner) *
+ * stride_outer + (j % n_inner) * stride_inner (floats, row stride ldx) and writes xp_dev + j * tile_bytes.  New surface (tests). */
+int vv_pack16_case(void* stream, const float* x_dev, int ldx, int mode, const float* nw_dev, float eps, const float* sc_dev,
+                   const float* sh_dev, int ld_mod, void* xp_dev, int T, int K);
+int vv_pack16_tiles_case(void* stream, const float* x_dev, int ldx, int64_t stride_outer, int n_inner, int64_t stride_inner,
+                         void* xp_dev, int64_t tile_bytes, int T, int K, int n_tiles);
 /* The prompt-prefill GEMM (bf16-activation mode): x_dev fp32 [T][K] is packed (RMS-normalised when nw_dev != NULL) into
  * xp_scratch (vv_packed_bytes(T, K)); epi 0/1/4 (store / bias / residual) -> fp32 y_dev [T][N]; epi 3 (SwiGLU: w = gate,
  * w2 = up) -> packed bf16 in yp_scratch (vv_packed_bytes(T, N), zero-initialised), unpacked into y_dev.  K % 8 == 0, N % 4 == 0.

@@ -45,6 +45,19 @@ class VVGemvCase(C.Structure):
     ]
 
 
+class VVGemv16pCase(C.Structure):
+    """vv_gemv16p_case_args (include/vvhip.h): every operand of one launch of the batch-decode packed GEMV"""
+    _fields_ = [
+        ("W", _P), ("W2", _P), ("Xp", _P), ("Y", _P), ("Yp", _P), ("bias", _P), ("gate", _P),
+        ("T", C.c_int), ("N", C.c_int), ("K", C.c_int), ("ldy", C.c_int), ("ld_gate", C.c_int),
+        ("ssq_in", _P), ("ssq_tiles", C.c_int), ("eps", C.c_float),
+        ("Xs", _P),
+        ("pk_nw", _P), ("pk_sc", _P), ("ld_pk", C.c_int), ("ssq_out", _P),
+        ("z", _P), ("x0p", _P), ("coef", _P), ("cfg", C.c_float), ("n_cfg", C.c_int), ("sde_noise", _P),
+        ("cfg_rows", _P),
+    ]
+
+
 class VVNoiseKey(C.Structure):
     """vv_noise_key (include/vvhip.h): the seed's two halves, the first counter word t and aux of one row of vv_noise_rows"""
     _fields_ = [("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("t0", C.c_uint32), ("aux", C.c_uint32)]
@@ -158,6 +171,9 @@ _SIGS = {
     "vv_w13_pack_matrix": (C.c_int, [_P, _P, _P, C.c_int, C.c_int]),
     "vv_w13_unpack_matrix": (C.c_int, [_P, _P, _P, C.c_int, C.c_int]),
     "vv_w13_gemv_case": (C.c_int, [_P, C.POINTER(VVGemvCase), _P, _P, C.c_int, C.c_int]),
+    "vv_gemv16p_case": (C.c_int, [_P, C.POINTER(VVGemv16pCase), C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "vv_pack16_case": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_float, _P, _P, C.c_int, _P, C.c_int, C.c_int]),
+    "vv_pack16_tiles_case": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, C.c_int]),
     "vv_gemm3_raw": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_float, _P, _P, _P, _P]),
     "vv_profile_begin": (C.c_int, [_P]),
     "vv_profile_end": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -150,6 +150,34 @@ extern "C" int vv_w13_gemv_case(void* stream, const vv_gemv_case_args* c, const 
     const int r = vv_gemv_w13_form_launch(g, mr, wpb, (hipStream_t)stream);
     return r == VV_RC_NO_FORM ? VV_GEMV_REFUSED : r;
 }
+// tests: one launch of the batch-decode packed GEMV (gemv16p.hip) through its own launcher, or a refusal; and its two activation packers
+extern "C" int vv_gemv16p_case(void* stream, const vv_gemv16p_case_args* c, int epi, int flags, int* wpb_out) {
+    if (!c) return -1;
+    VVGemv16p a{};
+    a.W = (const u32x4*)c->W; a.W2 = (const u32x4*)c->W2; a.Xp = (const u32x4*)c->Xp; a.Y = c->Y; a.Yp = (unsigned char*)c->Yp;
+    a.bias = c->bias; a.gate = c->gate;
+    a.T = c->T; a.N = c->N; a.K = c->K; a.ldy = c->ldy; a.ld_gate = c->ld_gate;
+    a.ssq_in = c->ssq_in; a.ssq_tiles = c->ssq_tiles; a.eps = c->eps;
+    a.Xs = (const u32x4*)c->Xs;
+    a.pk_nw = c->pk_nw; a.pk_sc = c->pk_sc; a.ld_pk = c->ld_pk; a.ssq_out = c->ssq_out;
+    a.z = c->z; a.x0p = c->x0p; a.coef = c->coef; a.cfg = c->cfg; a.n_cfg = c->n_cfg; a.sde_noise = c->sde_noise;
+    a.cfg_rows = c->cfg_rows;
+    int wpb = 0;
+    const int r = vv_gemv16p_launch2(&a, epi, flags, (hipStream_t)stream, &wpb);
+    if (r == VV_RC_NO_FORM) return VV_GEMV_REFUSED;
+    if (r == 0 && wpb_out) *wpb_out = wpb;
+    return r;
+}
+extern "C" int vv_pack16_case(void* stream, const float* x_dev, int ldx, int mode, const float* nw_dev, float eps, const float* sc_dev,
+                              const float* sh_dev, int ld_mod, void* xp_dev, int T, int K) {
+    const int r = vv_pack16_launch(x_dev, ldx, mode, nw_dev, eps, sc_dev, sh_dev, ld_mod, xp_dev, T, K, (hipStream_t)stream);
+    return r == -1 ? VV_GEMV_REFUSED : r;
+}
+extern "C" int vv_pack16_tiles_case(void* stream, const float* x_dev, int ldx, int64_t stride_outer, int n_inner, int64_t stride_inner,
+                                    void* xp_dev, int64_t tile_bytes, int T, int K, int n_tiles) {
+    const int r = vv_pack16_tiles_launch(x_dev, ldx, stride_outer, n_inner, stride_inner, xp_dev, tile_bytes, T, K, n_tiles, (hipStream_t)stream);
+    return r == -1 ? VV_GEMV_REFUSED : r;
+}
 // tests: Y = f(X) . W^T through the prefill GEMM (prefill.hip): X fp32 [T][K] is packed (optionally RMS-normalised) into xp_scratch,
 // epi STORE/BIAS/RESID write fp32 Y [T][N]; epi SWIGLU (W = gate, W2 = up) writes packed bf16 into yp_scratch, unpacked to Y.
 extern "C" int vv_gemm3_raw(vv_ctx* ctx, void* stream, const void* w, const void* w2, const float* x_dev, int T, int N, int K, int epi,

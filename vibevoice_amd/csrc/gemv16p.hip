@@ -86,7 +86,6 @@ __global__ __launch_bounds__(256) void vv_pack16_tiles_kernel(const float* __res
     const int t = blockIdx.x, j = blockIdx.y;
     const float* xr = x + (int64_t)(j / n_inner) * stride_outer + (int64_t)(j % n_inner) * stride_inner + (int64_t)t * ldx;
     unsigned char* out = xp + (int64_t)j * tile_bytes;
-    const int KT = K >> 5;
     for (int q = threadIdx.x; q < (K >> 2); q += 256) {
         const int k = q * 4;
         const float4 v = (t < T) ? *reinterpret_cast<const float4*>(xr + k) : float4{0.f, 0.f, 0.f, 0.f};
@@ -96,7 +95,6 @@ __global__ __launch_bounds__(256) void vv_pack16_tiles_kernel(const float* __res
         const int ol = (t & 15) + 16 * ((k & 31) >> 3);
         *reinterpret_cast<uint2*>(out + ((tile * 64 + ol) * 16 + (k & 7) * 2)) = __builtin_bit_cast(uint2, b);
     }
-    (void)KT;
 }
 
 constexpr int PU = 8;      // k-steps per batch
@@ -336,7 +334,8 @@ int vv_pack16_tiles_launch(const float* x, int ldx, int64_t stride_outer, int n_
 
 // Y / Yp (op)= W . Xp for one packed 16-row activation tile.  flags: 1 = RS (operand un-normalised, row scale from ssq_in), 2 = SH (second
 // operand Xs), 4 = PK (residual epilogue also packs the new rows for the next projection).  Returns VV_RC_NO_FORM when the combination has no instantiation.
-int vv_gemv16p_launch2(const VVGemv16p* ap, int epi, int flags, hipStream_t s) {
+// wpb_out (tests): the waves per workgroup of the instantiation that was launched.
+int vv_gemv16p_launch2(const VVGemv16p* ap, int epi, int flags, hipStream_t s, int* wpb_out) {
     const VVGemv16p& a = *ap;
     if (a.T < 1 || a.T > 16 || (a.N & 3) || a.K < 32 || (a.K & 31)) return VV_RC_NO_FORM;
     const int n_tiles = (a.N + 15) / 16;
@@ -346,7 +345,8 @@ int vv_gemv16p_launch2(const VVGemv16p* ap, int epi, int flags, hipStream_t s) {
     // waves per workgroup as in vv_gemv_launch: 4 once there are more tiles than CUs (every workgroup resident at once), else 8
     constexpr int wide_tiles = 256;
     const bool w4 = n_tiles > wide_tiles;
-#define VV_P(E_, RS_, SH_, PK_) do { if (w4) hipLaunchKernelGGL((vv_gemv16p_kernel<E_, 4, RS_, SH_, PK_>), dim3(n_tiles), dim3(256), 0, s, a); \
+#define VV_P(E_, RS_, SH_, PK_) do { if (wpb_out) *wpb_out = w4 ? 4 : 8; \
+                                   if (w4) hipLaunchKernelGGL((vv_gemv16p_kernel<E_, 4, RS_, SH_, PK_>), dim3(n_tiles), dim3(256), 0, s, a); \
                                    else hipLaunchKernelGGL((vv_gemv16p_kernel<E_, 8, RS_, SH_, PK_>), dim3(n_tiles), dim3(512), 0, s, a); return vv_launch_rc(0); } while (0)
     if (epi == VV_EPI_SWIGLU) {
         if (!a.W2 || !a.Yp || (a.N & 7)) return VV_RC_NO_FORM;

@@ -81,7 +81,7 @@ int vv_pack16_launch(const float* x, int ldx, int mode, const float* nw, float e
                      int K, hipStream_t s);
 int vv_gemv16p_launch(const void* W, const void* W2, const void* Xp, float* Y, void* Yp, const float* bias, const float* gate, int T, int N, int K,
                       int ldy, int ld_gate, int epi, hipStream_t s);
-int vv_gemv16p_launch2(const VVGemv16p* a, int epi, int flags, hipStream_t s);
+int vv_gemv16p_launch2(const VVGemv16p* a, int epi, int flags, hipStream_t s, int* wpb_out = nullptr);
 int vv_head_tail_ok(const VVTail* a);
 int vv_head_tail_init();
 int vv_head_tail_launch(const VVTail* a, hipStream_t s);

@@ -1111,6 +1111,143 @@ class Engine:
             raise EngineError(f"vv_gemv_case failed ({rc})")
         return tuple(form)
 
+    def _case_need(self, who, name, t, numel, dtype=torch.float32, required=False):
+        """the operand check of the one-launch test entries: device, dtype, contiguity, 16-byte alignment, at least numel elements"""
+        if t is None:
+            if required:
+                raise ValueError(f"{who}: {name} is required here")
+            return
+        if not isinstance(t, torch.Tensor) or t.device != self.device:
+            raise ValueError(f"{who}: {name} is not a tensor on {self.device}")
+        if t.dtype != dtype:
+            raise ValueError(f"{who}: {name} is {t.dtype}, expected {dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{who}: {name} is not contiguous")
+        if t.data_ptr() % 16:
+            raise ValueError(f"{who}: {name} is not 16-byte aligned")
+        if t.numel() < numel:
+            raise ValueError(f"{who}: {name} holds {t.numel()} elements, the launch addresses {numel}")
+
+    @staticmethod
+    def _case_ints(who, **ints):
+        for k, v in ints.items():
+            if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v < 0 or v >= (1 << 30):
+                raise ValueError(f"{who}: {k} = {v!r} is not an int in [0, 2^30)")
+
+    FLAG_RS, FLAG_SH, FLAG_PK = 1, 2, 4      # vv_gemv16p_case's flags
+
+    def gemv16p_case(self, wp, xp, T, N, K, *, epi=0, flags=0, w2p=None, y=None, yp=None, bias=None, gate=None, ldy=None, ld_gate=0,
+                     ssq_in=None, ssq_tiles=0, eps=1e-6, xs=None, pk_nw=None, pk_sc=None, ld_pk=0, ssq_out=None,
+                     z=None, x0p=None, coef=None, cfg=0.0, n_cfg=0, sde_noise=None, cfg_rows=None):
+        """One launch of the batch-decode packed GEMV (vv_gemv16p_case), or a refusal.  Returns the waves per workgroup the launcher
+        chose (4 or 8), or None when nothing was launched.  xp / xs: one packed 16-row activation tile each (uint8, ceil(K / 32) KiB);
+        yp: one such tile of the N output features; fp32 everywhere else.
+
+        As in gemv_case every tensor is checked BEFORE the call -- device, dtype, contiguity, 16-byte alignment and a size that covers
+        every address the kernel can form -- and a mismatch raises ValueError.  An operand the launcher itself insists on (ssq_in
+        with RS, xs with SH, ...) may be None: that is its refusal to give.  Asynchronous: the caller syncs."""
+        who = "gemv16p_case"
+        ldy = N if ldy is None else ldy
+        self._case_ints(who, T=T, N=N, K=K, epi=epi, flags=flags, ldy=ldy, ld_gate=ld_gate, ssq_tiles=ssq_tiles, ld_pk=ld_pk, n_cfg=n_cfg)
+        if N < 1 or K < 1 or T > 64:
+            raise ValueError(f"{who}: T, N, K = {T}, {N}, {K}")
+        if not 0 <= epi <= 6 or not 0 <= flags <= 7:
+            raise ValueError(f"{who}: epi = {epi}, flags = {flags}")
+        need = lambda *a, **k: self._case_need(who, *a, **k)
+        k_tiles, n4 = (K + 31) // 32, 4 * ((N + 3) // 4)
+        rows = lambda ld: max(T - 1, 0) * ld + n4             # the last row's last float4
+        wbytes = int(self.lib.vv_packed_bytes(N, K))
+        need("wp", wp, wbytes, torch.uint8, required=True)
+        need("w2p", w2p, wbytes, torch.uint8, required=epi == self.EPI_SWIGLU)
+        need("xp", xp, k_tiles * 1024, torch.uint8, required=True)
+        need("xs", xs, k_tiles * 1024, torch.uint8)
+        if y is not None and ldy < n4:
+            raise ValueError(f"{who}: ldy = {ldy} < N = {N}")
+        need("y", y, rows(ldy))
+        need("yp", yp, ((N + 31) // 32) * 1024, torch.uint8)
+        need("bias", bias, n4)
+        if gate is not None and ld_gate < n4:
+            raise ValueError(f"{who}: ld_gate = {ld_gate} < N = {N}")
+        need("gate", gate, rows(ld_gate))
+        if ssq_in is not None and ssq_tiles < 1:
+            raise ValueError(f"{who}: ssq_in with ssq_tiles = {ssq_tiles}")
+        need("ssq_in", ssq_in, ssq_tiles * 16)
+        need("pk_nw", pk_nw, n4)
+        if pk_sc is not None and ld_pk < n4:
+            raise ValueError(f"{who}: ld_pk = {ld_pk} < N = {N}")
+        need("pk_sc", pk_sc, rows(ld_pk))
+        need("ssq_out", ssq_out, ((N + 15) // 16) * 16)
+        need("z", z, 2 * n_cfg * N)                          # dense [2 n_cfg][N]: addressed by n_cfg, not by T or ldy
+        need("x0p", x0p, n_cfg * N)
+        need("coef", coef, 6)
+        need("sde_noise", sde_noise, n_cfg * N)
+        need("cfg_rows", cfg_rows, n_cfg)
+
+        a = _lib.VVGemv16pCase()
+        p = lambda t: t.data_ptr() if t is not None else None
+        a.W, a.W2, a.Xp, a.Y, a.Yp, a.bias, a.gate = p(wp), p(w2p), p(xp), p(y), p(yp), p(bias), p(gate)
+        a.T, a.N, a.K, a.ldy, a.ld_gate = T, N, K, ldy, ld_gate
+        a.ssq_in, a.ssq_tiles, a.eps, a.Xs = p(ssq_in), ssq_tiles, float(eps), p(xs)
+        a.pk_nw, a.pk_sc, a.ld_pk, a.ssq_out = p(pk_nw), p(pk_sc), ld_pk, p(ssq_out)
+        a.z, a.x0p, a.coef, a.cfg, a.n_cfg, a.sde_noise, a.cfg_rows = p(z), p(x0p), p(coef), float(cfg), n_cfg, p(sde_noise), p(cfg_rows)
+        wpb = C.c_int(0)
+        rc = self.lib.vv_gemv16p_case(self._s, C.byref(a), epi, flags, C.byref(wpb))
+        if rc == _lib.GEMV_REFUSED:
+            return None
+        if rc != 0:
+            raise EngineError(f"vv_gemv16p_case failed ({rc})")
+        return wpb.value
+
+    def pack16_case(self, x, xp, T, K, *, mode=1, ldx=None, nw=None, eps=1e-6, sc=None, sh=None, ld_mod=0, unaligned_ld_ok=False):
+        """One launch of vv_pack16_kernel (vv_pack16_case): rows x [T][ldx] fp32 -> the packed 16-row tile xp (uint8, K / 32 KiB), or a
+        refusal (None).  Returns 4, the kernel's waves per workgroup.  Operands are checked as in gemv16p_case; unaligned_ld_ok waives
+        the multiple-of-4 check of ldx for a caller that tests the launcher's refusal of it (sizes are still checked)."""
+        who = "pack16_case"
+        ldx = K if ldx is None else ldx
+        self._case_ints(who, T=T, K=K, mode=mode, ldx=ldx, ld_mod=ld_mod)
+        if K < 32 or T > 64:
+            raise ValueError(f"{who}: T, K = {T}, {K}")
+        if ldx < K or (ldx % 4 and not unaligned_ld_ok):
+            raise ValueError(f"{who}: ldx = {ldx}")
+        need = lambda *a, **k: self._case_need(who, *a, **k)
+        need("x", x, max(T - 1, 0) * ldx + K, required=True)
+        need("xp", xp, ((K + 31) // 32) * 1024, torch.uint8, required=True)
+        need("nw", nw, K)
+        if (sc is not None or sh is not None) and (ld_mod < K or ld_mod % 4):
+            raise ValueError(f"{who}: ld_mod = {ld_mod}")
+        need("sc", sc, max(T - 1, 0) * ld_mod + K)
+        need("sh", sh, max(T - 1, 0) * ld_mod + K)
+        p = lambda t: t.data_ptr() if t is not None else None
+        rc = self.lib.vv_pack16_case(self._s, p(x), ldx, mode, p(nw), float(eps), p(sc), p(sh), ld_mod, p(xp), T, K)
+        if rc == _lib.GEMV_REFUSED:
+            return None
+        if rc != 0:
+            raise EngineError(f"vv_pack16_case failed ({rc})")
+        return 4
+
+    def pack16_tiles_case(self, x, xp, T, K, n_tiles, *, ldx=None, stride_outer=0, n_inner=1, stride_inner=0, tile_bytes=None):
+        """One launch of vv_pack16_tiles_kernel (vv_pack16_tiles_case): n_tiles row blocks [T][ldx] of x, block j at float offset
+        (j // n_inner) * stride_outer + (j % n_inner) * stride_inner, -> plain bf16 packed tiles at xp + j * tile_bytes; None on a
+        refusal, else 4 (waves per workgroup).  Operands are checked as in gemv16p_case."""
+        who = "pack16_tiles_case"
+        ldx = K if ldx is None else ldx
+        tb = ((K + 31) // 32) * 1024
+        tile_bytes = tb if tile_bytes is None else tile_bytes
+        self._case_ints(who, T=T, K=K, n_tiles=n_tiles, ldx=ldx, stride_outer=stride_outer, n_inner=n_inner, stride_inner=stride_inner,
+                        tile_bytes=tile_bytes)
+        if K < 32 or T > 64 or n_tiles < 1 or n_inner < 1 or ldx < K or tile_bytes < tb:
+            raise ValueError(f"{who}: T, K, n_tiles, n_inner, ldx, tile_bytes = {T}, {K}, {n_tiles}, {n_inner}, {ldx}, {tile_bytes}")
+        last = max(((j // n_inner) * stride_outer + (j % n_inner) * stride_inner) for j in range(n_tiles))
+        need = lambda *a, **k: self._case_need(who, *a, **k)
+        need("x", x, last + max(T - 1, 0) * ldx + K, required=True)
+        need("xp", xp, (n_tiles - 1) * tile_bytes + tb, torch.uint8, required=True)
+        rc = self.lib.vv_pack16_tiles_case(self._s, x.data_ptr(), ldx, stride_outer, n_inner, stride_inner, xp.data_ptr(), tile_bytes, T, K, n_tiles)
+        if rc == _lib.GEMV_REFUSED:
+            return None
+        if rc != 0:
+            raise EngineError(f"vv_pack16_tiles_case failed ({rc})")
+        return 4
+
 
 class TempoCapacityError(EngineError):
     """A Tempo.push row that brings more input, or emits more output, than one launch takes per row; nothing ran, no state changed:
