@@ -360,6 +360,35 @@ int vv_pitch_rows(vv_ctx* ctx, void* stream, int pt, int n, const vv_pitch_row* 
  * Bit-identical to the same signal pushed and flushed through vv_pitch_rows. */
 int vv_pitch_once(vv_ctx* ctx, void* stream, const float* table_dev, int n_table, int R, int n, const int* pq_host, int n_in,
                   const float* audio_dev, int ld_in, float* out_dev, int ld_out);
+/* ---- formants: a streaming spectral-envelope warp A / B, both terms in 1..10^4, A / B in [1/2, 2], each row of a push at its own
+ * fraction, at 24 kHz (vibevoice_amd/formant.py defines it): frames of 1024 at hop 256 under a periodic Hann window, per frame the
+ * cepstral envelope (quefrencies below 64) read at k * B / A by linear interpolation, a real gain exp(clamp(Ew - E, +-30 dB)) on the
+ * spectrum, overlap-add in ascending frame order with the scale 2/3.  The envelope moves up by A / B, the pitch stays; in front of
+ * vv_pitch_rows at P / Q, A / B = Q / P keeps the formants where they were.  1 / 1 is the identity, nothing held back.  n samples in,
+ * n out.  What a stream emits does not depend on how its input was cut into pushes: a push emits every block of 256 whose input
+ * through 768 samples past its end has arrived (at most 1023 samples wait for the next push), the flush emits the rest against zeros.
+ * vv_formant_set: configuration fm (0..3) of this context: twiddles_host [2][1024] fp32 in HOST memory, cos and sin of 2 pi i / 1024;
+ * n_streams streams at their first sample.  Replaces what fm held.  Synchronous.  The pushes of one configuration are ordered on one
+ * stream: the frames of a launch pass through a buffer of the configuration. */
+int vv_formant_set(vv_ctx* ctx, int fm, const float* twiddles_host, int n_streams, void* stream);
+/* Back to the state after vv_formant_set for n streams (stream_ids_host == NULL: all of them): history and partial sums zeroed by a
+ * kernel on `stream`, input total 0, fraction and flush mark cleared. */
+int vv_formant_reset(vv_ctx* ctx, void* stream, int fm, int n, const int* stream_ids_host);
+/* One push of n <= 16 rows, TWO launches on `stream` (the frames; the sums, the outputs and the new state): row i = n_in samples at
+ * audio_dev + i * ld_in for stream rows_host[i].stream (distinct) at the fraction A / B (a stream keeps the fraction of its first push
+ * until its reset), flush != 0: the stream's last push.  Its outputs go to out_dev + i * ld_out, fp32.  n_out_host [n]: what each row
+ * emitted, computed on the host from the streams' input totals (no sync).  Refused with a message, nothing written, no state changed:
+ * as vv_pitch_rows, and A or B outside 1..10^4 or A / B outside [1/2, 2], a stream whose fraction changes, a row of more than 7552
+ * input samples or one that emits more than ld_out, and out_fmt = 1: a level stage follows this one, it never writes int16. */
+typedef struct vv_formant_row { int stream; int n_in; int flush; int A; int B; } vv_formant_row;
+int vv_formant_rows(vv_ctx* ctx, void* stream, int fm, int n, const vv_formant_row* rows_host, const float* audio_dev, int ld_in,
+                    void* out_dev, int ld_out, int out_fmt, int* n_out_host);
+/* Stateless: n whole signals of n_in samples (audio_dev + i * ld_in), signal i at the fraction ab_host[2 i] / ab_host[2 i + 1] (HOST
+ * memory) -> n_in fp32 samples (out_dev + i * ld_out); twiddles_dev [2][1024] on the device; scratch_dev: scratch_floats fp32 on the
+ * device, at least min(n, 16) * (ceil(n_in / 256) + 3) * 1024, for the frames.  One launch group per 16 signals.  Bit-identical to
+ * the same signal pushed and flushed through vv_formant_rows. */
+int vv_formant_once(vv_ctx* ctx, void* stream, const float* twiddles_dev, int n, const int* ab_host, int n_in, const float* audio_dev,
+                    int ld_in, float* out_dev, int ld_out, float* scratch_dev, long long scratch_floats);
 /* ---- output level: a streaming gain and look-ahead peak limiter (vibevoice_amd/level.py defines it).  A: look-ahead and ramp, H: hold,
  * in samples; g: the gain, c: the ceiling.  u = fl(g x) (non-finite: 0), r = 1 where |u| <= c else fl(c / |u|), q = floor(r 2^20),
  * h[j] = min q[j - H .. j + A - 1], S[i] = sum h[i - A + 1 .. i], a = fl(float(S) / float(A 2^20)), y = clamp(fl(a u), -c, c): no

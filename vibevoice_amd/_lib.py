@@ -73,6 +73,11 @@ class VVTempoRow(C.Structure):
     _fields_ = [("stream", C.c_int), ("n_in", C.c_int), ("flush", C.c_int), ("P", C.c_int), ("Q", C.c_int)]
 
 
+class VVFormantRow(C.Structure):
+    """vv_formant_row (include/vvhip.h): the stream, the input samples, the flush mark and the warp A / B of one row of vv_formant_rows"""
+    _fields_ = [("stream", C.c_int), ("n_in", C.c_int), ("flush", C.c_int), ("A", C.c_int), ("B", C.c_int)]
+
+
 class VVPitchRow(C.Structure):
     """vv_pitch_row (include/vvhip.h): the stream, the input samples, the flush mark and the ratio P / Q of one row of vv_pitch_rows"""
     _fields_ = [("stream", C.c_int), ("n_in", C.c_int), ("flush", C.c_int), ("P", C.c_int), ("Q", C.c_int)]
@@ -145,6 +150,10 @@ _SIGS = {
     "vv_pitch_reset": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "vv_pitch_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(VVPitchRow), _P, C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "vv_pitch_once": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _P, C.c_int, _P, C.c_int]),
+    "vv_formant_set": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),
+    "vv_formant_reset": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "vv_formant_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(VVFormantRow), _P, C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "vv_formant_once": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(C.c_int), C.c_int, _P, C.c_int, _P, C.c_int, _P, C.c_longlong]),
     "vv_level_set": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P]),
     "vv_level_reset": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "vv_level_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(VVLevelRow), _P, C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_int)]),

@@ -848,6 +848,107 @@ extern "C" int vv_pitch_once(vv_ctx* ctx, void* stream, const float* table_dev, 
     return 0;
 }
 
+// ------------------------------------------------------------------ formants (kernels: formant.hip; vibevoice_amd/formant.py defines it)
+static const char* const FM_RATIO_MSG = "must have both terms in [1,10000] and lie in [1/2, 2]";
+
+extern "C" int vv_formant_set(vv_ctx* ctx, int fm, const float* twiddles_host, int n_streams, void* stream) {
+    VV_SHARED;
+    if (fm < 0 || fm >= vv_ctx::N_FORMANTS) return fail(ctx, "vv_formant_set: configuration %d out of range [0,%d)", fm, vv_ctx::N_FORMANTS);
+    if (n_streams < 1 || n_streams > 65536) return fail(ctx, "vv_formant_set: n_streams = %d must be in [1,65536]", n_streams);
+    if (!twiddles_host) return fail(ctx, "vv_formant_set: null twiddle table");
+    vv_ctx::Formant& f = ctx->fm[fm];
+    HIPCHK(ctx, hipStreamSynchronize((hipStream_t)stream));      // pushes that still read what is replaced
+    dfree(ctx, f.tw); dfree(ctx, f.hist); dfree(ctx, f.tail); dfree(ctx, f.scratch);
+    f = vv_ctx::Formant();
+    float* tw = (float*)dalloc(ctx, (size_t)2 * VV_FM_N * 4, false);
+    float* hist = (float*)dalloc(ctx, (size_t)n_streams * VV_FM_HIST * 4, true);
+    float* tail = (float*)dalloc(ctx, (size_t)n_streams * VV_FM_TAIL * 4, true);
+    float* scratch = (float*)dalloc(ctx, (size_t)16 * VV_FM_MAX_FRAMES * VV_FM_N * 4, false);
+    if (!tw || !hist || !tail || !scratch || hipMemcpy(tw, twiddles_host, (size_t)2 * VV_FM_N * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        dfree(ctx, tw); dfree(ctx, hist); dfree(ctx, tail); dfree(ctx, scratch);
+        return fail(ctx, "vv_formant_set: allocating the state or uploading the table failed");
+    }
+    f.n_streams = n_streams; f.tw = tw; f.hist = hist; f.tail = tail; f.scratch = scratch;
+    f.total.assign(n_streams, 0); f.A.assign(n_streams, 0); f.B.assign(n_streams, 0); f.flushed.assign(n_streams, 0);
+    return 0;
+}
+
+extern "C" int vv_formant_reset(vv_ctx* ctx, void* stream, int fm, int n, const int* stream_ids_host) {
+    VV_SHARED;
+    vv_ctx::Formant* f = fm >= 0 && fm < vv_ctx::N_FORMANTS && ctx->fm[fm].hist ? &ctx->fm[fm] : nullptr;
+    return stage_reset(ctx, "vv_formant_reset", f, fm, n, stream_ids_host,
+                       [&](const int* ids, int k) { return vv_formant_reset_launch(f->hist, f->tail, f->n_streams, ids, k, (hipStream_t)stream); },
+                       [&](int id) { f->A[id] = 0; f->B[id] = 0; });
+}
+
+extern "C" int vv_formant_rows(vv_ctx* ctx, void* stream, int fm, int n, const vv_formant_row* rows_host, const float* audio_dev, int ld_in,
+                               void* out_dev, int ld_out, int out_fmt, int* n_out_host) {
+    VV_SHARED;
+    vv_ctx::Formant* fp = fm >= 0 && fm < vv_ctx::N_FORMANTS && ctx->fm[fm].hist ? &ctx->fm[fm] : nullptr;
+    const RowCheck ck{ctx, "vv_formant_rows", fp, audio_dev, ld_in};
+    VVTRY(ck.head(fm, n, rows_host, out_dev, n_out_host, out_fmt));
+    if (out_fmt != 0) return fail(ctx, "vv_formant_rows: out_fmt = 1 (int16) is not served: the warp is never the last stage, a level stage follows it");
+    vv_ctx::Formant& f = *fp;
+    VVFmRows kr;
+    memset(&kr, 0, sizeof(kr));
+    for (int i = 0; i < n; ++i) {
+        const vv_formant_row& q = rows_host[i];
+        VVTRY(ck.stream(rows_host, i));
+        VVTRY(ck.input(i, q.n_in));
+        if (q.n_in > VV_FM_MAX_IN) return fail(ctx, "vv_formant_rows: row %d brings %d samples, one push takes at most %d per row; push it in pieces", i, q.n_in, VV_FM_MAX_IN);
+        if (!vv_fm_ratio_ok(q.A, q.B)) return fail(ctx, "vv_formant_rows: row %d: warp %d / %d %s", i, q.A, q.B, FM_RATIO_MSG);
+        if (f.A[q.stream] && (f.A[q.stream] != q.A || f.B[q.stream] != q.B))
+            return fail(ctx, "vv_formant_rows: stream %d runs at warp %d / %d since its first push; reset it before it changes to %d / %d", q.stream,
+                        f.A[q.stream], f.B[q.stream], q.A, q.B);
+        VVTRY(ck.open(q.stream));
+        const int64_t before = f.total[q.stream], after = before + q.n_in;
+        int64_t n_out = q.n_in, nf = 0, F0 = 3;                 // 1 / 1: the identity, nothing held back
+        if (q.A != q.B) {
+            F0 = before / VV_FM_H;
+            const int64_t F1 = q.flush ? (after + VV_FM_H - 1) / VV_FM_H + 3 : after / VV_FM_H;
+            nf = F1 - F0;
+            n_out = (q.flush ? after : VV_FM_H * std::max<int64_t>(0, F1 - 3)) - VV_FM_H * std::max<int64_t>(0, F0 - 3);
+        }
+        if (n_out > ld_out) return fail(ctx, "vv_formant_rows: row %d emits %lld samples, the output rows hold %d", i, (long long)n_out, ld_out);
+        kr.r[i].stream = q.stream; kr.r[i].n_in = q.n_in; kr.r[i].n_out = (int)n_out; kr.r[i].A = q.A; kr.r[i].B = q.B;
+        kr.r[i].nf = (int)nf; kr.r[i].r = q.A != q.B ? (int)(before % VV_FM_H) : 0; kr.r[i].c_min = (int)std::max<int64_t>(0, 3 - F0);
+    }
+    VVTRY(stage_launch(ctx, f, rows_host, n, kr, n_out_host, [&] {
+        return vv_formant_rows_launch(&kr, n, f.tw, f.hist, f.tail, f.n_streams, audio_dev, ld_in, (float*)out_dev, ld_out, f.scratch, VV_FM_MAX_FRAMES,
+                                      (hipStream_t)stream); }));
+    for (int i = 0; i < n; ++i) { f.A[rows_host[i].stream] = rows_host[i].A; f.B[rows_host[i].stream] = rows_host[i].B; }
+    return 0;
+}
+
+extern "C" int vv_formant_once(vv_ctx* ctx, void* stream, const float* twiddles_dev, int n, const int* ab_host, int n_in, const float* audio_dev,
+                               int ld_in, float* out_dev, int ld_out, float* scratch_dev, long long scratch_floats) {
+    VV_SHARED;
+    if (n < 1 || n > 65535 || n_in < 1 || n_in > ld_in || n_in > ((int64_t)1 << 31) - 4 * VV_FM_N)
+        return fail(ctx, "vv_formant_once: n = %d in [1,65535], n_in = %d in [1, ld_in = %d]", n, n_in, ld_in);
+    if (n_in > ld_out) return fail(ctx, "vv_formant_once: %d output samples per row, the output rows hold %d", n_in, ld_out);
+    if (!twiddles_dev || !ab_host || !audio_dev || !out_dev || !scratch_dev) return fail(ctx, "vv_formant_once: null table / fractions / audio / out / scratch pointer");
+    const int nf = (n_in + VV_FM_H - 1) / VV_FM_H + 3;
+    if ((int64_t)std::min(n, 16) * nf * VV_FM_N > scratch_floats)
+        return fail(ctx, "vv_formant_once: the frames of %d signals of %d samples need %lld floats of scratch, %lld are given", std::min(n, 16), n_in,
+                    (long long)std::min(n, 16) * nf * VV_FM_N, scratch_floats);
+    for (int i = 0; i < n; ++i)
+        if (!vv_fm_ratio_ok(ab_host[2 * i], ab_host[2 * i + 1]))
+            return fail(ctx, "vv_formant_once: signal %d: warp %d / %d %s", i, ab_host[2 * i], ab_host[2 * i + 1], FM_RATIO_MSG);
+    for (int i0 = 0; i0 < n; i0 += 16) {
+        const int k = std::min(16, n - i0);
+        VVFmRows kr;
+        memset(&kr, 0, sizeof(kr));
+        for (int i = 0; i < k; ++i) {
+            const int A = ab_host[2 * (i0 + i)], B = ab_host[2 * (i0 + i) + 1];
+            kr.r[i].stream = -1; kr.r[i].n_in = n_in; kr.r[i].n_out = n_in; kr.r[i].A = A; kr.r[i].B = B;
+            kr.r[i].nf = A == B ? 0 : nf; kr.r[i].r = 0; kr.r[i].c_min = 3;
+        }
+        VVCHK(vv_formant_rows_launch(&kr, k, twiddles_dev, nullptr, nullptr, 0, audio_dev + (size_t)i0 * ld_in, ld_in, out_dev + (size_t)i0 * ld_out, ld_out,
+                                     scratch_dev, nf, (hipStream_t)stream));
+    }
+    return 0;
+}
+
 // ------------------------------------------------------------------ output level (kernels: level.hip; vibevoice_amd/level.py defines it)
 // Outputs a stream has emitted before its flush once `total` input samples have arrived: every sample whose A - 1 samples of look-ahead
 // are there.  vibevoice_amd/level.py (emitted) is the same arithmetic.

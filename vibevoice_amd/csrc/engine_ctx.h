@@ -207,6 +207,12 @@ struct vv_ctx {
     struct Pitch : RowStage { int R = 0; float* table = nullptr; float* hist = nullptr; std::vector<int> P, Q; };
     static constexpr int N_PITCHES = 4;
     Pitch pt[N_PITCHES];
+    // streaming formant warps (vv_formant_set, engine_codec.hip; kernels: formant.hip): the twiddle table, per stream VV_FM_HIST history
+    // samples and VV_FM_TAIL partial sums on the device, on the host its fraction A / B (fixed by its first push, 0 before), and the frames
+    // of one launch (16 rows) between its two kernels: the pushes of one configuration are ordered on one stream.  Kept like the resamplers.
+    struct Formant : RowStage { float* tw = nullptr; float* hist = nullptr; float* tail = nullptr; float* scratch = nullptr; std::vector<int> A, B; };
+    static constexpr int N_FORMANTS = 4;
+    Formant fm[N_FORMANTS];
     // streaming output levels (vv_level_set, engine_codec.hip; kernels: level.hip): look-ahead A, hold H, ceiling c, per stream H + 2 A - 2
     // history samples on the device and on the host its gain (fixed by its first push, 0 before).  Kept like the resamplers.
     struct Level : RowStage { int A = 0, H = 0; float c = 0.f; float* hist = nullptr; std::vector<float> gain; };

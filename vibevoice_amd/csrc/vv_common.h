@@ -213,6 +213,28 @@ static inline int vv_pt_taps(int P, int Q) { return P == Q ? 0 : (VV_PT_Z * (P >
 // the ratios a row may run at: both terms in 1..100, P / Q in [1/2, 2]
 static inline bool vv_pt_ratio_ok(int P, int Q) { return P >= 1 && P <= 100 && Q >= 1 && Q <= 100 && P <= 2 * Q && Q <= 2 * P; }
 
+// ---- streaming formant warp (formant.hip): one row of a launch, passed by value in the kernel arguments, each at its own fraction ----
+// The host keeps each stream's 64-bit input total and its fraction A / B; the kernels see a push relative to its first new frame.  With
+// F0 = total / H frames done before the push: the push computes frames F0 .. F0 + nf - 1, frame f of them covers samples
+// [f * H - 3 * H - r, f * H + H - r) counted from the chunk's first, r = total % H (below 0: the stream's history, beyond n_in: zeros).
+// Block c = 0 .. nf + 2 of the push is output block F0 - 3 + c: blocks c < 3 start from the stream's partial sums, blocks c < c_min lie
+// before the signal (c_min = max(0, 3 - F0)) and are dropped, blocks c < nf are complete and go to out at (c - c_min) * H, cut at n_out;
+// blocks nf .. nf + 2 are the stream's new partial sums.  A == B: the identity, n_out = n_in copied, no frame.  32-bit arithmetic
+// whatever the stream's age.  stream < 0 (vv_formant_once): no history, no partial sums.
+struct VVFmRow { int stream, n_in, n_out, A, B, nf, r, c_min; };
+struct VVFmRows { VVFmRow r[16]; };
+constexpr int VV_FM_N = 1024;              // frame length (vibevoice_amd/formant.py: N)
+constexpr int VV_FM_H = 256;               // hop
+constexpr int VV_FM_K = VV_FM_N / 2 + 1;   // bins
+constexpr int VV_FM_QC = 64;               // the lifter keeps quefrencies |q| < QC
+constexpr int VV_FM_HIST = VV_FM_N;        // input samples a stream keeps between pushes: N - H behind the at most H - 1 of its open block
+constexpr int VV_FM_TAIL = VV_FM_N - VV_FM_H;  // partial sums of a stream's overlap-add tail
+constexpr int VV_FM_MAX_IN = 7552;         // input samples one row of a push may bring, as in the pitch stage
+constexpr int VV_FM_MAX_FRAMES = 36;       // frames one row of a push computes: (255 + MAX_IN) / H = 30 complete ones, + 4 at a flush
+constexpr int VV_FM_MAX_TERM = 10000;
+// the fractions a row may run at: both terms in 1..10^4, A / B in [1/2, 2]
+static inline bool vv_fm_ratio_ok(int A, int B) { return A >= 1 && A <= VV_FM_MAX_TERM && B >= 1 && B <= VV_FM_MAX_TERM && A <= 2 * B && B <= 2 * A; }
+
 // ---- streaming output level (level.hip): one row of a push, passed by value in the kernel arguments ----
 // The host keeps each stream's 64-bit input total and its gain; the row's staging buffer is [H + 2 A - 2 history | n_in chunk | A - 1
 // zeros], its first output sits at index b0 = (first output's signal index) - total + H + 2 A - 2 of it, n_out outputs follow.

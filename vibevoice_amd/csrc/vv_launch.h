@@ -132,6 +132,12 @@ int vv_pitch_rows_launch(const VVPitchRows* rows, int n, const float* table, int
 int vv_pitch_once_launch(const float* table, int R, const VVPitchRatios* pq, int n, int n_in, const float* x, int ld_in, float* out, int ld_out,
                          hipStream_t s);
 int vv_pitch_reset_launch(float* hist, int n_streams, const int* ids, int n, hipStream_t s);
+// formant.hip.  tw [2][VV_FM_N] cos and sin of 2 pi i / N; hist [n_streams][VV_FM_HIST], tail [n_streams][VV_FM_TAIL] (both null: stateless,
+// whole signals); scratch [>= n][cap_frames][VV_FM_N] the windowed frames between the two launches of a push, row i of the launch at
+// scratch + i * cap_frames * VV_FM_N.  Two launches: the frames, then the sums, the outputs and the streams' new state.
+int vv_formant_rows_launch(const VVFmRows* rows, int n, const float* tw, float* hist, float* tail, int n_streams, const float* x, int ld_in,
+                           float* out, int ld_out, float* scratch, int cap_frames, hipStream_t s);
+int vv_formant_reset_launch(float* hist, float* tail, int n_streams, const int* ids, int n, hipStream_t s);
 // level.hip.  A look-ahead / ramp, H hold (samples), c the ceiling; hist [n_streams][nh], nh = H + 2 A - 2.
 int vv_level_rows_launch(const VVLvRows* rows, int n, int A, int H, float c, float* hist, int n_streams, const float* x, int ld_in, void* out,
                          int ld_out, int pcm16, hipStream_t s);

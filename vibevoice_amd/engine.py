@@ -535,7 +535,7 @@ class Engine:
                   "vv_audio_to_pcm16")
 
     # ------------------------------------------------------------------ streaming row stages and their whole-signal forms
-    _STAGE_USED = {"resampler": "_rs_used", "tempo": "_tp_used", "pitch": "_pt_used", "level": "_lv_used", "loudness": "_ld_used"}
+    _STAGE_USED = {"resampler": "_rs_used", "tempo": "_tp_used", "pitch": "_pt_used", "formant": "_fm_used", "level": "_lv_used", "loudness": "_ld_used"}
 
     def _take_stage_slot(self, kind, make):
         """make(k) for the first free k of this engine's four `kind` configurations; the stage's close() gives k back"""
@@ -628,18 +628,26 @@ class Engine:
             h = self.__dict__["_pt_table"] = torch.from_numpy(np.array(_pt.table())).to(self.device)
         return h
 
-    def pitch_shift(self, audio: torch.Tensor, semitones, speed: float = 1.0, stream=None) -> torch.Tensor:
+    def pitch_shift(self, audio: torch.Tensor, semitones, speed: float = 1.0, stream=None, formant=None) -> torch.Tensor:
         """Whole signals at another pitch: audio [samples] or [n, samples] (24 kHz, any float dtype, any device) -> fp32 on the engine's
         device, moved by `semitones` in [-12, +12] and played at `speed`: time_stretch() at speed * Q / P (none where that is exactly
         1), then pitch_resample() at P / Q = ratio(semitones), the definition of vibevoice_amd/pitch.py (shift_ref):
-        ceil(ceil(n Qt / Pt) Q / P) samples.  A resampling shifter: the formants move with the pitch.  A combined speed outside
-        [0.5, 2.0] is refused.  Stateless; runs on `stream` (default: the current torch stream of the device)."""
+        ceil(ceil(n Qt / Pt) Q / P) samples.  formant=None: a resampling shifter, the formants move with the pitch.  formant=F (semitones
+        in [-12, +12]): formant_warp() at ratio(F) * Q / P between the two (vibevoice_amd/formant.py), so the formants end up F semitones
+        from the untouched voice's -- 0.0 keeps them.  A combined speed outside [0.5, 2.0] is refused, and so is a warp outside [1/2, 2].
+        Stateless; runs on `stream` (default: the current torch stream of the device)."""
         from . import pitch as _pt
         from . import tempo as _tp
         P, Q = _pt.ratio(semitones)
         v = _pt.tempo_speed(speed, semitones)
+        ab = None
+        if formant is not None:
+            from . import formant as _fm
+            ab = _fm.fraction(formant, semitones)
         if _tp.ratio(v) != (1, 1):
             audio = self.time_stretch(audio, v, stream=stream)
+        if ab is not None and ab != (1, 1):
+            audio = self.formant_warp(audio, fractions=ab, stream=stream)
         if P == Q:
             return audio.detach().to(device=self.device, dtype=torch.float32)
         out, counts = self.pitch_resample(audio, semitones, stream=stream)
@@ -665,6 +673,43 @@ class Engine:
             self._chk(self.lib.vv_pitch_once(self._ctx, st, self._p(h), int(h.shape[0]), _pt.R, nn, (C.c_int * (2 * nn))(*flat), n_in, self._p(x),
                                              n_in, self._p(out), n_out), "vv_pitch_once")
         return self._whole("pitch_resample", audio, n_out, run, stream)[0], counts
+
+    # formants (formant.py, csrc/formant.hip)
+    def formant(self, n_streams: int) -> "Formant":
+        """A streaming spectral-envelope warp with n_streams independent streams, each at its own fraction A / B, in one of this
+        engine's four formant configurations (close() it to give the configuration back).  Alone it moves the formants and keeps the
+        pitch; in front of a pitch stage at P / Q, at Q / P, it keeps the formants where they were."""
+        return self._take_stage_slot("formant", lambda k: Formant(self, k, n_streams))
+
+    def _formant_table(self):
+        from . import formant as _fm
+        t = self.__dict__.get("_fm_table")
+        if t is None:
+            t = self.__dict__["_fm_table"] = torch.from_numpy(np.array(_fm.twiddles())).to(self.device)
+        return t
+
+    def formant_warp(self, audio: torch.Tensor, semitones=None, stream=None, fractions=None) -> torch.Tensor:
+        """Whole signals with their formants moved and their pitch kept: audio [samples] or [n, samples] (24 kHz, any float dtype, any
+        device) -> fp32 on the engine's device, as many samples, the definition of vibevoice_amd/formant.py.  semitones in [-12, +12]: one
+        value, or one per row (the warp is pitch.ratio of it); fractions: the warp (A, B) itself, or one per row, in place of semitones.
+        A row at 1 / 1 is copied.  Stateless; two launches per 16 rows, each row at its own warp, on `stream` (default: the current
+        torch stream of the device)."""
+        from . import formant as _fm
+        rows = int(audio.numel() // audio.shape[-1]) if audio.dim() and audio.shape[-1] else 0
+        ab = _fm_fractions(_fm, "Engine.formant_warp", rows, semitones, fractions)
+        n_out = int(audio.shape[-1]) if audio.dim() else 0
+        ts = stream if stream is not None else torch.cuda.current_stream(self.device)
+
+        def run(st, nn, n_in, x, out, _):
+            tw = self._formant_table()
+            i0 = rows - int(x.shape[0])                        # _whole hands over the tile's first row onwards
+            flat = [v for A, B in ab[i0:i0 + nn] for v in (A, B)]
+            floats = min(nn, 16) * (-(-n_in // _fm.H) + 3) * _fm.N
+            with torch.cuda.stream(ts):                        # the frames between the two launches: this stream's
+                scratch = torch.empty(floats, dtype=torch.float32, device=self.device)
+            self._chk(self.lib.vv_formant_once(self._ctx, st, self._p(tw), nn, (C.c_int * (2 * nn))(*flat), n_in, self._p(x), n_in, self._p(out),
+                                               n_out, self._p(scratch), floats), "vv_formant_once")
+        return self._whole("formant_warp", audio, n_out, run, stream)[0]
 
     # output level (level.py, csrc/level.hip)
     def level(self, n_streams: int, rate: int = 24000, ceiling_db: float = -1.0) -> "Level":
@@ -1255,7 +1300,7 @@ class TempoCapacityError(EngineError):
 
 
 class _RowStage:
-    """What the streaming row stages share (Loudness, Tempo, Pitch, Resampler, Level): n_streams chunk-continuous streams in
+    """What the streaming row stages share (Loudness, Tempo, Formant, Pitch, Resampler, Level): n_streams chunk-continuous streams in
     one of the engine's configurations, pushed up to 16 rows a launch.  A stage supplies KIND (Engine._STAGE_USED), its row struct ROW
     and how push() fills it, its C entry points ROWS_FN / RESET_FN, counts(), max_out() and take()."""
     KIND = ROW = ROWS_FN = RESET_FN = None
@@ -1459,6 +1504,75 @@ class Pitch(_RowStage):
         for i in range(n):
             rows[i].stream, rows[i].n_in, rows[i].flush, rows[i].P, rows[i].Q = ids[i], nin[i], int(fl[i]), pq[i][0], pq[i][1]
         return out, self._launch(audio, samples, ids, nin, rows, out, pcm16, stream, took=lambda i: self.ratio.__setitem__(ids[i], pq[i]))
+
+    def _cleared(self, stream_id):
+        self.total[stream_id], self.ratio[stream_id] = 0, None
+
+
+def _fm_fractions(_fm, who, n, semitones, fractions):
+    """the warps (A, B) of n rows from semitones (one value or one per row) or from fractions ((A, B) or one pair per row)"""
+    if fractions is not None:
+        ab = [tuple(fractions)] * n if not hasattr(fractions[0], "__len__") else [tuple(v) for v in fractions]
+        name = "fractions"
+    else:
+        ab = [semitones] * n if not hasattr(semitones, "__len__") else list(semitones)
+        name = "semitones"
+    if len(ab) != n:
+        raise ValueError(f"{who}: {name} names one value, or one per row ({n}), got {len(ab)}")
+    return [_fm.check(*v) for v in ab] if fractions is not None else [_fm.warp_of(v) for v in ab]
+
+
+class Formant(_RowStage):
+    """One streaming formant configuration of an engine (Engine.formant): n_streams chunk-continuous spectral-envelope warps at 24 kHz,
+    each at the fraction A / B of its first push until its reset (which clears the fraction with the rest); the rows of one launch run at
+    different fractions.  What a stream delivers does not depend on how its input was cut into pushes (vibevoice_amd/formant.py): the
+    concatenation of its pushes and its flush equals Engine.formant_warp() of the concatenated input, bit for bit, as many samples; a
+    stream at 1 / 1 passes bit for bit.  The pushes of one configuration are ordered on one stream.  delay_samples: the input samples
+    (1023, 42.6 ms) a stream holds back at most until its next push; max_in: the input samples one row of a push may bring."""
+    KIND, ROW, ROWS_FN, RESET_FN = "formant", _lib.VVFormantRow, "vv_formant_rows", "vv_formant_reset"
+    NO_ROWS = (0,)                                        # one launch, which vv_formant_rows refuses by name
+
+    def __init__(self, engine: Engine, slot: int, n_streams: int):
+        from . import formant as _fm
+        super().__init__(engine, slot, n_streams)
+        self.delay_samples, self.max_in = _fm.DELAY, _fm.MAX_IN
+        self.ratio = [None] * self.n_streams              # (A, B) of each stream, None before its first push
+        t = np.ascontiguousarray(_fm.twiddles())
+        engine._chk(engine.lib.vv_formant_set(engine._ctx, slot, C.c_void_p(t.ctypes.data), self.n_streams, engine._s), "vv_formant_set")
+
+    def counts(self, stream_id: int, n_in: int, semitones=None, flush: bool = False, fraction=None) -> int:
+        """samples a push of n_in samples to stream_id would emit now (host integers, no device sync); semitones or fraction = (A, B):
+        for its first push"""
+        from . import formant as _fm
+        A, B = self.ratio[stream_id] or (_fm.check(*fraction) if fraction is not None else _fm.warp_of(semitones))
+        return _fm.counts(self.total[stream_id], n_in, flush, A, B)[1]
+
+    def max_out(self, n_in: int) -> int:
+        """upper bound of what any push of up to n_in samples emits, the flush included: at most 1023 held samples join the chunk"""
+        return int(n_in) + self.delay_samples
+
+    def take(self, ids, remaining, flush=False):
+        from . import formant as _fm
+        return _fm.push_width(remaining)
+
+    def push(self, audio: Optional[torch.Tensor], stream_ids: Sequence[int], semitones=None, flush=False, out: Optional[torch.Tensor] = None,
+             n_in=None, stream=None, pcm16: bool = False, fractions=None):
+        """Row i of audio [n, samples] (contiguous fp32 on the engine's device; None where no row brings samples) goes to stream
+        stream_ids[i] (distinct) at the warp of semitones[i] (or one shift for all rows), or at fractions[i] = (A, B) (or one pair for all
+        rows) in their place; a stream keeps the fraction of its first push.  n_in: samples of each row that count (default: all),
+        flush: bool or one per row -- a stream's last push, after which it takes no more until reset().  -> (out, counts):
+        out[i, :counts[i]] is what row i emitted, fp32 (pcm16 is refused by name: a level stage follows this one).  out: a contiguous
+        fp32 [>= n, capacity] tensor to write into (default: a new one of max_out(samples) columns).  Two launches per 16 rows on `stream`
+        (default: the device's current torch stream); the counts are host integers, nothing waits for the device.  A row of more than
+        max_in samples is refused: push it in pieces of take()."""
+        from . import formant as _fm
+        ids, samples, nin, fl = self._args(audio, stream_ids, flush, n_in)
+        ab = _fm_fractions(_fm, "Formant.push", len(ids), semitones, fractions)
+        n, out = len(ids), self._out(out, len(ids), nin, pcm16)
+        rows = (self.ROW * max(n, 1))()
+        for i in range(n):
+            rows[i].stream, rows[i].n_in, rows[i].flush, rows[i].A, rows[i].B = ids[i], nin[i], int(fl[i]), ab[i][0], ab[i][1]
+        return out, self._launch(audio, samples, ids, nin, rows, out, pcm16, stream, took=lambda i: self.ratio.__setitem__(ids[i], ab[i]))
 
     def _cleared(self, stream_id):
         self.total[stream_id], self.ratio[stream_id] = 0, None

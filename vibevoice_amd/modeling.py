@@ -593,13 +593,21 @@ class _AudioRates:
         time_stretch(out.speech_outputs[0], 1.2); in front of resample_audio where both are wanted.  generate() itself has no rate input."""
         return self.engine.time_stretch(audio, speed)
 
-    def pitch_shift(self, audio: torch.Tensor, semitones: float, speed: float = 1.0) -> torch.Tensor:
+    def pitch_shift(self, audio: torch.Tensor, semitones: float, speed: float = 1.0, formant=None) -> torch.Tensor:
         """audio [samples] or [n, samples] at 24 kHz -> fp32 on the engine's device, the pitch moved by `semitones` (-12 .. +12) and the
         speaking rate by `speed` (Engine.pitch_shift): a tempo change by speed * Q / P, then resampling by P / Q, samples / speed samples
-        to within one and the tempo stage's rounding.  A resampling shifter: the formants move with the pitch, so a few semitones read as
-        the same voice and more changes its character.  For speech_outputs after the fact -- pitch_shift(out.speech_outputs[0], -2);
-        in place of time_stretch where both are wanted.  generate() itself has no pitch input."""
-        return self.engine.pitch_shift(audio, semitones, speed)
+        to within one and the tempo stage's rounding.  formant=None: a resampling shifter, the formants move with the pitch, so a few
+        semitones read as the same voice and more changes its character.  formant=0.0 keeps the voice's formants (a spectral-envelope
+        warp by Q / P in front of the resampler), formant=F leaves them F semitones from where they were.  For speech_outputs after the
+        fact -- pitch_shift(out.speech_outputs[0], -4, formant=0.0); in place of time_stretch where both are wanted.  generate() itself
+        has no pitch input."""
+        return self.engine.pitch_shift(audio, semitones, speed, formant=formant)
+
+    def formant_shift(self, audio: torch.Tensor, semitones) -> torch.Tensor:
+        """audio [samples] or [n, samples] at 24 kHz -> fp32 on the engine's device, as many samples, the formants moved by `semitones`
+        (-12 .. +12; one value, or one per row) and the pitch kept (Engine.formant_warp): timbre, or voice size.  For speech_outputs
+        after the fact -- formant_shift(out.speech_outputs[0], -2).  generate() itself has no formant input."""
+        return self.engine.formant_warp(audio, semitones)
 
     def apply_level(self, audio: torch.Tensor, volume_db: float = 0.0, ceiling_db: float = -1.0, rate: int = 24000) -> torch.Tensor:
         """audio [samples] or [n, samples] at `rate` Hz -> fp32 on the engine's device, as many samples: volume_db of gain (-40 .. +24),

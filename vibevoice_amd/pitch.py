@@ -5,7 +5,9 @@ in fp32, each row of a launch at its own ratio (Engine.pitch / Engine.pitch_shif
 tested against.
 
 This is a resampling shifter: FORMANTS MOVE WITH THE PITCH.  A few semitones read as the same voice, higher or lower; beyond that the
-character of the voice changes (towards a smaller or a larger speaker).  Nothing here estimates or restores the spectral envelope.
+character of the voice changes (towards a smaller or a larger speaker).  Nothing here estimates or restores the spectral envelope:
+formant.py does, as a stage of its own in front of this one -- a warp of the envelope by exactly Q / P (AudioStreamer(pitch=s,
+formant=0.0), Engine.pitch_shift(..., formant=0.0)) puts the formants back where they were.
 
 Ratio.  ratio(s), s in [-12, +12]: the fraction P / Q with 1 <= P, Q <= 100 (and 1/2 <= P / Q <= 2) nearest to 2^(s / 12) in log
 frequency, reduced, ties to the smaller Q.  Both terms stay at or below 100 so that tempo.ratio(Q / P) recovers Q / P exactly.  The

@@ -30,12 +30,25 @@ block of 240 delivers nothing for that row; end(indices) flushes the tempo tail,
 stage runs each index at speed * Q / P and a variable-ratio resampler behind it (Engine.pitch, csrc/pitch.hip; vibevoice_amd/pitch.py is the
 definition) plays its output at P / Q = the fraction within 1..100 nearest to 2^(S / 12), each row of a launch at its own ratio, at 24 kHz,
 in front of the rate resampler; float chunks arrive as fp32.  A resampling shifter: the formants move with the pitch, so a few semitones
-read as the same voice higher or lower and more changes its character.  Chunk-continuous: per sample, the concatenated chunks equal
+read as the same voice higher or lower and more changes its character -- unless formant=0.0 is given with it (below).  Chunk-continuous: per sample, the concatenated chunks equal
 Engine.pitch_shift(whole signal, S, speed), n / speed samples to within one and the tempo stage's rounding, bit for bit in float mode.
 An index at 0 semitones passes the stage bit for bit; a combined speed outside [0.5, 2.0] is refused, one of exactly 1 (speed 1.5 with
 +7 semitones) builds no tempo stage.  A sample holds back at most 64 more input samples (2.7 ms) behind the tempo stage's; end(indices)
-flushes the tails in order: tempo, pitch, resampler, level.  Device chunks need an engine (as above), CPU chunks go through tempo.HostTempo
-and pitch.HostPitch.
+flushes the tails in order: tempo, formant, pitch, resampler, level.  Device chunks need an engine (as above), CPU chunks go through
+tempo.HostTempo and pitch.HostPitch.
+
+`formant=F` (a float in [-12, +12] semitones, or one per sample index, None among them) says where the formants end up relative to the
+untouched voice: a spectral-envelope warp (Engine.formant, csrc/formant.hip; vibevoice_amd/formant.py is the definition) between the tempo
+stage and the pitch stage, at 24 kHz, each index at its own fraction ratio(F) * Q / P, reduced, P / Q the index's pitch ratio.  With
+pitch=S, formant=0.0 is exactly Q / P and keeps the voice's formants (the same voice, higher or lower); formant=None leaves the pitch
+stage's behaviour as it is.  Without pitch it is a timbre control on its own (voice size).  An index whose fraction is 1 / 1 (or None)
+passes the stage bit for bit; a fraction outside [1/2, 2] is refused at construction, naming both arguments.  Chunk-continuous: per
+sample, what reaches the next stage equals Engine.formant_warp() of what the stages in front deliver, as many samples, bit for bit.  A
+sample holds back at most 1023 more input samples (42.6 ms, more than the tempo stage's 640) until its next chunk: a put that completes
+no block of 256 delivers nothing for that row.  A gain of up to +30 dB per bin can pass full scale, so, as with loudness_lufs, such a
+streamer always has a level stage behind it (ceiling -1 dB unless ceiling_db is given): no delivered sample exceeds the ceiling, and
+under pcm16 the per-chunk rescale of the 16-bit rule never fires.  Device chunks need an engine (as above), CPU chunks go through
+formant.HostFormant.
 
 `volume_db=V` (a float in [-40, +24], or one per sample index) and `ceiling_db=C` (in [-20, 0]) set the output level: a gain and a
 look-ahead peak limiter (Engine.level, csrc/level.hip; vibevoice_amd/level.py is the definition), the last stage, at the delivered rate.
@@ -55,7 +68,7 @@ full scale, so such a streamer always has a level stage behind it (ceiling -1 dB
 exceeds the ceiling.  Chunk-continuous: per sample, what reaches the next stage equals Engine.apply_loudness() of the concatenated
 input, bit for bit.  Device chunks need an engine (as above), CPU chunks go through loudness.HostLoudness.
 
-The device stages form one chain (self._stages, _put_device): the leveller, the tempo change, the pitch resampler, the rate resampler, the level, whichever exist, each an engine
+The device stages form one chain (self._stages, _put_device): the leveller, the tempo change, the formant warp, the pitch resampler, the rate resampler, the level, whichever exist, each an engine
 row stage (engine._RowStage) pushed on the producing stream; the last one writes the ring slot's staging, as int16 under pcm16 (over
 each row's own chunk), and with no stage the 16-bit conversion does, else the chunk itself is copied.  A chunk longer than one push of
 a stage takes (stage.take()) is pushed in pieces and arrives as several.
@@ -143,6 +156,22 @@ def _pitch_of(pitch, speed, batch_size):
     return semis, [tempo_speed(v, s) for v, s in zip(speeds, semis)]    # refuses a combined speed outside [0.5, 2.0], naming both
 
 
+def _formant_of(formant, pitch, batch_size):
+    """AudioStreamer's formant argument as the warp (A, B) of each sample index, ratio(formant) * Q / P reduced ((1, 1) where the index
+    has None); None where it asks for no stage (absent, or every index at 1 / 1)"""
+    if formant is None:
+        return None
+    from .formant import fraction
+    shifts = [formant] * batch_size if not hasattr(formant, "__len__") else list(formant)
+    if len(shifts) != batch_size:
+        raise ValueError(f"AudioStreamer(formant=...): one value (or None), or one per sample index ({batch_size}), got {len(shifts)}")
+    semis = [None] * batch_size if pitch is None else ([float(pitch)] * batch_size if not hasattr(pitch, "__len__") else [float(v) for v in pitch])
+    if len(semis) != batch_size:
+        raise ValueError(f"AudioStreamer(pitch=...): one value, or one per sample index ({batch_size}), got {len(semis)}")
+    ab = [(1, 1) if f is None else fraction(float(f), s) for f, s in zip(shifts, semis)]   # refuses a warp outside [1/2, 2], naming both
+    return None if all(a == b for a, b in ab) else ab
+
+
 def _volumes_of(volume_db, ceiling_db, batch_size):
     """AudioStreamer's level arguments as (one volume in dB per sample index, the ceiling in dB); None where they ask for no level
     stage (no ceiling, and no volume or 0 dB everywhere)"""
@@ -186,14 +215,17 @@ def _loudness_of(loudness_lufs, loudness_start_db, max_boost_db, batch_size):
 class AudioStreamer:
     def __init__(self, batch_size: int, stop_signal=None, timeout: Optional[float] = None, ring_slots: int = 8, pcm16=None,
                  sample_rate: Optional[int] = None, engine=None, speed=None, volume_db=None, ceiling_db=None, loudness_lufs=None,
-                 loudness_start_db=None, max_boost_db=None, pitch=None):
+                 loudness_start_db=None, max_boost_db=None, pitch=None, formant=None):
         self.batch_size = batch_size
         self._loud = _loudness_of(loudness_lufs, loudness_start_db, max_boost_db, batch_size)   # (targets, start gains, bounds) or None
         self._ld = None                            # Engine.loudness (device chunks), one stream per sample index
         self._ld_host = {}                         # sample index -> loudness.HostLoudness (CPU chunks)
-        if self._loud is not None and ceiling_db is None:
+        self._formant = _formant_of(formant, pitch, batch_size)   # the warp (A, B) of each sample index, or None: no formant stage
+        self._fm = None                            # Engine.formant (device chunks), one stream per sample index
+        self._fm_host = {}                         # sample index -> formant.HostFormant (CPU chunks)
+        if (self._loud is not None or self._formant is not None) and ceiling_db is None:
             from .level import DEFAULT_CEILING_DB
-            ceiling_db = DEFAULT_CEILING_DB        # a boost can pass full scale: the leveller is always followed by the limiter
+            ceiling_db = DEFAULT_CEILING_DB        # a boost can pass full scale: the leveller and the warp are always followed by the limiter
         self._level = _volumes_of(volume_db, ceiling_db, batch_size)    # (volumes in dB, one per sample index; ceiling in dB), or None
         self._lv = None                            # Engine.level (device chunks), one stream per sample index
         self._lv_host = {}                         # sample index -> level.HostLevel (CPU chunks)
@@ -225,6 +257,10 @@ class AudioStreamer:
             eng = engine if engine is not None else pcm16
             if eng is not None:
                 self._tp = eng.tempo(batch_size)
+        if self._formant is not None:
+            eng = engine if engine is not None else pcm16
+            if eng is not None:
+                self._fm = eng.formant(batch_size)
         if self._pitch is not None:
             eng = engine if engine is not None else pcm16
             if eng is not None:
@@ -234,7 +270,7 @@ class AudioStreamer:
             if eng is not None:
                 self._lv = eng.level(batch_size, rate=self.sample_rate, ceiling_db=self._level[1])
         # the device stages between a chunk and the ring, in the order they run; a further stage takes its place in this list
-        self._stages = [st for st in (self._ld, self._tp, self._pt, self._rs, self._lv) if st is not None]
+        self._stages = [st for st in (self._ld, self._tp, self._fm, self._pt, self._rs, self._lv) if st is not None]
         self.stop_signal = stop_signal
         self.timeout = timeout
         self.audio_queues = [self._make_queue() for _ in range(batch_size)]
@@ -280,6 +316,9 @@ class AudioStreamer:
         if self.sample_rate != SOURCE_RATE and self._rs is None:
             raise ValueError(f"AudioStreamer(sample_rate={self.sample_rate}): device chunks are resampled on the device and need an engine "
                              "(pcm16=engine for 16-bit chunks, engine=engine for float chunks)")
+        if self._formant is not None and self._fm is None:
+            raise ValueError("AudioStreamer(formant=...): device chunks are warped on the device and need an engine "
+                             "(pcm16=engine for 16-bit chunks, engine=engine for float chunks)")
         if self._pitch is not None and self._pt is None:
             raise ValueError("AudioStreamer(pitch=...): device chunks are shifted on the device and need an engine "
                              "(pcm16=engine for 16-bit chunks, engine=engine for float chunks)")
@@ -315,6 +354,14 @@ class AudioStreamer:
                 t = self._tp_host[idx] = HostTempo(self._speeds[idx])
             if t is not None:
                 y = t.flush() if flush else t.push(y)
+        if self._formant is not None:
+            from .formant import HostFormant
+            fm = self._fm_host.get(idx)
+            if fm is None:
+                if y is None:
+                    return None
+                fm = self._fm_host[idx] = HostFormant(*self._formant[idx])
+            y = fm.push(y if y is not None else torch.zeros(0), flush=flush)
         if self._pitch is not None:
             from .pitch import HostPitch
             p = self._pt_host.get(idx)
@@ -389,6 +436,8 @@ class AudioStreamer:
         tk = {}
         if stage is self._pt:
             kw = tk = {"semitones": [self._pitch[idx] for idx in ids]}
+        if stage is self._fm:
+            kw = {"fractions": [self._formant[idx] for idx in ids]}
         if stage is self._lv:
             kw = {"volumes_db": [self._level[0][idx] for idx in ids]}
         if stage is self._ld:
@@ -556,6 +605,8 @@ class AudioStreamer:
                 self._tp.close()                         # ... and its tempo configuration
             if self._pt is not None:
                 self._pt.close()                         # ... and its pitch configuration
+            if self._fm is not None:
+                self._fm.close()                         # ... and its formant configuration
             if self._lv is not None:
                 self._lv.close()                         # ... and its level configuration
             if self._ld is not None:
@@ -625,11 +676,11 @@ class AsyncAudioStreamer(AudioStreamer):
 
     def __init__(self, batch_size: int, stop_signal=None, timeout: Optional[float] = None, ring_slots: int = 8, pcm16=None,
                  sample_rate: Optional[int] = None, engine=None, speed=None, volume_db=None, ceiling_db=None, loudness_lufs=None,
-                 loudness_start_db=None, max_boost_db=None, pitch=None):
+                 loudness_start_db=None, max_boost_db=None, pitch=None, formant=None):
         self.loop = asyncio.get_running_loop()
         super().__init__(batch_size, stop_signal, timeout, ring_slots=ring_slots, pcm16=pcm16, sample_rate=sample_rate, engine=engine,
                          speed=speed, volume_db=volume_db, ceiling_db=ceiling_db, loudness_lufs=loudness_lufs,
-                         loudness_start_db=loudness_start_db, max_boost_db=max_boost_db, pitch=pitch)
+                         loudness_start_db=loudness_start_db, max_boost_db=max_boost_db, pitch=pitch, formant=formant)
 
     def _make_queue(self):
         return asyncio.Queue()
