@@ -450,6 +450,39 @@ int vv_loud_energy(vv_ctx* ctx, void* stream, const double* taps_dev, int n, int
  * call leaves there.  Bit-identical to the same signal pushed through vv_loud_rows. */
 int vv_loud_once(vv_ctx* ctx, void* stream, const double* taps_dev, float t, float g0, float wmax, int n, int n_in, const float* audio_dev,
                  int ld_in, float* out_dev, int ld_out, float* gain_dev, int ld_gain, long long* energies_dev, int ld_e);
+/* ---- pauses: cap the silences of a stream and trim its lead-in, the last stage, at the delivered rate (vibevoice_amd/pause.py defines
+ * it).  seg = rate / 100 samples a segment (80 .. 480).  q = clamp(rint(fl(x 32768)), +-32768), non-finite x: 0; E = sum of q^2 over
+ * the segment (64-bit); the segment is quiet iff E < theta.  A cap is C segments (2^31 - 1: none): C0 for the quiet run in front of the
+ * stream's first loud segment, C for every run behind it.  With the cap in force, T = min(C / 2, 10), H = C - T: the first H segments
+ * of a quiet run go out as they arrive; from segment H + 1 on the stream holds the last T back and keeps a copy of segment H + 1
+ * (`first`); the next loud segment, or the flush, releases them: verbatim where the run had R <= C segments (a stream with no run above
+ * its cap passes bit for bit), else (R - C) seg samples are dropped and the oldest held segment b goes out joined,
+ * fl(fl(first[j] u[j]) + fl(b[j] w[j])), w[j] = fl32((j + 0.5) / seg), u[j] = fl32(1 - (j + 0.5) / seg), the rest verbatim.  Samples
+ * short of a segment wait for the next push; the flush releases what is held, then emits them.  What a stream emits does not depend on
+ * how its input was cut into pushes; how much a push emits depends on the data, at most n_in + (seg - 1) + 10 seg.
+ * vv_pause_set: configuration ps (0..3) of this context: seg in [80,480], weights_host [2][seg] = w, u, n_streams streams at their first
+ * sample.  Replaces what ps held.  Synchronous. */
+int vv_pause_set(vv_ctx* ctx, int ps, int seg, const float* weights_host, int n_streams, void* stream);
+/* Back to the state after vv_pause_set for n streams (stream_ids_host == NULL: all of them): counters zeroed by a kernel on `stream`
+ * (nothing held, no open run, totals 0), input total 0, parameters and flush mark cleared. */
+int vv_pause_reset(vv_ctx* ctx, void* stream, int ps, int n, const int* stream_ids_host);
+/* One push of n <= 16 rows, ONE launch on `stream`, one workgroup per row: row i = n_in <= 7680 samples at audio_dev + i * ld_in for
+ * stream rows_host[i].stream (distinct) with seg (the configuration's), C, C0 >= 0 and theta >= 0 (a stream keeps the parameters of its
+ * first push until its reset), flush != 0: the stream's last push.  Its outputs go to out_dev + i * ld_out (elements): out_fmt 0 =
+ * fp32, 1 = int16 with the arithmetic of vv_audio_to_pcm16 over the row's own emitted samples.  n_out_dev [n], int32 in DEVICE memory:
+ * what each row emitted, written by the launch; the host does not know it.  Refused with a message, nothing written, no state changed:
+ * as vv_resample_rows, a stream whose parameters change, a row of more than 7680 samples, and ld_out < n_in + (seg - 1) + 10 seg. */
+typedef struct vv_pause_row { int stream; int n_in; int flush; int seg; int C; int C0; long long theta; } vv_pause_row;
+int vv_pause_rows(vv_ctx* ctx, void* stream, int ps, int n, const vv_pause_row* rows_host, const float* audio_dev, int ld_in, void* out_dev,
+                  int ld_out, int out_fmt, int* n_out_dev);
+/* totals_host [n][3]: the samples streams stream_ids_host[i] have taken, emitted and dropped.  Waits for `stream`. */
+int vv_pause_totals(vv_ctx* ctx, void* stream, int ps, int n, const int* stream_ids_host, long long* totals_host);
+/* Stateless: n whole signals of n_in samples (audio_dev + i * ld_in) -> at most n_in fp32 samples each (out_dev + i * ld_out);
+ * weights_dev [2][seg] on the device; scratch_dev: scratch_floats fp32 on the device, at least n * 5760; counts_dev [n][2], int32 on the
+ * device: what each signal emitted and what it dropped (their sum is n_in).  Bit-identical to the same signal pushed and flushed
+ * through vv_pause_rows. */
+int vv_pause_once(vv_ctx* ctx, void* stream, const float* weights_dev, int seg, int C, int C0, long long theta, int n, int n_in,
+                  const float* audio_dev, int ld_in, float* out_dev, int ld_out, float* scratch_dev, long long scratch_floats, int* counts_dev);
 /* acoustic_cache.set_to_zero + semantic_cache.set_to_zero for a slot (:542-546) */
 int vv_codec_reset(vv_ctx* ctx, void* stream, int slot);
 /* acoustic_connector(latent) [+ semantic_connector(sem)] (:667-669, :161); sem_dev may be NULL */

@@ -93,6 +93,12 @@ class VVLoudRow(C.Structure):
     _fields_ = [("stream", C.c_int), ("n_in", C.c_int), ("flush", C.c_int), ("t", C.c_float), ("g0", C.c_float), ("wmax", C.c_float)]
 
 
+class VVPauseRow(C.Structure):
+    """vv_pause_row (include/vvhip.h): the stream, the input samples, the flush mark, seg, the caps C, C0 and theta of one row of vv_pause_rows"""
+    _fields_ = [("stream", C.c_int), ("n_in", C.c_int), ("flush", C.c_int), ("seg", C.c_int), ("C", C.c_int), ("C0", C.c_int),
+                ("theta", C.c_longlong)]
+
+
 GEMV_REFUSED = 1     # VV_GEMV_REFUSED
 TEMPO_OVER_CAPACITY = 3     # VV_TEMPO_OVER_CAPACITY
 _SIGS = {
@@ -163,6 +169,12 @@ _SIGS = {
     "vv_loud_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(VVLoudRow), _P, C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "vv_loud_energy": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, _P, C.c_int]),
     "vv_loud_once": (C.c_int, [_P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, _P, C.c_int, _P, C.c_int]),
+    "vv_pause_set": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "vv_pause_reset": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "vv_pause_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(VVPauseRow), _P, C.c_int, _P, C.c_int, C.c_int, _P]),
+    "vv_pause_totals": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
+    "vv_pause_once": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, _P, C.c_longlong,
+                                _P]),
     "vv_codec_reset": (C.c_int, [_P, _P, C.c_int]),
     "vv_connect": (C.c_int, [_P, _P, C.c_int, _P, _P, _P]),
     "vv_packed_bytes": (C.c_int64, [C.c_int, C.c_int]),

@@ -10,7 +10,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvvhip.so")
-SOURCES = ["gemm.hip", "gemv.hip", "w13.hip", "gemv16p.hip", "headtail.hip", "solver.hip", "tile.hip", "prefill.hip", "attn.hip", "misc.hip", "warp.hip", "noise.hip", "kvspan.hip", "block1d.hip", "lora.hip", "resample.hip", "tempo.hip", "pitch.hip", "formant.hip", "level.hip", "loudness.hip", "engine.hip",
+SOURCES = ["gemm.hip", "gemv.hip", "w13.hip", "gemv16p.hip", "headtail.hip", "solver.hip", "tile.hip", "prefill.hip", "attn.hip", "misc.hip", "warp.hip", "noise.hip", "kvspan.hip", "block1d.hip", "lora.hip", "resample.hip", "tempo.hip", "pitch.hip", "formant.hip", "level.hip", "loudness.hip", "pause.hip", "engine.hip",
            "engine_lm.hip", "engine_head.hip", "engine_codec.hip", "engine_prof.hip", "engine_lora.hip"]
 HEADERS = [os.path.join(CSRC, "vv_common.h"), os.path.join(CSRC, "vv_device.h"), os.path.join(CSRC, "vv_launch.h"), os.path.join(CSRC, "gemv_plan.h"), os.path.join(CSRC, "vv_w13.h"),
            os.path.join(CSRC, "prefill_plan.h"), os.path.join(CSRC, "pass_plan.h"), os.path.join(CSRC, "engine_ctx.h"),

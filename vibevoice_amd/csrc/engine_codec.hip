@@ -1125,3 +1125,109 @@ extern "C" int vv_loud_once(vv_ctx* ctx, void* stream, const double* taps_dev, f
     VVCHK(vv_loud_once_launch(taps_dev, t, g0, wmax, n, n_in, audio_dev, ld_in, out_dev, ld_out, gain_dev, ld_gain, energies_dev, ld_e, (hipStream_t)stream));
     return 0;
 }
+
+// ------------------------------------------------------------------ pauses (kernels: pause.hip; vibevoice_amd/pause.py defines them)
+// The one stage whose counts the host does not know: what a push emits depends on the data, the kernel writes it to device memory.  The
+// host still keeps each stream's input total (the open segment's samples are total % seg) and its parameters.
+extern "C" int vv_pause_set(vv_ctx* ctx, int ps, int seg, const float* weights_host, int n_streams, void* stream) {
+    VV_SHARED;
+    if (ps < 0 || ps >= vv_ctx::N_PAUSES) return fail(ctx, "vv_pause_set: configuration %d out of range [0,%d)", ps, vv_ctx::N_PAUSES);
+    if (seg < VV_PS_MIN_SEG || seg > VV_PS_MAX_SEG) return fail(ctx, "vv_pause_set: seg = %d must be in [%d,%d] (8 to 48 kHz)", seg, VV_PS_MIN_SEG, VV_PS_MAX_SEG);
+    if (n_streams < 1 || n_streams > 65536) return fail(ctx, "vv_pause_set: n_streams = %d must be in [1,65536]", n_streams);
+    if (!weights_host) return fail(ctx, "vv_pause_set: null weight table");
+    vv_ctx::Pause& p = ctx->ps[ps];
+    HIPCHK(ctx, hipStreamSynchronize((hipStream_t)stream));      // pushes that still read what is replaced
+    dfree(ctx, p.wt); dfree(ctx, p.sbuf); dfree(ctx, p.state);
+    p = vv_ctx::Pause();
+    float* wt = (float*)dalloc(ctx, (size_t)2 * seg * 4, false);
+    float* sbuf = (float*)dalloc(ctx, (size_t)n_streams * VV_PS_FLOATS * 4, true);
+    VVPsState* state = (VVPsState*)dalloc(ctx, (size_t)n_streams * sizeof(VVPsState), true);
+    if (!wt || !sbuf || !state || hipMemcpy(wt, weights_host, (size_t)2 * seg * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        dfree(ctx, wt); dfree(ctx, sbuf); dfree(ctx, state);
+        return fail(ctx, "vv_pause_set: allocating the state or uploading the weights failed");
+    }
+    p.seg = seg; p.n_streams = n_streams; p.wt = wt; p.sbuf = sbuf; p.state = state;
+    p.total.assign(n_streams, 0); p.flushed.assign(n_streams, 0);
+    p.C.assign(n_streams, 0); p.C0.assign(n_streams, 0); p.theta.assign(n_streams, -1);
+    return 0;
+}
+
+extern "C" int vv_pause_reset(vv_ctx* ctx, void* stream, int ps, int n, const int* stream_ids_host) {
+    VV_SHARED;
+    vv_ctx::Pause* p = ps >= 0 && ps < vv_ctx::N_PAUSES && ctx->ps[ps].state ? &ctx->ps[ps] : nullptr;
+    return stage_reset(ctx, "vv_pause_reset", p, ps, n, stream_ids_host,
+                       [&](const int* ids, int k) { return vv_pause_reset_launch(p->state, p->n_streams, ids, k, (hipStream_t)stream); },
+                       [&](int id) { p->theta[id] = -1; });
+}
+
+extern "C" int vv_pause_rows(vv_ctx* ctx, void* stream, int ps, int n, const vv_pause_row* rows_host, const float* audio_dev, int ld_in,
+                             void* out_dev, int ld_out, int out_fmt, int* n_out_dev) {
+    VV_SHARED;
+    vv_ctx::Pause* pp = ps >= 0 && ps < vv_ctx::N_PAUSES && ctx->ps[ps].state ? &ctx->ps[ps] : nullptr;
+    const RowCheck ck{ctx, "vv_pause_rows", pp, audio_dev, ld_in};
+    VVTRY(ck.head(ps, n, rows_host, out_dev, n_out_dev, out_fmt));
+    vv_ctx::Pause& p = *pp;
+    VVPsRows kr;
+    memset(&kr, 0, sizeof(kr));
+    for (int i = 0; i < n; ++i) {
+        const vv_pause_row& q = rows_host[i];
+        VVTRY(ck.stream(rows_host, i));
+        VVTRY(ck.input(i, q.n_in));
+        if (q.n_in > VV_PS_MAX_IN)
+            return fail(ctx, "vv_pause_rows: row %d brings %d samples, one push takes at most %d per row; push it in pieces", i, q.n_in, VV_PS_MAX_IN);
+        if (q.seg != p.seg) return fail(ctx, "vv_pause_rows: row %d: seg = %d, the configuration was set for %d", i, q.seg, p.seg);
+        if (!vv_ps_params_ok(q.seg, q.C, q.C0, q.theta))
+            return fail(ctx, "vv_pause_rows: row %d: C = %d, C0 = %d and theta = %lld must be >= 0", i, q.C, q.C0, q.theta);
+        if (p.theta[q.stream] >= 0 && (p.theta[q.stream] != q.theta || p.C[q.stream] != q.C || p.C0[q.stream] != q.C0))
+            return fail(ctx, "vv_pause_rows: stream %d runs at C = %d, C0 = %d, theta = %lld since its first push; reset it before they change", q.stream,
+                        p.C[q.stream], p.C0[q.stream], p.theta[q.stream]);
+        VVTRY(ck.open(q.stream));
+        const int64_t most = (int64_t)q.n_in + (p.seg - 1) + (int64_t)VV_PS_MAX_T * p.seg;
+        if (most > ld_out) return fail(ctx, "vv_pause_rows: row %d may emit %lld samples, the output rows hold %d", i, (long long)most, ld_out);
+        VVPsRow& k = kr.r[i];
+        k.stream = q.stream; k.n_in = q.n_in; k.flush = q.flush != 0; k.carry = (int)(p.total[q.stream] % p.seg);
+        k.seg = q.seg; k.C = q.C; k.C0 = q.C0; k.theta = q.theta;
+    }
+    for (int i = n; i < 16; ++i) kr.r[i] = kr.r[0];
+    VVCHK(vv_pause_rows_launch(&kr, n, p.seg, p.sbuf, p.state, p.n_streams, p.wt, audio_dev, ld_in, out_dev, ld_out, out_fmt, n_out_dev, (hipStream_t)stream));
+    for (int i = 0; i < n; ++i) {
+        const vv_pause_row& q = rows_host[i];
+        p.total[q.stream] += q.n_in;
+        if (q.flush) p.flushed[q.stream] = 1;
+        p.C[q.stream] = q.C; p.C0[q.stream] = q.C0; p.theta[q.stream] = q.theta;
+    }
+    return 0;
+}
+
+extern "C" int vv_pause_totals(vv_ctx* ctx, void* stream, int ps, int n, const int* stream_ids_host, long long* totals_host) {
+    VV_SHARED;
+    vv_ctx::Pause* p = ps >= 0 && ps < vv_ctx::N_PAUSES && ctx->ps[ps].state ? &ctx->ps[ps] : nullptr;
+    if (!p) return fail(ctx, "vv_pause_totals: configuration %d is not set", ps);
+    if (n < 1 || !stream_ids_host || !totals_host) return fail(ctx, "vv_pause_totals: n = %d must be >= 1, with ids and totals", n);
+    for (int i = 0; i < n; ++i)
+        if (stream_ids_host[i] < 0 || stream_ids_host[i] >= p->n_streams)
+            return fail(ctx, "vv_pause_totals: stream id %d out of range [0,%d)", stream_ids_host[i], p->n_streams);
+    std::vector<VVPsState> h(p->n_streams);
+    HIPCHK(ctx, hipMemcpyAsync(h.data(), p->state, h.size() * sizeof(VVPsState), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(ctx, hipStreamSynchronize((hipStream_t)stream));
+    for (int i = 0; i < n; ++i) {
+        const VVPsState& s = h[stream_ids_host[i]];
+        totals_host[3 * i] = s.tin; totals_host[3 * i + 1] = s.tout; totals_host[3 * i + 2] = s.dropped;
+    }
+    return 0;
+}
+
+extern "C" int vv_pause_once(vv_ctx* ctx, void* stream, const float* weights_dev, int seg, int C, int C0, long long theta, int n, int n_in,
+                             const float* audio_dev, int ld_in, float* out_dev, int ld_out, float* scratch_dev, long long scratch_floats,
+                             int* counts_dev) {
+    VV_SHARED;
+    if (!vv_ps_params_ok(seg, C, C0, theta))
+        return fail(ctx, "vv_pause_once: seg = %d must be in [%d,%d], C = %d, C0 = %d and theta = %lld >= 0", seg, VV_PS_MIN_SEG, VV_PS_MAX_SEG, C, C0, theta);
+    if (n < 1 || n > 65535 || n_in < 1 || n_in > ld_in) return fail(ctx, "vv_pause_once: n = %d in [1,65535], n_in = %d in [1, ld_in = %d]", n, n_in, ld_in);
+    if (n_in > ld_out) return fail(ctx, "vv_pause_once: up to %d output samples per row, the output rows hold %d", n_in, ld_out);
+    if (!weights_dev || !audio_dev || !out_dev || !scratch_dev || !counts_dev) return fail(ctx, "vv_pause_once: null weights / audio / out / scratch / counts pointer");
+    if (scratch_floats < (long long)n * VV_PS_ONCE_FLOATS)
+        return fail(ctx, "vv_pause_once: the scratch holds %lld floats, %d signals need %lld", scratch_floats, n, (long long)n * VV_PS_ONCE_FLOATS);
+    VVCHK(vv_pause_once_launch(seg, C, C0, theta, weights_dev, n, n_in, audio_dev, ld_in, out_dev, ld_out, scratch_dev, counts_dev, (hipStream_t)stream));
+    return 0;
+}

@@ -225,6 +225,13 @@ struct vv_ctx {
                              std::vector<float> t, g0, wmax; };
     static constexpr int N_LOUDS = 4;
     Loud loud[N_LOUDS];
+    // streaming pause shorteners (vv_pause_set, engine_codec.hip; kernels: pause.hip): seg samples a segment, the join's weights, per stream
+    // VV_PS_FLOATS samples and a VVPsState on the device, and on the host its caps and threshold (fixed by its first push, theta = -1
+    // before).  Kept like the resamplers.
+    struct Pause : RowStage { int seg = 0; float* wt = nullptr; float* sbuf = nullptr; VVPsState* state = nullptr;
+                              std::vector<int> C, C0; std::vector<long long> theta; };
+    static constexpr int N_PAUSES = 4;
+    Pause ps[N_PAUSES];
     int64_t launches = 0;
     int64_t solver_fused = 0;         // general-path step ends that carried the next in-projection, last recorded body (vv_stat 8)
     int64_t seam_launches = 0;        // head-tail seam launches the last recorded sampler body issued (vv_stat 6; a replay keeps its capture's count)

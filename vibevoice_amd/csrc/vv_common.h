@@ -265,6 +265,30 @@ static inline bool vv_ld_params_ok(float t, float g0, float wmax) {
     return t > 0.f && t < 1.0f && g0 > 0.f && g0 <= 16.0f && wmax >= 1.0f && wmax <= 16.0f;
 }
 
+// ---- streaming pause shortener (pause.hip): one row of a push, passed by value in the kernel arguments ----
+// The host keeps each stream's 64-bit input total and its parameters; of the total the kernel needs carry = total % seg, the samples of
+// the stream's open segment that wait in its state.  What a row emits depends on the data: the kernel counts it (VVPsState, and the
+// launch's count word), the host does not know it.  seg = rate / 100 samples a segment, C / C0 the caps in segments (2^31 - 1: none),
+// theta the integer a segment's energy is compared with.
+struct VVPsRow { int stream, n_in, flush, carry, seg, C, C0, pad; long long theta; };
+struct VVPsRows { VVPsRow r[16]; };
+constexpr int VV_PS_MIN_SEG = 80;          // 8 kHz
+constexpr int VV_PS_MAX_SEG = 480;         // 48 kHz
+constexpr int VV_PS_MAX_T = 10;            // segments a stream holds back at most (vibevoice_amd/pause.py: MAX_T)
+constexpr int VV_PS_MAX_IN = 7680;         // input samples one row of a push may bring (pause.py: MAX_IN)
+constexpr int VV_PS_MAX_SEGS = (VV_PS_MAX_IN + VV_PS_MIN_SEG - 1) / VV_PS_MIN_SEG;     // whole segments a push completes at most: 96
+// what a stream keeps on the device: VV_PS_FLOATS samples [open segment, < seg | ring: held segments of seg samples, oldest first |
+// first, seg], each part at its VV_PS_*_AT, and its counters: the samples taken, emitted and dropped, the open quiet run's length in
+// segments, whether a loud segment has arrived, and the segments held
+constexpr int VV_PS_RING_AT = VV_PS_MAX_SEG, VV_PS_FIRST_AT = VV_PS_RING_AT + VV_PS_MAX_T * VV_PS_MAX_SEG;
+constexpr int VV_PS_FLOATS = VV_PS_FIRST_AT + VV_PS_MAX_SEG;
+struct VVPsState { long long tin, tout, dropped; int run, started, held, pad; };
+// scratch of one signal of vv_pause_once, in floats: the stream's samples and room for nothing else (its counters live in LDS)
+constexpr int VV_PS_ONCE_FLOATS = VV_PS_FLOATS;
+static inline bool vv_ps_params_ok(int seg, int C, int C0, long long theta) {
+    return seg >= VV_PS_MIN_SEG && seg <= VV_PS_MAX_SEG && C >= 0 && C0 >= 0 && theta >= 0;
+}
+
 // Raise the dynamic-LDS limit of one or more kernels above the 64 KiB default; returns the first error.  A launcher calls it as
 // the initialiser of a function-local `static const hipError_t`: C++11 runs that initialiser once per process and makes
 // concurrent first calls wait for it (generate_interleaved and fork() drive two contexts from two host threads).

@@ -152,4 +152,12 @@ int vv_loud_energy_launch(const double* taps, int n, int n_in, const float* x, i
 int vv_loud_once_launch(const double* taps, float t, float g0, float wmax, int n, int n_in, const float* x, int ld_in, float* out, int ld_out,
                         float* gain, int ld_gain, long long* E, int ld_e, hipStream_t s);
 int vv_loud_reset_launch(int* hist, VVLdState* state, int n_streams, const int* ids, int n, hipStream_t s);
+// pause.hip.  seg samples a segment; sbuf [n_streams][VV_PS_FLOATS] each stream's open segment, ring and `first`, state [n_streams] its counters;
+// wt [2][seg] the join's weights w, u; counts [n] (device): what each row emitted.  _once: scratch [n][VV_PS_ONCE_FLOATS], counts [n][2]
+// (device): what each signal emitted and dropped.
+int vv_pause_rows_launch(const VVPsRows* rows, int n, int seg, float* sbuf, VVPsState* state, int n_streams, const float* wt, const float* x,
+                         int ld_in, void* out, int ld_out, int pcm16, int* counts, hipStream_t s);
+int vv_pause_once_launch(int seg, int C, int C0, long long theta, const float* wt, int n, int n_in, const float* x, int ld_in, float* out,
+                         int ld_out, float* scratch, int* counts, hipStream_t s);
+int vv_pause_reset_launch(VVPsState* state, int n_streams, const int* ids, int n, hipStream_t s);
 }

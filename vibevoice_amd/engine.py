@@ -535,7 +535,8 @@ class Engine:
                   "vv_audio_to_pcm16")
 
     # ------------------------------------------------------------------ streaming row stages and their whole-signal forms
-    _STAGE_USED = {"resampler": "_rs_used", "tempo": "_tp_used", "pitch": "_pt_used", "formant": "_fm_used", "level": "_lv_used", "loudness": "_ld_used"}
+    _STAGE_USED = {"resampler": "_rs_used", "tempo": "_tp_used", "pitch": "_pt_used", "formant": "_fm_used", "level": "_lv_used", "loudness": "_ld_used",
+                   "pause": "_ps_used"}
 
     def _take_stage_slot(self, kind, make):
         """make(k) for the first free k of this engine's four `kind` configurations; the stage's close() gives k back"""
@@ -800,6 +801,48 @@ class Engine:
             return out
         g = torch.cat(gains) if gains else torch.empty((0, n_out), dtype=torch.float32, device=self.device)
         return out, g.reshape(out.shape)
+
+    # pauses (pause.py, csrc/pause.hip)
+    def pause(self, n_streams: int, rate: int = 24000) -> "Pause":
+        """A streaming pause shortener at `rate` Hz (8000 .. 48000) with n_streams independent streams, each with its own caps and
+        threshold, in one of this engine's four pause configurations (close() it to give the configuration back)."""
+        return self._take_stage_slot("pause", lambda k: Pause(self, k, n_streams, rate))
+
+    def _pause_weights(self, rate):
+        from . import pause as _ps
+        cache = self.__dict__.setdefault("_ps_weights", {})
+        wt = cache.get(int(rate))
+        if wt is None:
+            wt = cache[int(rate)] = torch.from_numpy(np.concatenate(_ps.weights(rate))).to(self.device)
+        return wt
+
+    def shorten_pauses(self, audio: torch.Tensor, max_pause_ms=None, max_lead_ms=None, threshold_db: float = -50.0, rate: int = 24000,
+                       stream=None):
+        """Whole signals with their silences capped: audio [samples] or [n, samples] (at `rate` Hz, any float dtype, any device) ->
+        (a list of 1-D fp32 tensors on the engine's device, one per signal and of its own length, and the samples each dropped, a list
+        of ints): quiet runs (10 ms segments below threshold_db, -80 .. -20) longer than max_pause_ms (100 .. 5000; None: no cap) keep
+        their beginning and their end around a 10 ms cross-fade, the run in front of the first loud segment is capped at max_lead_ms
+        (0 .. 5000; None: max_pause_ms applies): the definition of vibevoice_amd/pause.py, bit for bit.  A signal with no run above its
+        cap comes back as it is.  Stateless; runs on `stream` (default: the device's current torch stream) and waits for it: the
+        lengths depend on the data."""
+        from . import pause as _ps
+        seg, th = _ps.seg_of(rate), _ps.theta(rate, threshold_db)
+        Cc, C0 = _ps.caps(rate, max_pause_ms, max_lead_ms)
+        n_out = int(audio.shape[-1]) if audio.dim() else 0
+        ts = stream if stream is not None else torch.cuda.current_stream(self.device)
+
+        def run(st, nn, n_in, x, out, aux):
+            with torch.cuda.stream(ts):                        # the streams' samples during the launch: this stream's
+                scratch = torch.empty(nn * _ps.STATE_FLOATS, dtype=torch.float32, device=self.device)
+            self._chk(self.lib.vv_pause_once(self._ctx, st, self._p(self._pause_weights(rate)), seg, Cc, C0, th, nn, n_in, self._p(x), n_in,
+                                             self._p(out), n_out, self._p(scratch), scratch.numel(), self._p(aux)), "vv_pause_once")
+        out, aux = self._whole("shorten_pauses", audio, n_out, run, ts, aux_cols=2)
+        rows = out.reshape(-1, n_out)
+        if not n_out:
+            return [rows[i] for i in range(rows.shape[0])], [0] * rows.shape[0]
+        ts.synchronize()
+        cnt = aux.cpu().tolist()
+        return [rows[i, :cnt[i][0]] for i in range(rows.shape[0])], [int(c[1]) for c in cnt]
 
     def codec_reset(self, slot: int):
         self._chk(self.lib.vv_codec_reset(self._ctx, self._s, slot), "vv_codec_reset")
@@ -1300,9 +1343,10 @@ class TempoCapacityError(EngineError):
 
 
 class _RowStage:
-    """What the streaming row stages share (Loudness, Tempo, Formant, Pitch, Resampler, Level): n_streams chunk-continuous streams in
-    one of the engine's configurations, pushed up to 16 rows a launch.  A stage supplies KIND (Engine._STAGE_USED), its row struct ROW
-    and how push() fills it, its C entry points ROWS_FN / RESET_FN, counts(), max_out() and take()."""
+    """What the streaming row stages share (Loudness, Tempo, Formant, Pitch, Resampler, Level, Pause): n_streams chunk-continuous streams
+    in one of the engine's configurations, pushed up to 16 rows a launch.  A stage supplies KIND (Engine._STAGE_USED), its row struct ROW
+    and how push() fills it, its C entry points ROWS_FN / RESET_FN, counts(), max_out() and take().  Pause alone has no counts(): what
+    it emits depends on the data, its push() launches itself and returns the counts as a device tensor."""
     KIND = ROW = ROWS_FN = RESET_FN = None
     NO_ROWS = ()                                          # the launches of a push that names no stream
 
@@ -1673,6 +1717,83 @@ class Level(_RowStage):
         for i in range(n):
             rows[i].stream, rows[i].n_in, rows[i].flush, rows[i].gain = ids[i], nin[i], int(fl[i]), gains[i]
         return out, self._launch(audio, samples, ids, nin, rows, out, pcm16, stream)
+
+
+class Pause(_RowStage):
+    """One streaming pause configuration of an engine (Engine.pause): n_streams chunk-continuous streams at `rate` Hz, each with the caps
+    and the threshold of its first push until its reset (which clears them with the rest).  What a stream delivers does not depend on how
+    its input was cut into pushes (vibevoice_amd/pause.py): the concatenation of its pushes and its flush equals pause.shorten() of the
+    concatenated input, bit for bit in float mode.  The one stage whose counts depend on the data: push() returns them as a DEVICE
+    tensor, and total[] counts input samples only.  delay_samples: the input samples (seg - 1, under 10 ms) that wait for their segment
+    to fill; silence, never speech, waits longer (up to ten segments).  max_in: the input samples one row of a push may bring."""
+    KIND, ROW, ROWS_FN, RESET_FN = "pause", _lib.VVPauseRow, "vv_pause_rows", "vv_pause_reset"
+
+    def __init__(self, engine: Engine, slot: int, n_streams: int, rate: int = 24000):
+        from . import pause as _ps
+        super().__init__(engine, slot, n_streams)
+        self.seg, self.rate = _ps.seg_of(rate), int(rate)   # refuses a rate outside 8 .. 48 kHz, by name
+        self.delay_samples, self.max_in = self.seg - 1, _ps.MAX_IN
+        wt = np.ascontiguousarray(np.concatenate(_ps.weights(rate)))
+        engine._chk(engine.lib.vv_pause_set(engine._ctx, slot, self.seg, C.c_void_p(wt.ctypes.data), self.n_streams, engine._s), "vv_pause_set")
+
+    def max_out(self, n_in: int) -> int:
+        """upper bound of what any push of up to n_in samples emits, the flush included: the open segment and ten held ones with it"""
+        from . import pause as _ps
+        return _ps.max_out(n_in, self.rate)
+
+    def take(self, ids, remaining, flush=False):
+        return min(self.max_in, max(remaining))
+
+    def push(self, audio: Optional[torch.Tensor], stream_ids: Sequence[int], max_pause_ms=None, max_lead_ms=None, threshold_db=-50.0,
+             flush=False, out: Optional[torch.Tensor] = None, n_in=None, stream=None, pcm16: bool = False):
+        """Row i of audio [n, samples] (contiguous fp32 on the engine's device; None where no row brings samples) goes to stream
+        stream_ids[i] (distinct) under max_pause_ms[i], max_lead_ms[i] (None: no cap / max_pause_ms applies) and threshold_db[i] (or
+        one value for all rows; a stream keeps the parameters of its first push); n_in: samples of each row that count (default: all),
+        flush: bool or one per row -- a stream's last push, after which it takes no more until reset().  -> (out, counts_dev):
+        out[i, :counts_dev[i]] is what row i emitted, fp32, or int16 under pcm16 (the arithmetic of Engine.audio_to_pcm16 over the
+        row's own emitted samples, in the same launch); counts_dev: int32 [n] on the device, written by the launch -- the host does
+        not know them, and reading them waits for `stream`.  out: a contiguous [>= n, capacity >= max_out(samples)] tensor of that
+        dtype to write into (default: a new one).  One launch per 16 rows on `stream` (default: the device's current torch stream);
+        nothing waits for the device.  A row of more than max_in samples is refused: push it in pieces of take()."""
+        from . import pause as _ps
+        ids, samples, nin, fl, mp, ml, th = self._args(audio, stream_ids, flush, n_in, max_pause_ms=max_pause_ms, max_lead_ms=max_lead_ms,
+                                                       threshold_db=threshold_db)
+        par = [_ps.caps(self.rate, a, b) + (_ps.theta(self.rate, c),) for a, b, c in zip(mp, ml, th)]
+        e, n, out = self.engine, len(ids), self._out(out, len(ids), nin, pcm16)
+        ts = stream if stream is not None else torch.cuda.current_stream(e.device)
+        with torch.cuda.stream(ts):
+            cnts = torch.zeros(max(n, 1), dtype=torch.int32, device=e.device)
+        rows = (self.ROW * max(n, 1))()
+        for i in range(n):
+            rows[i].stream, rows[i].n_in, rows[i].flush, rows[i].seg = ids[i], nin[i], int(fl[i]), self.seg
+            rows[i].C, rows[i].C0, rows[i].theta = par[i]
+        cap = int(out.shape[1])
+        for i0 in range(0, n, 16) or (0,):                   # no rows: one launch, which vv_pause_rows refuses by name
+            nn = min(16, n - i0)
+            a = C.c_void_p(audio.data_ptr() + i0 * samples * 4) if audio is not None else C.c_void_p()
+            o = C.c_void_p(out.data_ptr() + i0 * cap * out.element_size())
+            self._refused(e.lib.vv_pause_rows(e._ctx, e._sp(ts), self.slot, nn, C.cast(C.byref(rows, i0 * C.sizeof(self.ROW)), C.POINTER(self.ROW)),
+                                              a, samples, o, cap, int(pcm16), C.c_void_p(cnts.data_ptr() + i0 * 4)))
+            for i in range(i0, i0 + nn):
+                self.total[ids[i]] += nin[i]
+        return out, cnts[:n]
+
+    def totals(self, ids: Optional[Sequence[int]] = None, stream=None):
+        """(taken, emitted, dropped) samples of streams `ids` (default: all), read from the device: this call WAITS for `stream`
+        (default: the device's current torch stream), the one the pushes ran on"""
+        e = self.engine
+        ids = list(range(self.n_streams)) if ids is None else [int(i) for i in ids]
+        if not ids:
+            return []
+        st = e._sp(stream if stream is not None else torch.cuda.current_stream(e.device))
+        tot = (C.c_longlong * (3 * len(ids)))()
+        e._chk(e.lib.vv_pause_totals(e._ctx, st, self.slot, len(ids), (C.c_int * len(ids))(*ids), tot), "vv_pause_totals")
+        return [(int(tot[3 * i]), int(tot[3 * i + 1]), int(tot[3 * i + 2])) for i in range(len(ids))]
+
+    def dropped(self, ids: Optional[Sequence[int]] = None, stream=None):
+        """the samples streams `ids` (default: all) have dropped so far, a list of ints.  It synchronises: the totals live on the
+        device, this call waits for `stream` (default: the device's current torch stream)."""
+        return [t[2] for t in self.totals(ids, stream)]
 
 
 class Loudness(_RowStage):

@@ -616,6 +616,15 @@ class _AudioRates:
         are wanted, at the rate they deliver.  generate() itself has no level input."""
         return self.engine.apply_level(audio, volume_db, ceiling_db, int(rate))
 
+    def shorten_pauses(self, audio: torch.Tensor, max_pause_ms=None, max_lead_ms=None, threshold_db: float = -50.0, rate: int = 24000):
+        """audio [samples] or [n, samples] at `rate` Hz -> (a list of 1-D fp32 tensors on the engine's device, one per signal; the samples
+        each dropped): silences (10 ms segments below threshold_db, -80 .. -20) longer than max_pause_ms (100 .. 5000) keep their
+        beginning and their end around a 10 ms cross-fade, the lead-in in front of the first loud segment is capped at max_lead_ms
+        (0 .. 5000; None: max_pause_ms applies) (Engine.shorten_pauses).  For speech_outputs after the fact --
+        shorten_pauses(out.speech_outputs[0], 400, 50); the last step, behind apply_level, at the rate that delivers.  It waits for the
+        device: the lengths depend on the data.  generate() itself has no pause input."""
+        return self.engine.shorten_pauses(audio, max_pause_ms, max_lead_ms, threshold_db, int(rate))
+
     def measure_loudness(self, audio: torch.Tensor) -> torch.Tensor:
         """The ITU-R BS.1770-4 loudness in LUFS of audio [samples] or [n, samples] at 24 kHz -> a float64 CPU tensor, one value per row;
         -inf for silence and for less than 400 ms (Engine.measure_loudness).  For speech_outputs, and for a voice sample: its reading

@@ -68,7 +68,21 @@ full scale, so such a streamer always has a level stage behind it (ceiling -1 dB
 exceeds the ceiling.  Chunk-continuous: per sample, what reaches the next stage equals Engine.apply_loudness() of the concatenated
 input, bit for bit.  Device chunks need an engine (as above), CPU chunks go through loudness.HostLoudness.
 
-The device stages form one chain (self._stages, _put_device): the leveller, the tempo change, the formant warp, the pitch resampler, the rate resampler, the level, whichever exist, each an engine
+`max_pause_ms=P` (a float in [100, 5000], or one per sample index, None among them) caps every silence, `max_lead_ms=L` (in [0, 5000],
+likewise) the one in front of a sample's first speech (None there: P applies), `pause_threshold_db` (in [-80, -20], default -50) says
+what counts as silence: 10 ms segments whose energy lies below it (Engine.pause, csrc/pause.hip; vibevoice_amd/pause.py is the
+definition), the last stage, behind the level, at the delivered rate (8 .. 48 kHz), so the caps mean what the listener gets.  A silence
+longer than its cap keeps its beginning and its end around a 10 ms cross-fade; everything else passes bit for bit, an index with neither
+cap included.  The stage exists when either cap is given for any index; the threshold alone is refused; float chunks arrive as fp32.
+Chunk-continuous: per sample, the concatenated chunks equal pause.shorten() of what the stages in front deliver, bit for bit in float
+mode.  Speech waits for its 10 ms segment to fill and no longer; only silence is held back (up to ten segments, released by the next
+speech or by end()).  This is the one stage whose counts depend on the data: the host does not know how much a put delivers.  The launch
+writes each row's count to device memory, the count words ride to a pinned companion of the ring slot on the copy stream in front of the
+event the drain thread waits on anyway, and the thread trims the rows by them: put() still never waits for the device.  A put that
+releases nothing for a row delivers nothing for it; end(indices) flushes this stage last: tempo, formant, pitch, resampler, level, pause.
+Device chunks need an engine (as above), CPU chunks go through pause.HostPause.
+
+The device stages form one chain (self._stages, _put_device): the leveller, the tempo change, the formant warp, the pitch resampler, the rate resampler, the level, the pauses, whichever exist, each an engine
 row stage (engine._RowStage) pushed on the producing stream; the last one writes the ring slot's staging, as int16 under pcm16 (over
 each row's own chunk), and with no stage the 16-bit conversion does, else the chunk itself is copied.  A chunk longer than one push of
 a stage takes (stage.take()) is pushed in pieces and arrives as several.
@@ -212,11 +226,42 @@ def _loudness_of(loudness_lufs, loudness_start_db, max_boost_db, batch_size):
     return tuple(cols)
 
 
+def _pauses_of(max_pause_ms, max_lead_ms, pause_threshold_db, batch_size):
+    """AudioStreamer's pause arguments as (caps in ms, lead caps in ms, thresholds in dB), one per sample index each, None among the
+    caps where an index has none; None where no index has a cap.  The threshold alone is refused."""
+    from .pause import DEFAULT_THRESHOLD_DB, MAX_THRESHOLD_DB, MIN_THRESHOLD_DB, lead_ms_of, pause_ms_of
+    cols = []
+    for name, v, check in (("max_pause_ms", max_pause_ms, pause_ms_of), ("max_lead_ms", max_lead_ms, lead_ms_of)):
+        col = [v] * batch_size if not hasattr(v, "__len__") else list(v)
+        if len(col) != batch_size:
+            raise ValueError(f"AudioStreamer({name}=...): one value (or None), or one per sample index ({batch_size}), got {len(col)}")
+        cols.append([check(u) for u in col])                  # refuses what lies outside the parameter's range, by name
+    if all(u is None for col in cols for u in col):
+        if pause_threshold_db is not None:
+            raise ValueError("AudioStreamer(pause_threshold_db=...) belongs to max_pause_ms=... / max_lead_ms=..., neither of which is given")
+        return None
+    th = [pause_threshold_db] * batch_size if not hasattr(pause_threshold_db, "__len__") else list(pause_threshold_db)
+    if len(th) != batch_size:
+        raise ValueError(f"AudioStreamer(pause_threshold_db=...): one value, or one per sample index ({batch_size}), got {len(th)}")
+    for i, u in enumerate(th):
+        try:
+            th[i] = DEFAULT_THRESHOLD_DB if u is None else float(u)
+        except (TypeError, ValueError):
+            th[i] = float("nan")
+        if not (MIN_THRESHOLD_DB <= th[i] <= MAX_THRESHOLD_DB):   # a NaN compares false
+            raise ValueError(f"AudioStreamer(pause_threshold_db=...) must lie in [{MIN_THRESHOLD_DB:g}, {MAX_THRESHOLD_DB:g}] dB, got {u!r}")
+    return cols[0], cols[1], th
+
+
 class AudioStreamer:
     def __init__(self, batch_size: int, stop_signal=None, timeout: Optional[float] = None, ring_slots: int = 8, pcm16=None,
                  sample_rate: Optional[int] = None, engine=None, speed=None, volume_db=None, ceiling_db=None, loudness_lufs=None,
-                 loudness_start_db=None, max_boost_db=None, pitch=None, formant=None):
+                 loudness_start_db=None, max_boost_db=None, pitch=None, formant=None, max_pause_ms=None, max_lead_ms=None,
+                 pause_threshold_db=None):
         self.batch_size = batch_size
+        self._pause = _pauses_of(max_pause_ms, max_lead_ms, pause_threshold_db, batch_size)   # (caps, lead caps, thresholds) or None
+        self._ps = None                            # Engine.pause (device chunks), one stream per sample index
+        self._ps_host = {}                         # sample index -> pause.HostPause (CPU chunks)
         self._loud = _loudness_of(loudness_lufs, loudness_start_db, max_boost_db, batch_size)   # (targets, start gains, bounds) or None
         self._ld = None                            # Engine.loudness (device chunks), one stream per sample index
         self._ld_host = {}                         # sample index -> loudness.HostLoudness (CPU chunks)
@@ -269,8 +314,14 @@ class AudioStreamer:
             eng = engine if engine is not None else pcm16
             if eng is not None:
                 self._lv = eng.level(batch_size, rate=self.sample_rate, ceiling_db=self._level[1])
+        if self._pause is not None:
+            from .pause import seg_of
+            seg_of(self.sample_rate)               # refuses a delivered rate outside 8 .. 48 kHz, by name
+            eng = engine if engine is not None else pcm16
+            if eng is not None:
+                self._ps = eng.pause(batch_size, rate=self.sample_rate)
         # the device stages between a chunk and the ring, in the order they run; a further stage takes its place in this list
-        self._stages = [st for st in (self._ld, self._tp, self._fm, self._pt, self._rs, self._lv) if st is not None]
+        self._stages = [st for st in (self._ld, self._tp, self._fm, self._pt, self._rs, self._lv, self._ps) if st is not None]
         self.stop_signal = stop_signal
         self.timeout = timeout
         self.audio_queues = [self._make_queue() for _ in range(batch_size)]
@@ -278,6 +329,7 @@ class AudioStreamer:
         self._pcm_engine = pcm16                  # vibevoice_amd.Engine (or None: chunks keep the producer's dtype)
         self._ring = [None] * ring_slots          # pinned host buffers, allocated on first use (shape of the first chunk)
         self._pcm_dev = [None] * ring_slots       # device staging per ring slot: what the last stage, or the 16-bit conversion, writes
+        self._ring_cnt = [None] * ring_slots      # pinned int32 per ring slot: the rows' counts where the last stage counts on the device
         self._copy_stream = None                  # D2H copies run here: the module's copy stream of the chunks' device
         self._free = Queue()
         for i in range(ring_slots):
@@ -304,7 +356,8 @@ class AudioStreamer:
         if not audio_chunks.is_cuda:
             for row, idx in live:
                 chunk = audio_chunks[row].detach().clone()
-                if self.sample_rate != SOURCE_RATE or self._speeds is not None or self._level is not None or self._pitch is not None:
+                if self.sample_rate != SOURCE_RATE or self._speeds is not None or self._level is not None or self._pitch is not None \
+                        or self._pause is not None:
                     chunk = self._host_chunk(idx, chunk)
                     if chunk is None:
                         continue
@@ -327,6 +380,9 @@ class AudioStreamer:
                              "(pcm16=engine for 16-bit chunks, engine=engine for float chunks)")
         if self._level is not None and self._lv is None:
             raise ValueError("AudioStreamer(volume_db=... / ceiling_db=...): device chunks are levelled on the device and need an engine "
+                             "(pcm16=engine for 16-bit chunks, engine=engine for float chunks)")
+        if self._pause is not None and self._ps is None:
+            raise ValueError("AudioStreamer(max_pause_ms=... / max_lead_ms=...): device chunks are shortened on the device and need an engine "
                              "(pcm16=engine for 16-bit chunks, engine=engine for float chunks)")
         self._put_device(audio_chunks, live)
 
@@ -386,6 +442,14 @@ class AudioStreamer:
                     return None
                 lv = self._lv_host[idx] = HostLevel(self._level[0][idx], self._level[1], self.sample_rate)
             y = lv.push(y if y is not None else torch.zeros(0), flush=flush)
+        if self._pause is not None:
+            from .pause import HostPause
+            ps = self._ps_host.get(idx)
+            if ps is None:
+                if y is None:
+                    return None
+                ps = self._ps_host[idx] = HostPause(self.sample_rate, self._pause[0][idx], self._pause[1][idx], self._pause[2][idx])
+            y = ps.push(y if y is not None else torch.zeros(0), flush=flush)
         if y is None or not y.shape[0]:
             return None
         return y.reshape(self._lead + (y.shape[0],))
@@ -393,7 +457,8 @@ class AudioStreamer:
     def _put_device(self, audio_chunks, live, flush=False):
         """The live rows of a device chunk batch (audio_chunks None: their flush) through the stage chain on the producing stream, then
         the ring.  Every stage but the last writes an fp32 temporary there; the last one writes the slot's staging, as int16 under pcm16
-        (the launch converts, over each row's own chunk), with each row's count in the work item; one ring slot and one work item per
+        (the launch converts, over each row's own chunk), with each row's count in the work item (a last stage that counts on the device,
+        the pauses: a word of the slot's pinned companion, filled by the copy stream in front of the slot's event); one ring slot and one work item per
         last-stage launch that delivers.  A chunk longer than a stage's push takes (stage.take()) goes in pieces and arrives as several.
         No stages: the chunk batch itself is the source of the ring copy, behind Engine.audio_to_pcm16 into the staging under pcm16."""
         pcm = self._pcm_engine
@@ -443,6 +508,9 @@ class AudioStreamer:
         if stage is self._ld:
             kw = {"targets_lufs": [self._loud[0][idx] for idx in ids], "start_db": [self._loud[1][idx] for idx in ids],
                   "max_boost_db": [self._loud[2][idx] for idx in ids]}
+        if stage is self._ps:
+            kw = {"max_pause_ms": [self._pause[0][idx] for idx in ids], "max_lead_ms": [self._pause[1][idx] for idx in ids],
+                  "threshold_db": [self._pause[2][idx] for idx in ids]}
         dt = torch.int16 if ends and self._pcm_engine is not None else torch.float32
         at = 0
         while True:                                        # one push, but for a chunk longer than it takes
@@ -458,7 +526,10 @@ class AudioStreamer:
                 def deliver(slot):
                     pd = self._staging(slot, n, stage.max_out(w), dt, dev)
                     cnts = push(pd)
-                    self._ring_copy(pd[:n], [(i, idx, cnts[i]) for i, idx in enumerate(ids)], slot, prod)
+                    if torch.is_tensor(cnts):              # the stage counts on the device: the counts travel with the copy
+                        self._ring_copy(pd[:n], [(i, idx, None) for i, idx in enumerate(ids)], slot, prod, counts_dev=cnts)
+                    else:
+                        self._ring_copy(pd[:n], [(i, idx, cnts[i]) for i, idx in enumerate(ids)], slot, prod)
                 if not self._with_slot(deliver):
                     return False
             else:
@@ -472,9 +543,19 @@ class AudioStreamer:
                 return True
             at += w
 
-    def _ring_copy(self, src, rows, slot, prod):
+    def _ring_copy(self, src, rows, slot, prod, counts_dev=None):
         """the device rows src to the slot's pinned buffer behind the producing stream; rows: (row of src, sample index, samples of the row
-        that count or None: the row as it is) for the drain thread"""
+        that count or None: the row as it is) for the drain thread.  counts_dev (int32, one per row of src, on the device): the counts
+        are the device's; they go to the slot's pinned companion on the copy stream in front of the same event, and the drain thread
+        reads them there once it has waited for it.  Nothing here waits for the device."""
+        cbuf = None
+        if counts_dev is not None:
+            cbuf = self._ring_cnt[slot]
+            if cbuf is None or cbuf.shape[0] < counts_dev.shape[0]:
+                if cbuf is not None:
+                    _pinned_give([cbuf])
+                cbuf = self._ring_cnt[slot] = _pinned_take((max(counts_dev.shape[0], self.batch_size),), torch.int32)
+            rows = [(row, idx, cbuf[row]) for row, idx, _ in rows]      # a view of the pinned word: read behind the event
         buf = self._ring[slot]
         if buf is None or buf.shape[1:] != src.shape[1:] or buf.shape[0] < src.shape[0] or buf.dtype != src.dtype:
             if buf is not None:
@@ -492,7 +573,11 @@ class AudioStreamer:
         self._copy_stream.wait_event(ready)
         with torch.cuda.stream(self._copy_stream):
             buf[:src.shape[0]].copy_(src, non_blocking=True)       # staged rows are whole rows: both sides contiguous, one asynchronous copy
+            if counts_dev is not None:
+                cbuf[:counts_dev.shape[0]].copy_(counts_dev, non_blocking=True)
         src.record_stream(self._copy_stream)
+        if counts_dev is not None:
+            counts_dev.record_stream(self._copy_stream)
         ev = torch.cuda.Event()
         ev.record(self._copy_stream)
         self._work.put(("slot", rows, slot, ev, self._lead))
@@ -522,8 +607,8 @@ class AudioStreamer:
         else:
             idxs = [int(i.item()) if torch.is_tensor(i) else int(i) for i in sample_indices]
         idxs = [idx for idx in dict.fromkeys(idxs) if idx < self.batch_size and not self.finished_flags[idx]]
-        if (self.sample_rate != SOURCE_RATE or self._speeds is not None or self._level is not None or self._pitch is not None) and idxs \
-                and not self._closed:
+        if (self.sample_rate != SOURCE_RATE or self._speeds is not None or self._level is not None or self._pitch is not None
+                or self._pause is not None) and idxs and not self._closed:
             self._flush_tails(idxs)
         for idx in idxs:
             self.finished_flags[idx] = True
@@ -570,6 +655,8 @@ class AudioStreamer:
                 ev.synchronize()
                 buf = self._ring[b]
                 for row, idx, cnt in a:
+                    if torch.is_tensor(cnt):             # a word of the slot's pinned companion: the copy behind ev has filled it
+                        cnt = min(int(cnt), buf.shape[1])
                     if cnt is None:
                         self._deliver(idx, buf[row].clone())
                     elif cnt:
@@ -597,7 +684,9 @@ class AudioStreamer:
                 self._free.put(item[2])                  # a producer still blocked in _free.get() wakes up, sees _closed, returns
         with self._lock:
             _pinned_give(self._ring)                     # every copy into them has completed (their events have been waited on)
+            _pinned_give(self._ring_cnt)
             self._ring = [None] * len(self._ring)
+            self._ring_cnt = [None] * len(self._ring_cnt)
             self._pcm_dev = [None] * len(self._pcm_dev)  # release the device staging
             if self._rs is not None:
                 self._rs.close()                         # the engine's resampler configuration is free for the next streamer
@@ -611,6 +700,8 @@ class AudioStreamer:
                 self._lv.close()                         # ... and its level configuration
             if self._ld is not None:
                 self._ld.close()                         # ... and its loudness configuration
+            if self._ps is not None:
+                self._ps.close()                         # ... and its pause configuration
 
     # ---- consumer side ----
     def __iter__(self):
@@ -676,11 +767,13 @@ class AsyncAudioStreamer(AudioStreamer):
 
     def __init__(self, batch_size: int, stop_signal=None, timeout: Optional[float] = None, ring_slots: int = 8, pcm16=None,
                  sample_rate: Optional[int] = None, engine=None, speed=None, volume_db=None, ceiling_db=None, loudness_lufs=None,
-                 loudness_start_db=None, max_boost_db=None, pitch=None, formant=None):
+                 loudness_start_db=None, max_boost_db=None, pitch=None, formant=None, max_pause_ms=None, max_lead_ms=None,
+                 pause_threshold_db=None):
         self.loop = asyncio.get_running_loop()
         super().__init__(batch_size, stop_signal, timeout, ring_slots=ring_slots, pcm16=pcm16, sample_rate=sample_rate, engine=engine,
                          speed=speed, volume_db=volume_db, ceiling_db=ceiling_db, loudness_lufs=loudness_lufs,
-                         loudness_start_db=loudness_start_db, max_boost_db=max_boost_db, pitch=pitch, formant=formant)
+                         loudness_start_db=loudness_start_db, max_boost_db=max_boost_db, pitch=pitch, formant=formant,
+                         max_pause_ms=max_pause_ms, max_lead_ms=max_lead_ms, pause_threshold_db=pause_threshold_db)
 
     def _make_queue(self):
         return asyncio.Queue()
