@@ -79,8 +79,10 @@ def scores(qop, k, limit, kv_of_head=None):
     -inf at and past the limit.  kv_of_head: the kv head of every query head (default h // G)"""
     T, Hq, _ = qop.shape
     Hkv, L, _ = k.shape
-    kv = torch.arange(Hq) // (Hq // Hkv) if kv_of_head is None else torch.as_tensor(kv_of_head)
-    s = torch.einsum("thd,hld->thl", qop.to(F64), k.to(F64)[kv])
+    if kv_of_head is None:          # head h reads kv head h // G: one product per kv head, K is not copied once per query head
+        s = torch.einsum("tkgd,kld->tkgl", qop.to(F64).reshape(T, Hkv, Hq // Hkv, -1), k.to(F64)).reshape(T, Hq, L)
+    else:
+        s = torch.einsum("thd,hld->thl", qop.to(F64), k.to(F64)[torch.as_tensor(kv_of_head)])
     hidden = torch.arange(L)[None, :] >= torch.as_tensor(limit)[:, None]
     return s.masked_fill(hidden[:, None, :], float("-inf"))
 
@@ -89,9 +91,12 @@ def softmax_v(s, v, kv_of_head=None):
     """s [T, Hq, L] (-inf = excluded), v [Hkv, L, D] -> (out, a, p): out = softmax(s) v, a = softmax(s) |v|, p the weights"""
     T, Hq, L = s.shape
     Hkv = v.shape[0]
-    kv = torch.arange(Hq) // (Hq // Hkv) if kv_of_head is None else torch.as_tensor(kv_of_head)
     p = torch.softmax(s, -1)
-    v = v.to(F64)[kv]
+    v = v.to(F64)
+    if kv_of_head is None:
+        pg = p.reshape(T, Hkv, Hq // Hkv, L)
+        return (torch.einsum("tkgl,kld->tkgd", pg, v).reshape(T, Hq, -1), torch.einsum("tkgl,kld->tkgd", pg, v.abs()).reshape(T, Hq, -1), p)
+    v = v[torch.as_tensor(kv_of_head)]
     return torch.einsum("thl,hld->thd", p, v), torch.einsum("thl,hld->thd", p, v.abs()), p
 
 

@@ -89,3 +89,49 @@ ATTN_CHUNKS = tuple((n, p0) for n in (8, 20, 63, 64, 100, 150) for p0 in (0, 37,
 ATTN_APPEND_DECODE = [0, 15, 16, 31, 32, 2040]
 ATTN_APPEND_POS0 = (0, 37, 2040)
 ATTN_APPEND_SPAN, ATTN_APPEND_CHUNKS = 5, (64, 150)
+
+# ---- test_gpu_attn_long.py: the same launches at the contexts the product decodes at (32K: 32 splits, 64K: 64) ----
+# The split counts are vv_lm_pass_plan's: one per 1024 positions of the longest row, at most 256 / (long rows x kv heads), rows past
+# 1024 positions counting as long; geometry A has 2 kv heads, B has 1.  vv_attn_merge2 reads eight partials per thread group at
+# once, slots b0 + u NG with NG = 512 / head_dim groups (A: 8, B: 4): 8 NG splits per outer iteration.
+ATTN_LONG_MAX_CTX, ATTN_LONG_SLOTS, ATTN_LONG_MAX_ROWS = 69632, 8, 160          # 68 x 1024 positions
+# test_fused_decode_long: cache lengths before the step (row i on cache i); per set the split count in A and in B
+#   L1    64 splits: B two outer iterations of merge2, A one full iteration with all eight slots of every group live
+#   L1x   67 splits: A a second iteration with three live groups and dead slots, B three iterations
+#   L2    a 64-split row beside a one-block row the attention kernel finishes itself
+#   L6    four rows past 1024 positions: rows with used == S, used < S (1022: 32 blocks, B) and used = 5 (129) in one launch; the
+#         packed batch route and out_packed in the bf16 mode
+#   L16   eight long rows from 2000 to 64,000 and eight short ones; 1024 is past 1024 positions once its token is appended, so nine
+#         rows count as long: ceil(256 / 18) = 15 and ceil(256 / 9) = 29 splits -- odd counts, dead slots in every group but one
+#   Lcap  attn_splits = 8 capping a 65,000-position row: 8 splits of about 8125 positions
+ATTN_LONG_DECODE_LENS = {"L1": (64999,), "L1x": (67900,), "L2": (65000, 31), "L6": (64990, 40000, 33000, 5000, 1022, 129),
+                         "L16": (2000, 9000, 17000, 25000, 33000, 41000, 52000, 64000, 0, 1, 31, 32, 63, 64, 1023, 1024)}
+ATTN_LONG_DECODE_SPLITS = {"L1": {"A": 64, "B": 64}, "L1x": {"A": 67, "B": 67}, "L2": {"A": 64, "B": 64}, "L6": {"A": 32, "B": 64},
+                           "L16": {"A": 15, "B": 29}}
+ATTN_LONG_DECODE_CAPPED, ATTN_LONG_CAP = (65000, 40), 8
+# test_split_merge_long: (rows, pos0) spans of one cache -- every row of a span is long, so the split count is ceil(256 / (rows x kv
+# heads)) unless one per 1024 positions is fewer --, a 5-row span at 6 beside a row at 65,000 of another cache (one-split rows in a
+# 64-split launch), and in the exact modes a 70-row chunk at 60,000 (two launches of the pair, 30,080 and 15,104 positions per split)
+ATTN_LONG_SPANS = ((5, 64990), (2, 32767), (7, 65530))
+ATTN_LONG_SPAN_SPLITS = {(5, 64990): {"A": 26, "B": 52}, (2, 32767): {"A": 33, "B": 33}, (7, 65530): {"A": 19, "B": 37}}
+ATTN_LONG_SHORT_LONG = tuple(span(0, 6, 5) + [(1, 65000)])
+ATTN_LONG_SHORT_LONG_SPLITS = {"A": 64, "B": 64}
+ATTN_LONG_EXACT_CHUNK = (70, 60000)
+ATTN_LONG_EXACT_CHUNK_SPLITS = {"A": 2, "B": 4}
+# test_prefill4_long (bf16 mode): (rows, pos0) chunks, about 500 to 1000 stages of 64 positions before the chunk
+ATTN_LONG_CHUNKS = ((8, 32760), (20, 65000), (64, 64960), (150, 60001))
+# test_append_exact_long: decode steps (all six in one launch, then each alone), 5-row spans, chunks of 64 and 150 rows
+ATTN_LONG_APPEND_DECODE = (4095, 4096, 32767, 32768, 65535, 69631)
+ATTN_LONG_APPEND_SPANS = (32766, 65534)
+ATTN_LONG_APPEND_CHUNKS, ATTN_LONG_APPEND_CHUNK_POS = (64, 150), 65000
+# test_qkv_rope_epilogue_append: a thin 7B-shaped layer (hidden 64, 28 query / 4 kv heads of 128) whose 3600-row chunk at 61,000 puts
+# 18 x 15 = 270 workgroups of 256 x 256 on the 4608-wide QKV GEMM: vv_qkv_rope_plan takes it (test_prefill_plan_cpu.py)
+QKV_ROPE_CFG = synth.LMCfg(hidden=64, layers=1, heads=28, kv_heads=4, inter=256, vocab=64, head_dim_override=128)
+QKV_ROPE_ROWS, QKV_ROPE_POS0, QKV_ROPE_MAX_CTX = 3600, 61000, 65536
+# test_far_cache_offsets: geometry A sixteen layers deep, 65,536 positions, 9 slots: 2^27 elements per cache, caches 16 and 17 start
+# at element 2^31 and 2^31 + 2^27 of the K and V arrays (18 x 2^27 x 2 bytes = 4.83 GB each)
+FAR_CFG = synth.LMCfg(hidden=256, layers=16, heads=4, kv_heads=2, inter=256, vocab=64)
+FAR_MAX_CTX, FAR_SLOTS, FAR_LAYER, FAR_MAX_ROWS = 65536, 9, 15, 64
+FAR_DECODE = ((0, 65000), (16, 40), (17, 3000))
+FAR_SPANS = ((0, 64990), (16, 37), (17, 3000))          # (cache, pos0) of a 5-row span each
+FAR_CHUNK = (17, 30000, 64)                             # (cache, pos0, rows), bf16 mode

@@ -12,7 +12,12 @@ tests/attn_cases.py, on the CPU:
       (attn_ref.rotated_k_steps): no fp32 rotation resolves a bf16 step of such a result -- one element of 294,912 sat 7 steps
       apart at a value of 1.4e-7 from operands of 0.36;
   (d) on the dimension that carries the planted logits the q operand of every row, before its bf16 rounding, lies at least 2^-12
-      (relative) from a rounding boundary: a last-bit difference of the device's fp32 value cannot move a planted logit."""
+      (relative) from a rounding boundary: a last-bit difference of the device's fp32 value cannot move a planted logit;
+  (e) the same at the contexts of test_gpu_attn_long.py (lm_shapes.ATTN_LONG_*: 64 and 67 splits over 65K positions), where the
+      engines run on attn_cases.long_inv_freq: (d) at positions up to 69,631 and (c) at the positions that file appends at; the
+      comb design holds >= 0.9 of the weight and the loss of ANY one split moves its row by >= 10 x the bf16 bound; the random
+      design moves by more than 2 x the xs = 2 bound when any one split or any one 32-position block is lost; the tail ramp
+      re-bases the up-ramp head in >= 4 of the last 16 prefix stages with |K| <= 64."""
 import pytest
 import torch
 
@@ -100,14 +105,14 @@ def mutated(cfg, qop, k, v, limit, kind, arg=None):
     return R.softmax_v(s, v[:, :n], kv_of_head)[0]
 
 
-def moved(cfg, xs, family, rows, x, caches, kind, arg=None, target_rows=None):
+def moved(cfg, xs, family, rows, x, caches, kind, arg=None, target_rows=None, w=None):
     """the smallest normalised move over the targeted rows and the +c heads (the heads that see a planted logit); inf = non-finite"""
-    w = FAM_W[(cfg.hidden, family)]
+    w = FAM_W[(cfg.hidden, family)] if w is None else w
     ref, a, _ = AC.reference(w, cfg, xs, family, rows, x, caches)
     T = len(rows)
     pos = torch.tensor([p for _, p in rows])
     qb = w["layers.0.self_attn.q_proj.bias"].view(1, cfg.heads, cfg.head_dim).expand(T, -1, -1)
-    qop = R.q_operand(R.rope(qb, pos, R.inv_freq(cfg.head_dim, cfg.theta)), xs, family)
+    qop = R.q_operand(R.rope(qb, pos, AC.rope_table(w, cfg)), xs, family)
     c = rows[0][0]
     idx = [i for i, (cc, _) in enumerate(rows) if cc == c]
     k, v = caches[c]
@@ -256,3 +261,158 @@ def test_planted_q_operand_is_far_from_a_rounding_boundary(geo, family):
     op = R.q_operand(R.rope(qb, pos, R.inv_freq(D, cfg.theta)), 1, family)[:, :, D // 2 - 1]
     assert float((op.abs() / want - 1).abs().max()) <= 1e-5
     assert float(R.q_operand(R.rope(qb, pos, R.inv_freq(D, cfg.theta)), 3, family)[:, :, D - 1].abs().max()) <= 4.0 * 4.1e-3
+
+
+# ---------------------------------------------------------------------------------------------- (e) the long contexts
+from test_gpu_attn_paths import ATTN_BOUND          # noqa: E402  (the bounds of the short file: what a fault has to exceed)
+
+
+def long_w(cfg, family="fused", k_zero=False):
+    return AC.readout_weights(cfg, family, k_zero, inv_freq=AC.long_inv_freq(cfg.head_dim, cfg.theta))
+
+
+@pytest.mark.parametrize("case", ["L1", "L1x"])
+@pytest.mark.parametrize("geo", ["A", "B"])
+def test_comb_shows_the_loss_of_any_split(geo, case):
+    """the decode row of L1 / L1x with one planted position per split (attn_cases.comb_fused): from the reference alone"""
+    cfg = ls.ATTN_GEO[geo]
+    w = long_w(cfg)
+    (n,), S = ls.ATTN_LONG_DECODE_LENS[case], ls.ATTN_LONG_DECODE_SPLITS[case][geo]
+    comb = AC.comb_fused(n, S)
+    assert len(comb) == S and sorted((p // 32) % S for p in comb) == list(range(S))
+    assert len({p % 32 for p in comb}) >= 16 and len({(p // 32) // S for p in comb}) >= 5       # offsets and blocks vary
+    pre = {0: AC.prefix(cfg, n, "comb", "fused", AC.LONG_SEED + n, spikes=comb)}
+    rows, x = [(0, n)], AC.x_rows(cfg, 1, 50)
+    caches = cpu_pass(w, cfg, rows, x, pre)
+    _, _, sc = AC.reference(w, cfg, 1, "fused", rows, x, caches)
+    for kvh in range(cfg.kv_heads):
+        assert sum(R.weight_of(sc[0][AC.plus_head(cfg, kvh)], p) for p in comb) >= 0.9
+    _, spl = losses(sc[0], *caches[0], cfg, S)
+    plus = list(range(0, cfg.heads, 2))             # the +c heads
+    # losses() against the mutation the other tests of this file use, on one split
+    own = [p for p in range(n + 1) if (p // 32) % S == 5]
+    assert abs(moved(cfg, 1, "fused", rows, x, caches, "omit_positions", own, w=w) - float(spl[plus, 5].min())) <= 1e-9
+    print(f"comb {geo} {case}: least move of a +c head without one split {float(spl[plus].min()):.3f} (10 x the bf16 bound: {10 * ATTN_BOUND[('fused', 1)]:.3f})")
+    assert float(spl[plus].min()) >= 10 * ATTN_BOUND[("fused", 1)], float(spl[plus].min())
+
+
+def losses(sc_row, k, v, cfg, S):
+    """one decode row's fp64 scores [Hq, L] over the cache v [Hkv, L, D]: the normalised move of every head when one 32-position
+    block, and when one split of S (the blocks s, s + S, ..), is left out -> ([Hq, blocks], [Hq, S])"""
+    Hq, L = sc_row.shape
+    G, D = cfg.heads // cfg.kv_heads, cfg.head_dim
+    nb = (L + 31) // 32
+    p = torch.zeros(Hq, nb * 32, dtype=F64)
+    p[:, :L] = torch.softmax(sc_row, -1)
+    vv = torch.zeros(cfg.kv_heads, nb * 32, D, dtype=F64)
+    vv[:, :L] = v[:, :L]
+    vv = vv[torch.arange(Hq) // G].view(Hq, nb, 32, D)
+    pb = p.view(Hq, nb, 32)
+    ob = torch.einsum("hbi,hbid->hbd", pb, vv)              # every block's share of the output
+    wb = pb.sum(-1)
+    out, a = ob.sum(1), torch.einsum("hbi,hbid->hd", pb, vv.abs())
+
+    def move(o_part, w_part):
+        without = (out[:, None] - o_part) / (1.0 - w_part)[..., None]
+        return (without - out[:, None]).norm(dim=-1) / a.norm(dim=-1)[:, None]
+    split_of = torch.arange(nb) % S
+    os_ = torch.stack([ob[:, split_of == s].sum(1) for s in range(S)], 1)
+    ws_ = torch.stack([wb[:, split_of == s].sum(1) for s in range(S)], 1)
+    return move(ob, wb), move(os_, ws_)
+
+
+@pytest.mark.parametrize("case", ["L1", "L1x"])
+@pytest.mark.parametrize("geo", ["A", "B"])
+def test_random_design_shows_the_loss_of_any_split_and_any_block(geo, case):
+    """a condition on the INPUTS of test_fused_decode_long's random design (same seeds): in the exact modes no split and no single
+    32-position block of the long row can go missing inside the bound.  A workgroup serves one kv head, so what it loses is lost to
+    every query head of that group: the move of the group's worst head is what the GPU test sees"""
+    cfg = ls.ATTN_GEO[geo]
+    w = long_w(cfg)
+    (n,), S = ls.ATTN_LONG_DECODE_LENS[case], ls.ATTN_LONG_DECODE_SPLITS[case][geo]
+    pre = {0: AC.prefix(cfg, n, "random", "fused", AC.LONG_SEED + n)}
+    rows, x = [(0, n)], AC.x_rows(cfg, 1, 50)
+    caches = cpu_pass(w, cfg, rows, x, pre)
+    _, _, sc = AC.reference(w, cfg, 2, "fused", rows, x, caches)
+    blk, spl = losses(sc[0], *caches[0], cfg, S)
+    group = lambda t: float(t.view(cfg.kv_heads, cfg.heads // cfg.kv_heads, -1).amax(1).min())
+    print(f"random design {geo} {case}: least move without one split {group(spl):.2e}, without one block {group(blk):.2e} "
+          f"(2 x the xs = 2 bound: {2 * ATTN_BOUND[('fused', 2)]:.2e})")
+    assert group(spl) > 2 * ATTN_BOUND[("fused", 2)] and group(blk) > 2 * ATTN_BOUND[("fused", 2)], (group(spl), group(blk))
+
+
+@pytest.mark.parametrize("geo", ["A", "B"])
+def test_tail_ramp_rebases_late_and_stays_small(geo):
+    cfg = ls.ATTN_GEO[geo]
+    w = long_w(cfg, "prefill4")
+    for n, p0 in ((8, 32760), (20, 65000)):
+        k, v = AC.prefix(cfg, p0, "tail", "prefill4", 35)
+        assert float(k.float().abs().max()) <= 64.0
+        rows, x = ls.span(0, p0, n), AC.x_rows(cfg, n, 36)
+        caches = cpu_pass(w, cfg, rows, x, {0: (k, v)})
+        _, _, sc = AC.reference(w, cfg, 1, "prefill4", rows, x, caches)
+        last16 = range(p0 // 64 - 16, p0 // 64)
+        for j in (0, n - 1):
+            assert len([s for s in R.rebase_stages(sc[j][0]) if s in last16]) >= 4
+            assert not [s for s in R.rebase_stages(sc[j][1]) if s in last16]
+        assert moved(cfg, 1, "prefill4", rows, x, caches, "never_rebase", w=w) >= MOVE
+
+
+def rope32(x, pos, invf):
+    """the reference model's fp32 form of attn_ref.rope: angle, cos, sin and the rotation all in fp32"""
+    ang = pos.to(torch.float32)[:, None] * invf.to(torch.float32)[None, :]
+    emb = torch.cat([ang, ang], -1)
+    cos, sin = emb.cos()[:, None, :], emb.sin()[:, None, :]
+    x = x.to(torch.float32)
+    half = x.shape[-1] // 2
+    return x * cos + torch.cat([-x[..., half:], x[..., :half]], -1) * sin
+
+
+def long_append_positions():
+    pos = list(ls.ATTN_LONG_APPEND_DECODE)
+    for p0 in ls.ATTN_LONG_APPEND_SPANS:
+        pos += range(p0, p0 + ls.ATTN_APPEND_SPAN)
+    pos += range(ls.ATTN_LONG_APPEND_CHUNK_POS, ls.ATTN_LONG_APPEND_CHUNK_POS + max(ls.ATTN_LONG_APPEND_CHUNKS))
+    pos += range(ls.QKV_ROPE_POS0, ls.QKV_ROPE_POS0 + ls.QKV_ROPE_ROWS, 7)
+    return torch.tensor(sorted(set(pos)))
+
+
+@pytest.mark.parametrize("geo", ["A", "B", "qkv"])
+def test_append_flip_cap_long(geo):
+    """(c) at the positions test_append_exact_long and test_qkv_rope_epilogue_append append at, on the table their engines hold"""
+    cfg = ls.QKV_ROPE_CFG if geo == "qkv" else ls.ATTN_GEO[geo]
+    D = cfg.head_dim
+    invf = R.inv_freq(D, cfg.theta) if geo == "qkv" else AC.long_inv_freq(D, cfg.theta)
+    kb = (synth_k_bias(cfg) if geo == "qkv" else long_w(cfg, k_zero=True)["layers.0.self_attn.k_proj.bias"]).view(1, cfg.kv_heads, D)
+    pos = long_append_positions()
+    kb = kb.expand(len(pos), -1, -1)
+    u, flat = R.rotated_k_steps(rope32(kb, pos, invf), R.rope(kb, pos, invf), kb)
+    assert float(flat.double().mean()) <= 1e-4 and int(u.max()) <= 1, (int(flat.sum()), int(u.max()))
+    assert float((u > 0).double().mean()) <= 0.0025, float((u > 0).double().mean())
+
+
+def synth_k_bias(cfg):
+    import synth
+    return synth.lm_weights(cfg, seed=31)["layers.0.self_attn.k_proj.bias"]
+
+
+@pytest.mark.parametrize("family", ["fused", "prefill4"])
+@pytest.mark.parametrize("geo", ["A", "B"])
+def test_planted_q_operand_stays_a_bf16_value_at_long_positions(geo, family):
+    """(d) on the long engines' table: its last entry is 0, the planted pair does not rotate, and the operand is the planted value at
+    every position -- 32,767, 65,535, 69,631 and a stride over the whole context.  On the model's own table it is not: the pair has
+    turned by 0.09 rad at 65,535 and c cos(phi) sits 4e-3 below c"""
+    cfg = ls.ATTN_GEO[geo]
+    D = cfg.head_dim
+    pos = torch.tensor(sorted({32767, 65535, 69631} | set(range(0, ls.ATTN_LONG_MAX_CTX, 997))))
+    qb = AC.q_bias(cfg, family).view(1, cfg.heads, D).expand(len(pos), -1, -1)
+    invf = AC.long_inv_freq(D, cfg.theta)
+    assert float(invf[-1]) == 0.0 and torch.equal(invf[:-1], R.inv_freq(D, cfg.theta)[:-1])
+    pre = R.q_prerounding(R.rope(qb, pos, invf), 1, family)[:, :, D // 2 - 1]
+    assert float(R.bf16_boundary_distance(pre).min()) >= 2.0 ** -12
+    want = 6.0 * R.LN2 if family == "prefill4" else 4.0
+    op = R.q_operand(R.rope(qb, pos, invf), 1, family)[:, :, D // 2 - 1]
+    assert float((op.abs() / want - 1).abs().max()) <= 1e-5
+    assert float(R.q_operand(R.rope(qb, pos, invf), 3, family)[:, :, D - 1].abs().max()) == 0.0
+    model = R.q_operand(R.rope(qb, torch.tensor([65535]), R.inv_freq(D, cfg.theta)), 3, family)[:, :, D // 2 - 1]
+    assert float((model.abs() / want - 1).abs().max()) >= 1e-3

@@ -441,8 +441,8 @@ def test_append_exact(engines, geo, xs):
     class (six rows in one launch -- the packed batch route in the bf16 mode -- and each alone: vv_attn_fused_kernel's table RoPE and
     knew / vnew), a 5-row span (vv_rope_append_kernel, trigonometric) and chunks of 64 and 150 rows (the packed prefill's QKV GEMM +
     vv_rope_append in the bf16 mode), at 0, 37 and 2040.  The RoPE epilogue of vv_gemm4 needs a QKV width that is a multiple of 256
-    and 256 workgroups of 256 x 256 tiles -- about 8000 rows at a 2048-wide QKV -- out of reach of shapes of a few thousand
-    positions: test_gpu_shipped.py keeps it.
+    and 256 workgroups of 256 x 256 tiles -- about 8000 rows at a 2048-wide QKV -- out of reach of this file's geometries:
+    test_gpu_attn_long.py::test_qkv_rope_epilogue_append reaches it with a thin layer whose QKV is 4608 wide (3600 rows).
     Exported K: never more than one bf16 step from the fp64 rotation rounded to bf16 and at most 1 % of the elements off at all
     (attn_ref.rotated_k_steps; the reference's own fp32 form stays under a quarter of that, test_attn_ref_cpu.py).
     Exported V at xs = 3: bit-exact against the fp64 projection rounded to bf16, but for the elements whose fp64 value lies within

@@ -311,3 +311,77 @@ def test_the_attention_path_tests_run_the_launches_they_name(probe):
                 owners[S] |= {((n + step) >> 5) % S for n in lens}
     assert owners == {2: {0, 1}, 3: {0, 1, 2}}, owners
     assert any(n < 64 for n, _ in ls.ATTN_CHUNKS) and any(n >= 64 for n, _ in ls.ATTN_CHUNKS)
+
+
+def merge2_walk(used, D):
+    """vv_attn_merge2_kernel over `used` partials: per outer iteration (live groups, groups with a dead slot, live slots of group 0)"""
+    NG = 512 // D
+    out = []
+    for it in range(-(-used // (8 * NG))):
+        live = [sum(1 for u in range(8) if it * 8 * NG + g + u * NG < used) for g in range(NG)]
+        out.append((sum(1 for n in live if n), sum(1 for n in live if 0 < n < 8), live[0]))
+    return out
+
+
+def test_the_long_attention_tests_run_the_launches_they_name(probe):
+    """test_gpu_attn_long.py: route and split count of every row set of lm_shapes.ATTN_LONG_*, QKV_ROPE_* and FAR_*, and the state of
+    vv_attn_merge2's outer loop those split counts reach"""
+    ragged = dict(fused=0, contiguous=0, route=GEMV, attn=SPLIT_MERGE, attn_groups=1, zero_v_tail=0)
+    for geo, cfg in ls.ATTN_GEO.items():
+        eng = (cfg, ls.ATTN_LONG_MAX_ROWS)
+        for xs in (1, 2, 3):
+            caps = engine_caps(eng, xs)
+            assert caps["ws"] == 64 and caps["tile3"] == caps["p16"] == caps["attn2"] == (xs == 1)
+            assert set(ls.ATTN_LONG_DECODE_LENS) == set(ls.ATTN_LONG_DECODE_SPLITS)
+            for case, lens in ls.ATTN_LONG_DECODE_LENS.items():
+                assert len(lens) <= 2 * ls.ATTN_LONG_SLOTS and max(lens) + 2 <= ls.ATTN_LONG_MAX_CTX
+                route = P16 if xs == 1 and 5 <= len(lens) <= 16 else GEMV
+                S = ls.ATTN_LONG_DECODE_SPLITS[case][geo]
+                check_lm(probe, [(lm(rows, **caps), dict(fused=1, attn=FUSED, route=route, attn_S=S, key_split=S))
+                                 for rows in ls.decode_steps(list(enumerate(lens)), 1 if case == "L16" else 2)])     # "own": two steps; L16 has no own
+            capped = engine_caps(eng, xs, attn_splits=ls.ATTN_LONG_CAP)
+            cap_rows = ls.decode_steps(list(enumerate(ls.ATTN_LONG_DECODE_CAPPED)), 2)
+            check_lm(probe, [(lm(rows, **capped), dict(fused=1, attn=FUSED, route=GEMV, attn_S=ls.ATTN_LONG_CAP)) for rows in cap_rows])
+            check_lm(probe, [(lm(cap_rows[0], **caps), dict(attn_S=64))])
+            check_lm(probe, [(lm(ls.span(0, p0, n), **caps), dict(ragged, attn_S=ls.ATTN_LONG_SPAN_SPLITS[(n, p0)][geo]))
+                             for n, p0 in ls.ATTN_LONG_SPANS])
+            check_lm(probe, [(lm(list(ls.ATTN_LONG_SHORT_LONG), **caps), dict(ragged, attn_S=ls.ATTN_LONG_SHORT_LONG_SPLITS[geo]))])
+            n, p0 = ls.ATTN_LONG_EXACT_CHUNK
+            if xs != 1:
+                check_lm(probe, [(lm(ls.span(0, p0, n), **caps), dict(contiguous=1, route=GEMV, attn=SPLIT_MERGE, attn_groups=2,
+                                                                      attn_S=ls.ATTN_LONG_EXACT_CHUNK_SPLITS[geo]))])
+            chunks = list(ls.ATTN_LONG_CHUNKS) + [(n, ls.ATTN_LONG_APPEND_CHUNK_POS) for n in ls.ATTN_LONG_APPEND_CHUNKS]
+            check_lm(probe, [(lm(ls.span(0, p0, n), **caps), span_claim(n, xs)) for n, p0 in chunks])
+            assert all(p0 + n <= ls.ATTN_LONG_MAX_CTX for n, p0 in chunks + list(ls.ATTN_LONG_SPANS) + [ls.ATTN_LONG_EXACT_CHUNK])
+            check_lm(probe, [(lm(list(enumerate(ls.ATTN_LONG_APPEND_DECODE)), **caps), dict(fused=1, attn=FUSED, route=P16 if xs == 1 else GEMV))] +
+                            [(lm([(0, p)], **caps), dict(fused=1, attn=FUSED, route=GEMV)) for p in ls.ATTN_LONG_APPEND_DECODE] +
+                            [(lm(ls.span(0, p0, ls.ATTN_APPEND_SPAN), **caps), ragged) for p0 in ls.ATTN_LONG_APPEND_SPANS])
+    assert max(ls.ATTN_LONG_APPEND_DECODE) == ls.ATTN_LONG_MAX_CTX - 1
+    # what the comments of lm_shapes.py say the split counts do to vv_attn_merge2 (a row of `used` = S partials)
+    S = ls.ATTN_LONG_DECODE_SPLITS
+    assert merge2_walk(S["L1"]["A"], 64) == [(8, 0, 8)]                             # one full iteration, all eight slots of every group
+    assert merge2_walk(S["L1"]["B"], 128) == [(4, 0, 8), (4, 0, 8)]                 # two outer iterations
+    assert merge2_walk(S["L1x"]["A"], 64) == [(8, 0, 8), (3, 3, 1)]                 # a second one: three live groups, dead slots
+    assert len(merge2_walk(S["L1x"]["B"], 128)) == 3 and merge2_walk(S["L1x"]["B"], 128)[2] == (3, 3, 1)
+    assert merge2_walk(S["L16"]["A"], 64) == [(8, 8, 2)] and merge2_walk(S["L16"]["B"], 128) == [(4, 3, 8)]
+    assert (S["L6"]["A"], S["L6"]["B"]) == (32, 64)
+    blocks = [(n + 32) // 32 for n in ls.ATTN_LONG_DECODE_LENS["L6"]]               # 32-position blocks of each row with its new token
+    for g in ("A", "B"):
+        assert any(b >= S["L6"][g] for b in blocks) and any(1 < b < S["L6"][g] for b in blocks) and 5 in blocks
+    assert [(n + 32) // 32 for n in ls.ATTN_LONG_DECODE_LENS["L2"]] == [2032, 1]
+    # test_qkv_rope_epilogue_append: a contiguous chunk on the packed prefill; test_far_cache_offsets: layer 15 of a 16-layer engine
+    caps = engine_caps((ls.QKV_ROPE_CFG, ls.QKV_ROPE_ROWS), 1)
+    assert caps["tile3"]
+    check_lm(probe, [(lm(ls.span(0, ls.QKV_ROPE_POS0, ls.QKV_ROPE_ROWS), **caps), dict(contiguous=1, route=PREFILL, attn=PREFILL4, zero_v_tail=1))])
+    assert ls.QKV_ROPE_POS0 + ls.QKV_ROPE_ROWS <= ls.QKV_ROPE_MAX_CTX
+    c = ls.FAR_CFG
+    stride = c.layers * c.kv_heads * ls.FAR_MAX_CTX * c.head_dim
+    assert stride == 2 ** 27 and 16 * stride == 2 ** 31 and 2 * ls.FAR_SLOTS == 18
+    for xs in (1, 2, 3):
+        caps = engine_caps((c, ls.FAR_MAX_ROWS), xs)
+        check_lm(probe, [(lm(list(ls.FAR_DECODE), **caps), dict(fused=1, attn=FUSED, route=GEMV, attn_S=64))] +
+                        [(lm(ls.span(cc, p0, 5), **caps), ragged) for cc, p0 in ls.FAR_SPANS])
+        if xs == 1:
+            cc, p0, n = ls.FAR_CHUNK
+            check_lm(probe, [(lm(ls.span(cc, p0, n), **caps), span_claim(n, 1))])
+    assert {cc for cc, _ in ls.FAR_DECODE} == {cc for cc, _ in ls.FAR_SPANS} == {0, 16, 17} and ls.FAR_CHUNK[0] >= 16

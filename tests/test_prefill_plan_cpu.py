@@ -138,6 +138,20 @@ def test_qkv_rope(probe):
     assert (got[6][1]["full_idx"], got[6][1]["split"], got[6][1]["grid_x"]) == (0, 1, 774), got[6]
 
 
+def test_the_thin_layer_reaches_the_qkv_rope_epilogue(probe):
+    """test_gpu_attn_long.py::test_qkv_rope_epilogue_append: lm_shapes.QKV_ROPE_* is a shape vv_qkv_rope_plan takes -- 18 x 15 = 270
+    workgroups of the 256 x 256 kernel with the VV_EPI_QKV_ROPE epilogue -- on an engine that has the partial-round workspace"""
+    import lm_shapes as ls
+    c, T = ls.QKV_ROPE_CFG, ls.QKV_ROPE_ROWS
+    assert (c.heads + 2 * c.kv_heads) * c.head_dim == 4608 and T >= 1024 and c.hidden % 8 == 0 and c.inter % 8 == 0
+    (rc, p), (rc1, _) = plans(probe, [f"qkv {T} {c.hidden} {c.head_dim} {c.heads} {c.kv_heads} 1 1",
+                                      f"qkv {T - 272} {c.hidden} {c.head_dim} {c.heads} {c.kv_heads} 1 1"])
+    assert rc == 1 and rc1 == 0, (rc, rc1)          # 3328 rows are 13 row blocks: 234 workgroups, the plain GEMM + vv_rope_append
+    want = dict(form=G4, epi=QKV_ROPE, n_blocks=18, t_blocks=15, grid_y=1, block=512, lds=128 * 1024, ks=1)
+    assert all(p[k] == v for k, v in want.items()), p
+    assert p["grid_x"] >= 270
+
+
 def engine_ws(geometry, max_rows, xsplit=1):
     """what vv_create's workspace offers an engine of that geometry: (partial round?, bytes of the short-prompt partial tensors)"""
     from test_gpu_geometry import GEOM
